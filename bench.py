@@ -25,6 +25,9 @@ workload : g1  perf.jl:5 instance family, cost ~ U{10..40}, N = 16384 (BASELINE 
            figure (an independent N = 16 384 instance per GPU, no collective, weak scaling) is a
            side field; --multi-mode replicas makes it the headline instead.
 
+--dump-outputs DIR : after the timed steps, rank 0 writes what the headline path returned in its last timed step
+           (row_to_col and total; for tick the whole td_tick result, for pool the merged pools) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -64,7 +67,41 @@ def parse():
                     help="off: td_set_line_metric(0), the general solver alone (matters for g2, whose |a-b| matrix the "
                          "default path answers with the sorted matching + certificate pass)")
     ap.add_argument("--no-extras", action="store_true", help="skip the g2 / g3 / tick side measurements (1 GPU)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline path returned in its last timed step as DIR/<name>.npy "
+                         "(float64, at most 64 MB in all; bench_outputs/ is git-ignored); the inputs are seeded, so two builds can be "
+                         "compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: every array as <path>/<name>.npy in float64 (integers below 2**53 stay exact).  Should the whole
+    exceed `limit` bytes, each large array is cut to a fixed, seeded sample of its elements, whose flat indices go to
+    <name>_index.npy."""
+    out = {}
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        if v.dtype.kind in "iu" and v.size and int(np.abs(v.astype(np.int64)).max()) >= 2**53:
+            raise ValueError("%s: integers beyond 2**53 are not exact in float64" % k)
+        out[k] = v.astype(np.float64)
+    if sum(a.nbytes for a in out.values()) > limit:
+        share = limit // (16 * len(out))   # elements per array: value + index, 8 bytes each
+        rng = np.random.default_rng(0)
+        for k in sorted(out):
+            a = out[k]
+            if a.size > share:
+                idx = np.sort(rng.choice(a.size, share, replace=False))
+                out[k], out[k + "_index"] = a.reshape(-1)[idx], idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(out)
 
 
 class TickWorkload:
@@ -88,7 +125,12 @@ class TickWorkload:
         t = self.td.tick(self.cab_to, self.dem_from, None, big_cost=250000, drop_time=10, max_non_lcm=600)
         rows, n2, total = t["lcm_rows"], t["n_rest"], t["total"]
         self.last = (len(rows), n2, total)
+        self.last_tick = t
         return total
+
+    def outputs(self):
+        """what td_tick handed back in the last step"""
+        return {k: np.atleast_1d(v) for k, v in self.last_tick.items()}
 
 
 class Workload:
@@ -160,6 +202,10 @@ class Workload:
             raise RuntimeError("wrong optimum: got %d expected %d" % (t, self.expected))
         return t
 
+    def outputs(self):
+        """what td_assign / td_build_assign handed back in the last step: row_to_col and the total"""
+        return {"row_to_col": self.r2c.cpu().numpy(), "total": np.array([self.total.value])}
+
 
 def kernel_profile(wl, ffi, reps):
     """Per-kernel-class device time with HIP events recorded on the library's stream."""
@@ -180,7 +226,7 @@ def kernel_profile(wl, ffi, reps):
     return out
 
 
-def sharded_leg(n, world, rank, torch, dist, ffi, steps, warmup, builder="gen"):
+def sharded_leg(n, world, rank, torch, dist, ffi, steps, warmup, builder="gen", outputs=None):
     """BASELINE configs[3]: ONE n x n perf.jl instance row-sharded over all ranks.  A step = every
     rank writes its row block in place (td_gen_uniform with its row window: the synthetic stand-in
     for the shard-local cost build, td_cost_build_rows) + the sharded solve: one RCCL MAX all-reduce
@@ -209,7 +255,7 @@ def sharded_leg(n, world, rank, torch, dist, ffi, steps, warmup, builder="gen"):
                                                    row0, nrows, rows.data_ptr()))
         elif nrows:
             ffi.check(ffi.lib().td_gen_uniform(n, 7, 10, 40, row0, nrows, rows.data_ptr()))
-        tot = sharded.solve_sharded(sh, dist)[1]
+        seq["r2c"], tot = sharded.solve_sharded(sh, dist)[:2]
         seq["path"], seq["left"] = sharded.solve_sharded.last_path, getattr(sharded.solve_sharded, "last_left", None)
         return tot
 
@@ -232,6 +278,11 @@ def sharded_leg(n, world, rank, torch, dist, ffi, steps, warmup, builder="gen"):
         if world > 1:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+        if outputs is not None:
+            # every rank holds the row_to_col of its own rows: gathered in rank order, after the timed steps
+            parts = [None] * world
+            dist.all_gather_object(parts, np.asarray(seq["r2c"], dtype=np.int32)[:nrows])
+            outputs.update({"row_to_col": np.concatenate(parts), "total": np.array([int(total)])})
     finally:
         sh.close()
     del rows
@@ -290,7 +341,7 @@ def pool_demand(seed, n, max_wait, losses):
     return np.stack([np.arange(n), frm, to, wait, loss], 1)
 
 
-def pool_workload(td, reps, cpu_seconds):
+def pool_workload(td, reps, cpu_seconds, outputs=None):
     """f-4 (pool_n.c:101-242 / findpool.c:122-176): pools of k = 2, 3, 4 passengers over findpool.c's 8 first-pick-up
     slices (8 td_pool_n calls) + the merge (td_pool_merge), timed per (n, k); beside it the oracle's single-thread C
     restatement of the same 8 children + merge on this box's host core (bounded), and — where the file exists — the
@@ -324,6 +375,9 @@ def pool_workload(td, reps, cpu_seconds):
                 merged, happy = gpu_once()
             torch.cuda.synchronize()
             ms = 1e3 * (time.perf_counter() - t0) / reps
+            if outputs is not None:
+                outputs["pools_%s_k%d" % (name, k)] = np.asarray(merged, np.int32).reshape(-1, 2 * k + 1)
+                outputs["happy_plans_%s_k%d" % (name, k)] = np.array([happy])
             # CPU port: the same 8 slices + the same merge rule, one thread, bounded
             t_budget = time.perf_counter() + cpu_seconds
             creps, spent, cm = 0, 0.0, None
@@ -553,17 +607,20 @@ def main():
     td.set_line_metric(args.line_metric == "on")
     # the library runs on its own stream; the timed region is bracketed by device-wide synchronisation
 
+    outputs = {} if args.dump_outputs else None
     if args.workload == "pool":
-        res = pool_workload(td, max(1, min(args.steps, 20)), 0.0 if args.no_cpu_baseline else min(args.cpu_seconds, 4.0))
+        res = pool_workload(td, args.steps, 0.0 if args.no_cpu_baseline else min(args.cpu_seconds, 4.0), outputs)
         head = res["n600_k4"]
         line = {"metric": "pool requests/sec (pools of 4, 8 first-pick-up slices + merge)", "value": head["requests_per_s"],
-                "unit": "requests/s", "n_gpus": 1, "steps": max(1, min(args.steps, 20)), "warmup": 1, "ms_per_step": head["gpu_ms"],
+                "unit": "requests/s", "n_gpus": 1, "steps": args.steps, "warmup": 1, "ms_per_step": head["gpu_ms"],
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32 / f64 happiness test", "data": "synthetic",
                 "config": {"workload": "pool_n.c:101-242 fan-out of findpool.c:122-176: n = 600 requests, pools of 4 (all sizes in `pool`)"},
                 "pool": res,
                 "cpu_baseline": {"value": 600.0 / (head["cpu_port_ms"] * 1e-3), "unit": "requests/s", "cores": 1, "kind": "port",
                                  "sample": "oracle_pool_n (oracle/td_oracle.c) over the same 8 slices + the merge rule, n = 600, k = 4, %d repetitions"
                                            % head["cpu_port_reps"], "cpu_model": cpu_model()}}
+        if outputs is not None:
+            line["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(line), flush=True)
         return
     if args.workload == "tick":
@@ -590,6 +647,8 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if outputs is not None:
+        outputs.update(wl.outputs())
     stats = td.last_stats()
 
     prof = kernel_profile(wl, ffi, reps=3) if rank == 0 else {}
@@ -655,7 +714,7 @@ def main():
                              "total_cost": shard_res["total_cost"]})
         return line
 
-    shard_res, single_ref = None, None
+    shard_res, single_ref, shard_out = None, None, None
     watchdog = None
     if world > 1 or args.force_sharded:
         # a collective that never returns on some rank (RCCL / IPC trouble on a node this path has not seen) must
@@ -678,9 +737,10 @@ def main():
         if args.sharded_n > 0:
             del wl.cost
             torch.cuda.empty_cache()
+            shard_out = {} if outputs is not None else None
             try:
                 shard_res = sharded_leg(args.sharded_n, world, rank, torch, dist, ffi, max(1, args.steps), args.warmup,
-                                        "cost" if args.shard_builder == "cost" else "gen")
+                                        "cost" if args.shard_builder == "cost" else "gen", shard_out)
                 if args.shard_builder == "both":
                     extra = sharded_leg(args.sharded_n, world, rank, torch, dist, ffi, max(1, args.steps), args.warmup, "cost")
                     shard_res["with_td_cost_build_rows"] = {k: extra[k] for k in ("ms_per_step", "assignments_per_s", "total_cost", "workload")}
@@ -697,6 +757,8 @@ def main():
         dist.destroy_process_group()
         return
     line = build_line(shard_res)
+    if outputs is not None and line.get("scaling") == "strong" and shard_out:
+        outputs = shard_out   # the headline is the row-sharded instance
     n = args.n
     if world == 1 and not args.no_extras and args.workload == "g1":
         # the other workloads of SURVEY 8d / BASELINE configs, measured in the same run (side fields)
@@ -743,6 +805,8 @@ def main():
         line["cpu_baseline"]["glpk"] = glpk_baseline()   # solver.py's own path, iff cvxopt imports here
         if args.workload == "tick":   # same instance (seed 1) through the C port: the totals must agree
             line["total_matches_cpu_port"] = bool(int(total) == int(line["cpu_baseline"]["last_total"]))
+    if outputs is not None:
+        line["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs)
     if dist.is_initialized():
         dist.destroy_process_group()
     # RCCL prints a version banner through C stdio: drain it so the JSON line is the LAST line
