@@ -154,6 +154,32 @@ TD_API int td_lcm(int n, const int32_t *cost, int32_t mask, int32_t threshold, i
            int32_t stop_value, int stop_size, int64_t sum_below, int max_pairs,
            int32_t *rows, int32_t *cols, int32_t *n_pairs, int64_t *total, int32_t *last_min);
 
+/* ---- a-4 / a-5 for MANY small models in one call (heuristic.py:20-40, split.py:61-120) -------------------------------
+ * B independent square models of size up to n (n <= 1024), model b's cells at cost + b*n*n, row-major,
+ * row = cab, column = request.  ns (int32[B], may be NULL = every model is n x n): model b is the top-left
+ * ns[b] x ns[b] block of its slab (0 <= ns[b] <= n); cells outside it are never read.
+ * One workgroup per model (csrc/td_batch.hip): no launch, copy or host synchronisation per model, which is what a
+ * td_assign / td_lcm call per model pays.  Cells are indexed with 64-bit arithmetic (B*n*n may exceed 2^31).
+ * Arrays may be host or device memory; calls are synchronous.  TD_EINVAL: n > 1024 (a large model is one td_assign
+ * call), batch < 0, ns[b] outside [0, n].
+ *
+ * td_assign_batched: the optimum of every model.  Outputs per model: row_to_col[b*n + i] (i < ns[b]; -1 for
+ * i >= ns[b]), total[b], dual_bound[b] (may be NULL), col_price[b*n + j] (int64, may be NULL; 0 for j >= ns[b]):
+ * column potentials v with sum_i min_j (c_ij - v_j) + sum_j v_j == dual_bound[b], recomputed from the cells;
+ * dual_bound == total certifies optimality.  TD_EINTERNAL if a model hit a defensive loop cap.
+ * When to use which (measured on MI355X): up to n = 256 the batched call wins (1000 models of 100 x 100:
+ * 1.3 ms against 371 ms for a loop of td_solver_assign); at n = 1024 one td_assign per model is faster for heavily tied
+ * costs (U{1..39}: 0.24 against 0.9 ms per model) while uniform costs still gain 7x batched.  Crossover: n ~ 512. */
+TD_API int td_assign_batched(int batch, int n, const int32_t *ns, const int32_t *cost, int32_t *row_to_col,
+                             int64_t *total, int64_t *dual_bound, int64_t *col_price);
+
+/* td_lcm's semantics and parameters applied to every model of the batch (same slab layout / ns as above;
+ * stop_size counts against ns[b]; at most ns[b] picks).  rows / cols: int32[B*n] (model b's pairs at b*n, in pick
+ * order), n_pairs / last_min: int32[B], total: int64[B]. */
+TD_API int td_lcm_batched(int batch, int n, const int32_t *ns, const int32_t *cost, int32_t mask, int32_t threshold,
+                          int stop_value_on, int32_t stop_value, int stop_size, int64_t sum_below,
+                          int32_t *rows, int32_t *cols, int32_t *n_pairs, int64_t *total, int32_t *last_min);
+
 /* Row-sharded LCM: rank r owns cost rows [row0, row0 + nrows).  Per pick every shard
  * reports its smallest live cell {value, global row, column} (value = INT64_MAX: none), the caller
  * takes the minimum in the reference's order (value, row, column) over all shards — one all-gather of

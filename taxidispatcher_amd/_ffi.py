@@ -45,7 +45,10 @@ SIGNATURES = {
                               ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_i32p, c_i32p,
                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),
                               ctypes.POINTER(ctypes.c_int32)]),
-    "td_lcm_shard_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p, ctypes.c_int, ctypes.c_int32,
+    "td_assign_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
+    "td_lcm_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int,
+                                      ctypes.c_int32, ctypes.c_int, ctypes.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
+    "td_lcm_shard_create":(ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p, ctypes.c_int, ctypes.c_int32,
                                            ctypes.POINTER(ctypes.c_void_p)]),
     "td_lcm_shard_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "td_lcm_shard_local_min": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),

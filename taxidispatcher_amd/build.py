@@ -3,14 +3,17 @@
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the CPU-only container too.
 The .so is git-ignored but travels with the repo snapshot to the GPU box.
 """
+import glob
 import os
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = [os.path.join(HERE, "csrc", f) for f in ("td_core.hip", "td_assign.hip", "td_lcm.hip", "td_pool.hip", "td_line.hip", "td_tick.hip")]
-HDR = [os.path.join(HERE, "csrc", "td_common.h"), os.path.join(HERE, "csrc", "td_forest.h"), os.path.join(ROOT, "include", "taxidispatcher_amd.h")]
+SRC = [os.path.join(HERE, "csrc", f) for f in ("td_core.hip", "td_assign.hip", "td_lcm.hip", "td_pool.hip", "td_line.hip", "td_tick.hip",
+                                               "td_batch.hip")]
+# every header a source may include: a header added later is part of the staleness check without being listed here
+HDR = sorted(glob.glob(os.path.join(HERE, "csrc", "*.h")) + glob.glob(os.path.join(ROOT, "include", "*.h")))
 LIB = os.environ.get("TD_LIB_OUT") or os.path.join(HERE, "libtaxidispatcher_amd.so")
 
 

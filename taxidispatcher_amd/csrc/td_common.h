@@ -85,6 +85,8 @@ int cost_build_async(const int32_t *cab_to, int n_s, const int32_t *dem_from, in
 // *ok = 0: not such a model, nothing done
 int lcm_stands(int n_s, int n_d, const int32_t *d_cab_to, const int32_t *d_dem_from, int32_t fill, int32_t threshold, int stop_size,
                int32_t *rows, int32_t *cols, int32_t *n_pairs, int32_t *last_min, int *ok);
+// td_batch.hip: frees the batched entry points' result buffer (td_shutdown)
+void batch_release_workspace();
 void prof_begin(int k);
 void prof_end(int k);
 void prof_flush();

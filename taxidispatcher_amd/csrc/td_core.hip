@@ -306,7 +306,7 @@ extern "C" void td_tick_release_workspace(void);
 
 extern "C" {
 
-int td_version(void) { return 100; }
+int td_version(void) { return 101; }
 
 const char *td_last_error(void) { return ctx().err; }
 
@@ -347,6 +347,7 @@ void td_shutdown(void)
     (void)hipDeviceSynchronize();
     td_assign_release_workspace();
     td_tick_release_workspace();
+    batch_release_workspace();
     Buf *bufs[] = {&c.stage_a, &c.stage_b, &c.stage_c, &c.stage_d, &c.stage_out, &c.cc,
                    &c.misc,    &c.lcm_a,   &c.lcm_b,   &c.lcm_c,   &c.lcm_d};
     for (Buf *b : bufs) {

@@ -18,6 +18,9 @@ Reference map (file:line in boguszjelinski/taxidispatcher):
     count_sum             greedy_opt.py:21-29
     filter_out            greedy_opt.py:32-37 (by id) / simulate.py:64-69 (by position)
     combined              greedy_opt.py:136-160
+    assign_batched        the optimum of many small models per call (heuristic.py:20-40, split.py:61-120)
+    LCM_batched           LCM of many small models per call (heuristic.py:24-33 per scenario)
+    heuristic_gap         heuristic.py:20-40 as two calls
 """
 import ctypes
 
@@ -457,3 +460,95 @@ def combined(distances, demand, cabs, threshold=10, big_cost=BIG_COST):
     n2, x2, cost_table2 = solve(distances, rest_demand, rest_cabs, big_cost)
     res2 = count_sum(n2, cost_table2, x2, big_cost) if n2 else 0
     return nn, res, n2, res2 + lcm
+
+
+# ----------------------------------------------------------------------------------------
+# many small models per call (td_assign_batched / td_lcm_batched)
+# ----------------------------------------------------------------------------------------
+BATCH_NMAX = 1024   # largest model of a batched call; a larger one is one assign() call
+
+
+def pack_batch(costs, ns=None):
+    """Batched input -> (cost, ns, batch, n).  `costs` is a (B, n, n) int32 array-like or torch CUDA int32 tensor
+    (handed on as it is), or a list of 2-D square arrays of different sizes: those are packed into a zero-padded
+    (B, n, n) slab with n = the largest size and ns = their sizes.  `ns` given with a list is refused."""
+    if isinstance(costs, (list, tuple)) and (len(costs) == 0 or np.ndim(costs[0]) == 2):
+        if ns is not None:
+            raise _ffi.TdError("ns is derived from the list of models; do not pass it as well")
+        mats = [_ffi.as_i32(c) for c in costs]
+        for k, m in enumerate(mats):
+            if m.ndim != 2 or m.shape[0] != m.shape[1]:
+                raise _ffi.TdError("model %d is not a square matrix: shape %s" % (k, m.shape))
+        sizes = np.array([m.shape[0] for m in mats], np.int32)
+        n = int(sizes.max()) if len(mats) else 0
+        slab = np.zeros((len(mats), n, n), np.int32)
+        for k, m in enumerate(mats):
+            slab[k, :m.shape[0], :m.shape[0]] = m
+        return slab, sizes, len(mats), n
+    if hasattr(costs, "data_ptr") and not isinstance(costs, np.ndarray):
+        _require_i32(costs, "costs")
+        cost = costs
+    else:
+        cost = _ffi.as_i32(costs)
+    if cost.ndim != 3 or cost.shape[1] != cost.shape[2]:
+        raise _ffi.TdError("costs must be a (B, n, n) batch of square models, got shape %s" % (tuple(cost.shape),))
+    batch, n = int(cost.shape[0]), int(cost.shape[1])
+    if ns is not None:
+        ns = ns if hasattr(ns, "data_ptr") and not isinstance(ns, np.ndarray) else _ffi.as_i32(ns).reshape(-1)
+        if int(ns.shape[0]) != batch:
+            raise _ffi.TdError("ns has %d entries for a batch of %d" % (int(ns.shape[0]), batch))
+    return cost, ns, batch, n
+
+
+def assign_batched(costs, ns=None, want_dual=False, want_prices=False):
+    """td_assign_batched: the optimum of B independent square models (n <= 1024) in one call (heuristic.py:20-40's 1000
+    scenarios, split.py:61-120's regions).  costs: see pack_batch; ns (int32[B]): model b is the top-left ns[b] x ns[b]
+    block of its slab.  Returns (row_to_col int32[B, n] (-1 beyond ns[b]), total int64[B][, dual_bound int64[B]]
+    [, col_price int64[B, n]])."""
+    lib = _ffi.lib()
+    cost, ns, batch, n = pack_batch(costs, ns)
+    r2c = np.empty((batch, n), np.int32)
+    total = np.empty(batch, np.int64)
+    dual = np.empty(batch, np.int64) if want_dual else None
+    price = np.empty((batch, n), np.int64) if want_prices else None
+    _ffi.check(lib.td_assign_batched(batch, n, _ffi.addr(ns), _ffi.addr(cost) if batch * n else None, _ffi.addr(r2c),
+                                     _ffi.addr(total), _ffi.addr(dual), _ffi.addr(price)))
+    out = (r2c, total)
+    if want_dual:
+        out += (dual,)
+    if want_prices:
+        out += (price,)
+    return out
+
+
+def LCM_batched(costs, ns=None, mask=BIG_COST, threshold=-1, stop_value_on=0, stop_value=0, stop_size=-1, sum_below=2**62):
+    """td_lcm_batched: td_lcm's greedy (same parameters as _lcm / td_lcm) on every model of a batch.  costs / ns: as
+    assign_batched.  Returns (total int64[B], rows int32[B, n], cols int32[B, n], last_min int32[B], n_pairs int32[B]);
+    model b's pairs are rows[b, :n_pairs[b]], cols[b, :n_pairs[b]] in pick order."""
+    lib = _ffi.lib()
+    cost, ns, batch, n = pack_batch(costs, ns)
+    rows = np.full((batch, n), -1, np.int32)
+    cols = np.full((batch, n), -1, np.int32)
+    k = np.empty(batch, np.int32)
+    total = np.empty(batch, np.int64)
+    lm = np.empty(batch, np.int32)
+    _ffi.check(lib.td_lcm_batched(batch, n, _ffi.addr(ns), _ffi.addr(cost) if batch * n else None, int(mask), int(threshold),
+                                  int(stop_value_on), int(stop_value), int(stop_size), int(sum_below), _ffi.addr(rows),
+                                  _ffi.addr(cols), _ffi.addr(k), _ffi.addr(total), _ffi.addr(lm)))
+    return total, rows, cols, lm, k
+
+
+def heuristic_gap(n=100, iters=1000, seed=None):
+    """heuristic.py:20-40 as two library calls: `iters` models of n x n costs U{1..39}, LCM with mask 100 and n picks
+    (every taken cell summed), then the optimum of each.  Returns (lcm_totals int64[iters], optima int64[iters],
+    mean gap in % = mean of 100 * (lcm - opt) / opt).  Raises when an optimum exceeds its LCM total (heuristic.py:40's
+    "!!!" detector: the solver failed)."""
+    rng = np.random.default_rng(seed)
+    c = rng.integers(1, 40, (iters, n, n)).astype(np.int32)
+    lcm_tot = LCM_batched(c, mask=100, threshold=-1)[0]
+    _, opt = assign_batched(c)
+    bad = np.nonzero(opt > lcm_tot)[0]
+    if bad.size:
+        raise _ffi.TdError("optimum above the LCM total in %d scenarios (first: %d: %d > %d)"
+                           % (bad.size, int(bad[0]), int(opt[bad[0]]), int(lcm_tot[bad[0]])))
+    return lcm_tot, opt, float(np.mean(100.0 * (lcm_tot - opt) / opt))
