@@ -28,6 +28,12 @@ workload : g1  perf.jl:5 instance family, cost ~ U{10..40}, N = 16384 (BASELINE 
 --dump-outputs DIR : after the timed steps, rank 0 writes what the headline path returned in its last timed step
            (row_to_col and total; for tick the whole td_tick result, for pool the merged pools) as DIR/<name>.npy.
 
+--full   : a plain run sets up, warms up, times the steps, dumps and prints; --full also measures what the headline
+           does not need, each after the timed steps: the per-kernel profile and the roofline (runs of their own), the
+           side workloads of a 1-GPU g1 run, the CPU baselines (the oracle's C port, the GLPK leg), for pool the CPU
+           port and the reference binary's timings, for the sharded leg the same instance on one GPU.
+           --no-extras and --no-cpu-baseline leave parts of it out.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -52,7 +58,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--n", type=int, default=16384)
     ap.add_argument("--workload", default="g1", choices=["g1", "g2", "g3", "tick", "pool"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel profile + roofline, side workloads, CPU "
+                         "baselines, pool CPU port and reference timings, the sharded leg's single-GPU reference")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the sharded leg even with one rank (exercises RCCL + the shard API on 1 GPU)")
     ap.add_argument("--sharded-n", type=int, default=65536,
@@ -66,7 +75,7 @@ def parse():
     ap.add_argument("--line-metric", default="on", choices=["on", "off"],
                     help="off: td_set_line_metric(0), the general solver alone (matters for g2, whose |a-b| matrix the "
                          "default path answers with the sorted matching + certificate pass)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the g2 / g3 / tick side measurements (1 GPU)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the g2 / g3 / tick side measurements (1 GPU)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline path returned in its last timed step as DIR/<name>.npy "
                          "(float64, at most 64 MB in all; bench_outputs/ is git-ignored); the inputs are seeded, so two builds can be "
@@ -346,11 +355,12 @@ def pool_workload(td, reps, cpu_seconds, outputs=None):
     slices (8 td_pool_n calls) + the merge (td_pool_merge), timed per (n, k); beside it the oracle's single-thread C
     restatement of the same 8 children + merge on this box's host core (bounded), and — where the file exists — the
     wall time of the REFERENCE binary oracle/_ref/pool_n measured in the build container
-    (tests/golden/pool_n/reference_timing.json, made by tests/golden/time_pool_reference.py)."""
+    (tests/golden/pool_n/reference_timing.json, made by tests/golden/time_pool_reference.py).
+    cpu_seconds=None: the GPU alone, neither the CPU port nor the reference binary's timings."""
     import torch
     from oracle import oracle
     ref_path = os.path.join(ROOT, "tests", "golden", "pool_n", "reference_timing.json")
-    ref = json.load(open(ref_path)) if os.path.exists(ref_path) else {}
+    ref = json.load(open(ref_path)) if cpu_seconds is not None and os.path.exists(ref_path) else {}
     out = {}
     cases = [(name, pool_demand(seed, n, mw, losses), ks) for name, seed, n, mw, losses, ks in POOL_CASES]
     for name, ks in POOL_FIXTURE_CASES:
@@ -378,6 +388,11 @@ def pool_workload(td, reps, cpu_seconds, outputs=None):
             if outputs is not None:
                 outputs["pools_%s_k%d" % (name, k)] = np.asarray(merged, np.int32).reshape(-1, 2 * k + 1)
                 outputs["happy_plans_%s_k%d" % (name, k)] = np.array([happy])
+            key = "%s_k%d" % (name, k)
+            out[key] = {"n": n, "k": k, "happy_plans": int(happy), "pools": int(len(merged)), "gpu_ms": ms,
+                        "requests_per_s": n / (ms * 1e-3)}
+            if cpu_seconds is None:
+                continue
             # CPU port: the same 8 slices + the same merge rule, one thread, bounded
             t_budget = time.perf_counter() + cpu_seconds
             creps, spent, cm = 0, 0.0, None
@@ -403,10 +418,8 @@ def pool_workload(td, reps, cpu_seconds, outputs=None):
                 creps += 1
                 if creps >= 8 or time.perf_counter() + spent / creps > t_budget:
                     break
-            key = "%s_k%d" % (name, k)
-            out[key] = {"n": n, "k": k, "happy_plans": int(happy), "pools": int(len(merged)), "gpu_ms": ms,
-                        "requests_per_s": n / (ms * 1e-3), "cpu_port_ms": 1e3 * spent / creps, "cpu_port_reps": creps,
-                        "pools_match_cpu_port": bool(np.array_equal(np.asarray(merged), np.asarray(cm, np.int32).reshape(-1, 2 * k + 1)))}
+            out[key].update({"cpu_port_ms": 1e3 * spent / creps, "cpu_port_reps": creps,
+                             "pools_match_cpu_port": bool(np.array_equal(np.asarray(merged), np.asarray(cm, np.int32).reshape(-1, 2 * k + 1)))})
             if key in ref:
                 out[key]["reference_binary_ms_build_container"] = ref[key]["wall_ms"]
                 out[key]["reference_binary_plans"] = ref[key].get("plans")
@@ -609,16 +622,18 @@ def main():
 
     outputs = {} if args.dump_outputs else None
     if args.workload == "pool":
-        res = pool_workload(td, args.steps, 0.0 if args.no_cpu_baseline else min(args.cpu_seconds, 4.0), outputs)
+        cpu_seconds = (0.0 if args.no_cpu_baseline else min(args.cpu_seconds, 4.0)) if args.full else None
+        res = pool_workload(td, args.steps, cpu_seconds, outputs)
         head = res["n600_k4"]
         line = {"metric": "pool requests/sec (pools of 4, 8 first-pick-up slices + merge)", "value": head["requests_per_s"],
                 "unit": "requests/s", "n_gpus": 1, "steps": args.steps, "warmup": 1, "ms_per_step": head["gpu_ms"],
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32 / f64 happiness test", "data": "synthetic",
                 "config": {"workload": "pool_n.c:101-242 fan-out of findpool.c:122-176: n = 600 requests, pools of 4 (all sizes in `pool`)"},
-                "pool": res,
-                "cpu_baseline": {"value": 600.0 / (head["cpu_port_ms"] * 1e-3), "unit": "requests/s", "cores": 1, "kind": "port",
-                                 "sample": "oracle_pool_n (oracle/td_oracle.c) over the same 8 slices + the merge rule, n = 600, k = 4, %d repetitions"
-                                           % head["cpu_port_reps"], "cpu_model": cpu_model()}}
+                "pool": res}
+        if args.full:
+            line["cpu_baseline"] = {"value": 600.0 / (head["cpu_port_ms"] * 1e-3), "unit": "requests/s", "cores": 1, "kind": "port",
+                                    "sample": "oracle_pool_n (oracle/td_oracle.c) over the same 8 slices + the merge rule, n = 600, k = 4, %d repetitions"
+                                              % head["cpu_port_reps"], "cpu_model": cpu_model()}
         if outputs is not None:
             line["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(line), flush=True)
@@ -651,7 +666,7 @@ def main():
         outputs.update(wl.outputs())
     stats = td.last_stats()
 
-    prof = kernel_profile(wl, ffi, reps=3) if rank == 0 else {}
+    prof = kernel_profile(wl, ffi, reps=3) if rank == 0 and args.full else {}
 
     def build_line(shard_res):
         n = args.n
@@ -693,8 +708,10 @@ def main():
                        "parallelism": "independent instance per GPU, no collective" if world > 1 else "single GPU"},
             "pairs_per_s": world * float(n) * n * args.steps / dt,
             "whole_step_algorithmic_GBps": 8.0 * n * n * world * args.steps / dt / 1e9,
-            "total_cost": int(total), "solver_stats": stats, "kernels": prof, "roofline": roof,
+            "total_cost": int(total), "solver_stats": stats,
         }
+        if args.full:
+            line.update({"kernels": prof, "roofline": roof})
         if args.line_metric == "off":
             line["config"]["line_metric_attempt"] = "off"
         if shard_res is not None:
@@ -744,7 +761,7 @@ def main():
                 if args.shard_builder == "both":
                     extra = sharded_leg(args.sharded_n, world, rank, torch, dist, ffi, max(1, args.steps), args.warmup, "cost")
                     shard_res["with_td_cost_build_rows"] = {k: extra[k] for k in ("ms_per_step", "assignments_per_s", "total_cost", "workload")}
-                if rank == 0:
+                if rank == 0 and args.full:
                     single_ref = single_gpu_reference(args.sharded_n, torch, ffi)
                     shard_res["single_gpu_ms_per_step"] = single_ref["ms_per_step"]
                     shard_res["speedup_vs_single_gpu"] = single_ref["ms_per_step"] / shard_res["ms_per_step"]
@@ -760,7 +777,7 @@ def main():
     if outputs is not None and line.get("scaling") == "strong" and shard_out:
         outputs = shard_out   # the headline is the row-sharded instance
     n = args.n
-    if world == 1 and not args.no_extras and args.workload == "g1":
+    if args.full and world == 1 and not args.no_extras and args.workload == "g1":
         # the other workloads of SURVEY 8d / BASELINE configs, measured in the same run (side fields)
         extras = {}
         del wl.cost
@@ -800,7 +817,7 @@ def main():
         except Exception as e:
             extras["pool_fanout_merge"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
         line["other_workloads"] = extras
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.workload, n, args.cpu_seconds)
         line["cpu_baseline"]["glpk"] = glpk_baseline()   # solver.py's own path, iff cvxopt imports here
         if args.workload == "tick":   # same instance (seed 1) through the C port: the totals must agree

@@ -8,7 +8,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 WL=${2:-g1}
-EXTRA="--workload $WL --no-extras"
+EXTRA="--workload $WL --no-extras --full"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline $EXTRA > $OUT/trace.log 2>&1
 if [ "${PMC:-1}" = "1" ]; then
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline $EXTRA > $OUT/pmc_fetch.log 2>&1
