@@ -180,6 +180,41 @@ TD_API int td_lcm_batched(int batch, int n, const int32_t *ns, const int32_t *co
                           int stop_value_on, int32_t stop_value, int stop_size, int64_t sum_below,
                           int32_t *rows, int32_t *cols, int32_t *n_pairs, int64_t *total, int32_t *last_min);
 
+/* ---- many dispatch models from their POSITIONS in one call (split.py's regions, zones / cities of one tick, sweeps) ----
+ * B ragged dispatch models: model b = cabs cab_to[cab_off[b] .. cab_off[b+1]), requests dem_from[dem_off[b] .. dem_off[b+1]);
+ * one shared distance table (S x S, or NULL = |a - b|).  n_s(b), n_d(b) are those counts and n(b) = max(n_s, n_d).
+ * Model b's cells follow td_cost_build's positional rule: dist[cab][dem] when threshold < 0 or it is below threshold, else
+ * fill; a stand outside [0, S) of a table, and rows / columns beyond n_s / n_d, are fill.  No cost matrix is ever written:
+ * one workgroup per model makes its cells from the positions (the table staged in LDS when it fits, else read through L2).
+ *   n: the caller's output stride; every n(b) <= n.  Offsets: int32[B+1], from 0, never decreasing.  Per-model outputs are
+ *   [B*n] with model b's entries at b*n; scalars [B].  Arrays may be host or device memory (outputs too); calls are
+ *   synchronous; batch == 0 is a no-op.
+ * td_build_assign_batched: model b = td_build_assign of its positions: row_to_col[b*n + i] (i < n(b); -1 beyond),
+ *   total[b] (dummy cells count fill), dual_bound[b] (may be NULL; recomputed from the cells: == total certifies the model).
+ *   TD_EINVAL: n > 1024.
+ * td_tick_batched: model b = td_tick on the same arguments: the LCM of Simulator.java:523-549 down to stop_size rows (stop on
+ *   fill; skipped when stop_size < 0 or >= n(b)), the shrink, the remainder's optimum.  lcm_rows / lcm_cols: the pairs in
+ *   the reference's pick order, n_pairs[b] of them; lcm_last_min[b] (fill when the LCM did not run); kept_cabs / kept_dems
+ *   (may be NULL): indices into model b's own lists, in order; n_rest[b] = the larger count; row_to_col (over the kept lists),
+ *   total, dual_bound (may be NULL): the remainder's optimum.  When the LCM ran and ended on fill (Simulator.java:188-189)
+ *   the model has no solve: row_to_col is -1, total and dual_bound are 0 (defined here, unlike td_tick).  stop_size < 0
+ *   equals td_build_assign_batched plus empty pair lists.  TD_EINVAL: n > 2048, or a model whose remainder has more than
+ *   1024 rows (min(n(b), stop_size) when the LCM runs, else n(b)).
+ * Both: TD_EINVAL for S <= 0 with a table, invalid offsets, null required outputs; TD_EINTERNAL if a model hit a
+ * defensive loop cap.  Two launches per tick call (LCM + shrink, then the solve), one per build call, whatever B is.
+ * When to use which: many models of up to a few hundred stands per side: these calls; a single large model,
+ * or 1300 x 900 ticks, where the per-model td_tick loop can win: see the measured crossover. */
+TD_API int td_build_assign_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab_to,
+                                   const int32_t *dem_off, const int32_t *dem_from, const int32_t *dist, int S,
+                                   int32_t fill, int32_t threshold, int32_t *row_to_col, int64_t *total,
+                                   int64_t *dual_bound);
+TD_API int td_tick_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab_to,
+                           const int32_t *dem_off, const int32_t *dem_from, const int32_t *dist, int S,
+                           int32_t fill, int32_t threshold, int stop_size,
+                           int32_t *lcm_rows, int32_t *lcm_cols, int32_t *n_pairs, int32_t *lcm_last_min,
+                           int32_t *kept_cabs, int32_t *kept_dems, int32_t *n_rest, int32_t *row_to_col,
+                           int64_t *total, int64_t *dual_bound);
+
 /* Row-sharded LCM: rank r owns cost rows [row0, row0 + nrows).  Per pick every shard
  * reports its smallest live cell {value, global row, column} (value = INT64_MAX: none), the caller
  * takes the minimum in the reference's order (value, row, column) over all shards — one all-gather of

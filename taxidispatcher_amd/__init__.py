@@ -5,11 +5,12 @@ kernels behind a C ABI (include/taxidispatcher_amd.h).  See DESIGN.md / INTEGRAT
 """
 from . import _ffi
 from ._ffi import TdError, init, shutdown
-from .dispatch import (BIG_COST, LCM, Solver, LCM_batched, LCM_heuristic, LCM_simulator, assign, assign_batched, build_assign, calculate_cost, calculate_cost_by_id,
+from .dispatch import (BIG_COST, LCM, Solver, LCM_batched, LCM_heuristic, LCM_simulator, assign, assign_batched, build_assign, build_assign_batched, calculate_cost, calculate_cost_by_id,
                        combined, cost_build, count_sum, expand_x, filter_out, find_pool, find_pool_n, heuristic_gap, last_stats, merge_pools,
-                       procedure_solve, set_line_metric, solve, solve_cost, tick)
+                       pack_ragged, procedure_solve, set_line_metric, solve, solve_cost, tick, tick_batched)
 
 __all__ = ["TdError", "init", "shutdown", "BIG_COST", "LCM", "Solver", "LCM_batched", "LCM_heuristic", "LCM_simulator", "assign",
-           "assign_batched", "build_assign",
+           "assign_batched", "build_assign", "build_assign_batched",
            "calculate_cost", "calculate_cost_by_id", "combined", "cost_build", "count_sum", "expand_x", "filter_out", "find_pool",
-           "find_pool_n", "heuristic_gap", "merge_pools", "last_stats", "procedure_solve", "set_line_metric", "solve", "solve_cost", "tick"]
+           "find_pool_n", "heuristic_gap", "merge_pools", "last_stats", "pack_ragged", "procedure_solve", "set_line_metric", "solve",
+           "solve_cost", "tick", "tick_batched"]

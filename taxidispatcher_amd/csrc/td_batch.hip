@@ -1,5 +1,7 @@
 // td_batch.hip — many small independent models in one call: optimal assignment (td_assign_batched) and the LCM greedy
-// (td_lcm_batched) of B square models of size <= 1024, one workgroup per model.  gfx950 only.
+// (td_lcm_batched) of B square models of size <= 1024, one workgroup per model; and the same solve and LCM for B ragged
+// dispatch models made from cab / request positions (td_build_assign_batched, td_tick_batched: cells through PosCells, no
+// cost matrix).  gfx950 only.
 //
 // Nothing here waits on another workgroup: a model's whole solve lives in one workgroup's LDS and registers (no
 // cross-workgroup atomics, no spins), and a grid-stride loop over the models covers batches larger than the grid.
@@ -35,7 +37,7 @@ constexpr uint64_t KEY_INF = ~0ull;
 constexpr int COL_BITS = 11;                             // column index of a packed Dijkstra key (n <= 1024 < 2^11)
 constexpr int64_t LABEL_LIM = (int64_t)1 << 52;          // labels at or above this cannot be packed
 constexpr size_t STAGE_LDS_MAX = 64 * 1024 - 1024;       // dynamic LDS a staged model may take
-enum { ERR_STEPS = 1, ERR_AUGMENT = 2, ERR_LABEL = 4 };
+enum { ERR_STEPS = 1, ERR_AUGMENT = 2, ERR_LABEL = 4, ERR_SIZE = 8 };
 
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t k)
 {
@@ -87,7 +89,259 @@ __device__ __forceinline__ uint64_t block_min_u64(uint64_t k, uint64_t *s_red, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// optimal assignment: T threads (64 or 256), CPT columns per thread (n <= T * CPT), STAGE: cells in LDS
+// cell sources: the solve and the LCM read a model's cells row by row through `C.row(i)(j)`
+// ---------------------------------------------------------------------------------------------------------------------
+// a slab model: its rows at `base` with stride n (global) or nb (STAGE: the LDS copy)
+template <bool STAGE>
+struct SlabCells {
+    const int32_t *base;
+    int nb, n;
+    struct Row {
+        const int32_t *p;
+        __device__ __forceinline__ int32_t operator()(int j) const { return p[j]; }
+    };
+    __device__ __forceinline__ Row row(int i) const { return Row{STAGE ? base + i * nb : base + (int64_t)i * n}; }
+};
+
+// a model made from positions (td_cost_build's positional rule, k_cost_build / CellSrc): cell (i, j) is the distance
+// dist[cab[i]][dem[j]] (|cab[i] - dem[j]| without a table) when threshold < 0 or it is below the threshold, else fill;
+// a row i >= ns, a column j >= nd or a stand outside [0, S) of a table is fill.  cab / dem are LDS copies; the table is
+// an LDS copy (LDS_DIST), a global array, or null.
+template <bool LDS_DIST>
+struct PosCells {
+    const int32_t *cab, *dem, *dist;
+    int ns, nd, S;
+    int32_t fill, thr;
+    struct Row {
+        const int32_t *drow, *dem;
+        int a, nd, S;
+        int32_t fill, thr;
+        bool ok;
+        __device__ __forceinline__ int32_t operator()(int j) const
+        {
+            if (!ok || j >= nd) return fill;
+            const int b = dem[j];
+            int x;
+            if (drow) {
+                if ((uint32_t)b >= (uint32_t)S) return fill;   // never index outside the table
+                x = drow[b];
+            } else {
+                x = a > b ? a - b : b - a;
+            }
+            return (thr < 0 || x < thr) ? x : fill;
+        }
+    };
+    __device__ __forceinline__ Row row(int i) const
+    {
+        const int a = i < ns ? cab[i] : 0;
+        const bool ok = i < ns && (!dist || (uint32_t)a < (uint32_t)S);
+        const int32_t *drow = dist && ok ? (LDS_DIST ? dist + a * S : dist + (int64_t)a * S) : nullptr;
+        return Row{drow, dem, a, nd, S, fill, thr, ok};
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// optimal assignment of one nb x nb model by one workgroup of T threads, CPT columns per thread (nb <= T * CPT).
+// s_x / s_y / s_pred / s_v: LDS arrays of at least nb entries.  Outputs: row b of r2c / price (stride n_out, -1 / 0 beyond
+// nb), total[b], dual[b].  The caller has put the model's cells in place before the call; they are read after its first
+// barrier.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int T, int CPT, class Cells>
+__device__ __forceinline__ void assign_model(const Cells &C, int nb, int b, int n_out, int64_t *s_v, int32_t *s_pred, int32_t *s_y,
+                                             int32_t *s_x, uint64_t *s_red, int64_t *s_sum, int &par, int32_t *__restrict__ r2c,
+                                             int64_t *__restrict__ total, int64_t *__restrict__ dual, int64_t *__restrict__ price,
+                                             int *__restrict__ err)
+{
+    constexpr int NW = T / 64;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int i = tid; i < nb; i += T) {
+        s_x[i] = INT_MAX;
+        s_y[i] = -1;
+    }
+    __syncthreads();
+    // 1. column reduction; each column's first minimum row is tight: the row takes the lowest such column
+    int64_t vr[CPT];
+#pragma unroll
+    for (int k = 0; k < CPT; k++) {
+        const int j = tid + k * T;
+        vr[k] = 0;
+        if (j < nb) {
+            int32_t m = C.row(0)(j);
+            int r = 0;
+            for (int i = 1; i < nb; i++) {
+                const int32_t cv = C.row(i)(j);
+                if (cv < m) {
+                    m = cv;
+                    r = i;
+                }
+            }
+            vr[k] = m;
+            s_v[j] = m;
+            atomicMin(&s_x[r], j);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < nb; i += T) {
+        const int j = s_x[i];
+        if (j == INT_MAX)
+            s_x[i] = -1;
+        else
+            s_y[j] = i;
+    }
+    __syncthreads();
+    // a free row takes its lowest free column of zero reduced cost (its u = 0 stays tight).  With heavy ties
+    // (U{1..39}) the claims above leave most rows free, all first minima sitting in the top rows; this pass
+    // matches nearly all of them, one row read and one reduction per free row, instead of a search each.
+    for (int f = 0; f < nb; f++) {
+        if (s_x[f] >= 0) continue;   // uniform: x changes only between barriers
+        const auto rf = C.row(f);
+        uint64_t key = KEY_INF;
+#pragma unroll
+        for (int k = 0; k < CPT; k++) {
+            const int j = tid + k * T;
+            if (j < nb && s_y[j] < 0 && (int64_t)rf(j) == vr[k]) key = key < (uint64_t)j ? key : (uint64_t)j;
+        }
+        key = block_min_u64<NW>(key, s_red, par);
+        if (key != KEY_INF) {
+            if (tid == 0) {
+                s_x[f] = (int)key;
+                s_y[key] = f;
+            }
+            __syncthreads();
+        }
+    }
+    // 2./3. one shortest augmenting path per free row
+    int bad = 0;
+    for (int f = 0; f < nb && !bad; f++) {
+        if (s_x[f] >= 0) continue;   // uniform: x changes only between barriers
+        int64_t d[CPT];
+        uint32_t vis = 0;   // bit k: column tid + k*T is visited (or does not exist)
+        const auto rf = C.row(f);
+#pragma unroll
+        for (int k = 0; k < CPT; k++) {
+            const int j = tid + k * T;
+            d[k] = 0;
+            if (j < nb) {
+                d[k] = (int64_t)rf(j) - vr[k];
+                s_pred[j] = f;
+            } else {
+                vis |= 1u << k;
+            }
+        }
+        int jstar = -1, steps = 0;
+        int64_t mu = 0;
+        for (;;) {
+            uint64_t key = KEY_INF;
+#pragma unroll
+            for (int k = 0; k < CPT; k++) {
+                if (!((vis >> k) & 1u)) {
+                    const int64_t dd = d[k] < LABEL_LIM ? d[k] : LABEL_LIM - 1;
+                    const uint64_t kk = ((uint64_t)dd << COL_BITS) | (uint64_t)(tid + k * T);
+                    key = kk < key ? kk : key;
+                }
+            }
+            key = block_min_u64<NW>(key, s_red, par);
+            if (key == KEY_INF || ++steps > nb) {   // a free column is always reachable within nb steps
+                bad = ERR_STEPS;
+                break;
+            }
+            mu = (int64_t)(key >> COL_BITS);
+            jstar = (int)(key & ((1u << COL_BITS) - 1));
+            if (mu >= LABEL_LIM - 1) {
+                bad = ERR_LABEL;
+                break;
+            }
+            if ((jstar & (T - 1)) == tid) vis |= 1u << (jstar / T);
+            const int i = s_y[jstar];
+            if (i < 0) break;   // a free column: augment
+            const auto ri_row = C.row(i);
+            const int64_t ri = (int64_t)ri_row(jstar) - s_v[jstar];
+#pragma unroll
+            for (int k = 0; k < CPT; k++) {
+                if (!((vis >> k) & 1u)) {
+                    const int j = tid + k * T;
+                    const int64_t nd = mu + ((int64_t)ri_row(j) - vr[k] - ri);
+                    if (nd < d[k]) {
+                        d[k] = nd;
+                        s_pred[j] = i;
+                    }
+                }
+            }
+        }
+        if (bad) break;
+        // potentials of the visited columns (the last one, label mu, does not move)
+#pragma unroll
+        for (int k = 0; k < CPT; k++) {
+            const int j = tid + k * T;
+            if (((vis >> k) & 1u) && j < nb) {
+                vr[k] += d[k] - mu;
+                s_v[j] = vr[k];
+            }
+        }
+        __syncthreads();   // pred of every column written
+        if (tid == 0) {
+            int j = jstar;
+            for (int g = 0;; g++) {
+                if (g > nb) {
+                    *err = ERR_AUGMENT;
+                    break;
+                }
+                const int i = s_pred[j];
+                s_y[j] = i;
+                const int nxt = s_x[i];
+                s_x[i] = j;
+                if (i == f) break;
+                j = nxt;
+            }
+        }
+        __syncthreads();
+    }
+    if (bad && tid == 0) *err = bad;   // any non-zero word fails the call: a plain store suffices
+    // 4. total and dual bound from the cells
+    int64_t tsum = 0, vsum = 0, rsum = 0;
+    for (int i = tid; i < nb; i += T) {
+        const int j = s_x[i];
+        tsum += j >= 0 ? (int64_t)C.row(i)(j) : 0;
+    }
+    if (dual) {
+#pragma unroll
+        for (int k = 0; k < CPT; k++)
+            if (tid + k * T < nb) vsum += vr[k];
+        for (int i = w; i < nb; i += NW) {
+            const auto ri = C.row(i);
+            int64_t m = INT64_MAX;
+            for (int j = lane; j < nb; j += 64) {
+                const int64_t r = (int64_t)ri(j) - s_v[j];
+                m = r < m ? r : m;
+            }
+            m = wave_min_i64(m);
+            if (lane == 0) rsum += m;
+        }
+    }
+    tsum = wave_sum_i64(tsum);
+    vsum = wave_sum_i64(vsum);
+    if (lane == 0) {
+        s_sum[w] = tsum;
+        s_sum[NW + w] = vsum + rsum;
+    }
+    for (int i = tid; i < n_out; i += T) {
+        r2c[(int64_t)b * n_out + i] = i < nb ? s_x[i] : -1;
+        if (price) price[(int64_t)b * n_out + i] = i < nb ? s_v[i] : 0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int64_t t = 0, dsum = 0;
+        for (int q = 0; q < NW; q++) {
+            t += s_sum[q];
+            dsum += s_sum[NW + q];
+        }
+        total[b] = t;
+        if (dual) dual[b] = dsum;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// optimal assignment of slab models: T threads (64 or 256), CPT columns per thread (n <= T * CPT), STAGE: cells in LDS
 // dynamic LDS: v int64[n] | pred int32[n] | y (column -> row) int32[n] | x (row -> column) int32[n] | cells int32[n*n]
 // ---------------------------------------------------------------------------------------------------------------------
 template <int T, int CPT, bool STAGE>
@@ -105,7 +359,7 @@ __global__ __launch_bounds__(T) void k_assign_batched(int batch, int n, const in
     int32_t *s_c = s_x + n;
     __shared__ uint64_t s_red[2 * NW];
     __shared__ int64_t s_sum[2 * NW];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     int par = 0;
     for (int b = blockIdx.x; b < batch; b += gridDim.x) {
         const int nb = ns ? ns[b] : n;
@@ -115,197 +369,156 @@ __global__ __launch_bounds__(T) void k_assign_batched(int batch, int n, const in
             for (int i = 0; i < nb; i++)
                 for (int j = tid; j < nb; j += T) s_c[i * nb + j] = base[(int64_t)i * n + j];
         }
-        for (int i = tid; i < nb; i += T) {
-            s_x[i] = INT_MAX;
-            s_y[i] = -1;
-        }
-        __syncthreads();
-#define CELL(i, j) (STAGE ? s_c[(i) * nb + (j)] : base[(int64_t)(i) * n + (j)])
-        // 1. column reduction; each column's first minimum row is tight: the row takes the lowest such column
-        int64_t vr[CPT];
-#pragma unroll
-        for (int k = 0; k < CPT; k++) {
-            const int j = tid + k * T;
-            vr[k] = 0;
-            if (j < nb) {
-                int32_t m = CELL(0, j);
-                int r = 0;
-                for (int i = 1; i < nb; i++) {
-                    const int32_t cv = CELL(i, j);
-                    if (cv < m) {
-                        m = cv;
-                        r = i;
-                    }
-                }
-                vr[k] = m;
-                s_v[j] = m;
-                atomicMin(&s_x[r], j);
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < nb; i += T) {
-            const int j = s_x[i];
-            if (j == INT_MAX)
-                s_x[i] = -1;
-            else
-                s_y[j] = i;
-        }
-        __syncthreads();
-        // a free row takes its lowest free column of zero reduced cost (its u = 0 stays tight).  With heavy ties
-        // (U{1..39}) the claims above leave most rows free, all first minima sitting in the top rows; this pass
-        // matches nearly all of them, one row read and one reduction per free row, instead of a search each.
-        for (int f = 0; f < nb; f++) {
-            if (s_x[f] >= 0) continue;   // uniform: x changes only between barriers
-            uint64_t key = KEY_INF;
-#pragma unroll
-            for (int k = 0; k < CPT; k++) {
-                const int j = tid + k * T;
-                if (j < nb && s_y[j] < 0 && (int64_t)CELL(f, j) == vr[k]) key = key < (uint64_t)j ? key : (uint64_t)j;
-            }
-            key = block_min_u64<NW>(key, s_red, par);
-            if (key != KEY_INF) {
-                if (tid == 0) {
-                    s_x[f] = (int)key;
-                    s_y[key] = f;
-                }
-                __syncthreads();
-            }
-        }
-        // 2./3. one shortest augmenting path per free row
-        int bad = 0;
-        for (int f = 0; f < nb && !bad; f++) {
-            if (s_x[f] >= 0) continue;   // uniform: x changes only between barriers
-            int64_t d[CPT];
-            uint32_t vis = 0;   // bit k: column tid + k*T is visited (or does not exist)
-#pragma unroll
-            for (int k = 0; k < CPT; k++) {
-                const int j = tid + k * T;
-                d[k] = 0;
-                if (j < nb) {
-                    d[k] = (int64_t)CELL(f, j) - vr[k];
-                    s_pred[j] = f;
-                } else {
-                    vis |= 1u << k;
-                }
-            }
-            int jstar = -1, steps = 0;
-            int64_t mu = 0;
-            for (;;) {
-                uint64_t key = KEY_INF;
-#pragma unroll
-                for (int k = 0; k < CPT; k++) {
-                    if (!((vis >> k) & 1u)) {
-                        const int64_t dd = d[k] < LABEL_LIM ? d[k] : LABEL_LIM - 1;
-                        const uint64_t kk = ((uint64_t)dd << COL_BITS) | (uint64_t)(tid + k * T);
-                        key = kk < key ? kk : key;
-                    }
-                }
-                key = block_min_u64<NW>(key, s_red, par);
-                if (key == KEY_INF || ++steps > nb) {   // a free column is always reachable within nb steps
-                    bad = ERR_STEPS;
-                    break;
-                }
-                mu = (int64_t)(key >> COL_BITS);
-                jstar = (int)(key & ((1u << COL_BITS) - 1));
-                if (mu >= LABEL_LIM - 1) {
-                    bad = ERR_LABEL;
-                    break;
-                }
-                if ((jstar & (T - 1)) == tid) vis |= 1u << (jstar / T);
-                const int i = s_y[jstar];
-                if (i < 0) break;   // a free column: augment
-                const int64_t ri = (int64_t)CELL(i, jstar) - s_v[jstar];
-#pragma unroll
-                for (int k = 0; k < CPT; k++) {
-                    if (!((vis >> k) & 1u)) {
-                        const int j = tid + k * T;
-                        const int64_t nd = mu + ((int64_t)CELL(i, j) - vr[k] - ri);
-                        if (nd < d[k]) {
-                            d[k] = nd;
-                            s_pred[j] = i;
-                        }
-                    }
-                }
-            }
-            if (bad) break;
-            // potentials of the visited columns (the last one, label mu, does not move)
-#pragma unroll
-            for (int k = 0; k < CPT; k++) {
-                const int j = tid + k * T;
-                if (((vis >> k) & 1u) && j < nb) {
-                    vr[k] += d[k] - mu;
-                    s_v[j] = vr[k];
-                }
-            }
-            __syncthreads();   // pred of every column written
-            if (tid == 0) {
-                int j = jstar;
-                for (int g = 0;; g++) {
-                    if (g > nb) {
-                        *err = ERR_AUGMENT;
-                        break;
-                    }
-                    const int i = s_pred[j];
-                    s_y[j] = i;
-                    const int nxt = s_x[i];
-                    s_x[i] = j;
-                    if (i == f) break;
-                    j = nxt;
-                }
-            }
-            __syncthreads();
-        }
-        if (bad && tid == 0) *err = bad;   // any non-zero word fails the call: a plain store suffices
-        // 4. total and dual bound from the cells
-        int64_t tsum = 0, vsum = 0, rsum = 0;
-        for (int i = tid; i < nb; i += T) {
-            const int j = s_x[i];
-            tsum += j >= 0 ? (int64_t)CELL(i, j) : 0;
-        }
-        if (dual) {
-#pragma unroll
-            for (int k = 0; k < CPT; k++)
-                if (tid + k * T < nb) vsum += vr[k];
-            for (int i = w; i < nb; i += NW) {
-                int64_t m = INT64_MAX;
-                for (int j = lane; j < nb; j += 64) {
-                    const int64_t r = (int64_t)CELL(i, j) - s_v[j];
-                    m = r < m ? r : m;
-                }
-                m = wave_min_i64(m);
-                if (lane == 0) rsum += m;
-            }
-        }
-#undef CELL
-        tsum = wave_sum_i64(tsum);
-        vsum = wave_sum_i64(vsum);
-        if (lane == 0) {
-            s_sum[w] = tsum;
-            s_sum[NW + w] = vsum + rsum;
-        }
-        for (int i = tid; i < n; i += T) {
-            r2c[(int64_t)b * n + i] = i < nb ? s_x[i] : -1;
-            if (price) price[(int64_t)b * n + i] = i < nb ? s_v[i] : 0;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int64_t t = 0, dsum = 0;
-            for (int q = 0; q < NW; q++) {
-                t += s_sum[q];
-                dsum += s_sum[NW + q];
-            }
-            total[b] = t;
-            if (dual) dual[b] = dsum;
-        }
+        const SlabCells<STAGE> C{STAGE ? s_c : base, nb, n};
+        assign_model<T, CPT>(C, nb, b, n, s_v, s_pred, s_y, s_x, s_red, s_sum, par, r2c, total, dual, price, err);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// LCM: dynamic LDS: row cache uint64[n] | rescan list int32[n] | column mask uint32[(n + 31) / 32]
+// optimal assignment of position models (td_build_assign_batched, td_tick_batched's remainder): model b's cabs are
+// cab[cab_off[b] ...], its requests dem[dem_off[b] ...]; the counts are cab_off[b + 1] - cab_off[b] (cnt == null) or
+// cnt[2b] / cnt[2b + 1] (the tick's kept lists, 0 / 0 = no solve).  nl >= every max(count) bounds the LDS arrays.
+// dynamic LDS: v int64[nl] | pred, y, x int32[nl] | cab, dem int32[nl] | table int32[S*S] (LDS_DIST)
+// ---------------------------------------------------------------------------------------------------------------------
+template <int T, int CPT, bool LDS_DIST>
+__global__ __launch_bounds__(T) void k_assign_pos_batched(int batch, int n_out, int nl, const int32_t *__restrict__ cab_off,
+                                                          const int32_t *__restrict__ cab, const int32_t *__restrict__ dem_off,
+                                                          const int32_t *__restrict__ dem, const int32_t *__restrict__ cnt,
+                                                          const int32_t *__restrict__ dist, int S, int32_t fill, int32_t thr,
+                                                          int32_t *__restrict__ r2c, int64_t *__restrict__ total,
+                                                          int64_t *__restrict__ dual, int *__restrict__ err)
+{
+    constexpr int NW = T / 64;
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    int64_t *s_v = reinterpret_cast<int64_t *>(s_dyn);
+    int32_t *s_pred = reinterpret_cast<int32_t *>(s_v + nl);
+    int32_t *s_y = s_pred + nl;
+    int32_t *s_x = s_y + nl;
+    int32_t *s_cab = s_x + nl;
+    int32_t *s_dem = s_cab + nl;
+    int32_t *s_dist = s_dem + nl;
+    __shared__ uint64_t s_red[2 * NW];
+    __shared__ int64_t s_sum[2 * NW];
+    const int tid = threadIdx.x;
+    int par = 0;
+    if constexpr (LDS_DIST)
+        for (int q = tid; q < S * S; q += T) s_dist[q] = dist[q];   // read after the first model's barrier
+    for (int b = blockIdx.x; b < batch; b += gridDim.x) {
+        const int c0 = cab_off[b], d0 = dem_off[b];
+        const int ns = cnt ? cnt[2 * b] : cab_off[b + 1] - c0;
+        const int nd = cnt ? cnt[2 * b + 1] : dem_off[b + 1] - d0;
+        const int nb = ns > nd ? ns : nd;
+        if (nb > nl) {   // validated on the host; never index LDS past nl
+            if (tid == 0) *err = ERR_SIZE;
+            continue;
+        }
+        __syncthreads();   // the previous model's LDS is no longer read
+        for (int i = tid; i < ns; i += T) s_cab[i] = cab[c0 + i];
+        for (int j = tid; j < nd; j += T) s_dem[j] = dem[d0 + j];
+        const PosCells<LDS_DIST> C{s_cab, s_dem, LDS_DIST ? s_dist : dist, ns, nd, S, fill, thr};
+        assign_model<T, CPT>(C, nb, b, n_out, s_v, s_pred, s_y, s_x, s_red, s_sum, par, r2c, total, dual, nullptr, err);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// LCM of one model by one workgroup: rows [0, nr) and columns [0, nc) are scanned, `size` counts down from nsize (the
+// model's n).  Every cell outside nr x nc must be one that is never a candidate (>= cand_limit): true of a slab (nr = nc =
+// nsize) and of the tick's padded rows and columns (fill, cand_limit = fill).  s_rb uint64[nr], s_list int32[nr],
+// s_cm uint32[(nc + 31) / 32]; s_rm (may be null) uint32[(nr + 31) / 32] gets the taken rows.  Pairs go to rows / cols.
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t lcm_bias(int32_t v) { return (uint32_t)v ^ 0x80000000u; }
 __device__ __forceinline__ int32_t lcm_unbias(uint64_t key) { return (int32_t)((uint32_t)(key >> 32) ^ 0x80000000u); }
 
+template <int T, class Cells>
+__device__ __forceinline__ void lcm_model(const Cells &C, int nr, int nc, int nsize, int64_t cand_limit, int32_t mask,
+                                          int32_t threshold, int stop_value_on, int32_t stop_value, int stop_size, int64_t sum_below,
+                                          uint64_t *s_rb, int32_t *s_list, uint32_t *s_cm, uint32_t *s_rm, uint64_t *s_red, int *s_cnt,
+                                          int &par, int32_t *__restrict__ rows, int32_t *__restrict__ cols, int &np_out,
+                                          int32_t &lm_out, int64_t &tot_out)
+{
+    constexpr int NW = T / 64;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int q = tid; q < (nc + 31) / 32; q += T) s_cm[q] = 0u;
+    if (s_rm)
+        for (int q = tid; q < (nr + 31) / 32; q += T) s_rm[q] = 0u;
+    for (int i = tid; i < nr; i += T) s_list[i] = i;
+    if (tid == 0) *s_cnt = nr;
+    __syncthreads();
+    int np = 0, size = nsize;
+    int32_t lm = stop_value;
+    int64_t tot = 0;
+    for (int it = 0; it <= nsize; it++) {
+        // rows in the list: first minimum among the live columns below cand_limit (one wave per row)
+        const int cnt = *s_cnt;
+        for (int q = w; q < cnt; q += NW) {
+            const int r = s_list[q];
+            const auto rr = C.row(r);
+            uint64_t key = KEY_INF;
+            for (int j = lane; j < nc; j += 64) {
+                if (!((s_cm[j >> 5] >> (j & 31)) & 1u)) {
+                    const int32_t v = rr(j);
+                    if ((int64_t)v < cand_limit) {
+                        const uint64_t kk = ((uint64_t)lcm_bias(v) << 32) | (uint32_t)j;
+                        key = kk < key ? kk : key;
+                    }
+                }
+            }
+            key = wave_min_u64(key);
+            if (lane == 0) s_rb[r] = key;
+        }
+        __syncthreads();
+        if (it == nsize) break;   // every row taken
+        // the pick: (value, row) minimum of the row caches
+        uint64_t key = KEY_INF;
+        for (int i = tid; i < nr; i += T) {
+            const uint64_t k = s_rb[i];
+            if (k != KEY_INF) {
+                const uint64_t kk = (k & 0xFFFFFFFF00000000ull) | (uint32_t)i;
+                key = kk < key ? kk : key;
+            }
+        }
+        key = block_min_u64<NW>(key, s_red, par);
+        if (key == KEY_INF) {   // nothing left to look at
+            lm = stop_value_on ? stop_value : mask;
+            break;
+        }
+        const int r = (int)(uint32_t)key;
+        const int32_t v = lcm_unbias(key);
+        const int c = (int)(uint32_t)s_rb[r];
+        lm = v;
+        if (threshold >= 0 && v > threshold) break;   // greedy_opt.py:68-69
+        if (stop_value_on && v >= stop_value) break;   // Simulator.java:538
+        if (v >= mask) break;                          // only masked-valued cells remain
+        if (tid == 0) {
+            rows[np] = r;
+            cols[np] = c;
+        }
+        np++;
+        if ((int64_t)v < sum_below) tot += v;
+        size--;
+        __syncthreads();   // everyone has read s_rb[r]
+        if (tid == 0) {
+            s_rb[r] = KEY_INF;
+            s_cm[c >> 5] |= 1u << (c & 31);
+            if (s_rm) s_rm[r >> 5] |= 1u << (r & 31);
+            *s_cnt = 0;
+        }
+        __syncthreads();
+        if (stop_size >= 0 && size == stop_size) break;   // Simulator.java:544-545
+        for (int i = tid; i < nr; i += T) {
+            const uint64_t k = s_rb[i];
+            if (k != KEY_INF && (int)(uint32_t)k == c) s_list[atomicAdd(s_cnt, 1)] = i;
+        }
+        __syncthreads();
+    }
+    np_out = np;
+    lm_out = lm;
+    tot_out = tot;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// LCM of slab models: dynamic LDS: row cache uint64[n] | rescan list int32[n] | column mask uint32[(n + 31) / 32]
+// ---------------------------------------------------------------------------------------------------------------------
 template <int T>
 __global__ __launch_bounds__(T) void k_lcm_batched(int batch, int n, const int32_t *__restrict__ ns, const int32_t *__restrict__ cost,
                                                    int64_t cand_limit, int32_t mask, int32_t threshold, int stop_value_on,
@@ -320,85 +533,120 @@ __global__ __launch_bounds__(T) void k_lcm_batched(int batch, int n, const int32
     uint32_t *s_cm = reinterpret_cast<uint32_t *>(s_list + n);
     __shared__ uint64_t s_red[2 * NW];
     __shared__ int s_cnt;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     int par = 0;
     for (int b = blockIdx.x; b < batch; b += gridDim.x) {
         const int nb = ns ? ns[b] : n;
-        const int32_t *base = cost + (int64_t)b * n * n;
         __syncthreads();
-        for (int q = tid; q < (nb + 31) / 32; q += T) s_cm[q] = 0u;
-        for (int i = tid; i < nb; i += T) s_list[i] = i;
-        if (tid == 0) s_cnt = nb;
-        __syncthreads();
-        int np = 0, size = nb;
-        int32_t lm = stop_value;
-        int64_t tot = 0;
-        for (int it = 0; it <= nb; it++) {
-            // rows in the list: first minimum among the live columns below cand_limit (one wave per row)
-            const int cnt = s_cnt;
-            for (int q = w; q < cnt; q += NW) {
-                const int r = s_list[q];
-                uint64_t key = KEY_INF;
-                for (int j = lane; j < nb; j += 64) {
-                    if (!((s_cm[j >> 5] >> (j & 31)) & 1u)) {
-                        const int32_t v = base[(int64_t)r * n + j];
-                        if ((int64_t)v < cand_limit) {
-                            const uint64_t kk = ((uint64_t)lcm_bias(v) << 32) | (uint32_t)j;
-                            key = kk < key ? kk : key;
-                        }
-                    }
-                }
-                key = wave_min_u64(key);
-                if (lane == 0) s_rb[r] = key;
-            }
-            __syncthreads();
-            if (it == nb) break;   // every row taken
-            // the pick: (value, row) minimum of the row caches
-            uint64_t key = KEY_INF;
-            for (int i = tid; i < nb; i += T) {
-                const uint64_t k = s_rb[i];
-                if (k != KEY_INF) {
-                    const uint64_t kk = (k & 0xFFFFFFFF00000000ull) | (uint32_t)i;
-                    key = kk < key ? kk : key;
-                }
-            }
-            key = block_min_u64<NW>(key, s_red, par);
-            if (key == KEY_INF) {   // nothing left to look at
-                lm = stop_value_on ? stop_value : mask;
-                break;
-            }
-            const int r = (int)(uint32_t)key;
-            const int32_t v = lcm_unbias(key);
-            const int c = (int)(uint32_t)s_rb[r];
-            lm = v;
-            if (threshold >= 0 && v > threshold) break;   // greedy_opt.py:68-69
-            if (stop_value_on && v >= stop_value) break;   // Simulator.java:538
-            if (v >= mask) break;                          // only masked-valued cells remain
-            if (tid == 0) {
-                rows[(int64_t)b * n + np] = r;
-                cols[(int64_t)b * n + np] = c;
-            }
-            np++;
-            if ((int64_t)v < sum_below) tot += v;
-            size--;
-            __syncthreads();   // everyone has read s_rb[r]
-            if (tid == 0) {
-                s_rb[r] = KEY_INF;
-                s_cm[c >> 5] |= 1u << (c & 31);
-                s_cnt = 0;
-            }
-            __syncthreads();
-            if (stop_size >= 0 && size == stop_size) break;   // Simulator.java:544-545
-            for (int i = tid; i < nb; i += T) {
-                const uint64_t k = s_rb[i];
-                if (k != KEY_INF && (int)(uint32_t)k == c) s_list[atomicAdd(&s_cnt, 1)] = i;
-            }
-            __syncthreads();
-        }
+        const SlabCells<false> C{cost + (int64_t)b * n * n, nb, n};
+        int np;
+        int32_t lm;
+        int64_t tot;
+        lcm_model<T>(C, nb, nb, nb, cand_limit, mask, threshold, stop_value_on, stop_value, stop_size, sum_below, s_rb, s_list, s_cm,
+                     nullptr, s_red, &s_cnt, par, rows + (int64_t)b * n, cols + (int64_t)b * n, np, lm, tot);
         if (tid == 0) {
             n_pairs[b] = np;
             total[b] = tot;
             last_min[b] = lm;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// td_tick_batched, first launch: per model the tick's LCM (Simulator.java:523-549: cells >= fill are never candidates,
+// stop on fill or when stop_size rows are left; skipped when stop_size < 0 or >= n(b)) over the real n_s x n_d cells,
+// then the shrink: the cabs / requests in no pair, in order (k_tick_shrink's ordered compaction, per model).  Their
+// indices go to kept_c / kept_d (may be null), their positions to cab2 / dem2 at the model's own offsets, their counts to
+// cnt[2b] / cnt[2b + 1] for the solve (0 / 0 when the LCM ended on fill: no solve, Simulator.java:188-189).
+// dynamic LDS (nl = the largest n(b)): row cache uint64[nl] | rescan list, cab, dem int32[nl] | column mask, row mask
+// uint32[(nl + 31) / 32] each | table int32[S*S] (LDS_DIST)
+// ---------------------------------------------------------------------------------------------------------------------
+template <int T, bool LDS_DIST>
+__global__ __launch_bounds__(T) void k_tick_lcm_batched(int batch, int n_out, int nl, const int32_t *__restrict__ cab_off,
+                                                        const int32_t *__restrict__ cab, const int32_t *__restrict__ dem_off,
+                                                        const int32_t *__restrict__ dem, const int32_t *__restrict__ dist, int S,
+                                                        int32_t fill, int32_t thr, int stop_size, int32_t *__restrict__ rows,
+                                                        int32_t *__restrict__ cols, int32_t *__restrict__ n_pairs,
+                                                        int32_t *__restrict__ last_min, int32_t *__restrict__ kept_c,
+                                                        int32_t *__restrict__ kept_d, int32_t *__restrict__ n_rest,
+                                                        int32_t *__restrict__ cab2, int32_t *__restrict__ dem2, int32_t *__restrict__ cnt)
+{
+    constexpr int NW = T / 64;
+    const int WL = (nl + 31) / 32;
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    uint64_t *s_rb = reinterpret_cast<uint64_t *>(s_dyn);
+    int32_t *s_list = reinterpret_cast<int32_t *>(s_rb + nl);
+    int32_t *s_cab = s_list + nl;
+    int32_t *s_dem = s_cab + nl;
+    uint32_t *s_cm = reinterpret_cast<uint32_t *>(s_dem + nl);
+    uint32_t *s_rm = s_cm + WL;
+    int32_t *s_dist = reinterpret_cast<int32_t *>(s_rm + WL);
+    __shared__ uint64_t s_red[2 * NW];
+    __shared__ int s_cnt, s_kept[2];
+    __shared__ int s_w[NW];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int par = 0;
+    if constexpr (LDS_DIST)
+        for (int q = tid; q < S * S; q += T) s_dist[q] = dist[q];   // read after the first model's barrier
+    for (int b = blockIdx.x; b < batch; b += gridDim.x) {
+        const int c0 = cab_off[b], d0 = dem_off[b];
+        const int ns = cab_off[b + 1] - c0, nd = dem_off[b + 1] - d0, nb = ns > nd ? ns : nd;
+        __syncthreads();   // the previous model's LDS is no longer read
+        for (int i = tid; i < ns; i += T) s_cab[i] = cab[c0 + i];
+        for (int j = tid; j < nd; j += T) s_dem[j] = dem[d0 + j];
+        const bool lcm_runs = stop_size >= 0 && stop_size < nb;
+        int np = 0;
+        int32_t lm = fill;
+        if (lcm_runs) {
+            const PosCells<LDS_DIST> C{s_cab, s_dem, LDS_DIST ? s_dist : dist, ns, nd, S, fill, thr};
+            int64_t tot;
+            lcm_model<T>(C, ns, nd, nb, (int64_t)fill, fill, -1, 1, fill, stop_size, (int64_t)fill, s_rb, s_list, s_cm, s_rm, s_red,
+                         &s_cnt, par, rows + (int64_t)b * n_out, cols + (int64_t)b * n_out, np, lm, tot);
+        } else {
+            for (int q = tid; q < WL; q += T) {
+                s_cm[q] = 0u;
+                s_rm[q] = 0u;
+            }
+        }
+        __syncthreads();   // the masks are final
+        // the shrink: per side a contiguous slice per thread, a wave scan of the slice counts, the waves' sums through LDS
+        for (int side = 0; side < 2; side++) {
+            const int m = side ? nd : ns;
+            const uint32_t *bits = side ? s_cm : s_rm;
+            const int32_t *pos = side ? s_dem : s_cab;
+            int32_t *pos2 = (side ? dem2 + d0 : cab2 + c0);
+            int32_t *keep = side ? kept_d : kept_c;
+            const int per = (m + T - 1) / T, lo = min(m, tid * per), hi = min(m, lo + per);
+            int cnt_t = 0;
+            for (int i = lo; i < hi; i++) cnt_t += ((bits[i >> 5] >> (i & 31)) & 1u) ? 0 : 1;
+            int incl = cnt_t;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int v = __shfl_up(incl, o);
+                if (lane >= o) incl += v;
+            }
+            if (lane == 63) s_w[w] = incl;
+            __syncthreads();
+            int base = 0;
+            for (int q = 0; q < w; q++) base += s_w[q];
+            int at = base + incl - cnt_t;
+            for (int i = lo; i < hi; i++)
+                if (!((bits[i >> 5] >> (i & 31)) & 1u)) {
+                    if (keep) keep[(int64_t)b * n_out + at] = i;
+                    pos2[at] = pos[i];
+                    at++;
+                }
+            if (tid == T - 1) s_kept[side] = base + incl;
+            __syncthreads();   // s_w is reused by the next side
+        }
+        if (tid == 0) {
+            const int kc = s_kept[0], kd = s_kept[1];
+            const bool solve = !(lcm_runs && lm == fill);   // Simulator.java:188-189
+            n_pairs[b] = np;
+            last_min[b] = lm;
+            n_rest[b] = kc > kd ? kc : kd;
+            cnt[2 * b] = solve ? kc : 0;
+            cnt[2 * b + 1] = solve ? kd : 0;
         }
     }
 }
@@ -484,7 +732,7 @@ int outputs_finish(const char *fn, const Out *o, int k, size_t err_off)
     const int e = *(int *)c.pinned;
     if (e)
         return fail(TD_EINTERNAL, "%s: a model hit a defensive loop cap (error word 0x%x: 1 search steps, 2 augmenting path, "
-                    "4 label range)", fn, e);
+                    "4 label range, 8 model size)", fn, e);
     return TD_OK;
 }
 
@@ -494,6 +742,146 @@ void launch_assign(int batch, int n, const int32_t *d_ns, const int32_t *d_cost,
 {
     const int grid = std::min(batch, 1 << 20);
     k_assign_batched<T, CPT, STAGE><<<grid, T, shm, ctx().stream>>>(batch, n, d_ns, d_cost, r2c, tot, dual, price, err);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// position models (td_build_assign_batched / td_tick_batched)
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int TICK_NMAX = 2048;                 // largest model of td_tick_batched (Simulator.java's 1300 x 900 tick)
+Buf g_in[5];                                    // device copies of host inputs: cab_off, dem_off, cab_to, dem_from, dist
+Buf g_ws;                                       // td_tick_batched: kept positions (ragged, at the models' offsets) + counts
+std::vector<int32_t> g_off[2];                  // host copies of the offsets (validated here)
+
+// dynamic LDS one workgroup may take (gfx950: 160 KiB per CU, all of it for one workgroup), less the static arrays
+size_t lds_budget()
+{
+    static size_t cap = 0;
+    if (!cap) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx().device) != hipSuccess || v <= 0) {
+            (void)hipGetLastError();
+            v = 64 * 1024;
+        }
+        cap = std::min<size_t>((size_t)v, 160 * 1024) - 1024;
+    }
+    return cap;
+}
+
+struct PosIn {
+    const int32_t *cab_off, *dem_off, *cab, *dem, *dist;   // device pointers
+    int nmax;                                              // the largest max(n_s, n_d)
+};
+
+// validates and uploads the arguments shared by both entry points; model b's n(b) must not exceed n (<= nlim)
+int pos_args(const char *fn, int batch, int n, int nlim, const int32_t *cab_off, const int32_t *cab_to, const int32_t *dem_off,
+             const int32_t *dem_from, const int32_t *dist, int S, PosIn *in)
+{
+    Ctx &c = ctx();
+    *in = PosIn{};
+    if (batch < 0) return fail(TD_EINVAL, "%s: batch = %d < 0", fn, batch);
+    if (n < 0) return fail(TD_EINVAL, "%s: n = %d < 0", fn, n);
+    if (n > nlim)
+        return fail(TD_EINVAL, "%s: n = %d > %d; a model this large is one td_build_assign / td_tick call", fn, n, nlim);
+    if (dist && (S <= 0 || S > 46340)) return fail(TD_EINVAL, "%s: S = %d outside [1, 46340] with a distance table", fn, S);
+    if (batch == 0) return TD_OK;
+    if (!cab_off || !dem_off) return fail(TD_EINVAL, "%s: null offsets", fn);
+    const int32_t *offs[2] = {cab_off, dem_off};
+    for (int s = 0; s < 2; s++) {
+        std::vector<int32_t> &h = g_off[s];
+        h.resize((size_t)batch + 1);
+        if (is_device_ptr(offs[s])) {
+            TD_HIP(hipMemcpyAsync(h.data(), offs[s], sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, c.stream));
+            TD_HIP(hipStreamSynchronize(c.stream));
+        } else {
+            memcpy(h.data(), offs[s], sizeof(int32_t) * h.size());
+        }
+        const char *what = s ? "dem_off" : "cab_off";
+        if (h[0] != 0) return fail(TD_EINVAL, "%s: %s[0] = %d, not 0", fn, what, h[0]);
+        for (int b = 0; b < batch; b++)
+            if (h[b + 1] < h[b]) return fail(TD_EINVAL, "%s: %s decreases at model %d (%d -> %d)", fn, what, b, h[b], h[b + 1]);
+    }
+    int nmax = 0;
+    for (int b = 0; b < batch; b++) {
+        const int ns = g_off[0][b + 1] - g_off[0][b], nd = g_off[1][b + 1] - g_off[1][b], nb = std::max(ns, nd);
+        if (nb > n) return fail(TD_EINVAL, "%s: model %d has %d cabs and %d requests, more than n = %d", fn, b, ns, nd, n);
+        nmax = std::max(nmax, nb);
+    }
+    const size_t nc = (size_t)g_off[0][batch], nd = (size_t)g_off[1][batch];
+    if ((nc && !cab_to) || (nd && !dem_from)) return fail(TD_EINVAL, "%s: null position array", fn);
+    const void *p;
+    int rc;
+    const int32_t *srcs[5] = {is_device_ptr(cab_off) ? cab_off : g_off[0].data(), is_device_ptr(dem_off) ? dem_off : g_off[1].data(),
+                              cab_to, dem_from, dist};
+    const size_t bytes[5] = {sizeof(int32_t) * ((size_t)batch + 1), sizeof(int32_t) * ((size_t)batch + 1), sizeof(int32_t) * nc,
+                             sizeof(int32_t) * nd, dist ? sizeof(int32_t) * (size_t)S * S : 0};
+    const int32_t **dsts[5] = {&in->cab_off, &in->dem_off, &in->cab, &in->dem, &in->dist};
+    for (int k = 0; k < 5; k++) {
+        if (!bytes[k]) continue;
+        if ((rc = to_device(srcs[k], bytes[k], g_in[k], &p))) return rc;
+        *dsts[k] = (const int32_t *)p;
+    }
+    in->nmax = nmax;
+    return TD_OK;
+}
+
+template <class K>
+void lds_allow(K kernel, size_t shm)
+{
+    if (shm > 64 * 1024) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+}
+
+// the optimum of every position model: nl >= every model's max(count); cnt: see k_assign_pos_batched
+template <int T, int CPT>
+void launch_pos_assign_t(int batch, int n_out, int nl, const PosIn &in, const int32_t *cab, const int32_t *dem, const int32_t *cnt, int S,
+                         int32_t fill, int32_t thr, int32_t *r2c, int64_t *tot, int64_t *dual, int *err)
+{
+    const size_t shm = (size_t)nl * (sizeof(int64_t) + 5 * sizeof(int32_t));
+    const size_t tab = in.dist ? sizeof(int32_t) * (size_t)S * S : 0;
+    const int grid = std::min(batch, 1 << 20);
+    hipStream_t st = ctx().stream;
+    if (in.dist && shm + tab <= lds_budget()) {
+        lds_allow(k_assign_pos_batched<T, CPT, true>, shm + tab);
+        k_assign_pos_batched<T, CPT, true><<<grid, T, shm + tab, st>>>(batch, n_out, nl, in.cab_off, cab, in.dem_off, dem, cnt, in.dist, S,
+                                                                       fill, thr, r2c, tot, dual, err);
+    } else {
+        k_assign_pos_batched<T, CPT, false><<<grid, T, shm, st>>>(batch, n_out, nl, in.cab_off, cab, in.dem_off, dem, cnt, in.dist, S,
+                                                                  fill, thr, r2c, tot, dual, err);
+    }
+}
+
+void launch_pos_assign(int batch, int n_out, int nl, const PosIn &in, const int32_t *cab, const int32_t *dem, const int32_t *cnt, int S,
+                       int32_t fill, int32_t thr, int32_t *r2c, int64_t *tot, int64_t *dual, int *err)
+{
+    if (nl <= 64)
+        launch_pos_assign_t<64, 1>(batch, n_out, nl, in, cab, dem, cnt, S, fill, thr, r2c, tot, dual, err);
+    else if (nl <= 128)
+        launch_pos_assign_t<64, 2>(batch, n_out, nl, in, cab, dem, cnt, S, fill, thr, r2c, tot, dual, err);
+    else if (nl <= 256)
+        launch_pos_assign_t<256, 1>(batch, n_out, nl, in, cab, dem, cnt, S, fill, thr, r2c, tot, dual, err);
+    else if (nl <= 512)
+        launch_pos_assign_t<256, 2>(batch, n_out, nl, in, cab, dem, cnt, S, fill, thr, r2c, tot, dual, err);
+    else
+        launch_pos_assign_t<256, 4>(batch, n_out, nl, in, cab, dem, cnt, S, fill, thr, r2c, tot, dual, err);
+}
+
+template <int T>
+void launch_tick_lcm_t(int batch, int n_out, int nl, const PosIn &in, int S, int32_t fill, int32_t thr, int stop_size, void *const *o,
+                       int32_t *cab2, int32_t *dem2, int32_t *cnt)
+{
+    const size_t shm = (size_t)nl * (sizeof(uint64_t) + 3 * sizeof(int32_t)) + 2 * sizeof(uint32_t) * (((size_t)nl + 31) / 32);
+    const size_t tab = in.dist ? sizeof(int32_t) * (size_t)S * S : 0;
+    const int grid = std::min(batch, 1 << 20);
+    hipStream_t st = ctx().stream;
+#define TD_TICK_LCM_ARGS                                                                                                          \
+    batch, n_out, nl, in.cab_off, in.cab, in.dem_off, in.dem, in.dist, S, fill, thr, stop_size, (int32_t *)o[0], (int32_t *)o[1],  \
+        (int32_t *)o[2], (int32_t *)o[3], (int32_t *)o[4], (int32_t *)o[5], (int32_t *)o[6], cab2, dem2, cnt
+    if (in.dist && shm + tab <= lds_budget()) {
+        lds_allow(k_tick_lcm_batched<T, true>, shm + tab);
+        k_tick_lcm_batched<T, true><<<grid, T, shm + tab, st>>>(TD_TICK_LCM_ARGS);
+    } else {
+        k_tick_lcm_batched<T, false><<<grid, T, shm, st>>>(TD_TICK_LCM_ARGS);
+    }
+#undef TD_TICK_LCM_ARGS
 }
 
 }  // namespace
@@ -566,11 +954,76 @@ int td_lcm_batched(int batch, int n, const int32_t *ns, const int32_t *cost, int
     return outputs_finish("td_lcm_batched", o, 5, err_off);
 }
 
+int td_build_assign_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab_to, const int32_t *dem_off,
+                            const int32_t *dem_from, const int32_t *dist, int S, int32_t fill, int32_t threshold, int32_t *row_to_col,
+                            int64_t *total, int64_t *dual_bound)
+{
+    TD_REQUIRE_INIT();
+    PosIn in;
+    int rc = pos_args("td_build_assign_batched", batch, n, BATCH_NMAX, cab_off, cab_to, dem_off, dem_from, dist, S, &in);
+    if (rc) return rc;
+    if (batch == 0) return TD_OK;
+    if (!row_to_col || !total) return fail(TD_EINVAL, "td_build_assign_batched: null row_to_col / total");
+    const size_t B = (size_t)batch, N = (size_t)n;
+    Out o[3] = {{row_to_col, sizeof(int32_t) * B * N}, {total, sizeof(int64_t) * B}, {dual_bound, sizeof(int64_t) * B}};
+    size_t err_off;
+    if ((rc = outputs_prepare(o, 3, &err_off))) return rc;
+    launch_pos_assign(batch, n, in.nmax, in, in.cab, in.dem, nullptr, S, fill, threshold, (int32_t *)o[0].dptr(), (int64_t *)o[1].dptr(),
+                      (int64_t *)o[2].dptr(), (int *)((char *)g_out.p + err_off));
+    return outputs_finish("td_build_assign_batched", o, 3, err_off);
+}
+
+int td_tick_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab_to, const int32_t *dem_off, const int32_t *dem_from,
+                    const int32_t *dist, int S, int32_t fill, int32_t threshold, int stop_size, int32_t *lcm_rows, int32_t *lcm_cols,
+                    int32_t *n_pairs, int32_t *lcm_last_min, int32_t *kept_cabs, int32_t *kept_dems, int32_t *n_rest,
+                    int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
+{
+    TD_REQUIRE_INIT();
+    PosIn in;
+    int rc = pos_args("td_tick_batched", batch, n, TICK_NMAX, cab_off, cab_to, dem_off, dem_from, dist, S, &in);
+    if (rc) return rc;
+    if (batch == 0) return TD_OK;
+    if (!lcm_rows || !lcm_cols || !n_pairs || !lcm_last_min || !n_rest || !row_to_col || !total)
+        return fail(TD_EINVAL, "td_tick_batched: null output array");
+    // the remainder that goes to the solver: stop_size rows where the LCM runs, the whole model where it does not
+    int nsol = 0;
+    for (int b = 0; b < batch; b++) {
+        const int nb = std::max(g_off[0][b + 1] - g_off[0][b], g_off[1][b + 1] - g_off[1][b]);
+        const int rest = stop_size >= 0 && stop_size < nb ? stop_size : nb;
+        if (rest > BATCH_NMAX)
+            return fail(TD_EINVAL, "td_tick_batched: model %d leaves %d rows to the solver, more than %d (stop_size = %d)", b, rest,
+                        BATCH_NMAX, stop_size);
+        nsol = std::max(nsol, rest);
+    }
+    const size_t B = (size_t)batch, N = (size_t)n;
+    const size_t nc = (size_t)g_off[0][batch], nd = (size_t)g_off[1][batch];
+    if ((rc = ensure(g_ws, sizeof(int32_t) * (nc + nd + 2 * B)))) return rc;
+    int32_t *cab2 = (int32_t *)g_ws.p, *dem2 = cab2 + nc, *cnt = dem2 + nd;
+    Out o[10] = {{lcm_rows, sizeof(int32_t) * B * N}, {lcm_cols, sizeof(int32_t) * B * N}, {n_pairs, sizeof(int32_t) * B},
+                 {lcm_last_min, sizeof(int32_t) * B},  {kept_cabs, sizeof(int32_t) * B * N}, {kept_dems, sizeof(int32_t) * B * N},
+                 {n_rest, sizeof(int32_t) * B},       {row_to_col, sizeof(int32_t) * B * N}, {total, sizeof(int64_t) * B},
+                 {dual_bound, sizeof(int64_t) * B}};
+    size_t err_off;
+    if ((rc = outputs_prepare(o, 10, &err_off))) return rc;
+    void *od[7];
+    for (int k = 0; k < 7; k++) od[k] = o[k].dptr();
+    if (in.nmax <= 128)
+        launch_tick_lcm_t<64>(batch, n, in.nmax, in, S, fill, threshold, stop_size, od, cab2, dem2, cnt);
+    else
+        launch_tick_lcm_t<256>(batch, n, in.nmax, in, S, fill, threshold, stop_size, od, cab2, dem2, cnt);
+    launch_pos_assign(batch, n, nsol, in, cab2, dem2, cnt, S, fill, threshold, (int32_t *)o[7].dptr(), (int64_t *)o[8].dptr(),
+                      (int64_t *)o[9].dptr(), (int *)((char *)g_out.p + err_off));
+    return outputs_finish("td_tick_batched", o, 10, err_off);
+}
+
 }  // extern "C"
 
 void td::batch_release_workspace()
 {
-    if (g_out.p) (void)hipFree(g_out.p);
-    g_out.p = nullptr;
-    g_out.cap = 0;
+    Buf *bs[] = {&g_out, &g_ws, &g_in[0], &g_in[1], &g_in[2], &g_in[3], &g_in[4]};
+    for (Buf *b : bs) {
+        if (b->p) (void)hipFree(b->p);
+        b->p = nullptr;
+        b->cap = 0;
+    }
 }

@@ -21,6 +21,8 @@ Reference map (file:line in boguszjelinski/taxidispatcher):
     assign_batched        the optimum of many small models per call (heuristic.py:20-40, split.py:61-120)
     LCM_batched           LCM of many small models per call (heuristic.py:24-33 per scenario)
     heuristic_gap         heuristic.py:20-40 as two calls
+    build_assign_batched  build_assign of many ragged position models per call (split.py's regions, zones of one tick)
+    tick_batched          tick() of many ragged position models per call (Simulator.java:163-208 per zone / per seed)
 """
 import ctypes
 
@@ -552,3 +554,108 @@ def heuristic_gap(n=100, iters=1000, seed=None):
         raise _ffi.TdError("optimum above the LCM total in %d scenarios (first: %d: %d > %d)"
                            % (bad.size, int(bad[0]), int(opt[bad[0]]), int(lcm_tot[bad[0]])))
     return lcm_tot, opt, float(np.mean(100.0 * (lcm_tot - opt) / opt))
+
+
+# ----------------------------------------------------------------------------------------
+# many dispatch models from their positions per call (td_build_assign_batched / td_tick_batched)
+# ----------------------------------------------------------------------------------------
+TICK_BATCH_NMAX = 2048   # largest model of tick_batched (Simulator.java's 1300 x 900 tick); its remainder is <= BATCH_NMAX
+
+
+def _ragged(side, what):
+    """one side of pack_ragged -> (values, offsets, host offsets int64)"""
+    if isinstance(side, tuple):
+        if len(side) != 2:
+            raise _ffi.TdError("%s: a ready ragged input is a (values, offsets) pair" % what)
+        vals, offs = side
+        if hasattr(vals, "data_ptr") and not isinstance(vals, np.ndarray):
+            _require_i32(vals, what + " values")
+            n_vals = int(vals.numel())
+        else:
+            vals = _ffi.as_i32(vals).reshape(-1)
+            n_vals = int(vals.size)
+        if hasattr(offs, "data_ptr") and not isinstance(offs, np.ndarray):
+            _require_i32(offs, what + " offsets")
+            h = offs.detach().cpu().numpy().astype(np.int64).reshape(-1)
+        else:
+            offs = _ffi.as_i32(offs).reshape(-1)
+            h = offs.astype(np.int64)
+        if h.size == 0 or h[0] != 0:
+            raise _ffi.TdError("%s: offsets must start at 0" % what)
+        if (np.diff(h) < 0).any():
+            raise _ffi.TdError("%s: offsets decrease" % what)
+        if h[-1] > n_vals:
+            raise _ffi.TdError("%s: offset %d beyond the %d values" % (what, int(h[-1]), n_vals))
+        return vals, offs, h
+    models = [_ffi.as_i32(m).reshape(-1) for m in side]
+    h = np.zeros(len(models) + 1, np.int64)
+    h[1:] = np.cumsum([m.size for m in models])
+    if h[-1] > 2**31 - 1:
+        raise _ffi.TdError("%s: more than 2^31 - 1 positions" % what)
+    vals = np.ascontiguousarray(np.concatenate(models)) if models else np.zeros(0, np.int32)
+    return vals.astype(np.int32, copy=False), h.astype(np.int32), h
+
+
+def pack_ragged(cab_tos, dem_froms):
+    """Ragged batch of dispatch models -> (cab_values, cab_offsets, dem_values, dem_offsets, batch, n).  Each side is a list
+    of 1-D position arrays (one per model), or a ready (values, offsets) tuple (numpy, or torch CUDA int32 tensors handed on as
+    they are; offsets int32[B+1] from 0, never decreasing, the last one within the values).  n = the largest max(n_s, n_d)."""
+    cv, co, ch = _ragged(cab_tos, "cab_tos")
+    dv, do, dh = _ragged(dem_froms, "dem_froms")
+    if ch.size != dh.size:
+        raise _ffi.TdError("%d cab lists for %d request lists" % (ch.size - 1, dh.size - 1))
+    batch = int(ch.size - 1)
+    n = int(np.maximum(np.diff(ch), np.diff(dh)).max()) if batch else 0
+    return cv, co, dv, do, batch, n
+
+
+def _out(shape, dtype):
+    """an output of `shape` whose address is never null (an empty model list still hands the C ABI an array)"""
+    size = int(np.prod(shape))
+    return np.empty(max(size, 1), dtype)[:size].reshape(shape)
+
+
+def build_assign_batched(cab_tos, dem_froms, distances=None, fill=BIG_COST, threshold=-1, want_dual=False):
+    """td_build_assign_batched: build_assign of B ragged dispatch models in one call, one shared distance table (None: |a - b|);
+    no cost matrix is written.  cab_tos / dem_froms: see pack_ragged.  Returns (row_to_col int32[B, n] (-1 beyond a model's
+    max(n_s, n_d)), total int64[B][, dual_bound int64[B]])."""
+    lib = _ffi.lib()
+    cv, co, dv, do, batch, n = pack_ragged(cab_tos, dem_froms)
+    dptr, S, keep = _dist_arg(distances)
+    r2c = _out((batch, n), np.int32)
+    total = _out((batch,), np.int64)
+    dual = _out((batch,), np.int64) if want_dual else None
+    _ffi.check(lib.td_build_assign_batched(batch, n, _ffi.addr(co), _ffi.addr(cv), _ffi.addr(do), _ffi.addr(dv), dptr, S, int(fill),
+                                           int(threshold), _ffi.addr(r2c), _ffi.addr(total), _ffi.addr(dual)))
+    del keep
+    return (r2c, total, dual) if want_dual else (r2c, total)
+
+
+def tick_batched(cab_tos, dem_froms, distances=None, big_cost=BIG_COST, drop_time=10, max_non_lcm=600):
+    """td_tick_batched: tick() of B ragged dispatch models in one call (two launches), one shared distance table.
+    cab_tos / dem_froms: see pack_ragged.  Returns a list of B dicts with tick()'s keys and meanings (lcm_min_val is
+    big_cost where the LCM did not run), plus dual_bound (== total certifies the remainder's optimum; 0 without a solve)."""
+    lib = _ffi.lib()
+    cv, co, dv, do, batch, n = pack_ragged(cab_tos, dem_froms)
+    ch = np.asarray(co.detach().cpu().numpy() if hasattr(co, "detach") else co, np.int64)
+    dh = np.asarray(do.detach().cpu().numpy() if hasattr(do, "detach") else do, np.int64)
+    dptr, S, keep = _dist_arg(distances)
+    rows, cols, kc, kd, r2c = (_out((batch, n), np.int32) for _ in range(5))
+    k, lm, n2 = (_out((batch,), np.int32) for _ in range(3))
+    total, dual = _out((batch,), np.int64), _out((batch,), np.int64)
+    stop = -1 if max_non_lcm is None else int(max_non_lcm)
+    _ffi.check(lib.td_tick_batched(batch, n, _ffi.addr(co), _ffi.addr(cv), _ffi.addr(do), _ffi.addr(dv), dptr, S, int(big_cost),
+                                   -1 if drop_time is None else int(drop_time), stop, _ffi.addr(rows), _ffi.addr(cols), _ffi.addr(k),
+                                   _ffi.addr(lm), _ffi.addr(kc), _ffi.addr(kd), _ffi.addr(n2), _ffi.addr(r2c), _ffi.addr(total),
+                                   _ffi.addr(dual)))
+    del keep
+    out = []
+    for b in range(batch):
+        n_s, n_d = int(ch[b + 1] - ch[b]), int(dh[b + 1] - dh[b])
+        kk, nr = int(k[b]), int(n2[b])
+        lcm_ran = 0 <= stop < max(n_s, n_d)
+        solved = nr > 0 and not (lcm_ran and int(lm[b]) == int(big_cost))
+        out.append({"lcm_rows": rows[b, :kk], "lcm_cols": cols[b, :kk], "lcm_min_val": int(lm[b]), "kept_cabs": kc[b, :n_s - kk],
+                    "kept_dems": kd[b, :n_d - kk], "n_rest": nr, "row_to_col": r2c[b, :nr if solved else 0], "total": int(total[b]),
+                    "solved": solved, "dual_bound": int(dual[b])})
+    return out
