@@ -271,6 +271,41 @@ TD_API void td_tick_release_workspace(void);
 TD_API int td_pool2(int n, const int32_t *from, const int32_t *to, const int32_t *dist, int S,
                     int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n_pairs);
 
+/* ---- maximum-weight matching of MANY general graphs, and optimal pools of two (pool_opt_min.py, pool_optimum.py) -------
+ * One workgroup (one wave) per model runs the primal-dual weighted blossom method (Edmonds; Galil's O(n^3) form) in exact
+ * int64 arithmetic (csrc/td_match.hip, csrc/td_match_core.h); no launch or host synchronisation per model.  Arrays may be
+ * host or device memory (outputs too); calls are synchronous; batch == 0 is a no-op; cells are indexed in 64 bits.
+ *
+ * td_match_batched: the slab layout of td_assign_batched (model b = the top-left ns[b] x ns[b] block of slab b; ns may be
+ *   NULL = every model is n x n), n <= 2048.  Edge {i, j} (i != j) has weight max(W[i][j], W[j][i]); a weight <= 0 is no
+ *   edge; the diagonal is never read.  Outputs: mate[b*n + i] = the partner of i or -1; total[b] = the matched weight;
+ *   dual_bound[b] (may be NULL) = the dual objective, recomputed on the device after every pair of the model was checked
+ *   against the duals: dual_bound == total certifies the maximum.  Optional duals, in doubled units (NULL = not wanted):
+ *   dual_vertex[b*n + i] = y_i; blossom_parent[b*2n + id] = the parent blossom of node id (vertices 0..n-1, blossoms
+ *   n..2n-1; -1 = top level; an id with no vertex under it is unused); dual_blossom[b*n + k] = z of blossom n + k.  They
+ *   satisfy 2 w_ij <= y_i + y_j + sum of z_B over the blossoms holding i and j, y, z >= 0, y_i = 0 for unmatched i, every
+ *   blossom with z_B > 0 is full, and dual_bound = (sum y + sum z_B * floor(|B| / 2)) / 2.
+ *   TD_EINVAL: n > 2048, batch < 0, ns[b] outside [0, n]; TD_EINTERNAL: a defensive loop cap or a violated pair.
+ *
+ * td_pool2_batched: B ragged pool models, customers from[off[b] .. off[b+1]) -> to[...] (positions within the model are the
+ *   customer indices), one shared table (dist S x S, or NULL = |a - b|).  n: the output stride, every model size <= n <= 2048;
+ *   model b's pools sit at b*(n/2): cust_a picks up cust_b, plan = 1 (CLNT_B_ENDS) iff cost1 < cost2, cost = min(cost1, cost2);
+ *   n_pools[b], total[b] = the sum of the listed costs.  Candidates (pool_opt_min.py:56-64): with max_loss > 0 the ordered
+ *   pair (A, B) is one iff plan 1 or plan 2 passes its loss test (compared in double); with max_loss <= 0 every ordered pair
+ *   is (Simulator.java:691, td_pool2).
+ *     optimal = 0: the greedy (stable sort by cost, A-major then B; keep a pair iff it shares no customer with an earlier kept
+ *       one), in the reference's keep order; with max_loss <= 0 it equals td_pool2 model by model.
+ *     optimal = 1: the lexicographic optimum, the most pools and among those the least total cost, each pool in its cheaper
+ *       candidate direction (the smaller cust_a on a tie), listed in ascending (cost, cust_a, cust_b).
+ *   TD_EINVAL: n > 2048, batch < 0, bad offsets, a model larger than n, a stand outside the table, null outputs; TD_ERANGE:
+ *   a pair cost outside int32, or (optimal = 1 only) pool weights K - cost, K = floor(m/2) * cost span + 1, of 2^33 or more;
+ *   TD_EINTERNAL as above. */
+TD_API int td_match_batched(int batch, int n, const int32_t *ns, const int32_t *weight, int32_t *mate, int64_t *total,
+                            int64_t *dual_bound, int64_t *dual_vertex, int32_t *blossom_parent, int64_t *dual_blossom);
+TD_API int td_pool2_batched(int batch, int n, const int32_t *off, const int32_t *from, const int32_t *to, const int32_t *dist,
+                            int S, double max_loss, int optimal, int32_t *cust_a, int32_t *cust_b, int32_t *plan,
+                            int32_t *cost, int32_t *n_pools, int64_t *total);
+
 /* ---- f-4 pools of up to 4 passengers ---------------------------------------------------
  * Replaces pool_n.c:101-207 (findPool / drop_customers / removeDuplicates; Pool.java:32-113 is the
  * same enumeration) for ONE first-pick-up slice [first0, first1) — the unit findpool.c:138-141 hands

@@ -68,6 +68,9 @@ SIGNATURES = {
     "td_tick_release_workspace": (None, []),
     "td_pool2": (ctypes.c_int, [ctypes.c_int, c_i32p, c_i32p, c_i32p, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p,
                                 ctypes.POINTER(ctypes.c_int32)]),
+    "td_match_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
+    "td_pool2_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_double,
+                                        ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
     "td_pool_n": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int,
                                  ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_i32p, ctypes.POINTER(ctypes.c_int32),
                                  ctypes.POINTER(ctypes.c_int64)]),

@@ -429,7 +429,9 @@ __global__ __launch_bounds__(T) void k_assign_pos_batched(int batch, int n_out, 
 __device__ __forceinline__ uint32_t lcm_bias(int32_t v) { return (uint32_t)v ^ 0x80000000u; }
 __device__ __forceinline__ int32_t lcm_unbias(uint64_t key) { return (int32_t)((uint32_t)(key >> 32) ^ 0x80000000u); }
 
-template <int T, class Cells>
+// SYM: a pick (r, c) retires row and column r AND row and column c (td_pool2's symmetric masking: both customers of a pool
+// leave the game in both roles); the slab callers use SYM = false.
+template <int T, bool SYM = false, class Cells>
 __device__ __forceinline__ void lcm_model(const Cells &C, int nr, int nc, int nsize, int64_t cand_limit, int32_t mask,
                                           int32_t threshold, int stop_value_on, int32_t stop_value, int stop_size, int64_t sum_below,
                                           uint64_t *s_rb, int32_t *s_list, uint32_t *s_cm, uint32_t *s_rm, uint64_t *s_red, int *s_cnt,
@@ -501,13 +503,18 @@ __device__ __forceinline__ void lcm_model(const Cells &C, int nr, int nc, int ns
             s_rb[r] = KEY_INF;
             s_cm[c >> 5] |= 1u << (c & 31);
             if (s_rm) s_rm[r >> 5] |= 1u << (r & 31);
+            if constexpr (SYM) {
+                s_rb[c] = KEY_INF;
+                s_cm[r >> 5] |= 1u << (r & 31);
+                if (s_rm) s_rm[c >> 5] |= 1u << (c & 31);
+            }
             *s_cnt = 0;
         }
         __syncthreads();
         if (stop_size >= 0 && size == stop_size) break;   // Simulator.java:544-545
         for (int i = tid; i < nr; i += T) {
             const uint64_t k = s_rb[i];
-            if (k != KEY_INF && (int)(uint32_t)k == c) s_list[atomicAdd(s_cnt, 1)] = i;
+            if (k != KEY_INF && ((int)(uint32_t)k == c || (SYM && (int)(uint32_t)k == r))) s_list[atomicAdd(s_cnt, 1)] = i;
         }
         __syncthreads();
     }
@@ -549,6 +556,37 @@ __global__ __launch_bounds__(T) void k_lcm_batched(int batch, int n, const int32
             total[b] = tot;
             last_min[b] = lm;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// td_pool2_batched's greedy (pool_opt_min.py:81-102 = Simulator.java:723-739): the LCM with symmetric masking over each
+// model's pair-cost block (slab stride n; INT_MAX = not a candidate).  Pairs go to rows / cols at b * (n / 2) in pick
+// order, which is the reference's keep order (stable sort by cost, A-major insertion order).
+// dynamic LDS: as k_lcm_batched
+// ---------------------------------------------------------------------------------------------------------------------
+template <int T>
+__global__ __launch_bounds__(T) void k_pool2_lcm_batched(int batch, int n, const int32_t *__restrict__ ns, const int32_t *__restrict__ cost,
+                                                         int32_t *__restrict__ rows, int32_t *__restrict__ cols, int32_t *__restrict__ n_pairs)
+{
+    constexpr int NW = T / 64;
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    uint64_t *s_rb = reinterpret_cast<uint64_t *>(s_dyn);
+    int32_t *s_list = reinterpret_cast<int32_t *>(s_rb + n);
+    uint32_t *s_cm = reinterpret_cast<uint32_t *>(s_list + n);
+    __shared__ uint64_t s_red[2 * NW];
+    __shared__ int s_cnt;
+    int par = 0;
+    for (int b = blockIdx.x; b < batch; b += gridDim.x) {
+        const int nb = ns[b];
+        __syncthreads();
+        const SlabCells<false> C{cost + (int64_t)b * n * n, nb, n};
+        int np;
+        int32_t lm;
+        int64_t tot;
+        lcm_model<T, true>(C, nb, nb, nb, (int64_t)INT_MAX, INT_MAX, -1, 0, 0, -1, (int64_t)INT64_MAX, s_rb, s_list, s_cm, nullptr, s_red,
+                           &s_cnt, par, rows + (int64_t)b * (n / 2), cols + (int64_t)b * (n / 2), np, lm, tot);
+        if (threadIdx.x == 0) n_pairs[b] = np;
     }
 }
 
@@ -885,6 +923,19 @@ void launch_tick_lcm_t(int batch, int n_out, int nl, const PosIn &in, int S, int
 }
 
 }  // namespace
+
+void td::pool2_greedy_launch(int batch, int n, const int32_t *d_ns, const int32_t *d_cost, int32_t *rows, int32_t *cols, int32_t *n_pairs)
+{
+    const size_t shm = (size_t)n * (sizeof(uint64_t) + sizeof(int32_t)) + sizeof(uint32_t) * (((size_t)n + 31) / 32);
+    const int grid = std::min(batch, 1 << 20);
+    Ctx &c = ctx();
+    if (n <= 128) {
+        k_pool2_lcm_batched<64><<<grid, 64, shm, c.stream>>>(batch, n, d_ns, d_cost, rows, cols, n_pairs);
+    } else {
+        lds_allow(k_pool2_lcm_batched<256>, shm);
+        k_pool2_lcm_batched<256><<<grid, 256, shm, c.stream>>>(batch, n, d_ns, d_cost, rows, cols, n_pairs);
+    }
+}
 
 extern "C" {
 

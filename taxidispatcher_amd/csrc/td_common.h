@@ -87,6 +87,11 @@ int lcm_stands(int n_s, int n_d, const int32_t *d_cab_to, const int32_t *d_dem_f
                int32_t *rows, int32_t *cols, int32_t *n_pairs, int32_t *last_min, int *ok);
 // td_batch.hip: frees the batched entry points' result buffer (td_shutdown)
 void batch_release_workspace();
+// td_batch.hip: td_pool2_batched's greedy, the LCM with symmetric masking over B pair-cost blocks (slab stride n, ns[b] <= n
+// <= 2048, INT_MAX = no candidate); pairs at b * (n / 2) in pick order.  Queued on the library stream.
+void pool2_greedy_launch(int batch, int n, const int32_t *d_ns, const int32_t *d_cost, int32_t *rows, int32_t *cols, int32_t *n_pairs);
+// td_match.hip: frees td_match_batched / td_pool2_batched's workspace (td_shutdown)
+void match_release_workspace();
 void prof_begin(int k);
 void prof_end(int k);
 void prof_flush();

@@ -348,6 +348,7 @@ void td_shutdown(void)
     td_assign_release_workspace();
     td_tick_release_workspace();
     batch_release_workspace();
+    match_release_workspace();
     Buf *bufs[] = {&c.stage_a, &c.stage_b, &c.stage_c, &c.stage_d, &c.stage_out, &c.cc,
                    &c.misc,    &c.lcm_a,   &c.lcm_b,   &c.lcm_c,   &c.lcm_d};
     for (Buf *b : bufs) {

@@ -23,6 +23,10 @@ Reference map (file:line in boguszjelinski/taxidispatcher):
     heuristic_gap         heuristic.py:20-40 as two calls
     build_assign_batched  build_assign of many ragged position models per call (split.py's regions, zones of one tick)
     tick_batched          tick() of many ragged position models per call (Simulator.java:163-208 per zone / per seed)
+    match_batched         maximum-weight matching of many general graphs per call (the optimum behind pool_opt_min.py)
+    pool2_batched         greedy (pool_opt_min.py:81-102) or optimal (:114-122) pools of two of many ragged models per call
+    find_pool_optimal     find_pool's format, optimal pools
+    pool_gap              pool_opt_min.py as two calls
 """
 import ctypes
 
@@ -659,3 +663,86 @@ def tick_batched(cab_tos, dem_froms, distances=None, big_cost=BIG_COST, drop_tim
                     "kept_dems": kd[b, :n_d - kk], "n_rest": nr, "row_to_col": r2c[b, :nr if solved else 0], "total": int(total[b]),
                     "solved": solved, "dual_bound": int(dual[b])})
     return out
+
+
+# ----------------------------------------------------------------------------------------
+# maximum-weight matching of many general graphs, optimal pools of two (td_match_batched / td_pool2_batched)
+# ----------------------------------------------------------------------------------------
+MATCH_NMAX = 2048   # largest model of match_batched / pool2_batched
+
+
+def match_batched(weights, ns=None, want_dual=False):
+    """td_match_batched: the maximum-weight matching of B general graphs (n <= 2048) in one call.  weights: see pack_batch
+    (edge {i, j} weighs max(W[i][j], W[j][i]); <= 0 is no edge).  Returns (mate int32[B, n] (-1: unmatched or beyond ns[b]),
+    total int64[B], dual_bound int64[B]) -- dual_bound == total certifies the maximum -- and with want_dual the certificate
+    (y int64[B, n], blossom_parent int32[B, 2n], z int64[B, n]) in doubled units (see the header)."""
+    lib = _ffi.lib()
+    w, ns, batch, n = pack_batch(weights, ns)
+    mate = _out((batch, n), np.int32)
+    total, bound = _out((batch,), np.int64), _out((batch,), np.int64)
+    y = _out((batch, n), np.int64) if want_dual else None
+    par = _out((batch, 2 * n), np.int32) if want_dual else None
+    z = _out((batch, n), np.int64) if want_dual else None
+    _ffi.check(lib.td_match_batched(batch, n, _ffi.addr(ns), _ffi.addr(w) if batch * n else None, _ffi.addr(mate), _ffi.addr(total),
+                                    _ffi.addr(bound), _ffi.addr(y), _ffi.addr(par), _ffi.addr(z)))
+    return (mate, total, bound, (y, par, z)) if want_dual else (mate, total, bound)
+
+
+def pool2_batched(froms, tos, distances=None, max_loss=None, optimal=True):
+    """td_pool2_batched: pools of two for B ragged models in one call, one shared distance table (None: |a - b|).
+    froms / tos: ragged lists as in pack_ragged (the same model sizes on both sides).  max_loss=None: every ordered pair is a
+    candidate (Simulator.java:691); else pool_opt_min.py:58-64's loss tests.  optimal=False: the reference's greedy in its
+    keep order; optimal=True: the most pools, then the least total cost, in ascending (cost, custA, custB).
+    Returns (cust_a, cust_b, plan, cost: int32[B, n // 2], n_pools int32[B], total int64[B]); model b's pools are the first
+    n_pools[b] entries of its rows; customer indices are positions within the model."""
+    lib = _ffi.lib()
+    fv, fo, fh = _ragged(froms, "froms")
+    tv, _, th = _ragged(tos, "tos")
+    if not np.array_equal(fh, th):
+        raise _ffi.TdError("froms and tos must describe the same models (equal offsets)")
+    batch = int(fh.size - 1)
+    n = int(np.diff(fh).max()) if batch else 0
+    dptr, S, keep = _dist_arg(distances)
+    half = n // 2
+    a, b, plan, cost = (_out((batch, half), np.int32) for _ in range(4))
+    k, total = _out((batch,), np.int32), _out((batch,), np.int64)
+    ml = 0.0 if max_loss is None else float(max_loss)
+    _ffi.check(lib.td_pool2_batched(batch, n, _ffi.addr(fo), _ffi.addr(fv), _ffi.addr(tv), dptr, S, ml, 1 if optimal else 0,
+                                    _ffi.addr(a), _ffi.addr(b), _ffi.addr(plan), _ffi.addr(cost), _ffi.addr(k), _ffi.addr(total)))
+    del keep
+    return a, b, plan, cost, k, total
+
+
+def find_pool_optimal(frm, to, distances=None, max_loss=None):
+    """The optimal pools of two of one model in find_pool's format: a list of (custA, custB, plan, cost), the most pools and
+    among those the least total cost, in ascending (cost, custA, custB); drops in where find_pool is used."""
+    frm, to = _ffi.as_i32(frm).reshape(-1), _ffi.as_i32(to).reshape(-1)
+    a, b, plan, cost, k, _ = pool2_batched([frm], [to], distances, max_loss, optimal=True)
+    return [(int(a[0, i]), int(b[0, i]), int(plan[0, i]), int(cost[0, i])) for i in range(int(k[0]))]
+
+
+def pool_gap(n=100, iters=5, seed=None, max_loss=1.01):
+    """pool_opt_min.py as two library calls: one n x n table U{1..39}, then per iteration n customers (from, to uniform over
+    the n stands, from == to removed), the greedy and the optimum of every iteration.  Returns (greedy_totals, optimal_totals,
+    greedy_counts, optimal_counts, mean gap in % = mean of 100 * (greedy - opt) / opt over the iterations with equal counts,
+    :124-125; nan when there is none).  Raises when an optimum has fewer pools than the greedy, or at equal counts a larger
+    total (the solver failed).  Two quirks of the reference are not reproduced: its removal loop skips the element after a
+    removed one (:38-43), and it carries the shrunken customer count into the next iteration (:45)."""
+    rng = np.random.default_rng(seed)
+    table = rng.integers(1, 40, (n, n)).astype(np.int32)
+    froms, tos = [], []
+    for _ in range(iters):
+        d = rng.integers(0, n, (n, 2)).astype(np.int32)
+        d = d[d[:, 0] != d[:, 1]]
+        froms.append(np.ascontiguousarray(d[:, 0]))
+        tos.append(np.ascontiguousarray(d[:, 1]))
+    gk, gt = pool2_batched(froms, tos, table, max_loss, optimal=False)[4:]
+    ok, ot = pool2_batched(froms, tos, table, max_loss, optimal=True)[4:]
+    bad = np.nonzero((ok < gk) | ((ok == gk) & (ot > gt)))[0]
+    if bad.size:
+        i = int(bad[0])
+        raise _ffi.TdError("optimal pooling worse than the greedy in %d iterations (first: %d: %d pools / %d against %d / %d)"
+                           % (bad.size, i, int(ok[i]), int(ot[i]), int(gk[i]), int(gt[i])))
+    eq = (ok == gk) & (ot > 0)
+    gap = float(np.mean(100.0 * (gt[eq] - ot[eq]) / ot[eq])) if eq.any() else float("nan")
+    return gt, ot, gk, ok, gap

@@ -1,0 +1,235 @@
+"""CPU tests of the optimal-pool ground truth (no GPU): the numpy restatement of pool_opt_min.py's candidate rule and greedy
+against a step-by-step restatement of its lines 51-102, the lexicographic objective against a brute-forced ILP of
+:8-18,114-122, and the host build of the blossom solver (csrc/td_match_core.h, tools/match_proto.cpp) against brute force
+and the numpy certificate checker."""
+import os
+import shutil
+import subprocess
+from functools import lru_cache
+
+import numpy as np
+import pytest
+
+import match_cert
+import pool_opt_data as D
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def script_steps(table, trips, max_loss):
+    """pool_opt_min.py:51-102 followed step by step with plain loops (small m only), as the script orders its work:
+    ordered pairs (a, b), a != b, a-major (:51-53); the two plan costs (:56-57) and the two loss tests (:58-64); a pair that
+    passes either test is listed with the cheaper of its two costs (:65-79); the list is sorted stably by cost (:81); walking
+    it from the second entry on, an entry is dropped when an earlier entry still standing shares a customer with it
+    (:84-102).  Returns (total cost, trips kept, the kept (a, b, cost) entries)."""
+    d = lambda x, y: table[x][y]
+    listed = []
+    for a, (a_from, a_to) in enumerate(trips):
+        for b, (b_from, b_to) in enumerate(trips):
+            if a == b:
+                continue
+            pick_b = d(a_from, b_from)
+            a_drops_first = pick_b + d(b_from, a_to) + d(a_to, b_to)
+            b_drops_first = pick_b + d(b_from, b_to) + d(b_to, a_to)
+            b_happy = d(b_from, a_to) + d(a_to, b_to) < d(b_from, b_to) * max_loss
+            a_happy = pick_b + d(b_from, a_to) < d(a_from, a_to) * max_loss
+            a_happy_last = b_drops_first < d(a_from, a_to) * max_loss
+            if (b_happy and a_happy) or a_happy_last:
+                listed.append((a, b, min(a_drops_first, b_drops_first)))
+    listed.sort(key=lambda entry: entry[2])
+    standing = [True] * len(listed)
+    for k in range(1, len(listed)):
+        for q in range(k):
+            if standing[q] and set(listed[k][:2]) & set(listed[q][:2]):
+                standing[k] = False
+                break
+    kept = [entry for entry, keep in zip(listed, standing) if keep]
+    return sum(entry[2] for entry in kept), len(kept), kept
+
+
+def test_restated_rule_and_greedy_equal_the_script_steps():
+    rng = np.random.default_rng(1)
+    for it in range(300):
+        S = int(rng.integers(5, 40))
+        m = int(rng.integers(2, 40))
+        ml = [1.01, 1.1, 1.3, 2.0][it % 4]
+        table = [[int(rng.integers(1, 40)) for _ in range(S)] for _ in range(S)]
+        trips = [(int(rng.integers(0, S)), int(rng.integers(0, S))) for _ in range(m)]
+        trips = [t for t in trips if t[0] != t[1]]
+        c, _ = D.pair_costs([t[0] for t in trips], [t[1] for t in trips], np.array(table), ml)
+        total, count, kept = script_steps(table, trips, ml)
+        ref = D.greedy(c)
+        assert kept == ref and count == len(ref) and total == sum(r[2] for r in ref), it
+
+
+def test_every_pair_rule_is_simulator_rule():
+    """max_loss None / <= 0: every ordered pair A != B is a candidate (Simulator.java:691)"""
+    rng = np.random.default_rng(2)
+    frm, to = rng.integers(0, 30, 25), rng.integers(0, 30, 25)
+    for ml in (None, 0, -1.0):
+        c, _ = D.pair_costs(frm, to, None, ml)
+        assert ((c >= 0) == ~np.eye(25, dtype=bool)).all()
+
+
+def _ilp_bruteforce(n, c):
+    """pool_opt_min.py:8-18,114-122: n rows (stands), customers 0..m-1; every row is in exactly one unit: a pair x[A][B] (or
+    x[B][A]) costs its candidate cost, any other unit (single, non-candidate pair, phantom row) costs n^2.  Min total."""
+    m = c.shape[0]
+    big = n * n
+
+    def unit(i, j):
+        best = big
+        if i < m and j < m:
+            for x in (c[i, j], c[j, i]):
+                if x >= 0:
+                    best = min(best, int(x))
+        return best
+
+    @lru_cache(maxsize=None)
+    def f(mask):
+        if mask == 0:
+            return 0
+        i = (mask & -mask).bit_length() - 1
+        rest = mask & ~(1 << i)
+        best = big + f(rest)
+        r = rest
+        while r:
+            j = (r & -r).bit_length() - 1
+            best = min(best, unit(i, j) + f(rest & ~(1 << j)))
+            r &= r - 1
+        return best
+
+    return f((1 << n) - 1)
+
+
+def _lex_bruteforce(c):
+    """the most candidate pairs, then the least total cost: (count, total)"""
+    m = c.shape[0]
+
+    @lru_cache(maxsize=None)
+    def g(mask):
+        if mask == 0:
+            return (0, 0)
+        i = (mask & -mask).bit_length() - 1
+        rest = mask & ~(1 << i)
+        best = g(rest)
+        r = rest
+        while r:
+            j = (r & -r).bit_length() - 1
+            w = [int(x) for x in (c[i, j], c[j, i]) if x >= 0]
+            if w:
+                k, t = g(rest & ~(1 << j))
+                cand = (k + 1, t + min(w))
+                if cand[0] > best[0] or (cand[0] == best[0] and cand[1] < best[1]):
+                    best = cand
+            r &= r - 1
+        return best
+
+    return g((1 << m) - 1)
+
+
+def test_lexicographic_optimum_is_the_ilp_optimum():
+    """ILP* = ceil(n/2) n^2 - W* with W* the max-weight matching of n^2 - w; when n^2 > floor(m/2) max w that optimum is the
+    lexicographic one: ILP* = t + ceil((n - 2k) / 2) n^2 for the lexicographic (k pools, total t)"""
+    rng = np.random.default_rng(3)
+    checked = 0
+    for it in range(250):
+        n = int(rng.integers(2, 11))
+        m = int(rng.integers(0, n + 1))
+        table = rng.integers(1, 4, (n, n))
+        frm, to = rng.integers(0, n, m), rng.integers(0, n, m)
+        c, _ = D.pair_costs(frm, to, table, [None, 1.01, 1.3][it % 3])
+        maxw = int(c.max()) if (c >= 0).any() else 0
+        if not n * n > (m // 2) * maxw:
+            continue
+        k, t = _lex_bruteforce(c)
+        assert _ilp_bruteforce(n, c) == t + -(-(n - 2 * k) // 2) * n * n, it
+        # and the weights the library uses give the same optimum
+        K, W = D.lex_weights(c)
+        best = _max_weight_bruteforce(np.maximum(W, W.T))
+        assert best == k * K - t, it
+        checked += 1
+    assert checked > 150
+
+
+def _max_weight_bruteforce(w):
+    m = w.shape[0]
+
+    @lru_cache(maxsize=None)
+    def h(mask):
+        if mask == 0:
+            return 0
+        i = (mask & -mask).bit_length() - 1
+        rest = mask & ~(1 << i)
+        best = h(rest)
+        r = rest
+        while r:
+            j = (r & -r).bit_length() - 1
+            if w[i, j] > 0:
+                best = max(best, int(w[i, j]) + h(rest & ~(1 << j)))
+            r &= r - 1
+        return best
+
+    return h((1 << m) - 1)
+
+
+@pytest.fixture(scope="module")
+def proto(tmp_path_factory):
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
+    exe = str(tmp_path_factory.mktemp("proto") / "match_proto")
+    subprocess.check_call([cxx, "-O2", "-std=c++17", "-I", os.path.join(ROOT, "taxidispatcher_amd", "csrc"),
+                           os.path.join(ROOT, "tools", "match_proto.cpp"), "-o", exe])
+    return exe
+
+
+def _run_proto(exe, mats):
+    inp = [str(len(mats))]
+    for W in mats:
+        inp.append(str(W.shape[0]))
+        inp.append(" ".join(map(str, np.asarray(W).ravel().tolist())))
+    out = subprocess.run([exe], input="\n".join(inp), capture_output=True, text=True, check=True).stdout.split("\n")
+    res = []
+    for t in range(len(mats)):
+        err, tot, bnd = map(int, out[5 * t].split())
+        vals = [list(map(int, out[5 * t + r].split())) for r in range(1, 5)]
+        res.append((err, tot, bnd, *vals))
+    return res
+
+
+def test_host_build_of_the_solver(proto):
+    """the device solver's control code built for the host: brute force on small graphs, the certificate on larger ones,
+    networkx's blossom cases"""
+    rng = np.random.default_rng(4)
+    mats = []
+    for it in range(400):
+        n = int(rng.integers(0, 13)) if it < 300 else int(rng.integers(13, 80))
+        fam = it % 4
+        if fam == 0:
+            W = rng.integers(1, 6, (n, n))
+        elif fam == 1:
+            W = rng.integers(-3, 1000, (n, n))
+        elif fam == 2:
+            W = np.where(rng.random((n, n)) < 0.7, 0, rng.integers(1, 50, (n, n)))
+        else:
+            W = 2**31 - 1 - rng.integers(0, 50, (n, n))
+        mats.append(W.astype(np.int64))
+    names = sorted(D.BLOSSOM_CASES)
+    mats += [D.blossom_matrix(D.BLOSSOM_CASES[k]).astype(np.int64) for k in names]
+    for k, (err, tot, bnd, mate, y, par, z) in enumerate(_run_proto(proto, mats)):
+        W = mats[k]
+        assert err == 0 and tot == bnd, k
+        match_cert.check(W, mate, tot, bnd, y, par, z)
+        if W.shape[0] <= 12:
+            assert tot == _max_weight_bruteforce(match_cert.edge_weights(W)), k
+
+
+def test_certificate_checker_rejects_a_wrong_answer(proto):
+    W = D.family("ties", 20, seed=1).astype(np.int64)
+    err, tot, bnd, mate, y, par, z = _run_proto(proto, [W])[0]
+    match_cert.check(W, mate, tot, bnd, y, par, z)
+    y2 = list(y)
+    y2[int(np.argmax(y))] -= 1
+    with pytest.raises(AssertionError):
+        match_cert.check(W, mate, tot, bnd, y2, par, z)
+    with pytest.raises(AssertionError):
+        match_cert.check(W, mate, tot + 1, bnd + 1, y, par, z)

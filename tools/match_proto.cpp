@@ -1,0 +1,47 @@
+// Host build of the blossom solver of td_match.hip (csrc/td_match_core.h, W = 1): reads graphs as text from stdin
+// (count, then per graph n and the n x n weight matrix, row-major) and prints per graph "err total bound", the mates,
+// the vertex duals, the blossom parents of the 2n nodes and the blossom duals z (doubled, as td_match_batched exports them).
+//   g++ -O2 -std=c++17 -I taxidispatcher_amd/csrc tools/match_proto.cpp -o match_proto
+#include <cstdio>
+#include <vector>
+
+#include "td_match_core.h"
+
+struct Mat {
+    const int *w;
+    int n;
+    int64_t operator()(int i, int j) const
+    {
+        const int a = w[(size_t)i * n + j], b = w[(size_t)j * n + i];
+        return a > b ? a : b;
+    }
+};
+
+int main()
+{
+    int T;
+    if (scanf("%d", &T) != 1) return 1;
+    for (int t = 0; t < T; t++) {
+        int n;
+        if (scanf("%d", &n) != 1) return 1;
+        std::vector<int> w((size_t)n * n);
+        for (auto &x : w)
+            if (scanf("%d", &x) != 1) return 1;
+        std::vector<unsigned char> mem(tdm::bytes(n > 0 ? n : 1) + 64);
+        const Mat m{w.data(), n};
+        tdm::Match<Mat> M(tdm::carve(mem.data(), n), m, n);
+        int err = n > 0 ? M.run() : 0;
+        int64_t total = 0, bound = 0;
+        if (!err && n > 0) err = M.certify(total, bound);
+        printf("%d %lld %lld\n", err, (long long)total, (long long)bound);
+        for (int i = 0; i < n; i++) printf("%d ", M.s.mate[i]);
+        printf("\n");
+        for (int i = 0; i < n; i++) printf("%lld ", (long long)M.s.dual[i]);
+        printf("\n");
+        for (int i = 0; i < 2 * n; i++) printf("%d ", M.s.par[i]);
+        printf("\n");
+        for (int i = n; i < 2 * n; i++) printf("%lld ", (long long)(M.s.base[i] >= 0 ? 2 * M.s.dual[i] : 0));
+        printf("\n");
+    }
+    return 0;
+}
