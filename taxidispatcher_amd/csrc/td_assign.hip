@@ -158,6 +158,14 @@ enum {
 };
 
 constexpr int ROW_BITS = 20;
+// the 64-bit totals of k_final / k_dual sit at byte FIN_OFF of the control block (misc), k_final's ticket right behind them;
+// the end-of-solve record k_final writes into the pinned host block (REC_OFF) has the same layout as the control block:
+// the control words, the totals at FIN_OFF, HopCtl::left at REC_LEFT (clear of the line probe's verdict at 4096 and of
+// td_assign's row_to_col at 8192)
+constexpr size_t FIN_OFF = 1024;
+constexpr size_t FIN_TICKET = FIN_OFF + 16;
+constexpr size_t REC_OFF = 0;
+constexpr size_t REC_LEFT = FIN_OFF + 16;
 constexpr int HOP_FMAX = 128;   // td_blocks.h: free rows / columns of a block the two-hop pass looks at
 constexpr int HOP_BMAX = 16;    // td_blocks.h: blocks per shard
 
@@ -221,6 +229,7 @@ int g_hop_passes = 2;       // TD_HOP_PASSES    two-hop passes at the end of pha
 int g_hop_max_rows = HOP_FMAX;   // TD_HOP_MAX_ROWS  a block with more free rows than this is left to the rounds
 int g_lazy_cc = 1;          // TD_LAZY_CC       td_assign, block-local start: the compress pass stores the diagonal slices of the narrow copy only; the rest is written (k_compress_rest) only if phase A + the two-hop pass over the whole matrix leave rows
 int g_hop_global = 1;       // TD_HOP_GLOBAL    td_assign: one two-hop pass over the whole matrix after phase A
+int g_one_trip = 1;         // TD_ONE_TRIP      td_assign, block-local start: the pass over the whole matrix and the end of the solve are queued behind phase A, gated on the device, with one read-back (0: the read-backs of the sequence before)
 int g_zs_global_rounds = 6; // TD_ZS_GLOBAL_ROUNDS  td_assign: bidding rounds launched for what the block-local start left
 int g_core = 1;             // TD_CORE          the warm start's eps-phases bid on a sparse core of every row (td_core_warm.h)
 int g_core_k = 64;          // TD_CORE_K        rank of the group minimum that becomes a row's threshold (about 256 * -ln(1 - k/256) cells per row: 74)
@@ -312,6 +321,7 @@ void read_tunables()
     if (const char *e = getenv("TD_HOP_PASSES")) g_hop_passes = std::max(0, std::min(8, atoi(e)));
     if (const char *e = getenv("TD_HOP_MAX_ROWS")) g_hop_max_rows = std::max(1, atoi(e));
     if (const char *e = getenv("TD_HOP_GLOBAL")) g_hop_global = atoi(e) != 0;
+    if (const char *e = getenv("TD_ONE_TRIP")) g_one_trip = atoi(e) != 0;
     if (const char *e = getenv("TD_LAZY_CC")) g_lazy_cc = atoi(e) != 0;
     if (const char *e = getenv("TD_ZS_GLOBAL_ROUNDS")) g_zs_global_rounds = std::max(1, std::min(48, atoi(e)));
 }
@@ -735,14 +745,18 @@ template <typename PT>
 __global__ __launch_bounds__(256) void k_init_state(int n, int npad, int nrows, PT *pk, PT padkey, int *owner, int *r2c,
                                                     unsigned long long *bid, int *ctl, const int *rconst,
                                                     const int32_t *probe_cost /* non-null: run the shape probe */,
-                                                    int probe_tickets = 0 /* > 0: the compress pass that FOLLOWS takes tickets too and decides */)
+                                                    int probe_tickets = 0 /* > 0: the compress pass that FOLLOWS takes tickets too and decides */,
+                                                    uint8_t *ob = nullptr /* non-null: phase A's owned-column bytes, cleared */,
+                                                    unsigned long long *fin = nullptr /* non-null: the totals and k_final's ticket, cleared */)
 {
     int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < npad) {
         pk[j] = (j < n) ? (PT)0 : padkey;
         bid[j] = 0ull;
         owner[j] = (j < n) ? -1 : -2;
+        if (ob) ob[j] = 0;
     }
+    if (fin && j < 3) fin[j] = 0ull;
     // -1: free row; -2: constant row, deferred to k_place_const (never bids, never searched)
     if (j < nrows) r2c[j] = (rconst && rconst[j]) ? -2 : -1;
     if (j < CTL_WORDS && j != CTL_FLAG && j != CTL_NCONST && j != CTL_RANGE && j != CTL_RANGE + 1) ctl[j] = 0;
@@ -1126,11 +1140,13 @@ __device__ __forceinline__ void place_const_tail(int n, int *__restrict__ r2c, i
     }
 }
 
+// gate_left non-null: queued before it is known whether the two-hop passes placed every row; nothing to do unless they did
 __global__ __launch_bounds__(1024) void k_place_const(int n, int *__restrict__ r2c, int *__restrict__ owner,
                                                       int *__restrict__ lista, int *__restrict__ listb,
-                                                      int *__restrict__ ctl)
+                                                      int *__restrict__ ctl, const int *__restrict__ gate_left = nullptr)
 {
     if (ctl[CTL_FLAG]) return;
+    if (gate_left && *gate_left != 0) return;
     place_const_tail(n, r2c, owner, lista, listb, ctl);
 }
 
@@ -3005,17 +3021,48 @@ __global__ __launch_bounds__(1024) void k_pcommit(int n, PT *__restrict__ pk, in
 // =====================================================================================
 // k_final: total from the original costs + permutation check; k_dual: LP bound
 // =====================================================================================
+// The end-of-solve record (td_assign's one-trip sequence): the last workgroup to take the ticket copies the control
+// words, the totals and HopCtl::left into the pinned host block with plain stores and puts the ticket back to 0.  Every
+// workgroup takes the ticket, whether it summed anything or not: the record is written by every launch.
+__device__ __forceinline__ void fin_record(const int *ctl, const unsigned long long *out, const int *left, unsigned int *ticket, int *rec)
+{
+    __shared__ int s_last;
+    __syncthreads();   // every wave of the workgroup has added its share
+    if (threadIdx.x == 0) {
+        __threadfence();
+        s_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    for (int k = threadIdx.x; k < CTL_ALL; k += blockDim.x) rec[k] = __hip_atomic_load(ctl + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) {
+        long long *rt = reinterpret_cast<long long *>(reinterpret_cast<char *>(rec) + FIN_OFF);
+        rt[0] = (long long)__hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rt[1] = (long long)__hip_atomic_load(out + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rec[REC_LEFT / sizeof(int)] = __hip_atomic_load(left, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *ticket = 0u;
+    }
+}
+
+// gate_left non-null: queued right behind the two-hop pass over the whole matrix; it sums only if that pass (or phase A)
+// left no row free, and then also stores every row's column into r2c_out (the caller's row_to_col, or the pinned host
+// block) and, rec non-null, the end-of-solve record
 template <bool GEN = false>
 __global__ __launch_bounds__(256) void k_final(int n, int nrows, int row0, const int32_t *__restrict__ cost,
                                                const int *__restrict__ r2c, const int *__restrict__ owner,
                                                unsigned long long *__restrict__ out, int *__restrict__ ctl, int cost_is_transposed = 0,
-                                               const CellSrc src = CellSrc())
+                                               const CellSrc src = CellSrc(), const int *__restrict__ gate_left = nullptr,
+                                               int *__restrict__ r2c_out = nullptr, unsigned int *__restrict__ ticket = nullptr,
+                                               int *__restrict__ rec = nullptr)
 {
-    if (ctl[CTL_FLAG]) return;
+    const bool go = !ctl[CTL_FLAG] && !(gate_left && *gate_left != 0);
+    if (go) {
     long long s = 0;
     int bad = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += gridDim.x * blockDim.x) {
         const int j = r2c[i];
+        if (r2c_out) r2c_out[i] = j;
         if (j < 0 || j >= n || owner[j] != row0 + i)
             bad = 1;
         else   // the fused transposed solve never materialises the transposed int32 matrix: its cell (i, j) is the caller's (j, i)
@@ -3031,6 +3078,8 @@ __global__ __launch_bounds__(256) void k_final(int n, int nrows, int row0, const
         atomicAdd(&out[0], (unsigned long long)s);
         if (bad) atomicOr(&ctl[CTL_ERR], 4);
     }
+    }
+    if (rec) fin_record(ctl, out, gate_left, ticket, rec);
 }
 
 __global__ void k_pack_totals(const long long *__restrict__ tot2, const int *__restrict__ ctl, long long *__restrict__ out3)
@@ -3101,10 +3150,12 @@ __global__ void k_fill_i32(int *p, int count, int v)
 template <typename CT>
 __global__ __launch_bounds__(256) void k_dual(int n, int nrows, int row0, int nchunks, const CT *__restrict__ cc,
                                               const typename Tr<CT>::PT *__restrict__ pk,
-                                              const int32_t *__restrict__ rowmin, unsigned long long *__restrict__ out)
+                                              const int32_t *__restrict__ rowmin, unsigned long long *__restrict__ out,
+                                              const int *__restrict__ gate_left = nullptr, const int *__restrict__ ctl = nullptr)
 {
     using PT = typename Tr<CT>::PT;
     constexpr int E = Tr<CT>::E;
+    if (gate_left && (*gate_left != 0 || ctl[CTL_FLAG] != 0)) return;   // (see k_final)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const size_t pitch = (size_t)nchunks * E;
     long long acc = 0;
@@ -3178,6 +3229,8 @@ struct td_shard {
     bool zs_round0 = false;    // ... round 0 of phase A is still to be bid (rows of <= 16 384 columns: the plain compress pass + one k_zs_bid round over 1/8 of every row beat the pass that also scans for the bids, 216 + ~10 against 243 us)
     bool began = false;        // the state (prices, owners, row_to_col, bid keys) has been initialised for the current compressed copy
     bool state_ready = false;  // sharded solve: the state was initialised in front of the compress pass and phase A has run on it (td_shard_begin must not redo it)
+    bool ctl_clear = false;    // the control words were cleared by a kernel queued in front of the next compress pass (the line probe): no memset
+    bool ob_clear = false;     // phase A's owned-column bytes were cleared by k_init_state in front of the compress pass: no memset
     Buf ob, esc, hop, hoptab;  // owned bytes per column, escape masks per row, HopCtl, the two-hop tables
     Buf core, core_n, core_t, core_need;   // sparse core of the warm start (td_core_warm.h): lists, their lengths, the smallest value outside, the rows that need their dense row
     void free_all()
@@ -3232,7 +3285,9 @@ int sv_compress_t(Solver &sv, bool *fits, bool speculate = false)
     int rc;
     if ((rc = ensure(sv.cc, std::max<size_t>((size_t)nrows * nchunks * 16, 256)))) return rc;
     int *ctl = (int *)sv.misc.p;
-    TD_HIP(hipMemsetAsync(ctl, 0, CTL_ALL * sizeof(int), c.stream));  // flag, error, stats, range, shape
+    if (!sv.ctl_clear) TD_HIP(hipMemsetAsync(ctl, 0, CTL_ALL * sizeof(int), c.stream));  // flag, error, stats, range, shape
+    sv.ctl_clear = false;
+    sv.ob_clear = false;
     const bool vec = (n % 4 == 0) && (((uintptr_t)sv.d_cost & 15) == 0);
     const int grid = std::max(1, std::min(nrows, c.n_cu * 8));
     sv.bid0_done = false;
@@ -3281,9 +3336,17 @@ int sv_compress_t(Solver &sv, bool *fits, bool speculate = false)
             const int gi = (std::max(npad, (int)CTL_WORDS) + 255) / 256;
             const int gc = nq <= 256 * 16 ? gb : std::max(1, std::min(nrows, c.n_cu * 2));
             tickets = sv.probe ? gi + gc : 0;
+            // one-trip sequence: the state init also clears phase A's owned-column bytes and the totals (no memsets)
+            uint8_t *ob_z = nullptr;
+            if (g_one_trip && zs_rpb > 0) {
+                if ((rc = ensure(sv.ob, (size_t)npad + 64))) return rc;
+                ob_z = (uint8_t *)sv.ob.p;
+            }
+            unsigned long long *fin_z = g_one_trip ? (unsigned long long *)((char *)sv.misc.p + FIN_OFF) : nullptr;
             k_init_state<PT><<<gi, 256, 0, c.stream>>>(n, npad, nrows, (PT *)sv.price.p, padkey, (int *)sv.owner.p, (int *)sv.r2c.p,
-                                                       (unsigned long long *)sv.bid.p, ctl, nullptr, sv.probe, tickets);
-            TD_HIP(hipMemsetAsync((char *)sv.misc.p + 1024, 0, 16, c.stream));
+                                                       (unsigned long long *)sv.bid.p, ctl, nullptr, sv.probe, tickets, ob_z, fin_z);
+            if (!fin_z) TD_HIP(hipMemsetAsync((char *)sv.misc.p + FIN_OFF, 0, 16, c.stream));
+            sv.ob_clear = ob_z != nullptr;
             sv.bid0_done = true;
         }
         ProfScope ps(TD_K_COMPRESS);
@@ -3476,8 +3539,9 @@ int sv_complete_cc(Solver &sv)
 
 // raw: the cells come from the caller's int32 matrix and the row minima (a solve whose narrow copy holds the diagonal
 // slices only, sv.cc_partial)
+// gate: the pass is queued without a read-back and runs only if the device's HopCtl::left says so (k_hop_lists)
 template <typename CT>
-int sv_hop_t(Solver &sv, int rpb, int ncols_blk, int col_lo, int nb, bool window_zero, uint8_t *ob, bool raw = false)
+int sv_hop_t(Solver &sv, int rpb, int ncols_blk, int col_lo, int nb, bool window_zero, uint8_t *ob, bool raw = false, bool gate = false)
 {
     Ctx &c = ctx();
     using PT = typename Tr<CT>::PT;
@@ -3488,7 +3552,9 @@ int sv_hop_t(Solver &sv, int rpb, int ncols_blk, int col_lo, int nb, bool window
     HopCtl *hc = (HopCtl *)sv.hop.p;
     int *frl = (int *)sv.list.p, *fcl = (int *)sv.pred.p;   // free until the finisher
     const int *ctl = (const int *)sv.misc.p;
-    k_hop_lists<<<nb, 1024, 0, c.stream>>>(rpb, ncols_blk, col_lo, (const int *)sv.r2c.p, (const int *)sv.owner.p, frl, fcl, hc, ctl);
+    if (gate && nb != 1) return fail(TD_EINTERNAL, "a gated two-hop pass takes one block");
+    k_hop_lists<<<nb, 1024, 0, c.stream>>>(rpb, ncols_blk, col_lo, (const int *)sv.r2c.p, (const int *)sv.owner.p, frl, fcl, hc, ctl,
+                                           gate ? g_hop_max_rows : 0);
     if (raw) {
         if (!sv.d_cost || sv.n % 4) return fail(TD_EINVAL, "two-hop pass on the int32 matrix: no matrix, or n %% 4 != 0");
         k_hop_esc<CT, true><<<(sv.nrows + 3) / 4, 256, 0, c.stream>>>(sv.nrows, sv.n / 4, rpb, ncols_blk, col_lo, g_hop_max_rows,
@@ -3528,7 +3594,8 @@ int sv_phase_a(Solver &sv, int hop_passes)
     const int col_lo = (sv.row0 / rpb) * rpb, col_hi = col_lo + nb * rpb;
     int rc;
     if ((rc = ensure(sv.ob, (size_t)sv.npad + 64))) return rc;
-    TD_HIP(hipMemsetAsync(sv.ob.p, 0, (size_t)sv.npad, c.stream));
+    if (!sv.ob_clear) TD_HIP(hipMemsetAsync(sv.ob.p, 0, (size_t)sv.npad, c.stream));
+    sv.ob_clear = false;
     ProfScope ps(TD_K_BID);
     int *ctl = (int *)sv.misc.p;
     const int ga = (col_hi - col_lo + 255) / 256;
@@ -3574,8 +3641,9 @@ int sv_begin_t(Solver &sv)
     const PT padkey = (PT)(Tr<CT>::BIG << 1) | (PT)1;
     k_init_state<PT><<<(std::max(sv.npad, (int)CTL_WORDS) + 255) / 256, 256, 0, c.stream>>>(
         sv.n, sv.npad, sv.nrows, (PT *)sv.price.p, padkey, (int *)sv.owner.p, (int *)sv.r2c.p,
-        (unsigned long long *)sv.bid.p, (int *)sv.misc.p, sv.defer_const ? (const int *)sv.rconst.p : nullptr, sv.probe);
-    TD_HIP(hipMemsetAsync((char *)sv.misc.p + 1024, 0, 16, c.stream));
+        (unsigned long long *)sv.bid.p, (int *)sv.misc.p, sv.defer_const ? (const int *)sv.rconst.p : nullptr, sv.probe, 0, nullptr,
+        g_one_trip ? (unsigned long long *)((char *)sv.misc.p + FIN_OFF) : nullptr);
+    if (!g_one_trip) TD_HIP(hipMemsetAsync((char *)sv.misc.p + FIN_OFF, 0, 16, c.stream));
     TD_HIP(hipGetLastError());
     sv.began = true;
     return TD_OK;
@@ -4120,14 +4188,10 @@ int sv_warm_t(Solver &sv, int64_t range, int64_t *rounds_out, bool *random_like 
         }                                                           \
     } while (0)
 
-// read back ctl + totals (one sync)
-int sv_readback(Solver &sv, int64_t *total, int64_t *dual, int max_rounds, int *range_flag = nullptr)
+// the control words + totals as the host sees them (a copy of the control block, or k_final's end-of-solve record)
+int sv_readback_parse(Solver &sv, const char *pin, int64_t *total, int64_t *dual, int max_rounds, int *range_flag)
 {
     Ctx &c = ctx();
-    char *pin = (char *)c.pinned;
-    static_assert(CTL_ALL * sizeof(int) <= 1024, "the totals sit at byte 1024 of the control block");
-    TD_HIP(hipMemcpyAsync(pin, sv.misc.p, 1024 + 16, hipMemcpyDeviceToHost, c.stream));   // control words + totals: one copy
-    TD_HIP(hipStreamSynchronize(c.stream));
     const int *hctl = (const int *)pin;
     if (range_flag) {
         *range_flag = hctl[CTL_FLAG];
@@ -4141,8 +4205,8 @@ int sv_readback(Solver &sv, int64_t *total, int64_t *dual, int max_rounds, int *
         }
     }
     if (hctl[CTL_ERR]) return fail(TD_EINTERNAL, "device-side consistency check failed (code %d)", hctl[CTL_ERR]);
-    if (total) *total = ((const int64_t *)(pin + 1024))[0];
-    if (dual) *dual = ((const int64_t *)(pin + 1024))[1];
+    if (total) *total = ((const int64_t *)(pin + FIN_OFF))[0];
+    if (dual) *dual = ((const int64_t *)(pin + FIN_OFF))[1];
     int rounds = 0;
     for (int r = 0; r < max_rounds && r < 48; r++)
         if (hctl[CTL_PROG + r] > 0) rounds++;
@@ -4158,6 +4222,48 @@ int sv_readback(Solver &sv, int64_t *total, int64_t *dual, int max_rounds, int *
     c.stats[4] = sv.bpc == 5 ? 4 : (sv.bpc == 6 ? 1 : sv.bpc);   // bytes per stored cell (mode 5 = 4-byte cells with 32-bit prices, 6 = 1-byte cells + escape)
     c.stats[5] = hctl[CTL_PACC];
     c.stats[10] = hctl[CTL_FOREST];
+    return TD_OK;
+}
+
+// read back ctl + totals (one sync)
+int sv_readback(Solver &sv, int64_t *total, int64_t *dual, int max_rounds, int *range_flag = nullptr)
+{
+    Ctx &c = ctx();
+    char *pin = (char *)c.pinned;
+    static_assert(CTL_ALL * sizeof(int) <= FIN_OFF, "the totals sit at byte FIN_OFF of the control block");
+    TD_HIP(hipMemcpyAsync(pin, sv.misc.p, FIN_OFF + 16, hipMemcpyDeviceToHost, c.stream));   // control words + totals: one copy
+    TD_HIP(hipStreamSynchronize(c.stream));
+    return sv_readback_parse(sv, pin, total, dual, max_rounds, range_flag);
+}
+
+// td_assign's one-trip sequence, queued right behind the two-hop pass over the whole matrix (1-byte cells, square model,
+// block-local start): the constant rows, the dual bound and the total, every kernel gated on the device — it does
+// nothing unless HopCtl::left is 0 and the width flag is clear.  k_final stores every row's column into r2c_out (when
+// given) and writes the end-of-solve record into the pinned host block; the host reads it after one synchronisation.
+// When the record says "not done" nothing here has changed the state: the rounds and the finishers take over as before.
+int sv_end_gated(Solver &sv, bool want_dual, int *r2c_out)
+{
+    Ctx &c = ctx();
+    const int n = sv.n, nrows = sv.nrows;
+    const int *left = (const int *)((char *)sv.hop.p + offsetof(HopCtl, left));
+    int *ctl = (int *)sv.misc.p;
+    unsigned long long *out = (unsigned long long *)((char *)sv.misc.p + FIN_OFF);
+    int rc;
+    // (k_dual reads whole rows of the narrow copy: the rounds would need them too, so this is not speculative)
+    if (want_dual && (rc = sv_complete_cc(sv))) return rc;
+    ProfScope ps(TD_K_FINAL);
+    if (sv.defer_const)
+        k_place_const<<<1, 1024, 0, c.stream>>>(n, (int *)sv.r2c.p, (int *)sv.owner.p, (int *)sv.list.p, (int *)sv.pred.p, ctl, left);
+    // (k_dual before k_final: both read the final state only, and k_final's last workgroup then sees both totals)
+    if (want_dual)
+        k_dual<uint8_t><<<std::max(1, std::min((nrows + 3) / 4, c.n_cu * 8)), 256, 0, c.stream>>>(
+            n, nrows, sv.row0, sv.nchunks, (const uint8_t *)sv.cc.p, (const int32_t *)sv.price.p, (const int32_t *)sv.rowmin.p, out, left, ctl);
+    int *rec = (int *)((char *)c.pinned + REC_OFF);
+    rec[REC_LEFT / sizeof(int)] = -1;   // k_final's last workgroup overwrites it (no GPU work in flight writes this part of the block)
+    k_final<false><<<std::min((nrows + 255) / 256, 256), 256, 0, c.stream>>>(n, nrows, sv.row0, sv.d_cost, (const int *)sv.r2c.p,
+                                                                          (const int *)sv.owner.p, out, ctl, 0, CellSrc(), left, r2c_out,
+                                                                          (unsigned int *)((char *)sv.misc.p + FIN_TICKET), rec);
+    TD_HIP(hipGetLastError());
     return TD_OK;
 }
 
@@ -4300,13 +4406,17 @@ int assign_impl(Solver &sv, int n, const int32_t *cost, int32_t *row_to_col, int
         return TD_OK;
     };
     if (sv.gen && !hinted_fuse && (rc = materialise())) return rc;
+    sv.ctl_clear = false;
     if (!hinted_fuse && g_line && n >= g_line_min_n && !g_solver_eps) {
-        if ((rc = line_probe_launch(n, sv.d_cost, &sv.skip))) return rc;
+        // (one-trip sequence: the probe also clears the control words for the compress pass queued behind it)
+        if ((rc = line_probe_launch(n, sv.d_cost, &sv.skip, g_one_trip ? (int *)sv.misc.p : nullptr, CTL_ALL))) return rc;
         line_pending = true;
+        sv.ctl_clear = g_one_trip != 0;
     }
     c.stats[8] = 0;
     int max_rounds = g_max_rounds;
     bool solved = false, transposed = false, np_failed = false, no_fuse = false, fused_spec = false;
+    bool r2c_on_device = false;   // k_final has stored the result into the caller's device row_to_col
     int64_t range_hint = -1;
     sv.defer_const = g_defer_const && !g_solver_eps;
     sv.bid0_done = false;
@@ -4528,7 +4638,32 @@ restart:
             // same up to here, and identical altogether when the blocks leave nothing)
             const int passes_a = g_hop_passes;
             if ((rc = sv_phase_a(sv, passes_a))) return rc;
-            if (passes_a > 0) {
+            if (passes_a > 0 && g_one_trip && !transposed && !sv.gen) {
+                // one-trip sequence: the pass over the whole matrix and the end of the solve are queued at once, gated on
+                // the device (k_hop_lists, k_place_const, k_dual, k_final); one synchronisation reads k_final's record
+                if (g_hop_global && (rc = sv_hop_t<uint8_t>(sv, n, n, 0, 1, true, nullptr, sv.cc_partial, true))) return rc;
+                const bool dev_out = is_device_ptr(row_to_col);
+                r2c_in_pinned = !dev_out && (size_t)R2C_PIN_OFF + sizeof(int32_t) * (size_t)n <= c.pinned_cap;
+                int *r2c_out = dev_out ? row_to_col : (r2c_in_pinned ? (int *)((char *)c.pinned + R2C_PIN_OFF) : nullptr);
+                if ((rc = sv_end_gated(sv, dual_bound != nullptr, r2c_out))) return rc;
+                TD_HIP(hipStreamSynchronize(c.stream));
+                const char *rec = (const char *)c.pinned + REC_OFF;
+                const int left = ((const int *)rec)[REC_LEFT / sizeof(int)], rflag = ((const int *)rec)[CTL_FLAG];
+                if (left < 0) return fail(TD_EINTERNAL, "the end-of-solve record was not written");
+                if (getenv("TD_DEBUG")) fprintf(stderr, "[td] one trip: %d rows free after the two-hop passes, flag %d\n", left, rflag);
+                if (left == 0 && rflag == 0) {
+                    int flag = 0;
+                    if ((rc = sv_readback_parse(sv, rec, &tot, &dual, max_rounds, &flag))) return rc;
+                    c.stats[1] = 0;
+                    c.stats[6] = 0;
+                    r2c_on_device = dev_out;
+                    solved = true;
+                    break;
+                }
+                // rows left, or the width flag: the rounds and the finishers as before (nothing above has changed the state)
+                r2c_in_pinned = false;
+                round_cap = std::min(max_rounds, g_zs_global_rounds);
+            } else if (passes_a > 0) {
                 int *pin = (int *)c.pinned;
                 auto read_left = [&]() -> int {
                     TD_HIP(hipMemcpyAsync(pin, (char *)sv.hop.p + offsetof(HopCtl, left), sizeof(int), hipMemcpyDeviceToHost, c.stream));
@@ -4674,6 +4809,11 @@ restart:
     c.stats[7] = transposed ? 1 : 0;
     if (r2c_in_pinned) {
         memcpy(row_to_col, (const char *)c.pinned + R2C_PIN_OFF, sizeof(int32_t) * (size_t)n);
+        if (total) *total = tot;
+        if (dual_bound) *dual_bound = dual;
+        return TD_OK;
+    }
+    if (r2c_on_device) {   // (k_final stored it, and the stream has been synchronised)
         if (total) *total = tot;
         if (dual_bound) *dual_bound = dual;
         return TD_OK;

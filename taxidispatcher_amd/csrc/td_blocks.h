@@ -126,12 +126,27 @@ __global__ __launch_bounds__(256) void k_zs_assign(int col_lo, int col_hi, int n
 }
 
 // ---- two hops: free rows / columns of every local block (block-relative indices, ascending)
+// gate_max > 0 (one block only: the pass over the whole matrix queued without a read-back): the pass runs only if
+// 0 < HopCtl::left <= gate_max; otherwise the block's counts are set to 0, which makes the pass's other kernels exit,
+// and `left` keeps the value the previous pass left
 __global__ __launch_bounds__(1024) void k_hop_lists(int rpb, int ncols_blk, int col_lo, const int *__restrict__ r2c,
                                                     const int *__restrict__ owner, int *__restrict__ frl, int *__restrict__ fcl,
-                                                    HopCtl *__restrict__ hc, const int *__restrict__ ctl)
+                                                    HopCtl *__restrict__ hc, const int *__restrict__ ctl, int gate_max = 0)
 {
     if (ctl[CTL_FLAG]) return;
     const int lb = blockIdx.x;
+    if (gate_max > 0) {
+        __shared__ int s_go;
+        if (threadIdx.x == 0) {
+            const int left = hc->left;
+            s_go = left > 0 && left <= gate_max;
+        }
+        __syncthreads();
+        if (!s_go) {
+            if (threadIdx.x == 0) hc->nfr[lb] = 0, hc->nfc[lb] = 0;
+            return;
+        }
+    }
     const int nfr = build_free_list(rpb, r2c + (size_t)lb * rpb, frl + (size_t)lb * rpb, -1);
     const int nfc = build_free_list(ncols_blk, owner + col_lo + (size_t)lb * ncols_blk, fcl + (size_t)lb * ncols_blk, -1);
     if (threadIdx.x == 0) {

@@ -92,8 +92,11 @@ __device__ inline bool span_ok(long long x, long long y, long long D) { return x
 //      counted (k of them: verdict 3 when 1 <= k <= LINE_KMAX)
 //   rev: the column keys must be negated when the two key orders run in opposite directions
 __global__ __launch_bounds__(1024) void k_line_probe(int n, const int32_t *__restrict__ c, long long *__restrict__ ctl,
-                                                     long long *__restrict__ host_verdict)
+                                                     long long *__restrict__ host_verdict, int *__restrict__ clear_words = nullptr,
+                                                     int nclear = 0)
 {
+    // td_assign's control words, cleared here for the compress pass queued behind the probe (no memset in between)
+    for (int k = threadIdx.x; k < nclear; k += blockDim.x) clear_words[k] = 0;
     __shared__ ArgMax sh[16];
     __shared__ int s_cnt;
     const int t = threadIdx.x, T = blockDim.x;
@@ -867,7 +870,7 @@ __global__ void k_lsh_publish(const long long *__restrict__ ctl, long long *__re
 constexpr size_t VERDICT_OFF = 4096;   // byte offset of the probe's verdict in the pinned host block (clear of the other read-backs)
 hipEvent_t g_probe_done = nullptr;
 
-int line_probe_launch(int n, const int32_t *d_cost, const long long **skip_dev)
+int line_probe_launch(int n, const int32_t *d_cost, const long long **skip_dev, int *clear_words, int nclear)
 {
     Ctx &c = ctx();
     int rc;
@@ -876,7 +879,8 @@ int line_probe_launch(int n, const int32_t *d_cost, const long long **skip_dev)
     long long *ctl = (long long *)g_lw.ctl.p;
     {
         ProfScope ps(TD_K_LINE);
-        k_line_probe<<<1, 1024, 0, c.stream>>>(n, d_cost, ctl, (long long *)((char *)c.pinned + VERDICT_OFF));
+        k_line_probe<<<1, 1024, 0, c.stream>>>(n, d_cost, ctl, (long long *)((char *)c.pinned + VERDICT_OFF), clear_words,
+                                               clear_words ? nclear : 0);
         TD_HIP(hipGetLastError());
     }
     TD_HIP(hipEventRecord(g_probe_done, c.stream));
