@@ -12,7 +12,9 @@
  *   - plain C, no torch / HIP types in signatures; `void*` stream is a hipStream_t.
  *   - every data pointer may be a HOST pointer or a DEVICE pointer of the active device;
  *     the library detects which (hipPointerGetAttributes) and stages host buffers itself.
- *   - caller owns every buffer; the library keeps no pointer past return.
+ *   - caller owns every buffer; the library keeps no pointer past return (the shard handles td_shard_* /
+ *     td_lcm_shard_* excepted: they read their cost_rows until they are destroyed).  A pointer need only be
+ *     aligned to its element size; outputs are written within their stated capacity and nowhere else.
  *   - return 0 on success, a negative TD_E* code on failure; td_last_error() gives the text.
  *     No exceptions cross the ABI.
  *   - single-threaded like the reference (one solve at a time per process); calls are
@@ -56,6 +58,12 @@ TD_API const char *td_last_error(void);
  * results are complete. */
 TD_API int td_set_stream(void *hip_stream); /* run on the caller's stream (NULL -> library stream) */
 TD_API int td_synchronize(void);
+/* Device bytes currently held in the library's grow-only workspaces (the default solver, handles, shards, staging and
+ * result buffers).  Callable at any time, before td_init and after td_shutdown too.  After a *_destroy it is back at the
+ * value from before the matching *_create; after td_shutdown it is 0, PROVIDED every td_solver, td_shard and td_lcm_shard
+ * handle was destroyed first: td_shutdown does not release what a handle owns, and the shard *_destroy calls refuse to run
+ * once the library is shut down.  Pinned host blocks are not counted. */
+TD_API int td_workspace_bytes(int64_t *bytes);
 TD_API int td_version(void);
 
 /* ---- a-2 cost-matrix build ---------------------------------------------------------
@@ -195,8 +203,8 @@ TD_API int td_lcm_batched(int batch, int n, const int32_t *ns, const int32_t *co
  * td_tick_batched: model b = td_tick on the same arguments: the LCM of Simulator.java:523-549 down to stop_size rows (stop on
  *   fill; skipped when stop_size < 0 or >= n(b)), the shrink, the remainder's optimum.  lcm_rows / lcm_cols: the pairs in
  *   the reference's pick order, n_pairs[b] of them; lcm_last_min[b] (fill when the LCM did not run); kept_cabs / kept_dems
- *   (may be NULL): indices into model b's own lists, in order; n_rest[b] = the larger count; row_to_col (over the kept lists),
- *   total, dual_bound (may be NULL): the remainder's optimum.  When the LCM ran and ended on fill (Simulator.java:188-189)
+ *   (may be NULL): indices into model b's own lists, in order; n_rest[b] = the larger count; row_to_col (over the kept lists;
+ *   -1 for i >= n_rest[b]), total, dual_bound (may be NULL): the remainder's optimum.  When the LCM ran and ended on fill (Simulator.java:188-189)
  *   the model has no solve: row_to_col is -1, total and dual_bound are 0 (defined here, unlike td_tick).  stop_size < 0
  *   equals td_build_assign_batched plus empty pair lists.  TD_EINVAL: n > 2048, or a model whose remainder has more than
  *   1024 rows (min(n(b), stop_size) when the LCM runs, else n(b)).
@@ -314,7 +322,9 @@ TD_API int td_pool2_batched(int batch, int n, const int32_t *off, const int32_t 
  *   requests i = 0..n-1: from[i], to[i], max_wait[i] (pick-up path up to i may not be longer),
  *   max_loss[i] (percent a pooled ride may exceed the direct one);  dist: S x S or NULL => |a-b|.
  *   pools: max_pools records of 2k+1 ints (k pick-ups, k drop-offs, cost) in the reference's output
- *   order (stable by cost, de-duplicated);  n_happy: happy plans before de-duplication;  max_happy:
+ *   order (stable by cost, de-duplicated); a max_pools below the length of that list keeps its first
+ *   max_pools records (td_pool_merge alike) and nothing is written behind them;  n_happy: happy plans
+ *   before de-duplication;  max_happy:
  *   capacity of the plan buffer (<= 0: 4 Mi plans; TD_ERANGE when exceeded — the reference's
  *   pool[10000] simply overflows there).
  *   k = 2, 3 or 4 passengers (TD_EINVAL otherwise: with k = 1 the reference's duplicate test compares its 4 padded slots

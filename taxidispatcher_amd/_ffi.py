@@ -24,6 +24,7 @@ SIGNATURES = {
     "td_last_error": (ctypes.c_char_p, []),
     "td_set_stream": (ctypes.c_int, [ctypes.c_void_p]),
     "td_synchronize": (ctypes.c_int, []),
+    "td_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64)]),
     "td_version": (ctypes.c_int, []),
     "td_cost_build": (ctypes.c_int, [c_i32p, c_i32p, ctypes.c_int, c_i32p, c_i32p, ctypes.c_int, c_i32p, ctypes.c_int,
                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int, c_i32p]),

@@ -1348,7 +1348,7 @@ __global__ __launch_bounds__(256) void k_compress_tr8(int n, int npad, const int
     int mn[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX}, mx[4] = {INT_MIN, INT_MIN, INT_MIN, INT_MIN};
     bool bad = false;
     const int jc0 = bx + 4 * cg;
-    const bool vec = (n % 4 == 0);
+    const bool vec = (n % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) & 15) == 0);   // the caller's matrix: a 4-byte-aligned base takes the scalar loads
     constexpr int U = 8;
     for (int p0 = 0; p0 < TR8_ROWS / 16; p0 += U) {
         int4 v[U];
@@ -1443,7 +1443,7 @@ __global__ __launch_bounds__(256) void k_compress_tr8w(int n, int npad, const in
     bool bad = false;
     const int lc0 = 64 * wv + 4 * cg;   // the lane's first column inside the tile
     const int jc0 = bx + lc0;
-    const bool vec = (n % 4 == 0);
+    const bool vec = (n % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) & 15) == 0);   // the caller's matrix: a 4-byte-aligned base takes the scalar loads
     constexpr int U = 8;
     for (int p0 = 0; p0 < TR8W_ROWS / 4; p0 += U) {
         int4 v[U];
@@ -3236,11 +3236,7 @@ struct td_shard {
     void free_all()
     {
         Buf *bs[] = {&stage, &cc, &price, &owner, &r2c, &r2c_full, &bid, &pred, &list, &rowmin, &rconst, &misc, &psrec, &tbuf, &xbuf, &fbuf, &cmask, &ob, &esc, &hop, &hoptab, &core, &core_n, &core_t, &core_need, &genbuf, &gpos};
-        for (Buf *b : bs) {
-            if (b->p) (void)hipFree(b->p);
-            b->p = nullptr;
-            b->cap = 0;
-        }
+        for (Buf *b : bs) buf_free(*b);
     }
 };
 

@@ -1072,9 +1072,5 @@ int td_tick_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab
 void td::batch_release_workspace()
 {
     Buf *bs[] = {&g_out, &g_ws, &g_in[0], &g_in[1], &g_in[2], &g_in[3], &g_in[4]};
-    for (Buf *b : bs) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
+    for (Buf *b : bs) buf_free(*b);
 }

@@ -52,6 +52,8 @@ Ctx &ctx();
 int fail(int code, const char *fmt, ...);
 int hip_fail(hipError_t e, const char *what);
 int ensure(Buf &b, size_t bytes);
+// releases a workspace buffer (no-op when empty); with ensure() the only place that moves td_workspace_bytes' counter
+void buf_free(Buf &b);
 bool is_device_ptr(const void *p);
 // returns a device pointer holding `bytes` of src (src itself when already on the device)
 int to_device(const void *src, size_t bytes, Buf &stage, const void **out);
@@ -93,6 +95,8 @@ void batch_release_workspace();
 void pool2_greedy_launch(int batch, int n, const int32_t *d_ns, const int32_t *d_cost, int32_t *rows, int32_t *cols, int32_t *n_pairs);
 // td_match.hip: frees td_match_batched / td_pool2_batched's workspace (td_shutdown)
 void match_release_workspace();
+// td_pool.hip: frees td_pool_n / td_pool_merge's workspace (td_shutdown)
+void pool_release_workspace();
 void prof_begin(int k);
 void prof_end(int k);
 void prof_flush();

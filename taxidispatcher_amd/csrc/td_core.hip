@@ -25,15 +25,25 @@ int hip_fail(hipError_t e, const char *what)
     return TD_EHIP;
 }
 
+static int64_t g_ws_bytes = 0;   // device bytes held in Buf workspaces (td_workspace_bytes)
+
+void buf_free(Buf &b)
+{
+    if (b.p) {
+        (void)hipFree(b.p);
+        g_ws_bytes -= (int64_t)b.cap;
+    }
+    b.p = nullptr;
+    b.cap = 0;
+}
+
 int ensure(Buf &b, size_t bytes)
 {
     if (bytes <= b.cap && b.p) return TD_OK;
     if (b.p) {
         hipError_t e0 = hipStreamSynchronize(g_ctx.stream);
         if (e0 != hipSuccess) return hip_fail(e0, "hipStreamSynchronize(before realloc)");
-        (void)hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
+        buf_free(b);
     }
     size_t want = std::max<size_t>(bytes, 256);
     hipError_t e = hipMalloc(&b.p, want);
@@ -42,6 +52,7 @@ int ensure(Buf &b, size_t bytes)
         return hip_fail(e, "hipMalloc(workspace)");
     }
     b.cap = want;
+    g_ws_bytes += (int64_t)want;
     return TD_OK;
 }
 
@@ -349,13 +360,10 @@ void td_shutdown(void)
     td_tick_release_workspace();
     batch_release_workspace();
     match_release_workspace();
+    pool_release_workspace();
     Buf *bufs[] = {&c.stage_a, &c.stage_b, &c.stage_c, &c.stage_d, &c.stage_out, &c.cc,
                    &c.misc,    &c.lcm_a,   &c.lcm_b,   &c.lcm_c,   &c.lcm_d};
-    for (Buf *b : bufs) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
+    for (Buf *b : bufs) buf_free(*b);
     for (int i = 0; i < c.n_ev; i++) (void)hipEventDestroy(c.ev_pool[i]);
     c.n_ev = c.ev_next = c.n_pend = 0;
     if (c.pinned) (void)hipHostFree(c.pinned);
@@ -375,6 +383,13 @@ int td_set_stream(void *s)
     prof_flush();
     TD_HIP(hipStreamSynchronize(c.stream));
     c.stream = s ? (hipStream_t)s : c.own_stream;
+    return TD_OK;
+}
+
+int td_workspace_bytes(int64_t *bytes)
+{
+    if (!bytes) return fail(TD_EINVAL, "null argument");
+    *bytes = g_ws_bytes;
     return TD_OK;
 }
 

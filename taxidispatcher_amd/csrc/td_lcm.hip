@@ -1111,18 +1111,25 @@ extern "C" int td_lcm_shard_create(int n, int row0, int nrows, const int32_t *co
     if (!rc) rc = ensure(s->rowbest, sizeof(unsigned long long) * (size_t)std::max(nrows, 1));
     if (!rc) rc = ensure(s->colmask, sizeof(uint32_t) * (size_t)((n + 31) / 32 + 1));
     if (!rc) rc = ensure(s->out, 64);
+    if (!rc) {
+        s->d_cost = (const int32_t *)d;
+        hipError_t e = hipMemsetAsync(s->colmask.p, 0, sizeof(uint32_t) * (size_t)((n + 31) / 32 + 1), c.stream);
+        if (e == hipSuccess && nrows) {
+            ProfScope ps(TD_K_LCM);
+            k_lcmsh_init<<<std::max(1, std::min((nrows + 3) / 4, c.n_cu * 8)), 256, 0, c.stream>>>(n, nrows, s->d_cost, s->cand_limit,
+                                                                                                 (unsigned long long *)s->rowbest.p);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) rc = hip_fail(e, "td_lcm_shard_create");
+    }
     if (rc) {
+        // nothing of a failed create survives it: the staged rows and whatever was allocated before the failure
+        (void)hipStreamSynchronize(c.stream);
+        Buf *bs[] = {&s->stage, &s->rowbest, &s->colmask, &s->out};
+        for (Buf *b : bs) buf_free(*b);
         delete s;
         return rc;
     }
-    s->d_cost = (const int32_t *)d;
-    TD_HIP(hipMemsetAsync(s->colmask.p, 0, sizeof(uint32_t) * (size_t)((n + 31) / 32 + 1), c.stream));
-    if (nrows) {
-        ProfScope ps(TD_K_LCM);
-        k_lcmsh_init<<<std::max(1, std::min((nrows + 3) / 4, c.n_cu * 8)), 256, 0, c.stream>>>(n, nrows, s->d_cost, s->cand_limit,
-                                                                                             (unsigned long long *)s->rowbest.p);
-    }
-    TD_HIP(hipGetLastError());
     *out = s;
     return TD_OK;
 }
@@ -1133,8 +1140,7 @@ extern "C" int td_lcm_shard_destroy(td_lcm_shard *s)
     if (!s) return TD_OK;
     (void)hipStreamSynchronize(ctx().stream);
     Buf *bs[] = {&s->stage, &s->rowbest, &s->colmask, &s->out, &s->vec, &s->vec2};
-    for (Buf *b : bs)
-        if (b->p) (void)hipFree(b->p);
+    for (Buf *b : bs) buf_free(*b);
     delete s;
     return TD_OK;
 }

@@ -985,11 +985,7 @@ void line_release_workspace()
     g_probe_done = nullptr;
     Buf *bs[] = {&g_lw.ctl, &g_lw.kin,  &g_lw.kout, &g_lw.vin, &g_lw.vout, &g_lw.tmp, &g_lw.f,  &g_lw.v64, &g_lw.v32,
                  &g_lw.r2c, &g_lw.band, &g_lw.P,    &g_lw.E,   &g_lw.ARG,  &g_lw.Bk,  &g_lw.L,  &g_lw.mcol};
-    for (Buf *b : bs) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
+    for (Buf *b : bs) buf_free(*b);
 }
 
 }  // namespace td

@@ -535,9 +535,5 @@ int td_pool2_batched(int batch, int n, const int32_t *off, const int32_t *from, 
 void td::match_release_workspace()
 {
     Buf *bs[] = {&g_ws, &g_res, &g_pool, &g_in[0], &g_in[1], &g_in[2], &g_in[3]};
-    for (Buf *b : bs) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
+    for (Buf *b : bs) buf_free(*b);
 }

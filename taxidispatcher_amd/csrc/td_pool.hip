@@ -398,6 +398,12 @@ int greedy_and_emit(int k, int n, size_t count, const unsigned long long *sorted
 
 }  // namespace
 
+void td::pool_release_workspace()
+{
+    Buf *bs[] = {&g_pw.keys, &g_pw.keys2, &g_pw.kept, &g_pw.tmp, &g_pw.ctl, &g_pw.out, &g_pw.in};
+    for (Buf *b : bs) buf_free(*b);
+}
+
 extern "C" int td_pool_n(int k, int n, const int32_t *from, const int32_t *to, const int32_t *max_wait,
                          const int32_t *max_loss, const int32_t *dist, int S, int first0, int first1,
                          int64_t max_happy, int max_pools, int32_t *pools, int32_t *n_pools, int64_t *n_happy)

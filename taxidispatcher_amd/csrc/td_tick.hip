@@ -229,11 +229,7 @@ extern "C" void td_tick_release_workspace(void)
 {
     TickBufs &t = g_tick;
     Buf *bs[] = {&t.cost_a, &t.cost_b, &t.pos, &t.keep};
-    for (Buf *b : bs) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
+    for (Buf *b : bs) buf_free(*b);
     if (t.pin) (void)hipHostFree(t.pin);
     t.pin = nullptr;
     t.pin_cap = 0;
