@@ -1391,6 +1391,8 @@ extern "C" int td_pool2(int n, const int32_t *from, const int32_t *to, const int
 // One workgroup; the typical tick (supply above demand at most stands) is done at value 0: ~10 us instead of the ~110 us
 // of the level-list build + greedy walk over the 1300 x 900 matrix, whose 6.8 MB are then never written either.
 // Positions outside 0..63 (or a threshold above 64) raise a flag: the caller takes the general path.
+// The kernel never compares a value with fill: its rule is the reference's only while every value it can take, 0 .. threshold - 1,
+// is below fill (cells >= fill are never candidates, Simulator.java:529-538), so td::lcm_stands declines a model with fill < threshold.
 // =====================================================================================
 namespace {
 
@@ -1574,7 +1576,7 @@ __global__ __launch_bounds__(256) void k_lcm_stands(int n_s, int n_d, int thr, i
 }  // namespace
 
 // td_tick: the LCM of a thresholded |a - b| model straight from the position arrays (k_lcm_stands).  *ok = 0: the model is
-// not of that kind (a position outside 0..63) — nothing was done, the caller builds the matrix and calls lcm_hinted.
+// not of that kind (a position outside 0..63, fill < threshold) — nothing was done, the caller builds the matrix and calls lcm_hinted.
 int td::lcm_stands(int n_s, int n_d, const int32_t *d_cab_to, const int32_t *d_dem_from, int32_t fill, int32_t threshold, int stop_size,
                    int32_t *rows, int32_t *cols, int32_t *n_pairs, int32_t *last_min, int *ok)
 {
@@ -1582,6 +1584,7 @@ int td::lcm_stands(int n_s, int n_d, const int32_t *d_cab_to, const int32_t *d_d
     const int n = std::max(n_s, n_d);
     *ok = 0;
     if (threshold < 1 || threshold > 64 || n_s > LST_MAXN || n_d > LST_MAXN || stop_size < 0 || stop_size >= n) return TD_OK;
+    if (fill < threshold) return TD_OK;   // a value in 0 .. threshold - 1 would be >= fill: no candidate by the contract, one to the kernel
     int rc;
     if ((rc = ensure(c.lcm_b, sizeof(int32_t) * 2 * (size_t)n))) return rc;
     if ((rc = ensure(c.lcm_d, 512 + sizeof(LcmsInfo) * (size_t)c.n_cu * 4))) return rc;

@@ -1,5 +1,6 @@
 """Stress of the one-call tick (td_tick) and of the sharded paths against the oracle's pipeline (dev tool):
-random numbers of cabs / requests, stand counts, |a-b| or a general table, drop times, LCM stop sizes.
+random numbers of cabs / requests, stand counts, |a-b| or a general table, drop times, LCM stop sizes, big_cost at, below
+and far above the drop time.
 usage: python tools/gpu_stress_tick.py [seed] [seconds]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,15 +18,15 @@ t_end = time.time() + (float(sys.argv[2]) if len(sys.argv) > 2 else 120)
 BIG = 250000
 
 
-def reference(cab_to, dem_from, dist, drop, stop):
-    n_o, cost_o = oracle.cost_build(cab_to, dem_from, dist, BIG, drop)
+def reference(cab_to, dem_from, dist, drop, stop, fill=BIG):
+    n_o, cost_o = oracle.cost_build(cab_to, dem_from, dist, fill, drop)
     if 0 <= stop < n_o:
-        _, rows, cols, lm = oracle.lcm(cost_o, mask=BIG, stop_value_on=1, stop_value=BIG, stop_size=stop, sum_below=BIG, java_scan=1)
+        _, rows, cols, lm = oracle.lcm(cost_o, mask=fill, stop_value_on=1, stop_value=fill, stop_size=stop, sum_below=fill, java_scan=1)
     else:
-        rows, cols, lm = np.zeros(0, np.int64), np.zeros(0, np.int64), BIG
+        rows, cols, lm = np.zeros(0, np.int64), np.zeros(0, np.int64), fill
     keep_c = np.setdiff1d(np.arange(len(cab_to)), rows)
     keep_d = np.setdiff1d(np.arange(len(dem_from)), cols)
-    n2, cost2 = oracle.cost_build(np.asarray(cab_to)[keep_c], np.asarray(dem_from)[keep_d], dist, BIG, drop)
+    n2, cost2 = oracle.cost_build(np.asarray(cab_to)[keep_c], np.asarray(dem_from)[keep_d], dist, fill, drop)
     tot = oracle.assign(cost2)[0] if n2 else 0
     return rows, cols, lm, keep_c, keep_d, n2, cost2, tot
 
@@ -45,13 +46,14 @@ while time.time() < t_end and cnt < max_cnt:
             dist = rng.integers(0, int(rng.choice([5, 25, 400])), (S, S)).astype(np.int32)
         drop = int(rng.choice([1, 3, 10, 40, 10**6]))
         stop = int(rng.choice([-1, 0, 1, 50, 220, 600, 5000]))
-        rows, cols, lm, keep_c, keep_d, n2, cost2, tot = reference(cab_to, dem_from, dist, drop, stop)
-        t = td.tick(cab_to, dem_from, dist, big_cost=BIG, drop_time=drop, max_non_lcm=stop)
+        fill = int(rng.choice([BIG, drop, drop - 1, 0, 2**31 - 1]))   # cells >= big_cost are never LCM candidates
+        rows, cols, lm, keep_c, keep_d, n2, cost2, tot = reference(cab_to, dem_from, dist, drop, stop, fill)
+        t = td.tick(cab_to, dem_from, dist, big_cost=fill, drop_time=drop, max_non_lcm=stop)
         ok = t["lcm_rows"].tolist() == rows.tolist() and t["lcm_cols"].tolist() == cols.tolist()
         ok = ok and (not len(rows) or t["lcm_min_val"] == lm)
         ok = ok and t["kept_cabs"].tolist() == keep_c.tolist() and t["kept_dems"].tolist() == keep_d.tolist()
         ok = ok and t["n_rest"] == n2
-        if 0 <= stop < max(ns, nd) and lm == BIG:   # Simulator.java:188-189: the LCM ran and ended on big_cost (possibly at its first look), the tick has nothing for the solver
+        if 0 <= stop < max(ns, nd) and lm == fill:   # Simulator.java:188-189: the LCM ran and ended on big_cost (possibly at its first look), the tick has nothing for the solver
             ok = ok and not t["solved"] and t["total"] == 0 and len(t["row_to_col"]) == 0
             kinds["tick without a solve"] = kinds.get("tick without a solve", 0) + 1
         else:
@@ -59,7 +61,7 @@ while time.time() < t_end and cnt < max_cnt:
             r2c = t["row_to_col"]
             ok = ok and sorted(r2c.tolist()) == list(range(n2))
             ok = ok and (n2 == 0 or int(cost2[np.arange(n2), r2c].astype(np.int64).sum()) == tot)
-        desc = (what, ns, nd, S, dist is not None, drop, stop)
+        desc = (what, ns, nd, S, dist is not None, drop, stop, fill)
         if not ok and os.environ.get("STRESS_VERBOSE"):
             print("  detail: lcm rows ok %s cols ok %s (k %d vs %d) lm %s vs %s kept ok %s / %s n_rest %s vs %s total %s vs %s solved %s" % (
                 t["lcm_rows"].tolist() == rows.tolist(), t["lcm_cols"].tolist() == cols.tolist(), len(t["lcm_rows"]), len(rows), t["lcm_min_val"], lm,
