@@ -3549,13 +3549,21 @@ int sv_hop_t(Solver &sv, int rpb, int ncols_blk, int col_lo, int nb, bool window
     int *frl = (int *)sv.list.p, *fcl = (int *)sv.pred.p;   // free until the finisher
     const int *ctl = (const int *)sv.misc.p;
     if (gate && nb != 1) return fail(TD_EINTERNAL, "a gated two-hop pass takes one block");
+    // a row of the int32 matrix in more than one segment of k_hop_table (the pass over the whole matrix): one workgroup per
+    // (free row, segment), the table rows preset by k_hop_lists
+    const int nseg = raw && window_zero ? (ncols_blk / 4 + 1023) / 1024 : 1;
     k_hop_lists<<<nb, 1024, 0, c.stream>>>(rpb, ncols_blk, col_lo, (const int *)sv.r2c.p, (const int *)sv.owner.p, frl, fcl, hc, ctl,
-                                           gate ? g_hop_max_rows : 0);
+                                           gate ? g_hop_max_rows : 0, nseg > 1 ? (int *)sv.hoptab.p : nullptr);
     if (raw) {
         if (!sv.d_cost || sv.n % 4) return fail(TD_EINVAL, "two-hop pass on the int32 matrix: no matrix, or n %% 4 != 0");
         k_hop_esc<CT, true><<<(sv.nrows + 3) / 4, 256, 0, c.stream>>>(sv.nrows, sv.n / 4, rpb, ncols_blk, col_lo, g_hop_max_rows,
                                                                       (const CT *)sv.d_cost, (const PT *)sv.price.p, (const int *)sv.r2c.p, fcl,
                                                                       hc, (unsigned long long *)sv.esc.p, ctl, (const int32_t *)sv.rowmin.p);
+        if (nseg > 1)
+            k_hop_table<CT, true, true><<<nb * HOP_FMAX * nseg, 256, 0, c.stream>>>(
+                sv.n, sv.nrows, sv.row0, sv.n / 4, rpb, ncols_blk, col_lo, g_hop_max_rows, 1, (const CT *)sv.d_cost, (const PT *)sv.price.p,
+                (const int *)sv.owner.p, frl, hc, (const unsigned long long *)sv.esc.p, (int *)sv.hoptab.p, ctl, (const int32_t *)sv.rowmin.p, nseg);
+        else
         k_hop_table<CT, true><<<nb * HOP_FMAX, 256, 0, c.stream>>>(sv.n, sv.nrows, sv.row0, sv.n / 4, rpb, ncols_blk, col_lo, g_hop_max_rows,
                                                                    window_zero ? 1 : 0, (const CT *)sv.d_cost, (const PT *)sv.price.p,
                                                                    (const int *)sv.owner.p, frl, hc, (const unsigned long long *)sv.esc.p,
@@ -3569,7 +3577,10 @@ int sv_hop_t(Solver &sv, int rpb, int ncols_blk, int col_lo, int nb, bool window
                                                          (const int *)sv.owner.p, frl, hc, (const unsigned long long *)sv.esc.p,
                                                          (int *)sv.hoptab.p, ctl);
     }
-    k_hop_match<PT><<<nb, HOP_FMAX, sizeof(uint32_t) * (size_t)((rpb + 31) / 32), c.stream>>>(
+    const size_t match_lds = sizeof(uint32_t) * ((size_t)HOP_FMAX * HOP_FMAX + (size_t)((rpb + 31) / 32));   // the table, one bit per row
+    if (match_lds > 150 * 1024) return fail(TD_EINVAL, "two-hop pass: a block of that many rows does not fit the LDS");
+    TD_HIP(hipFuncSetAttribute((const void *)k_hop_match<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)match_lds));   // (above 64 KB)
+    k_hop_match<PT><<<nb, HOP_MATCH_T, match_lds, c.stream>>>(
         sv.nrows, sv.row0, rpb, ncols_blk, col_lo, g_hop_max_rows, (PT *)sv.price.p, (int *)sv.owner.p, (int *)sv.r2c.p, ob, frl, fcl, hc,
         (const int *)sv.hoptab.p, (int *)sv.misc.p);
     TD_HIP(hipGetLastError());

@@ -29,9 +29,10 @@
 //   k_hop_esc    per ASSIGNED row r' (one wave): bit b set iff free column b is tight for r' (c[r'][j'] + p[j'] equals
 //                c[r'][col(r')] + p[col(r')], the row's dual by complementary slackness)
 //   k_hop_table  per free row i (one workgroup): tab[i][b] = the smallest r' such that col(r') is tight for i and
-//                free column b is tight for r' (atomicMin in LDS: independent of scheduling)
-//   k_hop_match  per block (one workgroup): rows in order take the first free column in their rotated order whose
-//                r' is still unused; the winner thread rewires i -> col(r'), r' -> j'.  Deterministic.
+//                free column b is tight for r' (atomicMin in LDS, or per (row, segment) straight into the table:
+//                independent of scheduling)
+//   k_hop_match  per block (one workgroup, the walk in one wave): rows in order take the first free column in their
+//                rotated order whose r' is still unused; then i -> col(r'), r' -> j' is rewired.  Deterministic.
 // Nothing here changes a price, so every pair it creates is tight and the finishers' invariant holds.
 
 // HOP_FMAX (free rows / columns of a block the two-hop pass looks at) and HOP_BMAX (blocks per shard) are defined
@@ -129,9 +130,13 @@ __global__ __launch_bounds__(256) void k_zs_assign(int col_lo, int col_hi, int n
 // gate_max > 0 (one block only: the pass over the whole matrix queued without a read-back): the pass runs only if
 // 0 < HopCtl::left <= gate_max; otherwise the block's counts are set to 0, which makes the pass's other kernels exit,
 // and `left` keeps the value the previous pass left
+// tab_preset != nullptr: the table rows of the block's free rows are set to HOP_NONE, for a k_hop_table<.., SPLIT> whose
+// workgroups take their minima straight into the table
+constexpr int HOP_NONE = INT_MAX;   // table entry "no candidate" as k_hop_table<.., SPLIT> leaves it (the other layout writes -1)
 __global__ __launch_bounds__(1024) void k_hop_lists(int rpb, int ncols_blk, int col_lo, const int *__restrict__ r2c,
                                                     const int *__restrict__ owner, int *__restrict__ frl, int *__restrict__ fcl,
-                                                    HopCtl *__restrict__ hc, const int *__restrict__ ctl, int gate_max = 0)
+                                                    HopCtl *__restrict__ hc, const int *__restrict__ ctl, int gate_max = 0,
+                                                    int *__restrict__ tab_preset = nullptr)
 {
     if (ctl[CTL_FLAG]) return;
     const int lb = blockIdx.x;
@@ -153,6 +158,10 @@ __global__ __launch_bounds__(1024) void k_hop_lists(int rpb, int ncols_blk, int 
         hc->nfr[lb] = nfr;
         hc->nfc[lb] = nfc;
         if (lb == 0) hc->left = 0, hc->matched = 0;
+    }
+    if (tab_preset) {
+        int4 *t4 = reinterpret_cast<int4 *>(tab_preset + (size_t)lb * HOP_FMAX * HOP_FMAX);
+        for (int k = threadIdx.x; k < min(nfr, HOP_FMAX) * (HOP_FMAX / 4); k += 1024) t4[k] = make_int4(HOP_NONE, HOP_NONE, HOP_NONE, HOP_NONE);
     }
 }
 
@@ -215,13 +224,18 @@ __global__ __launch_bounds__(256) void k_hop_esc(int nrows, int nchunks, int rpb
 // per wave: 19 us for a 2048-column slice), then all 256 threads take list entries — owner, escape masks, atomicMin into
 // the table row.  A segment holds at most 256 * E (RAW: 256 * 4 * 4) candidates: the list cannot overflow, the result
 // does not depend on the order of the appends.
-template <typename CT, bool RAW = false>
+// SPLIT (window_zero only): one workgroup per (free row, segment), blockIdx.x = (lb * HOP_FMAX + a) * nseg + segment, and
+// the minima go straight into the table row, which k_hop_lists has preset to HOP_NONE.  The pass over the whole matrix
+// has few free rows and several segments a row (RAW: n / 4096); one workgroup per row left all but a handful of CUs
+// idle while it walked its segments one behind the other.  atomicMin: the table does not depend on the order.
+template <typename CT, bool RAW = false, bool SPLIT = false>
 __global__ __launch_bounds__(256) void k_hop_table(int n, int nrows, int row0, int nchunks, int rpb, int ncols_blk, int col_lo,
                                                    int max_rows, int window_zero, const CT *__restrict__ cc,
                                                    const typename Tr<CT>::PT *__restrict__ pk, const int *__restrict__ owner,
                                                    const int *__restrict__ frl, const HopCtl *__restrict__ hc,
                                                    const unsigned long long *__restrict__ esc, int *__restrict__ tab,
-                                                   const int *__restrict__ ctl, const int32_t *__restrict__ rowmin = nullptr)
+                                                   const int *__restrict__ ctl, const int32_t *__restrict__ rowmin = nullptr,
+                                                   int nseg = 1)
 {
     using PT = typename Tr<CT>::PT;
     constexpr int E = RAW ? 4 : Tr<CT>::E;   // cells per 16 bytes (RAW: the int32 matrix itself, nchunks = n / 4, see k_hop_esc)
@@ -231,7 +245,8 @@ __global__ __launch_bounds__(256) void k_hop_table(int n, int nrows, int row0, i
     __shared__ int s_ncand;
     __shared__ long long s_v[4];
     if (ctl[CTL_FLAG]) return;
-    const int lb = blockIdx.x / HOP_FMAX, a = blockIdx.x % HOP_FMAX;
+    const int seg = SPLIT ? (int)blockIdx.x % nseg : 0, ba = SPLIT ? (int)blockIdx.x / nseg : (int)blockIdx.x;
+    const int lb = ba / HOP_FMAX, a = ba % HOP_FMAX;
     const int nfr = hc->nfr[lb];
     if (nfr > max_rows || a >= min(nfr, HOP_FMAX)) return;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -246,7 +261,8 @@ __global__ __launch_bounds__(256) void k_hop_table(int n, int nrows, int row0, i
         } else
             unpack<CT>(raw, c);
     };
-    if (tid < HOP_FMAX) s_tab[tid] = INT_MAX;
+    int *tab_row = tab + ((size_t)lb * HOP_FMAX + a) * HOP_FMAX;
+    if (!SPLIT && tid < HOP_FMAX) s_tab[tid] = INT_MAX;
     if (tid == 0) s_ncand = 0;
     // the row's columns in question: its block's slice (phase A) or all of them
     const int ch_lo = window_zero ? (col_lo + lb * ncols_blk) / E : 0;
@@ -284,7 +300,7 @@ __global__ __launch_bounds__(256) void k_hop_table(int n, int nrows, int row0, i
         v = min(min(s_v[0], s_v[1]), min(s_v[2], s_v[3]));
     }
     __syncthreads();
-    for (int t0 = 0; t0 < ch_n; t0 += 256 * CHT) {
+    for (int t0 = SPLIT ? seg * 256 * CHT : 0; t0 < (SPLIT ? min(ch_n, (seg + 1) * 256 * CHT) : ch_n); t0 += 256 * CHT) {
         uint4 raws[CHT];
 #pragma unroll
         for (int u = 0; u < CHT; u++) {
@@ -330,98 +346,147 @@ __global__ __launch_bounds__(256) void k_hop_table(int n, int nrows, int row0, i
             if (r < row0 || r >= row0 + nrows) continue;   // a free column (then the rounds take it), or a row of another shard
             if ((r - row0) / rpb != lb) continue;          // (two hops inside the block)
             unsigned long long m0 = esc[(size_t)(r - row0) * 2], m1 = esc[(size_t)(r - row0) * 2 + 1];
+            int *dst = SPLIT ? tab_row : s_tab;
             while (m0) {
                 const int b = __builtin_ctzll(m0);
                 m0 &= m0 - 1;
-                atomicMin(&s_tab[b], r);
+                atomicMin(&dst[b], r);
             }
             while (m1) {
                 const int b = 64 + __builtin_ctzll(m1);
                 m1 &= m1 - 1;
-                atomicMin(&s_tab[b], r);
+                atomicMin(&dst[b], r);
             }
         }
         __syncthreads();
         if (tid == 0) s_ncand = 0;
         __syncthreads();
     }
-    if (tid < HOP_FMAX) tab[((size_t)lb * HOP_FMAX + a) * HOP_FMAX + tid] = s_tab[tid] == INT_MAX ? -1 : s_tab[tid];
+    if (!SPLIT && tid < HOP_FMAX) tab_row[tid] = s_tab[tid] == INT_MAX ? -1 : s_tab[tid];
 }
 
 // ---- two hops: one workgroup per block takes the table rows in order (deterministic greedy) and rewires
+// The walk over the free rows is a serial chain, so it runs in ONE wave and touches nothing but LDS and registers:
+//   - all HOP_MATCH_T threads stage the block's table rows, the rotated starts and the used-row bits in LDS (one barrier);
+//   - wave 0 walks: lane l holds the table entries of free columns l and l + 64.  Two ballots give the 128-bit set of
+//     columns whose r' is still unused, the used columns are two scalar words, and "the first column at or after the
+//     row's rotated start, cyclically" is a few scalar bit operations: the same column as the minimum over the keys
+//     t = (column - st) mod nc that the workgroup-wide version took through LDS and two barriers per row.  Table
+//     entries are read two rows ahead and the used-row bits one row ahead; a bit read one row early misses exactly the
+//     previous winner, which is compared by value.  The winner goes to s_win[], nothing is loaded from global memory;
+//   - after one more barrier thread a rewires match a.  The pairs of different matches share no row and no column (a
+//     free row, an r' and a free column are each used once, col(r') is r''s alone), so these loads and stores need no
+//     order among themselves; inside the walk the load of col(r') was a global round trip per matched row.
+// dynamic LDS: HOP_FMAX * HOP_FMAX table entries, then one bit per row of the block.
+constexpr int HOP_MATCH_T = 256;
 template <typename PT>
-__global__ __launch_bounds__(HOP_FMAX) void k_hop_match(int nrows, int row0, int rpb, int ncols_blk, int col_lo, int max_rows,
-                                                        PT *__restrict__ pk, int *__restrict__ owner, int *__restrict__ r2c,
-                                                        uint8_t *__restrict__ ob, const int *__restrict__ frl,
-                                                        const int *__restrict__ fcl, HopCtl *__restrict__ hc,
-                                                        const int *__restrict__ tab, int *__restrict__ ctl)
+__global__ __launch_bounds__(HOP_MATCH_T) void k_hop_match(int nrows, int row0, int rpb, int ncols_blk, int col_lo, int max_rows,
+                                                           PT *__restrict__ pk, int *__restrict__ owner, int *__restrict__ r2c,
+                                                           uint8_t *__restrict__ ob, const int *__restrict__ frl,
+                                                           const int *__restrict__ fcl, HopCtl *__restrict__ hc,
+                                                           const int *__restrict__ tab, int *__restrict__ ctl)
 {
-    extern __shared__ uint32_t s_usedr[];   // one bit per row of the block
-    __shared__ int s_usedc[HOP_FMAX];
-    __shared__ int s_key[2][2];
+    extern __shared__ uint32_t s_hop_dyn[];
+    __shared__ int s_st[HOP_FMAX];        // rotated start of free row a
+    __shared__ int s_win[HOP_FMAX][2];    // match of free row a: r' (-1: none), free column index
     if (ctl[CTL_FLAG]) return;
     const int lb = blockIdx.x;
     const int nfr = hc->nfr[lb];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     if (nfr == 0) return;
     if (nfr > max_rows) {
         if (tid == 0) atomicAdd(&hc->left, nfr);
         return;
     }
     const int na = min(nfr, HOP_FMAX), nc = min(hc->nfc[lb], HOP_FMAX);
-    for (int k = tid; k < (rpb + 31) / 32; k += HOP_FMAX) s_usedr[k] = 0u;
-    s_usedc[tid] = 0;
-    __syncthreads();
+    int *s_tab = reinterpret_cast<int *>(s_hop_dyn);
+    uint32_t *s_usedr = s_hop_dyn + HOP_FMAX * HOP_FMAX;
     const int *fr = frl + (size_t)lb * rpb, *fc = fcl + (size_t)lb * ncols_blk;
     const int blk_row0 = row0 + lb * rpb;
-    const int my_fc = tid < nc ? fc[tid] : 0;
-    int done = 0;
-    // the table entry and the row id of the NEXT iteration are loaded while this one is decided (the loop is a chain of
-    // dependent global loads otherwise: ~1 us per row)
-    int r_nx = tid < nc ? tab[((size_t)lb * HOP_FMAX + 0) * HOP_FMAX + tid] : -1;
-    int i_nx = blk_row0 + fr[0];
-    for (int a = 0; a < na; a++) {
-        const int r = r_nx, i_g = i_nx;
-        if (a + 1 < na) {
-            r_nx = tid < nc ? tab[((size_t)lb * HOP_FMAX + a + 1) * HOP_FMAX + tid] : -1;
-            i_nx = blk_row0 + fr[a + 1];
+    const int my_i = tid < na ? blk_row0 + fr[tid] : 0;   // free row `tid` of the block
+    {
+        const int4 *src = reinterpret_cast<const int4 *>(tab + (size_t)lb * HOP_FMAX * HOP_FMAX);
+        int4 *dst = reinterpret_cast<int4 *>(s_tab);
+        auto norm = [&](int r, int col) { return (r == HOP_NONE || col >= nc) ? -1 : r; };   // -1: no candidate
+        for (int k = tid; k < na * (HOP_FMAX / 4); k += HOP_MATCH_T) {
+            const int4 x = src[k];
+            const int col = (k * 4) & (HOP_FMAX - 1);
+            dst[k] = make_int4(norm(x.x, col), norm(x.y, col + 1), norm(x.z, col + 2), norm(x.w, col + 3));
         }
-        const uint32_t hsh = ((uint32_t)i_g + 1u) * 0x9E3779B1u;
-        const int st = nc ? (int)(((uint64_t)(hsh ^ (hsh >> 15)) * (uint64_t)nc) >> 32) : 0;
-        int key = INT_MAX;
-        if (r >= 0 && !s_usedc[tid]) {
-            const int rb = r - blk_row0;
-            if (!((s_usedr[rb >> 5] >> (rb & 31)) & 1u)) {
-                int t = tid - st;
-                t += t < 0 ? nc : 0;
-                key = t;
-            }
+        for (int k = tid; k < (rpb + 31) / 32; k += HOP_MATCH_T) s_usedr[k] = 0u;
+        if (tid < na) {
+            const uint32_t hsh = ((uint32_t)my_i + 1u) * 0x9E3779B1u;
+            s_st[tid] = nc ? (int)(((uint64_t)(hsh ^ (hsh >> 15)) * (uint64_t)nc) >> 32) : 0;
         }
-        int best = key;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
-        if (lane == 0) s_key[a & 1][w] = best;
-        __syncthreads();
-        best = min(s_key[a & 1][0], s_key[a & 1][1]);
-        if (best != INT_MAX && key == best) {   // exactly one thread: the keys of a row are distinct
-            const int rl = r - row0, il = i_g - row0;
-            const int j = r2c[rl], jp = col_lo + lb * ncols_blk + my_fc;
-            r2c[il] = j;
-            owner[j] = i_g;
-            r2c[rl] = jp;
-            owner[jp] = r;
-            pk[jp] = pk[jp] | (PT)1;
-            if (ob) ob[jp] = 1;
-            s_usedc[tid] = 1;
-            const int rb = r - blk_row0;
-            atomicOr(&s_usedr[rb >> 5], 1u << (rb & 31));
-        }
-        if (best != INT_MAX) done++;
-        __syncthreads();
     }
-    if (tid == 0) {
-        atomicAdd(&hc->left, nfr - done);
-        atomicAdd(&hc->matched, done);
+    __syncthreads();
+    if (tid < 64) {
+        const int lane = tid;
+        // (no branch around an LDS read: the compiler waits for every read it has to put behind a branch before it goes on,
+        // seven LDS round trips a row; the reads of a row are issued together and used one row later)
+        auto entry = [&](int a, int col) -> int {   // r' of (free row a, free column col < HOP_FMAX), -1: none
+            const int r = s_tab[min(a, HOP_FMAX - 1) * HOP_FMAX + col];
+            return a < na ? r : -1;
+        };
+        auto used = [&](int r) -> bool {   // (a missing entry counts as used)
+            const int rb = max(r - blk_row0, 0);
+            const uint32_t word = s_usedr[rb >> 5];
+            return r < 0 || ((word >> (rb & 31)) & 1u);
+        };
+        unsigned long long usedc0 = 0ull, usedc1 = 0ull;
+        int done = 0, r_prev = -1;
+        int ra0 = entry(0, lane), ra1 = entry(0, lane + 64);   // this row's entries
+        int rb0 = entry(1, lane), rb1 = entry(1, lane + 64);   // the next row's
+        bool ua0 = used(ra0), ua1 = used(ra1);
+        int st = s_st[0];
+        for (int a = 0; a < na; a++) {
+            // reads for the rows to come: issued in front of this row's write to s_usedr
+            const int rc0 = entry(a + 2, lane), rc1 = entry(a + 2, lane + 64);
+            const bool ub0 = used(rb0), ub1 = used(rb1);
+            const int st_nx = s_st[min(a + 1, HOP_FMAX - 1)];
+            const unsigned long long m0 = __ballot(!ua0 && ra0 != r_prev) & ~usedc0;
+            const unsigned long long m1 = __ballot(!ua1 && ra1 != r_prev) & ~usedc1;
+            int rw = -1, cw = 0;
+            if (m0 | m1) {
+                const unsigned long long h0 = st < 64 ? m0 & (~0ull << st) : 0ull;
+                const unsigned long long h1 = st < 64 ? m1 : m1 & (~0ull << (st - 64));
+                if (h0 | h1) cw = h0 ? __builtin_ctzll(h0) : 64 + __builtin_ctzll(h1);
+                else cw = m0 ? __builtin_ctzll(m0) : 64 + __builtin_ctzll(m1);
+                rw = __builtin_amdgcn_readlane(cw < 64 ? ra0 : ra1, cw & 63);   // (cw is wave-uniform)
+                if (cw < 64) usedc0 |= 1ull << cw;
+                else usedc1 |= 1ull << (cw - 64);
+                r_prev = rw;
+                done++;
+            }
+            if (lane == 0) {
+                s_win[a][0] = rw, s_win[a][1] = cw;
+                if (rw >= 0) {
+                    const int rb = rw - blk_row0;
+                    atomicOr(&s_usedr[rb >> 5], 1u << (rb & 31));   // (no value comes back: nothing to wait for)
+                }
+            }
+            // one wave: LDS takes its accesses in program order, the fence keeps the compiler to it
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            ra0 = rb0, ra1 = rb1, ua0 = ub0, ua1 = ub1;
+            rb0 = rc0, rb1 = rc1;
+            st = st_nx;
+        }
+        if (lane == 0) {
+            atomicAdd(&hc->left, nfr - done);
+            atomicAdd(&hc->matched, done);
+        }
+    }
+    __syncthreads();
+    if (tid < na && s_win[tid][0] >= 0) {
+        const int r = s_win[tid][0], i_g = my_i;
+        const int rl = r - row0, il = i_g - row0;
+        const int j = r2c[rl], jp = col_lo + lb * ncols_blk + fc[s_win[tid][1]];
+        r2c[il] = j;
+        owner[j] = i_g;
+        r2c[rl] = jp;
+        owner[jp] = r;
+        pk[jp] = pk[jp] | (PT)1;
+        if (ob) ob[jp] = 1;
     }
 }
 

@@ -60,7 +60,7 @@ int to_device(const void *src, size_t bytes, Buf &stage, const void **out);
 // td_line.hip: sorted matching + certificate pass for line-metric matrices (tried first by td_assign)
 //   line_probe_launch  queues the O(n) probe; *skip_dev = device word that is non-zero unless the probe refuses;
 //                      clear_words non-null: the probe also zeroes clear_words[0 .. nclear) (td_assign's control words)
-//   line_probe_wait    waits for the probe alone (an event, not the stream) and returns its verdict:
+//   line_probe_wait    waits for the probe alone (its call number in the pinned verdict block, not the stream) and returns its verdict:
 //                      0 refused, 1 plausible, 2 constant trailing columns (retry on the transpose),
 //                      3 plausible with *k constant rows (the unbalanced model)
 //   line_finish        keys, sort, prices, certificate pass; *accepted = 1: *r2c_dev / *total are proven optimal

@@ -26,6 +26,7 @@
 // (exact 64-bit arithmetic), otherwise td_assign runs the general solver as before.  Step 5 is the only
 // O(n^2) step and it is HBM-bound: 4 n^2 bytes read once.
 #include <limits.h>
+#include <chrono>
 
 #include <hipcub/hipcub.hpp>
 
@@ -37,6 +38,7 @@ namespace {
 // LC_PLAUS: 0 refused; 1 balanced line metric plausible; 2 constant trailing COLUMNS (retry on the transpose);
 //           3 plausible with LC_K constant rows (the unbalanced model: fewer cabs than requests)
 enum { LC_P = 0, LC_Q, LC_I1, LC_I2, LC_PLAUS, LC_REV, LC_FAIL, LC_FITS32, LC_TOTAL, LC_K, LC_FILL, LC_SKIP, LC_WORDS };
+constexpr int VERDICT_SEQ = 7;  // word of the probe's verdict block (pinned host memory) that takes the call number, last
 constexpr int LINE_KMAX = 256;  // most constant rows the unbalanced plan is made for: k prefix-min scans of n by one workgroup and O(k n) scratch (k = 256, n = 16 384: ~4 ms and 100 MB against > 400 ms for the general solver; 32 until round 3)
 
 struct LineWs {
@@ -93,7 +95,7 @@ __device__ inline bool span_ok(long long x, long long y, long long D) { return x
 //   rev: the column keys must be negated when the two key orders run in opposite directions
 __global__ __launch_bounds__(1024) void k_line_probe(int n, const int32_t *__restrict__ c, long long *__restrict__ ctl,
                                                      long long *__restrict__ host_verdict, int *__restrict__ clear_words = nullptr,
-                                                     int nclear = 0)
+                                                     int nclear = 0, long long seq = 0 /* this call's number: published behind the verdict */)
 {
     // td_assign's control words, cleared here for the compress pass queued behind the probe (no memset in between)
     for (int k = threadIdx.x; k < nclear; k += blockDim.x) clear_words[k] = 0;
@@ -297,6 +299,9 @@ __global__ __launch_bounds__(1024) void k_line_probe(int n, const int32_t *__res
         host_verdict[1] = kdummy;
         host_verdict[2] = suspicious;
         __threadfence_system();
+        // the host waits for this word (line_probe_wait): no event, whose barrier packet kept the kernel queued behind the
+        // probe waiting for about 5 us
+        __hip_atomic_store(&host_verdict[VERDICT_SEQ], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -868,22 +873,22 @@ __global__ void k_lsh_publish(const long long *__restrict__ ctl, long long *__re
 }  // namespace
 
 constexpr size_t VERDICT_OFF = 4096;   // byte offset of the probe's verdict in the pinned host block (clear of the other read-backs)
-hipEvent_t g_probe_done = nullptr;
+long long g_probe_seq = 0;   // number of the probe in flight (the verdict block's word VERDICT_SEQ once it is done)
 
 int line_probe_launch(int n, const int32_t *d_cost, const long long **skip_dev, int *clear_words, int nclear)
 {
     Ctx &c = ctx();
     int rc;
     if ((rc = ensure(g_lw.ctl, 256))) return rc;
-    if (!g_probe_done) TD_HIP(hipEventCreateWithFlags(&g_probe_done, hipEventDisableTiming));
     long long *ctl = (long long *)g_lw.ctl.p;
+    long long *verdict = (long long *)((char *)c.pinned + VERDICT_OFF);
+    ((volatile long long *)verdict)[VERDICT_SEQ] = 0;   // (no probe is in flight: the one before was waited for)
+    g_probe_seq++;
     {
         ProfScope ps(TD_K_LINE);
-        k_line_probe<<<1, 1024, 0, c.stream>>>(n, d_cost, ctl, (long long *)((char *)c.pinned + VERDICT_OFF), clear_words,
-                                               clear_words ? nclear : 0);
+        k_line_probe<<<1, 1024, 0, c.stream>>>(n, d_cost, ctl, verdict, clear_words, clear_words ? nclear : 0, g_probe_seq);
         TD_HIP(hipGetLastError());
     }
-    TD_HIP(hipEventRecord(g_probe_done, c.stream));
     *skip_dev = ctl + LC_SKIP;
     return TD_OK;
 }
@@ -891,8 +896,17 @@ int line_probe_launch(int n, const int32_t *d_cost, const long long **skip_dev, 
 int line_probe_wait(int *mode, int *k, int *suspicious, int *shape3)
 {
     Ctx &c = ctx();
-    TD_HIP(hipEventSynchronize(g_probe_done));
+    // The probe stores its call number behind the verdict in the pinned block.  The host looks at that word for a bounded
+    // time (the probe is a few microseconds behind whatever was queued in front of it), then waits for the stream.
     const volatile long long *h = (const volatile long long *)((char *)c.pinned + VERDICT_OFF);
+    const auto t0 = std::chrono::steady_clock::now();
+    while (__atomic_load_n((const long long *)&h[VERDICT_SEQ], __ATOMIC_ACQUIRE) != g_probe_seq) {
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
+            TD_HIP(hipStreamSynchronize(c.stream));
+            if (h[VERDICT_SEQ] != g_probe_seq) return fail(TD_EINTERNAL, "the line probe's verdict was not written");
+            break;
+        }
+    }
     *mode = (int)h[0];
     *k = (int)h[1];
     if (suspicious) *suspicious = (int)h[2];
@@ -981,8 +995,6 @@ int line_finish(int n, int k, const int32_t *d_cost, const int32_t **r2c_dev, in
 
 void line_release_workspace()
 {
-    if (g_probe_done) (void)hipEventDestroy(g_probe_done);
-    g_probe_done = nullptr;
     Buf *bs[] = {&g_lw.ctl, &g_lw.kin,  &g_lw.kout, &g_lw.vin, &g_lw.vout, &g_lw.tmp, &g_lw.f,  &g_lw.v64, &g_lw.v32,
                  &g_lw.r2c, &g_lw.band, &g_lw.P,    &g_lw.E,   &g_lw.ARG,  &g_lw.Bk,  &g_lw.L,  &g_lw.mcol};
     for (Buf *b : bs) buf_free(*b);
