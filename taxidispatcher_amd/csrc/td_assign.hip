@@ -3231,11 +3231,11 @@ struct td_shard {
     bool state_ready = false;  // sharded solve: the state was initialised in front of the compress pass and phase A has run on it (td_shard_begin must not redo it)
     bool ctl_clear = false;    // the control words were cleared by a kernel queued in front of the next compress pass (the line probe): no memset
     bool ob_clear = false;     // phase A's owned-column bytes were cleared by k_init_state in front of the compress pass: no memset
-    Buf ob, esc, hop, hoptab;  // owned bytes per column, escape masks per row, HopCtl, the two-hop tables
+    Buf ob, hop, hoptab;       // owned bytes per column, HopCtl, the two-hop tables
     Buf core, core_n, core_t, core_need;   // sparse core of the warm start (td_core_warm.h): lists, their lengths, the smallest value outside, the rows that need their dense row
     void free_all()
     {
-        Buf *bs[] = {&stage, &cc, &price, &owner, &r2c, &r2c_full, &bid, &pred, &list, &rowmin, &rconst, &misc, &psrec, &tbuf, &xbuf, &fbuf, &cmask, &ob, &esc, &hop, &hoptab, &core, &core_n, &core_t, &core_need, &genbuf, &gpos};
+        Buf *bs[] = {&stage, &cc, &price, &owner, &r2c, &r2c_full, &bid, &pred, &list, &rowmin, &rconst, &misc, &psrec, &tbuf, &xbuf, &fbuf, &cmask, &ob, &hop, &hoptab, &core, &core_n, &core_t, &core_need, &genbuf, &gpos};
         for (Buf *b : bs) buf_free(*b);
     }
 };
@@ -3542,7 +3542,6 @@ int sv_hop_t(Solver &sv, int rpb, int ncols_blk, int col_lo, int nb, bool window
     Ctx &c = ctx();
     using PT = typename Tr<CT>::PT;
     int rc;
-    if ((rc = ensure(sv.esc, sizeof(unsigned long long) * 2 * (size_t)std::max(sv.nrows, 1)))) return rc;
     if ((rc = ensure(sv.hop, sizeof(HopCtl)))) return rc;
     if ((rc = ensure(sv.hoptab, sizeof(int) * (size_t)nb * HOP_FMAX * HOP_FMAX))) return rc;
     HopCtl *hc = (HopCtl *)sv.hop.p;
@@ -3556,26 +3555,19 @@ int sv_hop_t(Solver &sv, int rpb, int ncols_blk, int col_lo, int nb, bool window
                                            gate ? g_hop_max_rows : 0, nseg > 1 ? (int *)sv.hoptab.p : nullptr);
     if (raw) {
         if (!sv.d_cost || sv.n % 4) return fail(TD_EINVAL, "two-hop pass on the int32 matrix: no matrix, or n %% 4 != 0");
-        k_hop_esc<CT, true><<<(sv.nrows + 3) / 4, 256, 0, c.stream>>>(sv.nrows, sv.n / 4, rpb, ncols_blk, col_lo, g_hop_max_rows,
-                                                                      (const CT *)sv.d_cost, (const PT *)sv.price.p, (const int *)sv.r2c.p, fcl,
-                                                                      hc, (unsigned long long *)sv.esc.p, ctl, (const int32_t *)sv.rowmin.p);
         if (nseg > 1)
             k_hop_table<CT, true, true><<<nb * HOP_FMAX * nseg, 256, 0, c.stream>>>(
                 sv.n, sv.nrows, sv.row0, sv.n / 4, rpb, ncols_blk, col_lo, g_hop_max_rows, 1, (const CT *)sv.d_cost, (const PT *)sv.price.p,
-                (const int *)sv.owner.p, frl, hc, (const unsigned long long *)sv.esc.p, (int *)sv.hoptab.p, ctl, (const int32_t *)sv.rowmin.p, nseg);
+                (const int *)sv.owner.p, frl, fcl, hc, (int *)sv.hoptab.p, ctl, (const int32_t *)sv.rowmin.p, nseg);
         else
         k_hop_table<CT, true><<<nb * HOP_FMAX, 256, 0, c.stream>>>(sv.n, sv.nrows, sv.row0, sv.n / 4, rpb, ncols_blk, col_lo, g_hop_max_rows,
                                                                    window_zero ? 1 : 0, (const CT *)sv.d_cost, (const PT *)sv.price.p,
-                                                                   (const int *)sv.owner.p, frl, hc, (const unsigned long long *)sv.esc.p,
-                                                                   (int *)sv.hoptab.p, ctl, (const int32_t *)sv.rowmin.p);
+                                                                   (const int *)sv.owner.p, frl, fcl, hc, (int *)sv.hoptab.p, ctl,
+                                                                   (const int32_t *)sv.rowmin.p);
     } else {
-    k_hop_esc<CT><<<(sv.nrows + 3) / 4, 256, 0, c.stream>>>(sv.nrows, sv.nchunks, rpb, ncols_blk, col_lo, g_hop_max_rows, (const CT *)sv.cc.p,
-                                                            (const PT *)sv.price.p, (const int *)sv.r2c.p, fcl, hc,
-                                                            (unsigned long long *)sv.esc.p, ctl);
     k_hop_table<CT><<<nb * HOP_FMAX, 256, 0, c.stream>>>(sv.n, sv.nrows, sv.row0, sv.nchunks, rpb, ncols_blk, col_lo, g_hop_max_rows,
                                                          window_zero ? 1 : 0, (const CT *)sv.cc.p, (const PT *)sv.price.p,
-                                                         (const int *)sv.owner.p, frl, hc, (const unsigned long long *)sv.esc.p,
-                                                         (int *)sv.hoptab.p, ctl);
+                                                         (const int *)sv.owner.p, frl, fcl, hc, (int *)sv.hoptab.p, ctl);
     }
     const size_t match_lds = sizeof(uint32_t) * ((size_t)HOP_FMAX * HOP_FMAX + (size_t)((rpb + 31) / 32));   // the table, one bit per row
     if (match_lds > 150 * 1024) return fail(TD_EINVAL, "two-hop pass: a block of that many rows does not fit the LDS");

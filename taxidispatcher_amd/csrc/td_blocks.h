@@ -26,11 +26,10 @@
 // The two-hop kernels are written for general prices (tight = reduced cost 0 against the row's dual), windowed to a
 // block's columns only in phase A, where the zero-cell rule stands in for the row minimum.
 //   k_hop_lists  per block: the free rows / free columns (block-relative, ordered), at most HOP_FMAX of each used
-//   k_hop_esc    per ASSIGNED row r' (one wave): bit b set iff free column b is tight for r' (c[r'][j'] + p[j'] equals
-//                c[r'][col(r')] + p[col(r')], the row's dual by complementary slackness)
 //   k_hop_table  per free row i (one workgroup): tab[i][b] = the smallest r' such that col(r') is tight for i and
-//                free column b is tight for r' (atomicMin in LDS, or per (row, segment) straight into the table:
-//                independent of scheduling)
+//                free column b is tight for r' (c[r'][j'] + p[j'] equals c[r'][col(r')] + p[col(r')], the row's dual by
+//                complementary slackness; tested for the rows r' the free row reaches: nobody reads anyone else's).
+//                atomicMin in LDS, or per (row, segment) straight into the table: independent of scheduling
 //   k_hop_match  per block (one workgroup, the walk in one wave): rows in order take the first free column in their
 //                rotated order whose r' is still unused; then i -> col(r'), r' -> j' is rewired.  Deterministic.
 // Nothing here changes a price, so every pair it creates is tight and the finishers' invariant holds.
@@ -165,65 +164,17 @@ __global__ __launch_bounds__(1024) void k_hop_lists(int rpb, int ncols_blk, int 
     }
 }
 
-// ---- two hops: which free columns of its block is an assigned row tight to (one wave per row)
-// RAW: `cc` is the caller's int32 matrix (row pitch = nchunks * 4 = n) and a cell is c - rowmin[row]: the same value the
-// narrow copy holds, for a solve whose compress pass stored the diagonal slices only (k_compress_reg diag_only).
-template <typename CT, bool RAW = false>
-__global__ __launch_bounds__(256) void k_hop_esc(int nrows, int nchunks, int rpb, int ncols_blk, int col_lo, int max_rows,
-                                                 const CT *__restrict__ cc, const typename Tr<CT>::PT *__restrict__ pk,
-                                                 const int *__restrict__ r2c, const int *__restrict__ fcl,
-                                                 const HopCtl *__restrict__ hc, unsigned long long *__restrict__ esc,
-                                                 const int *__restrict__ ctl, const int32_t *__restrict__ rowmin = nullptr)
-{
-    using PT = typename Tr<CT>::PT;
-    if (ctl[CTL_FLAG]) return;
-    const int lane = threadIdx.x & 63;
-    const int lrow = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (lrow >= nrows) return;
-    const int lb = lrow / rpb;
-    const int nfr = hc->nfr[lb];
-    if (nfr == 0 || nfr > max_rows) return;   // nothing to do for this block, or left to the rounds (uniform per wave)
-    const int nfc = min(hc->nfc[lb], HOP_FMAX);
-    const int j = r2c[lrow];
-    unsigned long long m0 = 0, m1 = 0;
-    if (j >= 0) {
-        const size_t pitch = (size_t)nchunks * (RAW ? 4 : Tr<CT>::E);
-        const CT *rp = cc + (RAW ? 0 : (size_t)lrow * pitch);
-        const int32_t *rr = reinterpret_cast<const int32_t *>(cc) + (RAW ? (size_t)lrow * pitch : 0);
-        const int32_t mn = RAW ? rowmin[lrow] : 0;
-        auto cell = [&](int col) -> long long {
-            if constexpr (RAW) return (long long)(uint32_t)(rr[col] - mn);
-            else return (long long)(uint32_t)rp[col];
-        };
-        const long long u = cell(j) + (long long)(pk[j] >> 1);   // the row's dual (its pair is tight)
-        const int *fc = fcl + (size_t)lb * ncols_blk;
-        const int cb = col_lo + lb * ncols_blk;
-        bool t0 = false, t1 = false;
-        if (lane < nfc) {
-            const int jb = cb + fc[lane];
-            t0 = cell(jb) + (long long)(pk[jb] >> 1) == u;
-        }
-        if (lane + 64 < nfc) {
-            const int jb = cb + fc[lane + 64];
-            t1 = cell(jb) + (long long)(pk[jb] >> 1) == u;
-        }
-        m0 = __ballot(t0);
-        m1 = __ballot(t1);
-    }
-    if (lane == 0) {
-        esc[(size_t)lrow * 2] = m0;
-        esc[(size_t)lrow * 2 + 1] = m1;
-    }
-}
-
 // ---- two hops: per free row the table row tab[b] = smallest r' (global id) with col(r') tight for the row and free
 // column b tight for r'.  window_zero = 1: only the block's column slice is read and "tight" means a zero cell at
 // price 0 (phase A); 0: the whole row, tight against the row's minimum of c + p.
 // The row is taken in segments of 256 chunks (one per thread): the tight cells of a segment go to a list in LDS first
 // (a thread-private walk over its 16 cells with three dependent loads behind every hit cost 16 serialised load chains
-// per wave: 19 us for a 2048-column slice), then all 256 threads take list entries — owner, escape masks, atomicMin into
-// the table row.  A segment holds at most 256 * E (RAW: 256 * 4 * 4) candidates: the list cannot overflow, the result
-// does not depend on the order of the appends.
+// per wave: 19 us for a 2048-column slice), then all 256 threads take list entries and keep those whose owner r' is a row
+// of the block in a second list, then one thread per (r', free column) pair tests the column against the row's dual and
+// takes atomicMin into the table row: the gathers of all pairs are independent of one another.  (A kernel of its own that
+// made a 128-bit mask of tight free columns for EVERY assigned row, one wave a row, cost 9.6 + 4.9 + 9.6 us per step at
+// n = 16 384 and 71 us in the first pass at n = 65 536; a pass reads the masks of a few dozen rows.)  A segment holds at most
+// 256 * E (RAW: 256 * 4 * 4) candidates: the lists cannot overflow, the result does not depend on the order of the appends.
 // SPLIT (window_zero only): one workgroup per (free row, segment), blockIdx.x = (lb * HOP_FMAX + a) * nseg + segment, and
 // the minima go straight into the table row, which k_hop_lists has preset to HOP_NONE.  The pass over the whole matrix
 // has few free rows and several segments a row (RAW: n / 4096); one workgroup per row left all but a handful of CUs
@@ -232,18 +183,21 @@ template <typename CT, bool RAW = false, bool SPLIT = false>
 __global__ __launch_bounds__(256) void k_hop_table(int n, int nrows, int row0, int nchunks, int rpb, int ncols_blk, int col_lo,
                                                    int max_rows, int window_zero, const CT *__restrict__ cc,
                                                    const typename Tr<CT>::PT *__restrict__ pk, const int *__restrict__ owner,
-                                                   const int *__restrict__ frl, const HopCtl *__restrict__ hc,
-                                                   const unsigned long long *__restrict__ esc, int *__restrict__ tab,
+                                                   const int *__restrict__ frl, const int *__restrict__ fcl,
+                                                   const HopCtl *__restrict__ hc, int *__restrict__ tab,
                                                    const int *__restrict__ ctl, const int32_t *__restrict__ rowmin = nullptr,
                                                    int nseg = 1)
 {
     using PT = typename Tr<CT>::PT;
-    constexpr int E = RAW ? 4 : Tr<CT>::E;   // cells per 16 bytes (RAW: the int32 matrix itself, nchunks = n / 4, see k_hop_esc)
+    constexpr int E = RAW ? 4 : Tr<CT>::E;   // cells per 16 bytes (RAW: the int32 matrix itself, nchunks = n / 4, and a cell is c - rowmin[row]: the value the narrow copy holds, for a solve whose compress pass stored the diagonal slices only, k_compress_reg diag_only)
     __shared__ int s_tab[HOP_FMAX];
     constexpr int CHT = RAW ? 4 : 1;   // 16-byte pieces per thread and segment (RAW: 4 cells a piece, the same 4096-entry list as 1-byte cells)
     __shared__ int s_cand[256 * E * CHT];
-    __shared__ int s_ncand;
+    __shared__ int s_hr[256 * E * CHT], s_hj[256 * E * CHT];   // the candidates owned by a row r' of the block: r' (local), its column
+    __shared__ int s_fc[HOP_FMAX];                             // the block's free columns, the first HOP_FMAX
+    __shared__ int s_ncand, s_nhit;
     __shared__ long long s_v[4];
+    constexpr int HU = 4;
     if (ctl[CTL_FLAG]) return;
     const int seg = SPLIT ? (int)blockIdx.x % nseg : 0, ba = SPLIT ? (int)blockIdx.x / nseg : (int)blockIdx.x;
     const int lb = ba / HOP_FMAX, a = ba % HOP_FMAX;
@@ -261,9 +215,17 @@ __global__ __launch_bounds__(256) void k_hop_table(int n, int nrows, int row0, i
         } else
             unpack<CT>(raw, c);
     };
+    // a cell of an assigned row r' (local id) as the row's dual sees it
+    auto ecell = [&](int rl, int col) -> long long {
+        if constexpr (RAW) return (long long)(uint32_t)(reinterpret_cast<const int32_t *>(cc)[(size_t)rl * pitch + col] - rowmin[rl]);
+        else return (long long)(uint32_t)cc[(size_t)rl * pitch + col];
+    };
+    const int nfc = min(hc->nfc[lb], HOP_FMAX);
+    const int cb = col_lo + lb * ncols_blk;
+    if (tid < nfc) s_fc[tid] = fcl[(size_t)lb * ncols_blk + tid];
     int *tab_row = tab + ((size_t)lb * HOP_FMAX + a) * HOP_FMAX;
     if (!SPLIT && tid < HOP_FMAX) s_tab[tid] = INT_MAX;
-    if (tid == 0) s_ncand = 0;
+    if (tid == 0) s_ncand = 0, s_nhit = 0;
     // the row's columns in question: its block's slice (phase A) or all of them
     const int ch_lo = window_zero ? (col_lo + lb * ncols_blk) / E : 0;
     const int ch_n = window_zero ? (ncols_blk + E - 1) / E : nchunks;
@@ -342,24 +304,43 @@ __global__ __launch_bounds__(256) void k_hop_table(int n, int nrows, int row0, i
         __syncthreads();
         const int nc = s_ncand;
         for (int k = tid; k < nc; k += 256) {
-            const int r = owner[s_cand[k]];
+            const int j = s_cand[k], r = owner[j];
             if (r < row0 || r >= row0 + nrows) continue;   // a free column (then the rounds take it), or a row of another shard
             if ((r - row0) / rpb != lb) continue;          // (two hops inside the block)
-            unsigned long long m0 = esc[(size_t)(r - row0) * 2], m1 = esc[(size_t)(r - row0) * 2 + 1];
-            int *dst = SPLIT ? tab_row : s_tab;
-            while (m0) {
-                const int b = __builtin_ctzll(m0);
-                m0 &= m0 - 1;
-                atomicMin(&dst[b], r);
-            }
-            while (m1) {
-                const int b = 64 + __builtin_ctzll(m1);
-                m1 &= m1 - 1;
-                atomicMin(&dst[b], r);
-            }
+            const int h = atomicAdd(&s_nhit, 1);
+            s_hr[h] = r - row0, s_hj[h] = j;
         }
         __syncthreads();
-        if (tid == 0) s_ncand = 0;
+        // one thread per (r', free column b) pair, HU pairs of a thread in flight: b is tight for r' iff c[r'][b] + p[b] equals
+        // c[r'][col(r')] + p[col(r')], the row's dual by complementary slackness (col(r') is the candidate column itself)
+        const int np = s_nhit * nfc;
+        int *dst = SPLIT ? tab_row : s_tab;
+        for (int p0 = 0; p0 < np; p0 += 256 * HU) {
+            long long du[HU], dx[HU];
+            int rg[HU], bb[HU];
+            bool live[HU];
+#pragma unroll
+            for (int q = 0; q < HU; q++) {
+                const int p = min(p0 + q * 256 + tid, np - 1);
+                const int h = p / nfc, b = p - h * nfc;
+                const int rl = s_hr[h], j = s_hj[h], jb = cb + s_fc[b];
+                rg[q] = rl + row0, bb[q] = b;
+                // (an entry that is no larger already cannot change: no gathers for the pair.  Entries only go down, so a stale
+                // read costs gathers, never a result; a row r' is reached by several free rows once a block has more free rows
+                // than a row has tight cells per free row, n = 65 536: 2.6 tests per (r', column) without this)
+                live[q] = SPLIT || s_tab[b] > rg[q];
+                du[q] = dx[q] = 0;
+                if (live[q]) {
+                    du[q] = ecell(rl, j) + (long long)(pk[j] >> 1);
+                    dx[q] = ecell(rl, jb) + (long long)(pk[jb] >> 1);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < HU; q++)
+                if (live[q] && p0 + q * 256 + tid < np && du[q] == dx[q]) atomicMin(&dst[bb[q]], rg[q]);
+        }
+        __syncthreads();
+        if (tid == 0) s_ncand = 0, s_nhit = 0;
         __syncthreads();
     }
     if (!SPLIT && tid < HOP_FMAX) tab_row[tid] = s_tab[tid] == INT_MAX ? -1 : s_tab[tid];

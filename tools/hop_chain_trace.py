@@ -1,11 +1,14 @@
-"""Per-step figures of a g1 benchmark run from a rocprofv3 kernel trace (profiles/hop_chain/README.md).
+"""Per-step figures of a g1 benchmark run from a rocprofv3 kernel trace (profiles/hop_chain/README.md,
+profiles/hop_fold/README.md).
 
     rocprofv3 --kernel-trace --stats -d DIR -o NAME --output-format csv -- python bench.py --steps 15
     python tools/hop_chain_trace.py DIR/NAME_kernel_trace.csv [warm-up steps to drop, default 3]
 
 A step runs from one k_gen_uniform to the last k_final before the next.  Prints the median (min - max) over the steps of
 every kernel's time in launch order, of the time from the end of k_gen_uniform to the start of the compress pass, and of
-the time from the end of the compress pass to the end of k_final.
+the time from the end of the compress pass to the end of k_final.  The k_hop_* launches carry the number of their two-hop
+pass (a pass ends with its k_hop_match, whichever kernels it is made of: four while k_hop_esc made the masks of tight
+free columns, three since k_hop_table tests them itself), and every pass gets a line with its sum.
 """
 import csv
 import re
@@ -38,8 +41,17 @@ def main():
         return "%7.1f (%.1f - %.1f)" % (statistics.median(v) / 1e3, min(v) / 1e3, max(v) / 1e3)
 
     print("%d steps of %d launches; us, median (min - max)" % (len(steps), len(shape)))
+    npass, passes = 1, {}
     for i, name in enumerate(shape):
-        print("  %-56s %s" % (name[:56], stat([s[i][2] - s[i][1] for s in steps])))
+        label = name
+        if name.startswith("k_hop_"):
+            label = "%s  [two-hop pass %d]" % (name, npass)
+            passes.setdefault(npass, []).append(i)
+            if name.startswith("k_hop_match"):
+                npass += 1
+        print("  %-72s %s" % (label[:72], stat([s[i][2] - s[i][1] for s in steps])))
+    for k, idx in sorted(passes.items()):
+        print("two-hop pass %d: %d launches, kernel time            %s" % (k, len(idx), stat([sum(s[i][2] - s[i][1] for i in idx) for s in steps])))
     ci = next(i for i, n in enumerate(shape) if n.startswith("k_compress"))
     fi = max(i for i, n in enumerate(shape) if n.startswith("k_final"))
     print("end of k_gen_uniform -> start of compress   %s" % stat([s[ci][1] - s[0][2] for s in steps]))
