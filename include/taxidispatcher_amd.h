@@ -268,6 +268,48 @@ TD_API int td_tick(const int32_t *cab_to, int n_s, const int32_t *dem_from, int 
                    int64_t *total);
 TD_API void td_tick_release_workspace(void);
 
+/* ---- a simulator world in device memory (Simulator.java:151-211, the whole tick loop) -----------------
+ * The handle owns the request table (id, from, to, at, cab_assigned, picked_at, pool_id, pool_plan, pool_cost) and the
+ * fleet (from, to, client, on_board, time_started) in HBM; they never leave the device.  Cab i starts at stand
+ * i % n_stands (initSupply :565-573); distances are |a - b| on n_stands stands.  A tick is
+ *   td_sim_begin   checkIfCabAtDestination (:220-254), createTempDemand incl. the drop (:329-355), createTempSupply
+ *                  (:358-372), findPool (td_pool2 on the device lists) and analyzePool (:760-784; skipped without supply).
+ *                  info = {has_demand, demand before pooling, supply, demand after pooling}; has_demand == 0: the tick
+ *                  is over (Simulator.java:160), no td_sim_apply follows.
+ *   td_sim_model   the tick's model: cab_to[supply], dem_from[demand after pooling], host or device destination.
+ *   td_sim_apply   the decisions, from any source: the LCM pairs (indices into the model; read only when the model is
+ *                  larger than max_non_lcm: analyzePairs :613-674, which also leaves the kept cabs / requests in order) and,
+ *                  when `solved`, row_to_col[n_r2c] over the kept lists (the whole model when no LCM ran):
+ *                  analyzeSolution :375-421.  *opt_count = the line's "OPT count", -1 when the LCM ran and solved == 0
+ *                  (:188-189, the line has none).  A cab and a request occur in at most one pair, a request in at most
+ *                  one row_to_col cell (what td_tick returns); a pair outside the model is TD_EINVAL and applies nothing.
+ *   td_sim_step    begin + td_tick(dist NULL, fill big_cost, threshold drop_time, stop_size max_non_lcm) on the device
+ *                  lists + apply.  line = {has line, demand, supply, LCM ran, pairs, sent to solver, demand and supply
+ *                  of the remainder, OPT count or -1}.
+ * Per tick only the counters and the small lists (pairs, kept lists, row_to_col) cross PCIe.  Request ids must be unique
+ * and not negative, stands lie in 0 .. n_stands - 1 (at most 2^18 stands), arrival times are not negative: td_sim_create
+ * checks it.  Input arrays may be host or device memory.  All calls are synchronous, on the library's one stream.
+ * Sequencing: ticks run forward (td_sim_begin with t <= the last begun tick is TD_EINVAL, and so is a begin while a tick
+ * with demand waits for its apply); td_sim_model / td_sim_apply need a begun tick with has_demand == 1.  Handles are
+ * independent worlds; td_workspace_bytes counts their memory until td_sim_destroy.
+ * td_sim_state: any pointer may be NULL; cab arrays [n_cabs] (client = the request id, -1 none), request arrays [n_req].
+ * td_sim_metrics: Simulator.m in its order: total_dropped, total_pickup_time, total_pickup_numb, total_LCM_used,
+ * max_model_size, max_solver_size, max_POOL_MEM_size, max_POOL_size, total_second_passengers. */
+typedef struct td_sim td_sim;
+#define TD_SIM_N_METRICS 9
+TD_API int td_sim_create(int n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost, int n_req,
+                         const int32_t *req_id, const int32_t *req_from, const int32_t *req_to, const int32_t *req_at,
+                         td_sim **out);
+TD_API int td_sim_destroy(td_sim *s);
+TD_API int td_sim_begin(td_sim *s, int t, int32_t info[4]);
+TD_API int td_sim_model(td_sim *s, int32_t *cab_to, int32_t *dem_from);
+TD_API int td_sim_apply(td_sim *s, int n_pairs, const int32_t *lcm_rows, const int32_t *lcm_cols, int solved, int n_r2c,
+                        const int32_t *row_to_col, int32_t *opt_count);
+TD_API int td_sim_step(td_sim *s, int t, int32_t line[9]);
+TD_API int td_sim_state(td_sim *s, int32_t *c_from, int32_t *c_to, int32_t *c_clnt, int32_t *c_onboard, int32_t *c_start,
+                        int32_t *d_cab, int32_t *d_pick, int32_t *d_pool_id, int32_t *d_pool_plan, int32_t *d_pool_cost);
+TD_API int td_sim_metrics(td_sim *s, int64_t out[TD_SIM_N_METRICS]);
+
 /* ---- f-3 pool of two (the step right before the path in every tick) -------------------
  * Replaces findPool: Simulator.java:681-758 (and pool.c:64-131): every ordered pair (A, B) of
  * requests is a candidate with cost = min(plan1, plan2) (:693-717); plans are taken in STABLE

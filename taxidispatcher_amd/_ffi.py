@@ -67,6 +67,16 @@ SIGNATURES = {
                                ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "td_tick_release_workspace": (None, []),
+    "td_sim_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int, c_i32p, c_i32p,
+                                     c_i32p, c_i32p, ctypes.POINTER(ctypes.c_void_p)]),
+    "td_sim_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "td_sim_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p]),
+    "td_sim_model": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p]),
+    "td_sim_apply": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int, c_i32p,
+                                    ctypes.POINTER(ctypes.c_int32)]),
+    "td_sim_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p]),
+    "td_sim_state": (ctypes.c_int, [ctypes.c_void_p] + [c_i32p] * 10),
+    "td_sim_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "td_pool2": (ctypes.c_int, [ctypes.c_int, c_i32p, c_i32p, c_i32p, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p,
                                 ctypes.POINTER(ctypes.c_int32)]),
     "td_match_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),

@@ -1,0 +1,99 @@
+// td_sim_core.h — the per-element rules of the device-resident simulator world (td_sim.hip), one place each.
+//
+// Every rule is a statement-by-statement port of taxidispatcher_amd/simulator.py (the harness with Simulator.java's
+// semantics; SURVEY.md Appendix A lists the bug-compatible details).  Requests are addressed by their INDEX in the
+// request table everywhere on the device (the reference looks ids up in a dictionary; ids are unique, so the index is
+// the same thing); ids appear again only where the reference stores one (pool_id, and the client reported by td_sim_state).
+#pragma once
+#include <stdint.h>
+
+namespace tdsim {
+
+constexpr int CB = 1024;                 // workgroup of every compaction pass: 16 waves, one element per thread
+constexpr int32_t NONE = 0x7f7f7f7f;     // "no pair / no plan" (what a byte-wise fill with 0x7f leaves)
+
+// the world in HBM; passed to the kernels by value
+struct World {
+    int n_cabs, n_req, n_stands, drop_time, big_cost;
+    // request table
+    const int32_t *r_id, *r_from, *r_to, *r_at;
+    int32_t *r_cab, *r_pick, *r_pid, *r_plan, *r_pcost;
+    // fleet (c_clnt = request INDEX, -1 = none)
+    int32_t *c_from, *c_to, *c_clnt, *c_onb, *c_start;
+};
+
+// device counters: the sums of Simulator.m (64-bit), the error word, and this tick's list sizes
+struct Ctl {
+    long long dropped, pickup_time, pickup_numb, second;
+    int32_t err;        // 1: internal, 2: a pair or plan index handed in lies outside its list
+    int32_t n_dem, n_sup, n_dem2, n_ks, n_kd, opt_count, pad;
+};
+
+// Simulator.java:469-474
+__host__ __device__ inline int cheat_a_bit(int frm, int cost, int n_stands)
+{
+    if (frm + cost >= n_stands) return frm - cost < 0 ? 0 : frm - cost;
+    return frm + cost;
+}
+
+__host__ __device__ inline int iabs(int v) { return v < 0 ? -v : v; }
+
+// Simulator._near: any flagged stand within distance < drop_time of s (bits = one bit per stand)
+__device__ inline bool near_window(const uint32_t *bits, int n_stands, int drop_time, int s)
+{
+    const int r = (drop_time - 1 < n_stands ? drop_time - 1 : n_stands);   // a wider window sees no more stands
+    const int lo = s - r < 0 ? 0 : s - r, hi = s + r > n_stands - 1 ? n_stands - 1 : s + r;
+    if (lo > hi) return false;
+    for (int w = lo >> 5; w <= hi >> 5; w++) {   // at most (2 r + 1) / 32 + 2 words
+        uint32_t m = 0xffffffffu;
+        if (w == lo >> 5) m &= 0xffffffffu << (lo & 31);
+        if (w == hi >> 5) m &= 0xffffffffu >> (31 - (hi & 31));
+        if (bits[w] & m) return true;
+    }
+    return false;
+}
+
+// Simulator.java:220-254 for ONE cab; returns 1 when a passenger was picked up
+__device__ inline int arrive(const World &w, int t, int c)
+{
+    const int f = w.c_from[c], to = w.c_to[c];
+    if (f == to || iabs(f - to) != t - w.c_start[c]) return 0;
+    if (w.c_onb[c] == 0) {
+        const int d = w.c_clnt[c];
+        if (d < 0) return 0;
+        w.r_cab[d] = c;
+        w.r_pick[d] = t;
+        w.c_from[c] = w.r_from[d];
+        w.c_to[c] = w.r_pid[d] == -1 ? w.r_to[d] : cheat_a_bit(w.r_from[d], w.r_pcost[d], w.n_stands);
+        w.c_onb[c] = 1;
+        w.c_start[c] = t;
+        return 1;
+    }
+    w.c_from[c] = to;
+    w.c_clnt[c] = -1;
+    w.c_onb[c] = 0;
+    w.c_start[c] = -1;
+    return 0;
+}
+
+// Simulator.java:424-490 _dispatch for cab `cab` (standing at sup_to) and the customer (request idx, pool partner / cost)
+__device__ inline void dispatch(const World &w, int t, int cab, int sup_to, int idx, int partner, int pcost, int &numb, int &ptime)
+{
+    const int cf = w.r_from[idx];
+    if (sup_to == cf) {   // assignToCabAndGo
+        w.c_from[cab] = cf;
+        w.c_to[cab] = partner == -1 ? w.r_to[idx] : cheat_a_bit(cf, pcost, w.n_stands);
+        w.c_clnt[cab] = idx;
+        w.c_onb[cab] = 1;
+        w.c_start[cab] = t;
+        numb++;
+    } else if (iabs(sup_to - cf) < w.drop_time) {   // goToPickup
+        w.c_to[cab] = cf;
+        w.c_clnt[cab] = idx;
+        w.c_onb[cab] = 0;
+        w.c_start[cab] = t;
+        ptime += iabs(w.c_from[cab] - cf);
+    }
+}
+
+}  // namespace tdsim

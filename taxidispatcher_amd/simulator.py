@@ -367,3 +367,127 @@ class Simulator:
             if line is not None:
                 self.log.append(line)
         return self.log
+
+
+class DeviceSimulator:
+    """The same world in device memory behind the C ABI (td_sim_*, csrc/td_sim.hip): the cab and request tables never leave
+    the GPU, a tick is ONE call (`tick` = td_sim_step: world kernels around td_pool2 and td_tick), and only the counters
+    of the log line come back.  `begin` / `model` / `apply` split the tick so that the assignment decisions can come from
+    any source.  Log lines, `m` and `metrics_text` are those of `Simulator` with `HipTickBackend`."""
+
+    M_KEYS = ("total_dropped", "total_pickup_time", "total_pickup_numb", "total_LCM_used", "max_model_size", "max_solver_size",
+              "max_POOL_MEM_size", "max_POOL_size", "total_second_passengers")
+    CAB_KEYS = ("c_from", "c_to", "c_clnt", "c_onboard", "c_start")
+    REQ_KEYS = ("d_cab", "d_pick", "d_pool_id", "d_pool_plan", "d_pool_cost")
+
+    def __init__(self, demand_rows, n_cabs=None, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None):
+        import ctypes
+        from . import _ffi
+        self._ffi, self._ct = _ffi, ctypes
+        self._lib = _ffi.lib()
+        self._h = None
+        d = np.asarray(demand_rows, dtype=np.int64).reshape(-1, 5)
+        self.n_req = int(d.shape[0])
+        self.n_cabs = int(N_CABS if n_cabs is None else n_cabs)
+        self.n_stands = int(N_STANDS if n_stands is None else n_stands)
+        self.drop_time = int(DROP_TIME if drop_time is None else drop_time)
+        self.max_non_lcm = int(MAX_NON_LCM if max_non_lcm is None else max_non_lcm)
+        self.big_cost = int(BIG_COST if big_cost is None else big_cost)
+        cols = [_ffi.as_i32(d[:, k]) for k in (0, 1, 2, 4)]      # id, from, to, at
+        h = ctypes.c_void_p()
+        _ffi.check(self._lib.td_sim_create(self.n_cabs, self.n_stands, self.drop_time, self.max_non_lcm, self.big_cost, self.n_req,
+                                           *[_ffi.addr(c) if self.n_req else None for c in cols], ctypes.byref(h)))
+        self._h = h
+        self._cap = max(self.n_cabs, self.n_req, 1)
+        self._info = None
+        self.log = []
+
+    def close(self):
+        if self._h is not None:
+            self._lib.td_sim_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- the split tick
+    def begin(self, t):
+        """-> (has_demand, demand before pooling, supply, demand after pooling)"""
+        info = np.zeros(4, np.int32)
+        self._ffi.check(self._lib.td_sim_begin(self._h, int(t), self._ffi.addr(info)))
+        self._t = int(t)
+        self._info = tuple(int(v) for v in info)
+        return self._info
+
+    def model(self):
+        """this tick's model: (cab_to, dem_from), the stands the free cabs stand at / the requests start from"""
+        if self._info is None:
+            raise self._ffi.TdError("DeviceSimulator.model: no tick has begun")
+        cab = np.empty(max(self._info[2], 1), np.int32)
+        dem = np.empty(max(self._info[3], 1), np.int32)
+        self._ffi.check(self._lib.td_sim_model(self._h, self._ffi.addr(cab), self._ffi.addr(dem)))
+        return cab[:self._info[2]], dem[:self._info[3]]
+
+    def apply(self, lcm_rows=(), lcm_cols=(), solved=True, row_to_col=()):
+        """the decisions of `dispatch.tick` (or of anything else) -> the line's OPT count (-1: the line has none)"""
+        rows, cols, r2c = (self._ffi.as_i32(np.asarray(a).reshape(-1)) for a in (lcm_rows, lcm_cols, row_to_col))
+        if rows.size != cols.size:
+            raise self._ffi.TdError("lcm_rows and lcm_cols differ in length")
+        opt = self._ct.c_int32(0)
+        self._ffi.check(self._lib.td_sim_apply(self._h, int(rows.size), self._ffi.addr(rows) if rows.size else None,
+                                               self._ffi.addr(cols) if cols.size else None, int(bool(solved)), int(r2c.size),
+                                               self._ffi.addr(r2c) if r2c.size else None, self._ct.byref(opt)))
+        return opt.value
+
+    @staticmethod
+    def format_line(t, line):
+        """the simulog_solv line of Simulator.tick / _tick_one_call from td_sim_step's nine counters (None: no line)"""
+        has, dem, sup, lcm, pairs, sent, dem2, sup2, opt = (int(v) for v in line)
+        if not has:
+            return None
+        s = "t:%d. Initial Count of demand=%d, supply=%d. " % (t, dem, sup)
+        if lcm:
+            s += "LCM n_pairs=%d" % pairs
+            if not sent:
+                return s
+            s += ". Sent to solver: demand=%d, supply=%d. " % (dem2, sup2)
+        return s + "; OPT count=%d" % opt
+
+    # ---- one tick in one call
+    def tick(self, t):
+        line = np.zeros(9, np.int32)
+        self._ffi.check(self._lib.td_sim_step(self._h, int(t), self._ffi.addr(line)))
+        self._info = None
+        return self.format_line(int(t), line)
+
+    def run(self, t_end=HOURS * 60):
+        for t in range(t_end):
+            line = self.tick(t)
+            if line is not None:
+                self.log.append(line)
+        return self.log
+
+    # ---- read-outs
+    @property
+    def m(self):
+        out = np.zeros(len(self.M_KEYS), np.int64)
+        self._ffi.check(self._lib.td_sim_metrics(self._h, self._ffi.addr(out)))
+        return {k: int(v) for k, v in zip(self.M_KEYS, out)}
+
+    def state(self):
+        """the ten state arrays under Simulator's attribute names (c_clnt holds request ids)"""
+        arrs = [np.empty(max(self.n_cabs, 1), np.int32) for _ in self.CAB_KEYS] + [np.empty(max(self.n_req, 1), np.int32) for _ in self.REQ_KEYS]
+        self._ffi.check(self._lib.td_sim_state(self._h, *[self._ffi.addr(a) for a in arrs]))
+        out = {k: a[:self.n_cabs] for k, a in zip(self.CAB_KEYS, arrs[:5])}
+        out.update({k: a[:self.n_req] for k, a in zip(self.REQ_KEYS, arrs[5:])})
+        return out
+
+    def metrics_text(self, total_simul_time=0, max_solver_time=0, max_lcm_time=0, max_pool_time=0):
+        view = Simulator.__new__(Simulator)
+        view.m = self.m
+        view.d_id = np.empty(self.n_req, np.int64)
+        view.d_cab = self.state()["d_cab"]
+        return Simulator.metrics_text(view, total_simul_time, max_solver_time, max_lcm_time, max_pool_time)
