@@ -310,6 +310,57 @@ TD_API int td_sim_state(td_sim *s, int32_t *c_from, int32_t *c_to, int32_t *c_cl
                         int32_t *d_cab, int32_t *d_pick, int32_t *d_pool_id, int32_t *d_pool_plan, int32_t *d_pool_cost);
 TD_API int td_sim_metrics(td_sim *s, int64_t out[TD_SIM_N_METRICS]);
 
+/* ---- B simulator worlds behind ONE handle (a sweep over fleet sizes / request files of one city) -----------------------
+ * td_simb is td_sim with a world dimension: B independent worlds in device memory, advanced one tick at a time by one call
+ * for all of them; the number of launches and read-backs of a call does not depend on B (csrc/td_simb.hip).
+ * The worlds share n_stands, drop_time, max_non_lcm and big_cost (distances are |a - b|); world b has its own n_cabs[b] and
+ * its own request table, the slice [req_off[b], req_off[b + 1]) of the concatenated request arrays (it may be empty).
+ * Per world, info, line, opt_count, the state arrays and the metrics mean exactly what they mean in td_sim_*; cab numbers,
+ * pair indices and row_to_col indices are world-local.  Ragged arrays are packed world after world behind offsets [B + 1]
+ * that start at 0 and never decrease.  Input arrays may be host or device memory, and so may the outputs of td_simb_model and
+ * td_simb_state; info, line, opt_count and the metrics are host arrays.  All calls are synchronous.
+ *   td_simb_create  TD_EINVAL: batch outside 1 .. 65535, n_cabs[b] outside 1 .. 2048, max_non_lcm > 1024 (so that a
+ *                   remainder always fits td_tick_batched), n_stands > 2^18, bad offsets, and per world td_sim_create's rules
+ *                   for the requests (ids unique within a world and not negative, stands inside the line, times not negative).
+ *   td_simb_begin   begins tick t in every world; info[4 b ..] = world b's td_sim_begin info.  A world without demand has
+ *                   info = {0,0,0,0} and empty segments in td_simb_model / td_simb_apply (its solved[b] is ignored, its
+ *                   opt_count[b] is 0).  If no world has demand the tick is over and no apply follows.
+ *   td_simb_model   every world's model: cab_off / cab_to, dem_off / dem_from (demand after pooling; a world without supply
+ *                   was not pooled and lists its demand as it is).
+ *   td_simb_apply   every world's decisions in one call: world b's pairs lcm_rows / lcm_cols[pair_off[b] .. pair_off[b + 1])
+ *                   are read only when its model is larger than max_non_lcm, its row_to_col[r2c_off[b] .. r2c_off[b + 1]) only
+ *                   when solved[b]; opt_count[b] as td_sim_apply's.  A pair outside its own world's model is TD_EINVAL,
+ *                   applies nothing in ANY world, and the tick keeps waiting for its apply.
+ *   td_simb_step    begin + td_pool2_batched's greedy (inside begin) + td_tick_batched(dist NULL, fill big_cost, threshold
+ *                   drop_time, stop_size max_non_lcm) on the device lists + apply; line[9 b ..] = world b's td_sim_step line.
+ *                   Its decisions are those two calls' decisions; td_tick and td_tick_batched may break ties between equal
+ *                   optima differently, so a world need not take td_sim_step's course.  A world with supply and more than 2048
+ *                   requests before pooling in a tick: TD_EINVAL (the message names the world and the count), nothing is
+ *                   applied, the tick stays begun and can be finished through td_simb_model / td_simb_apply (td_simb_begin
+ *                   pools such a tick world by world with td_pool2).
+ *   td_simb_state   td_sim_state of world `world` (TD_EINVAL outside 0 .. B - 1); td_simb_metrics: [B * TD_SIM_N_METRICS].
+ * Sequencing is td_sim's for the handle as a whole: time runs forward, a begin while a tick with demand waits for its apply is
+ * TD_EINVAL, td_simb_model / td_simb_apply need a begun tick.  A handle does not grow after create (the strided outputs of the
+ * two batched calls are part of it, sized from the limits above); td_workspace_bytes counts it until td_simb_destroy.
+ * When to use which (measured on one MI355X): many worlds of up to a few hundred cabs: one td_simb handle
+ * (64 worlds of 150 cabs: 21 times faster than a loop over td_sim handles); a few worlds of about 1000 cabs and more, where
+ * a tick is no longer launch latency and the batched calls give each model one workgroup: a loop over td_sim handles (8
+ * worlds of 900 .. 1300 cabs: the loop is 6.4 times faster). */
+typedef struct td_simb td_simb;
+TD_API int td_simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost,
+                          const int32_t *req_off, const int32_t *req_id, const int32_t *req_from, const int32_t *req_to,
+                          const int32_t *req_at, td_simb **out);
+TD_API int td_simb_destroy(td_simb *s);
+TD_API int td_simb_begin(td_simb *s, int t, int32_t *info);
+TD_API int td_simb_model(td_simb *s, int32_t *cab_off, int32_t *cab_to, int32_t *dem_off, int32_t *dem_from);
+TD_API int td_simb_apply(td_simb *s, const int32_t *pair_off, const int32_t *lcm_rows, const int32_t *lcm_cols,
+                         const int32_t *solved, const int32_t *r2c_off, const int32_t *row_to_col, int32_t *opt_count);
+TD_API int td_simb_step(td_simb *s, int t, int32_t *line);
+TD_API int td_simb_state(td_simb *s, int world, int32_t *c_from, int32_t *c_to, int32_t *c_clnt, int32_t *c_onboard,
+                         int32_t *c_start, int32_t *d_cab, int32_t *d_pick, int32_t *d_pool_id, int32_t *d_pool_plan,
+                         int32_t *d_pool_cost);
+TD_API int td_simb_metrics(td_simb *s, int64_t *out);
+
 /* ---- f-3 pool of two (the step right before the path in every tick) -------------------
  * Replaces findPool: Simulator.java:681-758 (and pool.c:64-131): every ordered pair (A, B) of
  * requests is a candidate with cost = min(plan1, plan2) (:693-717); plans are taken in STABLE

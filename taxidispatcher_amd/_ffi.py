@@ -77,6 +77,15 @@ SIGNATURES = {
     "td_sim_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p]),
     "td_sim_state": (ctypes.c_int, [ctypes.c_void_p] + [c_i32p] * 10),
     "td_sim_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "td_simb_create": (ctypes.c_int, [ctypes.c_int, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, c_i32p, c_i32p, c_i32p,
+                                      c_i32p, c_i32p, ctypes.POINTER(ctypes.c_void_p)]),
+    "td_simb_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "td_simb_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p]),
+    "td_simb_model": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p]),
+    "td_simb_apply": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
+    "td_simb_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p]),
+    "td_simb_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [c_i32p] * 10),
+    "td_simb_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "td_pool2": (ctypes.c_int, [ctypes.c_int, c_i32p, c_i32p, c_i32p, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p,
                                 ctypes.POINTER(ctypes.c_int32)]),
     "td_match_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),

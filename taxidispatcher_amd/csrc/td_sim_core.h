@@ -53,15 +53,16 @@ __device__ inline bool near_window(const uint32_t *bits, int n_stands, int drop_
     return false;
 }
 
-// Simulator.java:220-254 for ONE cab; returns 1 when a passenger was picked up
-__device__ inline int arrive(const World &w, int t, int c)
+// Simulator.java:220-254 for ONE cab; returns 1 when a passenger was picked up.  c = the cab's row in the fleet table,
+// cab_no = the number the request table stores for it (the same thing in one world; world-local in a batch of worlds)
+__device__ inline int arrive_as(const World &w, int t, int c, int cab_no)
 {
     const int f = w.c_from[c], to = w.c_to[c];
     if (f == to || iabs(f - to) != t - w.c_start[c]) return 0;
     if (w.c_onb[c] == 0) {
         const int d = w.c_clnt[c];
         if (d < 0) return 0;
-        w.r_cab[d] = c;
+        w.r_cab[d] = cab_no;
         w.r_pick[d] = t;
         w.c_from[c] = w.r_from[d];
         w.c_to[c] = w.r_pid[d] == -1 ? w.r_to[d] : cheat_a_bit(w.r_from[d], w.r_pcost[d], w.n_stands);
@@ -75,6 +76,8 @@ __device__ inline int arrive(const World &w, int t, int c)
     w.c_start[c] = -1;
     return 0;
 }
+
+__device__ inline int arrive(const World &w, int t, int c) { return arrive_as(w, t, c, c); }
 
 // Simulator.java:424-490 _dispatch for cab `cab` (standing at sup_to) and the customer (request idx, pool partner / cost)
 __device__ inline void dispatch(const World &w, int t, int cab, int sup_to, int idx, int partner, int pcost, int &numb, int &ptime)

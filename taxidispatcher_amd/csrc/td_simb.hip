@@ -1,0 +1,1179 @@
+// td_simb.hip — B independent simulator worlds in HBM behind one handle (td_simb_*): td_sim.hip with a world dimension.
+//
+// Layout.  The B fleets are ONE cab table and the B request tables ONE request table (world after world; cab_off / req_off
+// say where a world begins).  c_clnt and the pool partner stay indices into the concatenated request table; the cab number
+// a request stores (r_cab) and td_simb_state reports is world-local.  Every per-tick list (demand, supply, demand after
+// pooling, kept lists) is packed world-major, ascending within a world, with an offset array [B+1]: exactly the ragged
+// lists td_pool2_batched and td_tick_batched take.  Two stand bitsets and one Ctl per world.
+//
+// Grid.  Every world kernel runs on a grid (chunks, B): workgroup (x, b) owns elements [x * CB, (x + 1) * CB) of world b's
+// segment, so a workgroup never straddles a world boundary and a per-world sum is one atomic per workgroup on that world's
+// Ctl.  The index space is padded to a multiple of CB per world, the memory is not; `chunks` comes from sizes the host
+// knows (create-time table sizes, or list sizes from the last read-back), so neither the number of launches nor of
+// read-backs depends on B.
+//
+// Ordered compaction with a world dimension: k_count (per workgroup) -> k_offsets (ONE workgroup: per-world totals and their
+// exclusive scan = the list's offset array) -> k_scatter (out[off[b] + counts of the world's earlier chunks + rank]).  No
+// atomic append, no workgroup waits for another; the kernel boundary is the only barrier between workgroups.
+//
+//   begin   k_arrive, k_flags<cab>, k_dem_count (drop + count), k_flags<req>, k_count<supply>, k_offsets, k_scatter x 2,
+//           read-back, td_pool2_batched on the device lists, k_pool_mark, k_count / k_offsets / k_scatter, read-back
+//   apply   k_pair_map, k_apply_pairs, k_count x 2, k_offsets, k_scatter x 2, k_apply_solution, read-back
+//   step    begin + td_tick_batched on the device lists + apply (the decisions stay on the device, strided as written)
+//
+// A world without demand in a tick has empty lists (its supply is not listed either); a world with demand and no supply keeps
+// its demand list as its model and is left out of the pool and tick calls (their lists pl_* / tk_* hold the worlds WITH
+// supply only).  The error word is one for the handle: a pair outside its world's model applies nothing in any world.
+#include <limits.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "td_common.h"
+#include "td_sim_core.h"
+
+using namespace td;
+using namespace tdsim;
+
+namespace {
+constexpr int SIMB_NMAX = 2048;   // largest model of td_tick_batched / td_pool2_batched
+constexpr int N_OFF = 7;          // offset arrays of the head block
+constexpr int N_PER = 4;          // per-world words of the head block
+}  // namespace
+
+// decisions of a tick: packed ragged arrays from the caller (stride == 0), or td_tick_batched's strided outputs
+struct SimbDec {
+    const int32_t *rows, *cols, *r2c;
+    const int32_t *pair_off, *r2c_off, *solved;
+    const int32_t *n_pairs, *n_rest, *last_min;
+    int stride;
+};
+
+struct td_simb {
+    World w;                     // the concatenated tables
+    int B = 0, max_non_lcm = 0;
+    int words = 0;               // of one stand bitset
+    int max_cabs = 0, max_req = 0, nc_tot = 0, nr_tot = 0;
+    int ncap = 1, hcap = 1;      // strides the batched calls may use at most: models / pools per world
+    size_t pool_cap = 0, in_cap = 0;
+    std::vector<int32_t> cab_off, req_off;   // host copies
+    Buf mem;
+    // head block (device) and its pinned mirror: Ctl[B], the error word, the offset arrays, the per-world words
+    int32_t *head = nullptr;
+    size_t head_ints = 0;
+    Ctl *ctl = nullptr;
+    int32_t *gerr = nullptr;
+    int32_t *dem_off, *sup_off, *pl_off, *d2_off, *tk_off, *ks_off, *kd_off;
+    int32_t *n_pools, *tk_np, *tk_lm, *tk_rest;
+    int32_t *d_cab_off = nullptr, *d_req_off = nullptr;
+    uint32_t *bits = nullptr;    // world b: cab bits at (2 b) * words, request bits at (2 b + 1) * words
+    int32_t *cnt_a, *cnt_b;
+    int32_t *dem_idx, *dem_from, *dem_to, *pl_from, *pl_to;
+    int32_t *sup_cab, *sup_to;
+    int32_t *d2_idx, *d2_from, *d2_partner, *d2_plan, *d2_cost, *tk_from;
+    int32_t *ks_cab, *ks_to;
+    int32_t *kd_idx, *kd_from, *kd_partner, *kd_plan, *kd_cost;
+    int32_t *isb, *ainfo;
+    int32_t *pa, *pb, *pp, *pc;                 // the pool calls' plan lists
+    int64_t *p_total, *tk_total;
+    int32_t *pair_cab, *pair_dem;
+    int32_t *in_rows, *in_cols, *in_r2c, *in_pair_off, *in_r2c_off, *in_solved;
+    int32_t *tk_rows, *tk_cols, *tk_r2c;        // td_tick_batched's strided outputs
+    int32_t *tmp;
+    void *pin = nullptr;
+    int32_t *h_head = nullptr, *h_stage = nullptr;
+    // sequencing
+    int last_t = -1;
+    bool begun = false;
+    int pool_ragged = 0;         // this tick's plans lie at pl_off[b] / 2 (the per-world td_pool2 path) instead of b * pool_h
+    int pool_h = 1;
+    std::vector<int32_t> n_dem, n_sup, n_d2;
+    std::vector<int64_t> lcm_used, max_model, max_solver, max_pool_mem, max_pool;
+};
+
+namespace {
+
+template <class T>
+__device__ __forceinline__ T wave_sum(T v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    return v;
+}
+
+// sum over the workgroup, returned to every thread (s_red: one slot per wave)
+template <class T>
+__device__ __forceinline__ T block_sum(T v, T *s_red)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    v = wave_sum(v);
+    if (lane == 0) s_red[wv] = v;
+    __syncthreads();
+    T tot = 0;
+    for (int q = 0; q < nw; q++) tot += s_red[q];
+    __syncthreads();
+    return tot;
+}
+
+// rank of this thread among the flagged threads of the workgroup (ascending thread order), *tot = how many
+__device__ __forceinline__ int block_rank(bool f, int *s_w, int *tot)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    const unsigned long long m = __ballot(f);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_w[wv] = __popcll(m);
+    __syncthreads();
+    int off = 0, t = 0;
+    for (int q = 0; q < nw; q++) {
+        if (q < wv) off += s_w[q];
+        t += s_w[q];
+    }
+    __syncthreads();
+    *tot = t;
+    return off + before;
+}
+
+// exclusive scan of v over the workgroup (full waves), *tot = the sum
+__device__ __forceinline__ int block_excl_scan(int v, int *s_w, int *tot)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(inc, o);
+        if (lane >= o) inc += u;
+    }
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    int off = 0, t = 0;
+    for (int q = 0; q < nw; q++) {
+        if (q < wv) off += s_w[q];
+        t += s_w[q];
+    }
+    __syncthreads();
+    *tot = t;
+    return off + inc - v;
+}
+
+// the handle's error word as ONE value for the whole workgroup
+__device__ __forceinline__ int block_err(const int32_t *gerr)
+{
+    __shared__ int s_e;
+    if (threadIdx.x == 0) s_e = *gerr;
+    __syncthreads();
+    return s_e;
+}
+
+// does world b's model go through the LCM (analyzePairs)?  Without supply there is no model at all.
+__device__ __forceinline__ bool world_lcm(int n_s, int n_d, int max_non_lcm) { return n_s > 0 && (n_s > n_d ? n_s : n_d) > max_non_lcm; }
+
+__device__ __forceinline__ void dec_pairs(const SimbDec &d, int b, int *base, int *cnt)
+{
+    if (d.stride) {
+        *base = b * d.stride;
+        *cnt = d.n_pairs[b];
+    } else {
+        *base = d.pair_off[b];
+        *cnt = d.pair_off[b + 1] - *base;
+    }
+}
+
+// row_to_col of world b: where it begins and how many entries count (0 when the world was not solved)
+__device__ __forceinline__ void dec_r2c(const SimbDec &d, int b, bool lcm, int big_cost, int *base, int *nr, bool *solved)
+{
+    if (d.stride) {
+        *base = b * d.stride;
+        *solved = d.n_rest[b] > 0 && !(lcm && d.last_min[b] == big_cost);
+        *nr = *solved ? d.n_rest[b] : 0;
+    } else {
+        *base = d.r2c_off[b];
+        *solved = d.solved[b] != 0;
+        *nr = *solved ? d.r2c_off[b + 1] - *base : 0;
+    }
+}
+
+__global__ __launch_bounds__(CB) void k_arrive(World w, const int32_t *__restrict__ cab_off, int t, Ctl *ctl)
+{
+    __shared__ int s_red[16];
+    const int b = blockIdx.y, lo = cab_off[b], n = cab_off[b + 1] - lo, l = blockIdx.x * CB + threadIdx.x;
+    const int got = l < n ? arrive_as(w, t, lo + l, l) : 0;
+    const int tot = block_sum(got, s_red);
+    if (threadIdx.x == 0) {
+        if (blockIdx.x == 0) ctl[b].opt_count = 0;   // this tick's OPT count starts from zero
+        if (tot) atomicAdd((unsigned long long *)&ctl[b].pickup_numb, (unsigned long long)tot);
+    }
+}
+
+// world b's bitset `which` |= some element i of the world with who[i] == -1 has stand[i] == s
+__global__ __launch_bounds__(CB) void k_flags(const int32_t *__restrict__ off, int n_stands, const int32_t *__restrict__ stand,
+                                              const int32_t *__restrict__ who, uint32_t *__restrict__ bits, int which)
+{
+    extern __shared__ uint32_t s_bits[];
+    const int words = (n_stands + 31) / 32;
+    const int b = blockIdx.y, lo = off[b], n = off[b + 1] - lo, l = blockIdx.x * CB + threadIdx.x;
+    if ((int)blockIdx.x * CB >= n) return;   // the whole workgroup lies behind the world's segment
+    for (int i = threadIdx.x; i < words; i += CB) s_bits[i] = 0;
+    __syncthreads();
+    if (l < n && who[lo + l] == -1) {
+        const int s = stand[lo + l];
+        atomicOr(&s_bits[s >> 5], 1u << (s & 31));
+    }
+    __syncthreads();
+    uint32_t *out = bits + ((size_t)2 * b + which) * words;
+    for (int q = threadIdx.x; q < words; q += CB)
+        if (s_bits[q]) atomicOr(&out[q], s_bits[q]);
+}
+
+// predicates: (element in the concatenated index space, world)
+struct DemPred {
+    World w;
+    int t, words;
+    const uint32_t *bits;
+    __device__ bool operator()(int d, int b) const
+    {
+        return w.r_cab[d] == -1 && t >= w.r_at[d] && t - w.r_at[d] < w.drop_time &&
+               near_window(bits + (size_t)2 * b * words, w.n_stands, w.drop_time, w.r_from[d]);
+    }
+};
+// emitters: (position in the list, position in the list of the worlds with supply or -1, element, world)
+struct DemEmit {
+    World w;
+    int32_t *idx, *from, *to, *pl_from, *pl_to;
+    __device__ void operator()(int o, int o2, int d, int) const
+    {
+        idx[o] = d;
+        from[o] = w.r_from[d];
+        to[o] = w.r_to[d];
+        if (o2 >= 0) {
+            pl_from[o2] = w.r_from[d];
+            pl_to[o2] = w.r_to[d];
+        }
+    }
+};
+struct SupPred {
+    World w;
+    int words;
+    const uint32_t *bits;
+    __device__ bool operator()(int c, int b) const
+    {
+        return w.c_from[c] == w.c_to[c] && w.c_clnt[c] == -1 &&
+               near_window(bits + ((size_t)2 * b + 1) * words, w.n_stands, w.drop_time, w.c_to[c]);
+    }
+};
+struct SupEmit {
+    World w;
+    int32_t *cab, *to;
+    __device__ void operator()(int o, int, int c, int) const
+    {
+        cab[o] = c;
+        to[o] = w.c_to[c];
+    }
+};
+struct PoolPred {
+    const int32_t *isb;
+    __device__ bool operator()(int d, int) const { return !isb[d]; }
+};
+struct PoolEmit {
+    int pool_h, ragged;
+    const int32_t *dem_off, *pl_off, *n_pools, *dem_idx, *dem_from, *ainfo, *pl_b, *pl_plan, *pl_cost;
+    int32_t *idx, *from, *partner, *plan, *cost, *tk_from;
+    __device__ void operator()(int o, int o2, int d, int b) const
+    {
+        idx[o] = dem_idx[d];
+        from[o] = dem_from[d];
+        const int p = ainfo[d];
+        const bool a = p >= 0 && p < n_pools[b];
+        const int q = (ragged ? pl_off[b] >> 1 : b * pool_h) + (a ? p : 0);
+        const int pb = a ? pl_b[q] : -1;   // k_pool_mark raised the error word for a plan outside the list; never index by it
+        partner[o] = pb >= 0 && pb < dem_off[b + 1] - dem_off[b] ? dem_idx[dem_off[b] + pb] : -1;
+        plan[o] = a ? pl_plan[q] : -1;
+        cost[o] = a ? pl_cost[q] : 0;
+        if (o2 >= 0) tk_from[o2] = dem_from[d];
+    }
+};
+// the cabs / requests of an LCM world that are in no pair (analyzePairs' supply2 / demand2)
+struct KeptPred {
+    const int32_t *pair_of, *sup_off, *d2_off;
+    int max_non_lcm;
+    __device__ bool operator()(int i, int b) const
+    {
+        return world_lcm(sup_off[b + 1] - sup_off[b], d2_off[b + 1] - d2_off[b], max_non_lcm) && pair_of[i] == NONE;
+    }
+};
+struct KeptSupEmit {
+    const int32_t *cab, *to;
+    int32_t *cab2, *to2;
+    __device__ void operator()(int o, int, int s, int) const
+    {
+        cab2[o] = cab[s];
+        to2[o] = to[s];
+    }
+};
+struct KeptDemEmit {
+    const int32_t *idx, *from, *partner, *plan, *cost;
+    int32_t *idx2, *from2, *partner2, *plan2, *cost2;
+    __device__ void operator()(int o, int, int d, int) const
+    {
+        idx2[o] = idx[d];
+        from2[o] = from[d];
+        partner2[o] = partner[d];
+        plan2[o] = plan[d];
+        cost2[o] = cost[d];
+    }
+};
+
+// the request pass of createTempDemand: drop what waited DROP_TIME (cab_assigned = -2), count the kept per workgroup
+__global__ __launch_bounds__(CB) void k_dem_count(DemPred pred, const int32_t *__restrict__ req_off, int32_t *__restrict__ cnt, Ctl *ctl)
+{
+    __shared__ int s_red[16];
+    const World &w = pred.w;
+    const int b = blockIdx.y, lo = req_off[b], n = req_off[b + 1] - lo, l = blockIdx.x * CB + threadIdx.x;
+    int drop = 0, keep = 0;
+    if (l < n) {
+        const int d = lo + l;
+        if (w.r_cab[d] == -1 && pred.t >= w.r_at[d] && pred.t - w.r_at[d] >= w.drop_time) {
+            w.r_cab[d] = -2;
+            drop = 1;
+        }
+        keep = pred(d, b) ? 1 : 0;
+    }
+    const int nd = block_sum(drop, s_red), nk = block_sum(keep, s_red);
+    if (threadIdx.x == 0) {
+        cnt[b * gridDim.x + blockIdx.x] = nk;
+        if (nd) atomicAdd((unsigned long long *)&ctl[b].dropped, (unsigned long long)nd);
+    }
+}
+
+template <class P>
+__global__ __launch_bounds__(CB) void k_count(const int32_t *__restrict__ off, P pred, int32_t *__restrict__ cnt)
+{
+    __shared__ int s_red[16];
+    const int b = blockIdx.y, lo = off[b], n = off[b + 1] - lo, l = blockIdx.x * CB + threadIdx.x;
+    const int nk = block_sum((l < n && pred(lo + l, b)) ? 1 : 0, s_red);
+    if (threadIdx.x == 0) cnt[b * gridDim.x + blockIdx.x] = nk;
+}
+
+// ONE workgroup: per-workgroup counts -> per-world totals -> offset arrays (exclusive scans over the worlds, B in slices of CB).
+//   off_a = the list counted in cnt_a; off_b (cnt_b non-null) = the list counted in cnt_b.
+//   begin_mode: a = demand, b = supply: a world without demand lists no supply, off_c = the demand of the worlds WITH supply.
+//   else: off_c (non-null) = list a restricted to the worlds with gate[b + 1] > gate[b].
+__global__ __launch_bounds__(CB) void k_offsets(int B, const int32_t *__restrict__ cnt_a, int nc_a, const int32_t *__restrict__ cnt_b, int nc_b,
+                                                int begin_mode, const int32_t *__restrict__ gate, int32_t *__restrict__ off_a,
+                                                int32_t *__restrict__ off_b, int32_t *__restrict__ off_c)
+{
+    __shared__ int s_w[16];
+    int ca = 0, cb = 0, cc = 0;   // the running totals, the same in every thread
+    for (int b0 = 0; b0 < B; b0 += CB) {
+        const int b = b0 + threadIdx.x;
+        int na = 0, nb = 0, nc = 0;
+        if (b < B) {
+            for (int j = 0; j < nc_a; j++) na += cnt_a[b * nc_a + j];
+            if (cnt_b)
+                for (int j = 0; j < nc_b; j++) nb += cnt_b[b * nc_b + j];
+            if (begin_mode) {
+                if (na == 0) nb = 0;
+                nc = nb > 0 ? na : 0;
+            } else if (off_c) {
+                nc = gate[b + 1] > gate[b] ? na : 0;
+            }
+        }
+        int ta, tb, tc;
+        const int ea = block_excl_scan(na, s_w, &ta), eb = block_excl_scan(nb, s_w, &tb), ec = block_excl_scan(nc, s_w, &tc);
+        if (b < B) {
+            off_a[b] = ca + ea;
+            if (off_b) off_b[b] = cb + eb;
+            if (off_c) off_c[b] = cc + ec;
+        }
+        ca += ta;
+        cb += tb;
+        cc += tc;
+    }
+    if (threadIdx.x == 0) {
+        off_a[B] = ca;
+        if (off_b) off_b[B] = cb;
+        if (off_c) off_c[B] = cc;
+    }
+}
+
+// out[off_out[b] + the counts of the world's earlier chunks + rank] = element; a world whose output segment is empty
+// (no demand: its supply is not listed) writes nothing.  off_out2: the list of the worlds with a non-empty segment there.
+template <class P, class E>
+__global__ __launch_bounds__(CB) void k_scatter(const int32_t *__restrict__ off, P pred, E emit, const int32_t *__restrict__ cnt,
+                                                const int32_t *__restrict__ off_out, const int32_t *__restrict__ off_out2)
+{
+    __shared__ int s_red[16];
+    const int b = blockIdx.y, lo = off[b], n = off[b + 1] - lo, l = blockIdx.x * CB + threadIdx.x;
+    const int cap = off_out[b + 1] - off_out[b];
+    if (cap == 0 || (int)blockIdx.x * CB >= n) return;
+    int part = 0;
+    for (int j = threadIdx.x; j < (int)blockIdx.x; j += CB) part += cnt[b * gridDim.x + j];
+    const int before = block_sum(part, s_red);
+    const bool f = l < n && pred(lo + l, b);
+    int tot;
+    const int rank = block_rank(f, s_red, &tot);
+    const int pos = before + rank;
+    const bool two = off_out2 && off_out2[b + 1] > off_out2[b];
+    if (f && pos < cap) emit(off_out[b] + pos, two ? off_out2[b] + pos : -1, lo + l, b);
+}
+
+__global__ __launch_bounds__(256) void k_pool_mark(int pool_h, int ragged, const int32_t *__restrict__ dem_off, const int32_t *__restrict__ pl_off,
+                                                   const int32_t *__restrict__ n_pools, const int32_t *__restrict__ pl_a,
+                                                   const int32_t *__restrict__ pl_b, int32_t *__restrict__ isb, int32_t *__restrict__ ainfo,
+                                                   int32_t *gerr)
+{
+    const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n_act = pl_off[b + 1] - pl_off[b];   // 0 for a world without supply: it has no pool
+    if (p >= n_pools[b] || p >= n_act / 2) return;
+    const int q = (ragged ? pl_off[b] >> 1 : b * pool_h) + p;
+    const int a = pl_a[q], c = pl_b[q];
+    if (a < 0 || a >= n_act || c < 0 || c >= n_act) {
+        atomicMax(gerr, 1);
+        return;
+    }
+    isb[dem_off[b] + c] = 1;
+    atomicMin(&ainfo[dem_off[b] + a], p);   // the first plan of an A customer (plans are disjoint anyway)
+}
+
+// by_cab / by_clnt of analyzePairs (Simulator.java:613-674) in every LCM world: the FIRST pair of a cab / of a request
+__global__ __launch_bounds__(256) void k_pair_map(SimbDec dec, int max_non_lcm, const int32_t *__restrict__ sup_off,
+                                                  const int32_t *__restrict__ d2_off, int32_t *__restrict__ pair_cab,
+                                                  int32_t *__restrict__ pair_dem, int32_t *gerr)
+{
+    const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n_s = sup_off[b + 1] - sup_off[b], n_d = d2_off[b + 1] - d2_off[b];
+    if (!world_lcm(n_s, n_d, max_non_lcm)) return;
+    int base, cnt;
+    dec_pairs(dec, b, &base, &cnt);
+    if (p >= cnt) return;
+    const int r = dec.rows[base + p], c = dec.cols[base + p];
+    if (r < 0 || r >= n_s || c < 0 || c >= n_d) {
+        atomicMax(gerr, 2);
+        return;
+    }
+    atomicMin(&pair_cab[sup_off[b] + r], p);
+    atomicMin(&pair_dem[d2_off[b] + c], p);
+}
+
+// analyzePairs: thread l < n_s of a world is the cab loop, the rest the request loop (td_sim.hip's k_apply_pairs per world)
+__global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, SimbDec dec, int max_non_lcm, const int32_t *__restrict__ cab_off,
+                                                    const int32_t *__restrict__ sup_off, const int32_t *__restrict__ d2_off,
+                                                    const int32_t *__restrict__ pair_cab, const int32_t *__restrict__ pair_dem,
+                                                    const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
+                                                    const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_partner,
+                                                    const int32_t *__restrict__ d_cost, Ctl *ctl, const int32_t *gerr)
+{
+    __shared__ int s_red[16];
+    if (block_err(gerr)) return;
+    const int b = blockIdx.y, s0 = sup_off[b], n_s = sup_off[b + 1] - s0, d0 = d2_off[b], n_d = d2_off[b + 1] - d0;
+    if (!world_lcm(n_s, n_d, max_non_lcm) || (int)blockIdx.x * CB >= n_s + n_d) return;
+    int base, cnt;
+    dec_pairs(dec, b, &base, &cnt);
+    const int l = blockIdx.x * CB + threadIdx.x;
+    int numb = 0, ptime = 0, second = 0;
+    if (l < n_s) {
+        const int p = pair_cab[s0 + l];
+        if (p != NONE) {
+            const int d = d0 + dec.cols[base + p];
+            dispatch(w, t, sup_cab[s0 + l], sup_to[s0 + l], d_idx[d], d_partner[d], d_cost[d], numb, ptime);
+        }
+    } else if (l < n_s + n_d) {
+        const int d = d0 + l - n_s, p = pair_dem[d];
+        if (p != NONE) {   // the request side is not guarded by the distance
+            const int cab = sup_cab[s0 + dec.rows[base + p]] - cab_off[b], idx = d_idx[d];
+            w.r_cab[idx] = cab;
+            w.r_pick[idx] = t;
+            if (d_partner[d] > -1) {
+                w.r_cab[d_partner[d]] = cab;   // assignPooled; pool info is NOT copied into the table on this path
+                second = 1;
+                numb = 1;
+            }
+        }
+    }
+    const int tn = block_sum(numb, s_red), tp = block_sum(ptime, s_red), ts = block_sum(second, s_red);
+    if (threadIdx.x == 0) {
+        if (tn) atomicAdd((unsigned long long *)&ctl[b].pickup_numb, (unsigned long long)tn);
+        if (tp) atomicAdd((unsigned long long *)&ctl[b].pickup_time, (unsigned long long)tp);
+        if (ts) atomicAdd((unsigned long long *)&ctl[b].second, (unsigned long long)ts);
+    }
+}
+
+// analyzeSolution (Simulator.java:375-421): one thread per cab of the solver's model of world b: the kept lists where the
+// LCM ran, else the whole model
+__global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, SimbDec dec, int max_non_lcm, const int32_t *__restrict__ cab_off,
+                                                       const int32_t *__restrict__ sup_off, const int32_t *__restrict__ d2_off,
+                                                       const int32_t *__restrict__ ks_off, const int32_t *__restrict__ kd_off,
+                                                       const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
+                                                       const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_from,
+                                                       const int32_t *__restrict__ d_partner, const int32_t *__restrict__ d_plan,
+                                                       const int32_t *__restrict__ d_cost, const int32_t *__restrict__ ks_cab,
+                                                       const int32_t *__restrict__ ks_to, const int32_t *__restrict__ kd_idx,
+                                                       const int32_t *__restrict__ kd_from, const int32_t *__restrict__ kd_partner,
+                                                       const int32_t *__restrict__ kd_plan, const int32_t *__restrict__ kd_cost, Ctl *ctl,
+                                                       const int32_t *gerr)
+{
+    __shared__ int s_red[16];
+    if (block_err(gerr)) return;
+    const int b = blockIdx.y;
+    const int n_s0 = sup_off[b + 1] - sup_off[b], n_d0 = d2_off[b + 1] - d2_off[b];
+    if (n_s0 == 0 || (int)blockIdx.x * CB >= n_s0) return;
+    const bool lcm = world_lcm(n_s0, n_d0, max_non_lcm);
+    int rb, nr;
+    bool solved;
+    dec_r2c(dec, b, lcm, w.big_cost, &rb, &nr, &solved);
+    if (lcm && !solved) return;
+    const int s0 = lcm ? ks_off[b] : sup_off[b], n_s = lcm ? ks_off[b + 1] - s0 : n_s0;
+    const int d0 = lcm ? kd_off[b] : d2_off[b], n_d = lcm ? kd_off[b + 1] - d0 : n_d0;
+    const int32_t *l_cab = lcm ? ks_cab : sup_cab, *l_to = lcm ? ks_to : sup_to, *l_idx = lcm ? kd_idx : d_idx, *l_from = lcm ? kd_from : d_from;
+    const int32_t *l_partner = lcm ? kd_partner : d_partner, *l_plan = lcm ? kd_plan : d_plan, *l_cost = lcm ? kd_cost : d_cost;
+    const int l = blockIdx.x * CB + threadIdx.x;
+    int count = 0, numb = 0, ptime = 0, second = 0;
+    if (l < n_s) {
+        const int s = s0 + l;
+        const int c = l < nr ? dec.r2c[rb + l] : -1;
+        if (c >= 0 && c < n_d) {
+            const int e = d0 + c;
+            const int dist = iabs(l_to[s] - l_from[e]);
+            const int cell = dist < w.drop_time ? dist : w.big_cost;   // the thresholded |a - b| model's cell
+            if (cell < w.big_cost) {
+                count = 1;
+                const int idx = l_idx[e], cab = l_cab[s], partner = l_partner[e];
+                w.r_cab[idx] = cab - cab_off[b];
+                w.r_pick[idx] = t;
+                if (partner > -1) {
+                    w.r_cab[partner] = cab - cab_off[b];
+                    second = 1;
+                    w.r_pid[idx] = w.r_id[partner];   // pool info reaches the table on the OPT path only (:391-396)
+                    w.r_plan[idx] = l_plan[e];
+                    w.r_pcost[idx] = l_cost[e];
+                    numb = 1;
+                }
+                dispatch(w, t, cab, l_to[s], idx, partner, l_cost[e], numb, ptime);
+            }
+        }
+    }
+    const int tc = block_sum(count, s_red), tn = block_sum(numb, s_red), tp = block_sum(ptime, s_red), ts = block_sum(second, s_red);
+    if (threadIdx.x == 0) {
+        if (tc) atomicAdd(&ctl[b].opt_count, tc);
+        if (tn) atomicAdd((unsigned long long *)&ctl[b].pickup_numb, (unsigned long long)tn);
+        if (tp) atomicAdd((unsigned long long *)&ctl[b].pickup_time, (unsigned long long)tp);
+        if (ts) atomicAdd((unsigned long long *)&ctl[b].second, (unsigned long long)ts);
+    }
+}
+
+// Simulator.c_clnt holds the request id; cabs [lo, lo + n)
+__global__ __launch_bounds__(256) void k_client_ids(World w, int lo, int n, int32_t *__restrict__ out)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    const int d = w.c_clnt[lo + c];
+    out[c] = d < 0 ? -1 : w.r_id[d];
+}
+
+inline int nchunks(int n) { return std::max(1, (n + CB - 1) / CB); }
+
+int put(int32_t *dst, const int32_t *src, size_t n)
+{
+    if (!n) return TD_OK;
+    TD_HIP(hipMemcpyAsync(dst, src, sizeof(int32_t) * n, is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx().stream));
+    return TD_OK;
+}
+
+int get(int32_t *dst, const int32_t *src, size_t n)
+{
+    if (!n || !dst) return TD_OK;
+    TD_HIP(hipMemcpyAsync(dst, src, sizeof(int32_t) * n, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx().stream));
+    return TD_OK;
+}
+
+// host copy of n values (host or device source)
+int host_copy(const int32_t *src, size_t n, std::vector<int32_t> &h)
+{
+    h.resize(n);
+    if (!n) return TD_OK;
+    if (is_device_ptr(src)) {
+        TD_HIP(hipMemcpyAsync(h.data(), src, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx().stream));
+        TD_HIP(hipStreamSynchronize(ctx().stream));
+    } else {
+        memcpy(h.data(), src, sizeof(int32_t) * n);
+    }
+    return TD_OK;
+}
+
+// the head block on the host: every world's Ctl, the error word, the offset arrays, the per-world words, in ONE copy
+int read_head(td_simb *s)
+{
+    Ctx &c = ctx();
+    TD_HIP(hipMemcpyAsync(s->h_head, s->head, sizeof(int32_t) * s->head_ints, hipMemcpyDeviceToHost, c.stream));
+    TD_HIP(hipStreamSynchronize(c.stream));
+    return TD_OK;
+}
+
+inline const Ctl *h_ctl(const td_simb *s) { return (const Ctl *)s->h_head; }
+inline const int32_t *h_of(const td_simb *s, const int32_t *dev) { return s->h_head + (dev - s->head); }
+
+int clear_err(td_simb *s)
+{
+    TD_HIP(hipMemsetAsync(s->gerr, 0, sizeof(int32_t), ctx().stream));
+    TD_HIP(hipStreamSynchronize(ctx().stream));
+    return TD_OK;
+}
+
+int simb_begin(td_simb *s, int t, int32_t *info)
+{
+    Ctx &c = ctx();
+    const World &w = s->w;
+    const int B = s->B;
+    int rc;
+    for (int q = 0; q < 4 * B; q++) info[q] = 0;
+    // this tick's offsets and per-world words start from zero; the sums and the error word stay
+    TD_HIP(hipMemsetAsync(s->dem_off, 0, sizeof(int32_t) * ((size_t)N_OFF * (B + 1) + (size_t)N_PER * B), c.stream));
+    TD_HIP(hipMemsetAsync(s->bits, 0, sizeof(uint32_t) * 2 * (size_t)s->words * B, c.stream));
+    const size_t shm = sizeof(uint32_t) * (size_t)s->words;
+    const int gc = nchunks(s->max_cabs), gr = nchunks(s->max_req);
+    const dim3 grid_c(gc, B), grid_r(gr, B);
+    k_arrive<<<grid_c, CB, 0, c.stream>>>(w, s->d_cab_off, t, s->ctl);
+    k_flags<<<grid_c, CB, shm, c.stream>>>(s->d_cab_off, w.n_stands, w.c_to, w.c_clnt, s->bits, 0);
+    const DemPred dp{w, t, s->words, s->bits};
+    k_dem_count<<<grid_r, CB, 0, c.stream>>>(dp, s->d_req_off, s->cnt_a, s->ctl);
+    k_flags<<<grid_r, CB, shm, c.stream>>>(s->d_req_off, w.n_stands, w.r_from, w.r_cab, s->bits, 1);
+    const SupPred sp{w, s->words, s->bits};
+    k_count<SupPred><<<grid_c, CB, 0, c.stream>>>(s->d_cab_off, sp, s->cnt_b);
+    k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, gr, s->cnt_b, gc, 1, nullptr, s->dem_off, s->sup_off, s->pl_off);
+    k_scatter<DemPred, DemEmit><<<grid_r, CB, 0, c.stream>>>(s->d_req_off, dp, DemEmit{w, s->dem_idx, s->dem_from, s->dem_to, s->pl_from, s->pl_to},
+                                                           s->cnt_a, s->dem_off, s->pl_off);
+    k_scatter<SupPred, SupEmit><<<grid_c, CB, 0, c.stream>>>(s->d_cab_off, sp, SupEmit{w, s->sup_cab, s->sup_to}, s->cnt_b, s->sup_off, nullptr);
+    TD_HIP(hipGetLastError());
+    if ((rc = read_head(s))) return rc;
+    if (*h_of(s, s->gerr)) return fail(TD_EINTERNAL, "td_simb: device error word %d", *h_of(s, s->gerr));
+    s->last_t = t;
+    s->pool_ragged = 0;
+    const int32_t *hd = h_of(s, s->dem_off), *hs = h_of(s, s->sup_off), *hp = h_of(s, s->pl_off);
+    int max_dem = 0, max_act = 0;
+    for (int b = 0; b < B; b++) {
+        s->n_dem[b] = s->n_d2[b] = hd[b + 1] - hd[b];
+        s->n_sup[b] = hs[b + 1] - hs[b];
+        max_dem = std::max(max_dem, s->n_dem[b]);
+        max_act = std::max(max_act, hp[b + 1] - hp[b]);
+    }
+    if (hd[B] == 0) return TD_OK;   // Simulator.java:160 in every world: nothing to do in this tick
+    s->begun = true;
+    // findPool for the worlds with supply, the plans stay on the device
+    if (max_act >= 2) {
+        for (int b = 0; b < B; b++)
+            if (s->n_sup[b] > 0 && s->n_dem[b] >= 2) s->max_pool_mem[b] = std::max(s->max_pool_mem[b], (int64_t)s->n_dem[b] * (s->n_dem[b] - 1));
+        if (max_act <= SIMB_NMAX) {
+            s->pool_h = std::max(1, max_act / 2);
+            if ((rc = td_pool2_batched(B, max_act, hp, s->pl_from, s->pl_to, nullptr, 0, 0.0, 0, s->pa, s->pb, s->pp, s->pc, s->n_pools, s->p_total)))
+                return rc;
+        } else {
+            // a world beyond the batched call's model size: td_pool2 world by world, plans packed at pl_off[b] / 2 (a world
+            // of m customers has at most m / 2 plans).  Only td_simb_begin / _model / _apply serve such a tick.
+            s->pool_ragged = 1;
+            int32_t *np = s->h_stage;
+            for (int b = 0; b < B; b++) {
+                const int m = hp[b + 1] - hp[b], q = hp[b] >> 1;
+                np[b] = 0;
+                if (m >= 2 && (rc = td_pool2(m, s->pl_from + hp[b], s->pl_to + hp[b], nullptr, 0, s->pa + q, s->pb + q, s->pp + q, s->pc + q, &np[b])))
+                    return rc;
+            }
+            TD_HIP(hipMemcpyAsync(s->n_pools, np, sizeof(int32_t) * B, hipMemcpyHostToDevice, c.stream));
+        }
+    }
+    const size_t nd_tot = (size_t)hd[B];
+    TD_HIP(hipMemsetAsync(s->isb, 0, sizeof(int32_t) * nd_tot, c.stream));
+    TD_HIP(hipMemsetAsync(s->ainfo, 0x7f, sizeof(int32_t) * nd_tot, c.stream));
+    if (max_act >= 2)
+        k_pool_mark<<<dim3((max_act / 2 + 255) / 256, B), 256, 0, c.stream>>>(s->pool_h, s->pool_ragged, s->dem_off, s->pl_off, s->n_pools, s->pa, s->pb,
+                                                                             s->isb, s->ainfo, s->gerr);
+    const dim3 grid_d(nchunks(max_dem), B);
+    const PoolPred pp{s->isb};
+    k_count<PoolPred><<<grid_d, CB, 0, c.stream>>>(s->dem_off, pp, s->cnt_a);
+    k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, (int)grid_d.x, nullptr, 0, 0, s->sup_off, s->d2_off, nullptr, s->tk_off);
+    k_scatter<PoolPred, PoolEmit><<<grid_d, CB, 0, c.stream>>>(
+        s->dem_off, pp,
+        PoolEmit{s->pool_h, s->pool_ragged, s->dem_off, s->pl_off, s->n_pools, s->dem_idx, s->dem_from, s->ainfo, s->pb, s->pp, s->pc, s->d2_idx,
+                 s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->tk_from},
+        s->cnt_a, s->d2_off, s->tk_off);
+    TD_HIP(hipGetLastError());
+    if ((rc = read_head(s))) return rc;
+    if (*h_of(s, s->gerr)) {
+        (void)clear_err(s);
+        return fail(TD_EINTERNAL, "td_simb: a pool plan names a customer outside the demand list");
+    }
+    const int32_t *h2 = h_of(s, s->d2_off), *hn = h_of(s, s->n_pools);
+    for (int b = 0; b < B; b++) {
+        s->n_d2[b] = h2[b + 1] - h2[b];
+        if (s->n_dem[b] == 0) continue;
+        info[4 * b] = 1;
+        info[4 * b + 1] = s->n_dem[b];
+        info[4 * b + 2] = s->n_sup[b];
+        info[4 * b + 3] = s->n_d2[b];
+        if (s->n_sup[b] > 0) {
+            if (s->n_dem[b] >= 2) s->max_pool[b] = std::max(s->max_pool[b], (int64_t)hn[b]);
+            s->max_model[b] = std::max(s->max_model[b], (int64_t)std::max(s->n_sup[b], s->n_d2[b]));
+        }
+    }
+    return TD_OK;
+}
+
+// the decisions are on the device (dec); h_solved: the packed path's flags on the host (NULL: td_tick_batched's words of the head)
+int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_solved, int32_t *opt_count)
+{
+    Ctx &c = ctx();
+    const World &w = s->w;
+    const int B = s->B, t = s->last_t, mnl = s->max_non_lcm;
+    int rc;
+    int max_s = 0, max_d = 0, max_sd = 0;
+    bool any_lcm = false, any_sup = false;
+    for (int b = 0; b < B; b++) {
+        const int n_s = s->n_sup[b], n_d = s->n_d2[b];
+        if (n_s == 0) continue;
+        any_sup = true;
+        max_s = std::max(max_s, n_s);
+        if (std::max(n_s, n_d) > mnl) {
+            any_lcm = true;
+            max_d = std::max(max_d, n_d);
+            max_sd = std::max(max_sd, n_s + n_d);
+        }
+    }
+    const int32_t *hs = h_of(s, s->sup_off), *h2 = h_of(s, s->d2_off);
+    if (any_lcm) {
+        TD_HIP(hipMemsetAsync(s->pair_cab, 0x7f, sizeof(int32_t) * (size_t)hs[B], c.stream));
+        TD_HIP(hipMemsetAsync(s->pair_dem, 0x7f, sizeof(int32_t) * (size_t)h2[B], c.stream));
+        if (max_pairs > 0)
+            k_pair_map<<<dim3((max_pairs + 255) / 256, B), 256, 0, c.stream>>>(dec, mnl, s->sup_off, s->d2_off, s->pair_cab, s->pair_dem, s->gerr);
+        k_apply_pairs<<<dim3(nchunks(max_sd), B), CB, 0, c.stream>>>(w, t, dec, mnl, s->d_cab_off, s->sup_off, s->d2_off, s->pair_cab, s->pair_dem,
+                                                                   s->sup_cab, s->sup_to, s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, s->gerr);
+        const dim3 grid_s(nchunks(max_s), B), grid_d(nchunks(max_d), B);
+        const KeptPred ps{s->pair_cab, s->sup_off, s->d2_off, mnl}, pd{s->pair_dem, s->sup_off, s->d2_off, mnl};
+        k_count<KeptPred><<<grid_s, CB, 0, c.stream>>>(s->sup_off, ps, s->cnt_a);
+        k_count<KeptPred><<<grid_d, CB, 0, c.stream>>>(s->d2_off, pd, s->cnt_b);
+        k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, (int)grid_s.x, s->cnt_b, (int)grid_d.x, 0, nullptr, s->ks_off, s->kd_off, nullptr);
+        k_scatter<KeptPred, KeptSupEmit><<<grid_s, CB, 0, c.stream>>>(s->sup_off, ps, KeptSupEmit{s->sup_cab, s->sup_to, s->ks_cab, s->ks_to}, s->cnt_a,
+                                                                    s->ks_off, nullptr);
+        k_scatter<KeptPred, KeptDemEmit><<<grid_d, CB, 0, c.stream>>>(
+            s->d2_off, pd, KeptDemEmit{s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost},
+            s->cnt_b, s->kd_off, nullptr);
+    }
+    if (any_sup)
+        k_apply_solution<<<dim3(nchunks(max_s), B), CB, 0, c.stream>>>(w, t, dec, mnl, s->d_cab_off, s->sup_off, s->d2_off, s->ks_off, s->kd_off, s->sup_cab,
+                                                                     s->sup_to, s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->ks_cab,
+                                                                     s->ks_to, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, s->gerr);
+    TD_HIP(hipGetLastError());
+    if ((rc = read_head(s))) return rc;
+    const int err = *h_of(s, s->gerr);
+    if (err) {
+        // nothing was applied in any world (every kernel after the failing one is skipped): the tick still waits
+        if ((rc = clear_err(s))) return rc;
+        if (err == 2) return fail(TD_EINVAL, "td_simb_apply: a pair lies outside its world's model");
+        return fail(TD_EINTERNAL, "td_simb: device error word %d", err);
+    }
+    s->begun = false;
+    const int32_t *hks = h_of(s, s->ks_off), *hkd = h_of(s, s->kd_off), *hrest = h_of(s, s->tk_rest), *hlm = h_of(s, s->tk_lm);
+    for (int b = 0; b < B; b++) {
+        opt_count[b] = 0;
+        const int n_s = s->n_sup[b], n = std::max(n_s, s->n_d2[b]);
+        if (s->n_dem[b] == 0 || n_s == 0) continue;
+        const bool lcm = n > mnl;
+        const bool solved = h_solved ? h_solved[b] != 0 : (hrest[b] > 0 && !(lcm && hlm[b] == w.big_cost));
+        if (lcm) s->lcm_used[b]++;
+        if (lcm && !solved) {
+            opt_count[b] = -1;
+            continue;
+        }
+        opt_count[b] = h_ctl(s)[b].opt_count;
+        s->max_solver[b] = std::max(s->max_solver[b], (int64_t)(lcm ? std::max(hks[b + 1] - hks[b], hkd[b + 1] - hkd[b]) : n));
+    }
+    return TD_OK;
+}
+
+// offsets [B + 1] from the caller: start at 0, never decrease, world b's segment at most cap(b) long
+int check_offsets(const td_simb *s, const char *what, const std::vector<int32_t> &h, int *longest)
+{
+    *longest = 0;
+    if (h[0] != 0) return fail(TD_EINVAL, "td_simb_apply: %s[0] = %d, not 0", what, h[0]);
+    for (int b = 0; b < s->B; b++) {
+        const int m = h[b + 1] - h[b];
+        const int cap = std::max(std::max(s->cab_off[b + 1] - s->cab_off[b], s->req_off[b + 1] - s->req_off[b]), 1);
+        if (m < 0) return fail(TD_EINVAL, "td_simb_apply: %s decreases at world %d (%d -> %d)", what, b, h[b], h[b + 1]);
+        if (m > cap) return fail(TD_EINVAL, "td_simb_apply: world %d's segment of %s has %d entries, more than %d", b, what, m, cap);
+        *longest = std::max(*longest, m);
+    }
+    return TD_OK;
+}
+
+}  // namespace
+
+extern "C" int td_simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost,
+                              const int32_t *req_off, const int32_t *req_id, const int32_t *req_from, const int32_t *req_to,
+                              const int32_t *req_at, td_simb **out)
+{
+    TD_REQUIRE_INIT();
+    Ctx &c = ctx();
+    if (!out) return fail(TD_EINVAL, "null handle pointer");
+    *out = nullptr;
+    if (batch < 1 || batch > 65535) return fail(TD_EINVAL, "td_simb_create: batch = %d outside 1 .. 65535", batch);
+    if (!n_cabs || !req_off) return fail(TD_EINVAL, "td_simb_create: null n_cabs / req_off");
+    if (n_stands < 1 || drop_time < 0 || max_non_lcm < 0 || big_cost < 0) return fail(TD_EINVAL, "td_simb_create: n_stands at least 1, nothing negative");
+    if (n_stands > (1 << 18)) return fail(TD_EINVAL, "td_simb_create: at most %d stands (one bit per stand in LDS)", 1 << 18);
+    if (max_non_lcm > 1024)
+        return fail(TD_EINVAL, "td_simb_create: max_non_lcm = %d > 1024 (the remainder td_tick_batched hands its solver)", max_non_lcm);
+    const int B = batch;
+    int rc;
+    std::vector<int32_t> hc, ho;
+    if ((rc = host_copy(n_cabs, (size_t)B, hc)) || (rc = host_copy(req_off, (size_t)B + 1, ho))) return rc;
+    if (ho[0] != 0) return fail(TD_EINVAL, "td_simb_create: req_off[0] = %d, not 0", ho[0]);
+    std::vector<int32_t> cab_off((size_t)B + 1, 0);
+    int max_cabs = 0, max_req = 0;
+    size_t in_cap = 0;
+    for (int b = 0; b < B; b++) {
+        if (hc[b] < 1 || hc[b] > SIMB_NMAX) return fail(TD_EINVAL, "td_simb_create: world %d has %d cabs, outside 1 .. %d", b, hc[b], SIMB_NMAX);
+        if (ho[b + 1] < ho[b]) return fail(TD_EINVAL, "td_simb_create: req_off decreases at world %d (%d -> %d)", b, ho[b], ho[b + 1]);
+        cab_off[b + 1] = cab_off[b] + hc[b];
+        max_cabs = std::max(max_cabs, hc[b]);
+        max_req = std::max(max_req, ho[b + 1] - ho[b]);
+        in_cap += (size_t)std::max(std::max(hc[b], ho[b + 1] - ho[b]), 1);
+    }
+    const int n_req = ho[B], nc_tot = cab_off[B];
+    if (n_req && (!req_id || !req_from || !req_to || !req_at)) return fail(TD_EINVAL, "null request array");
+    // the request files on the host once: ids unique within a world and not negative, stands inside the line, times not negative
+    std::vector<int32_t> h((size_t)4 * n_req);
+    const int32_t *src[4] = {req_id, req_from, req_to, req_at};
+    for (int q = 0; q < 4 && n_req; q++) TD_HIP(hipMemcpy(h.data() + (size_t)q * n_req, src[q], sizeof(int32_t) * (size_t)n_req, hipMemcpyDefault));
+    for (int b = 0; b < B; b++) {
+        for (int i = ho[b]; i < ho[b + 1]; i++) {
+            const int32_t id = h[i], f = h[(size_t)n_req + i], to = h[(size_t)2 * n_req + i], at = h[(size_t)3 * n_req + i];
+            if (id < 0 || f < 0 || f >= n_stands || to < 0 || to >= n_stands || at < 0)
+                return fail(TD_EINVAL, "td_simb_create: world %d, request %d (id %d, from %d, to %d, at %d) is outside the world", b, i - ho[b], id, f,
+                            to, at);
+        }
+        std::vector<int32_t> ids(h.begin() + ho[b], h.begin() + ho[b + 1]);
+        std::sort(ids.begin(), ids.end());
+        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end())
+            return fail(TD_EINVAL, "td_simb_create: request ids must be unique within world %d", b);
+    }
+    td_simb *s = new td_simb();
+    s->B = B;
+    s->max_non_lcm = max_non_lcm;
+    s->max_cabs = max_cabs;
+    s->max_req = max_req;
+    s->nc_tot = nc_tot;
+    s->nr_tot = n_req;
+    s->words = (n_stands + 31) / 32;
+    s->cab_off = cab_off;
+    s->req_off = ho;
+    s->ncap = std::max(1, std::min(SIMB_NMAX, std::max(max_cabs, max_req)));
+    s->hcap = std::max(1, std::min(SIMB_NMAX, max_req) / 2);
+    s->in_cap = in_cap;
+    for (std::vector<int32_t> *v : {&s->n_dem, &s->n_sup, &s->n_d2}) v->assign((size_t)B, 0);
+    for (std::vector<int64_t> *v : {&s->lcm_used, &s->max_model, &s->max_solver, &s->max_pool_mem, &s->max_pool}) v->assign((size_t)B, 0);
+    const size_t nb = (size_t)B, nr = (size_t)std::max(n_req, 1), nc = (size_t)nc_tot, words = (size_t)s->words;
+    const size_t n_cnt = nb * (size_t)nchunks(std::max(max_cabs, max_req));
+    s->pool_cap = std::max(nb * (size_t)s->hcap, nr / 2 + 1);
+    const size_t tk_cap = nb * (size_t)s->ncap;
+    s->head_ints = 16 * nb + 16 + (size_t)N_OFF * (nb + 1) + (size_t)N_PER * nb;
+    const size_t ints = s->head_ints + 2 * (nb + 1) + 2 * words * nb + 2 * n_cnt + 9 * nr + 5 * nc   // head, offsets, bits, counts, tables
+                        + 5 * nr + 2 * nc + 6 * nr + 2 * nc + 5 * nr + 2 * nr                        // dem / pl, sup, d2 / tk, ks, kd, isb / ainfo
+                        + 4 * s->pool_cap + 4 * nb + nc + nr                                         // plans, two int64 [B], pair maps
+                        + 3 * in_cap + 2 * (nb + 1) + nb + 3 * tk_cap + std::max<size_t>(max_cabs, 1) + 64;
+    rc = ensure(s->mem, sizeof(int32_t) * ints);
+    if (rc) {
+        delete s;
+        return rc;
+    }
+    int32_t *p = (int32_t *)s->mem.p;
+    auto take = [&](size_t k) {
+        int32_t *r = p;
+        p += k;
+        return r;
+    };
+    s->p_total = (int64_t *)take(2 * nb);   // the 64-bit arrays first: 8-byte aligned, and so is the head (Ctl holds 64-bit sums)
+    s->tk_total = (int64_t *)take(2 * nb);
+    s->head = p;
+    s->ctl = (Ctl *)take(16 * nb);
+    s->gerr = take(16);
+    s->dem_off = take(nb + 1);   // the seven offset arrays and the four per-world arrays are one block (zeroed per tick)
+    s->sup_off = take(nb + 1);
+    s->pl_off = take(nb + 1);
+    s->d2_off = take(nb + 1);
+    s->tk_off = take(nb + 1);
+    s->ks_off = take(nb + 1);
+    s->kd_off = take(nb + 1);
+    s->n_pools = take(nb);
+    s->tk_np = take(nb);
+    s->tk_lm = take(nb);
+    s->tk_rest = take(nb);
+    s->d_cab_off = take(nb + 1);
+    s->d_req_off = take(nb + 1);
+    s->bits = (uint32_t *)take(2 * words * nb);
+    s->cnt_a = take(n_cnt);
+    s->cnt_b = take(n_cnt);
+    World &w = s->w;
+    w.n_cabs = nc_tot;
+    w.n_req = n_req;
+    w.n_stands = n_stands;
+    w.drop_time = drop_time;
+    w.big_cost = big_cost;
+    int32_t *rid = take(nr), *rfrom = take(nr), *rto = take(nr), *rat = take(nr);
+    w.r_id = rid;
+    w.r_from = rfrom;
+    w.r_to = rto;
+    w.r_at = rat;
+    w.r_cab = take(nr);
+    w.r_pick = take(nr);
+    w.r_pid = take(nr);
+    w.r_plan = take(nr);
+    w.r_pcost = take(nr);
+    w.c_from = take(nc);
+    w.c_to = take(nc);
+    w.c_clnt = take(nc);
+    w.c_onb = take(nc);
+    w.c_start = take(nc);
+    s->dem_idx = take(nr);
+    s->dem_from = take(nr);
+    s->dem_to = take(nr);
+    s->pl_from = take(nr);
+    s->pl_to = take(nr);
+    s->sup_cab = take(nc);
+    s->sup_to = take(nc);
+    s->d2_idx = take(nr);
+    s->d2_from = take(nr);
+    s->d2_partner = take(nr);
+    s->d2_plan = take(nr);
+    s->d2_cost = take(nr);
+    s->tk_from = take(nr);
+    s->ks_cab = take(nc);
+    s->ks_to = take(nc);
+    s->kd_idx = take(nr);
+    s->kd_from = take(nr);
+    s->kd_partner = take(nr);
+    s->kd_plan = take(nr);
+    s->kd_cost = take(nr);
+    s->isb = take(nr);
+    s->ainfo = take(nr);
+    s->pa = take(s->pool_cap);
+    s->pb = take(s->pool_cap);
+    s->pp = take(s->pool_cap);
+    s->pc = take(s->pool_cap);
+    s->pair_cab = take(nc);
+    s->pair_dem = take(nr);
+    s->in_rows = take(in_cap);
+    s->in_cols = take(in_cap);
+    s->in_r2c = take(in_cap);
+    s->in_pair_off = take(nb + 1);
+    s->in_r2c_off = take(nb + 1);
+    s->in_solved = take(nb);
+    s->tk_rows = take(tk_cap);
+    s->tk_cols = take(tk_cap);
+    s->tk_r2c = take(tk_cap);
+    s->tmp = take(std::max<size_t>(max_cabs, 1));
+    auto bail = [&](int code) {
+        td_simb_destroy(s);
+        return code;
+    };
+    // pinned: the head's mirror, then a stage for the offsets / flags of td_simb_apply and the initial tables
+    const size_t stage_ints = std::max<size_t>(3 * (nb + 1), 2 * (nb + 1) + 5 * nc + 5 * nr);
+    hipError_t e = hipHostMalloc(&s->pin, sizeof(int32_t) * (s->head_ints + stage_ints + 16), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        s->pin = nullptr;
+        return bail(hip_fail(e, "hipHostMalloc(td_simb)"));
+    }
+    s->h_head = (int32_t *)s->pin;
+    s->h_stage = s->h_head + s->head_ints;
+    // the initial world, made on the host: cab c of a world stands at c % n_stands (initSupply :565-573), no request is assigned
+    int32_t *st = s->h_stage;
+    memcpy(st, cab_off.data(), sizeof(int32_t) * (nb + 1));
+    memcpy(st + nb + 1, ho.data(), sizeof(int32_t) * (nb + 1));
+    int32_t *ic = st + 2 * (nb + 1), *ir = ic + 5 * nc;
+    for (int b = 0; b < B; b++)
+        for (int l = 0; l < hc[b]; l++) {
+            const size_t g = (size_t)cab_off[b] + l;
+            ic[g] = ic[nc + g] = l % n_stands;
+            ic[2 * nc + g] = -1;
+            ic[3 * nc + g] = 0;
+            ic[4 * nc + g] = -1;
+        }
+    for (size_t d = 0; d < nr; d++) {
+        ir[d] = ir[nr + d] = ir[2 * nr + d] = ir[3 * nr + d] = -1;
+        ir[4 * nr + d] = 0;
+    }
+    if ((e = hipMemsetAsync(s->mem.p, 0, sizeof(int32_t) * (4 * nb + s->head_ints), c.stream)) != hipSuccess) return bail(hip_fail(e, "hipMemsetAsync"));
+    struct Up {
+        void *dst;
+        const void *src;
+        size_t n;
+    } ups[] = {{s->d_cab_off, st, nb + 1},           {s->d_req_off, st + nb + 1, nb + 1},  {w.c_from, ic, nc},
+               {w.c_to, ic + nc, nc},                 {w.c_clnt, ic + 2 * nc, nc},          {w.c_onb, ic + 3 * nc, nc},
+               {w.c_start, ic + 4 * nc, nc},          {w.r_cab, ir, nr},                    {w.r_pick, ir + nr, nr},
+               {w.r_pid, ir + 2 * nr, nr},            {w.r_plan, ir + 3 * nr, nr},          {w.r_pcost, ir + 4 * nr, nr},
+               {rid, h.data(), (size_t)n_req},        {rfrom, h.data() + (size_t)n_req, (size_t)n_req},
+               {rto, h.data() + (size_t)2 * n_req, (size_t)n_req}, {rat, h.data() + (size_t)3 * n_req, (size_t)n_req}};
+    for (const Up &u : ups)
+        if (u.n && (e = hipMemcpyAsync(u.dst, u.src, sizeof(int32_t) * u.n, hipMemcpyHostToDevice, c.stream)) != hipSuccess)
+            return bail(hip_fail(e, "hipMemcpyAsync(td_simb tables)"));
+    if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return bail(hip_fail(e, "hipStreamSynchronize"));   // `h` leaves scope
+    *out = s;
+    return TD_OK;
+}
+
+extern "C" int td_simb_destroy(td_simb *s)
+{
+    if (!s) return TD_OK;
+    if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
+    buf_free(s->mem);
+    if (s->pin) (void)hipHostFree(s->pin);
+    delete s;
+    return TD_OK;
+}
+
+extern "C" int td_simb_begin(td_simb *s, int t, int32_t *info)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !info) return fail(TD_EINVAL, "null argument");
+    if (t < 0) return fail(TD_EINVAL, "negative tick");
+    if (s->begun) return fail(TD_EINVAL, "td_simb_begin: tick %d still waits for td_simb_apply", s->last_t);
+    if (t <= s->last_t) return fail(TD_EINVAL, "td_simb_begin: tick %d after tick %d (a tick begins once, time runs forward)", t, s->last_t);
+    return simb_begin(s, t, info);
+}
+
+extern "C" int td_simb_model(td_simb *s, int32_t *cab_off, int32_t *cab_to, int32_t *dem_off, int32_t *dem_from)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (!s->begun) return fail(TD_EINVAL, "td_simb_model: no tick with demand has begun");
+    const size_t B = (size_t)s->B;
+    const int n_s = h_of(s, s->sup_off)[B], n_d = h_of(s, s->d2_off)[B];
+    if (!cab_off || !dem_off || (n_s && !cab_to) || (n_d && !dem_from)) return fail(TD_EINVAL, "null destination");
+    int rc;
+    // a world without supply was not pooled: its model's requests are its temp demand (d2 is a copy of it there)
+    if ((rc = get(cab_off, s->sup_off, B + 1)) || (rc = get(dem_off, s->d2_off, B + 1)) || (rc = get(cab_to, s->sup_to, (size_t)n_s)) ||
+        (rc = get(dem_from, s->d2_from, (size_t)n_d)))
+        return rc;
+    TD_HIP(hipStreamSynchronize(ctx().stream));
+    return TD_OK;
+}
+
+extern "C" int td_simb_apply(td_simb *s, const int32_t *pair_off, const int32_t *lcm_rows, const int32_t *lcm_cols, const int32_t *solved,
+                             const int32_t *r2c_off, const int32_t *row_to_col, int32_t *opt_count)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !opt_count || !pair_off || !solved || !r2c_off) return fail(TD_EINVAL, "null argument");
+    if (!s->begun) return fail(TD_EINVAL, "td_simb_apply: no tick with demand has begun");
+    Ctx &c = ctx();
+    const size_t B = (size_t)s->B;
+    int rc, max_pairs, max_r2c;
+    std::vector<int32_t> hp, hr, hsol;
+    if ((rc = host_copy(pair_off, B + 1, hp)) || (rc = host_copy(r2c_off, B + 1, hr)) || (rc = host_copy(solved, B, hsol))) return rc;
+    if ((rc = check_offsets(s, "pair_off", hp, &max_pairs)) || (rc = check_offsets(s, "r2c_off", hr, &max_r2c))) return rc;
+    if ((hp[B] && (!lcm_rows || !lcm_cols)) || (hr[B] && !row_to_col)) return fail(TD_EINVAL, "null decision array");
+    int32_t *st = s->h_stage;
+    memcpy(st, hp.data(), sizeof(int32_t) * (B + 1));
+    memcpy(st + B + 1, hr.data(), sizeof(int32_t) * (B + 1));
+    memcpy(st + 2 * (B + 1), hsol.data(), sizeof(int32_t) * B);
+    // in_pair_off, in_r2c_off and in_solved are one block of the handle's memory, in this order
+    TD_HIP(hipMemcpyAsync(s->in_pair_off, st, sizeof(int32_t) * (3 * B + 2), hipMemcpyHostToDevice, c.stream));
+    if ((rc = put(s->in_rows, lcm_rows, (size_t)hp[B])) || (rc = put(s->in_cols, lcm_cols, (size_t)hp[B])) ||
+        (rc = put(s->in_r2c, row_to_col, (size_t)hr[B])))
+        return rc;
+    const SimbDec dec{s->in_rows, s->in_cols, s->in_r2c, s->in_pair_off, s->in_r2c_off, s->in_solved, nullptr, nullptr, nullptr, 0};
+    return simb_apply(s, dec, max_pairs, hsol.data(), opt_count);
+}
+
+extern "C" int td_simb_step(td_simb *s, int t, int32_t *line)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !line) return fail(TD_EINVAL, "null argument");
+    const int B = s->B;
+    std::vector<int32_t> info((size_t)4 * B), opt((size_t)B, 0);
+    int rc = td_simb_begin(s, t, info.data());
+    if (rc) return rc;
+    for (int q = 0; q < 9 * B; q++) line[q] = 0;
+    if (!s->begun) return TD_OK;
+    int n = 0;
+    for (int b = 0; b < B; b++) {
+        if (s->n_sup[b] == 0) continue;
+        if (s->n_dem[b] > SIMB_NMAX)
+            return fail(TD_EINVAL,
+                        "td_simb_step: world %d has %d requests before pooling in tick %d, more than %d; finish the tick through td_simb_model / "
+                        "td_simb_apply",
+                        b, s->n_dem[b], t, SIMB_NMAX);
+        n = std::max(n, std::max(s->n_sup[b], s->n_d2[b]));
+    }
+    if (n > 0) {
+        // the arguments HipTickBackend.tick hands td_tick, for every world with supply at once; the lists stay where they are
+        if ((rc = td_tick_batched(B, n, h_of(s, s->sup_off), s->sup_to, h_of(s, s->tk_off), s->tk_from, nullptr, 0, s->w.big_cost, s->w.drop_time,
+                                  s->max_non_lcm, s->tk_rows, s->tk_cols, s->tk_np, s->tk_lm, nullptr, nullptr, s->tk_rest, s->tk_r2c, s->tk_total,
+                                  nullptr)))
+            return rc;
+    }
+    const int stride = std::max(n, 1);
+    const SimbDec dec{s->tk_rows, s->tk_cols, s->tk_r2c, nullptr, nullptr, nullptr, s->tk_np, s->tk_rest, s->tk_lm, stride};
+    if ((rc = simb_apply(s, dec, stride, nullptr, opt.data()))) return rc;
+    const int32_t *hk = h_of(s, s->tk_np), *hrest = h_of(s, s->tk_rest), *hlm = h_of(s, s->tk_lm);
+    for (int b = 0; b < B; b++) {
+        int32_t *ln = line + 9 * b;
+        if (s->n_dem[b] == 0) continue;
+        ln[0] = 1;
+        ln[1] = s->n_dem[b];
+        ln[2] = s->n_sup[b];
+        const int n_s = s->n_sup[b], n_d = s->n_d2[b];
+        if (n_s > 0) {
+            const bool lcm = s->max_non_lcm < std::max(n_s, n_d);
+            const bool solved = hrest[b] > 0 && !(lcm && hlm[b] == s->w.big_cost);
+            const int k = lcm ? hk[b] : 0;
+            ln[3] = lcm;
+            ln[4] = k;
+            ln[5] = lcm && solved;
+            ln[6] = n_d - k;
+            ln[7] = n_s - k;
+        }
+        ln[8] = opt[b];
+    }
+    return TD_OK;
+}
+
+extern "C" int td_simb_state(td_simb *s, int world, int32_t *c_from, int32_t *c_to, int32_t *c_clnt, int32_t *c_onboard, int32_t *c_start,
+                             int32_t *d_cab, int32_t *d_pick, int32_t *d_pool_id, int32_t *d_pool_plan, int32_t *d_pool_cost)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (world < 0 || world >= s->B) return fail(TD_EINVAL, "td_simb_state: world %d outside 0 .. %d", world, s->B - 1);
+    Ctx &c = ctx();
+    const World &w = s->w;
+    const int c0 = s->cab_off[world], ncab = s->cab_off[world + 1] - c0, r0 = s->req_off[world], nreq = s->req_off[world + 1] - r0;
+    int rc;
+    if (c_clnt) {
+        k_client_ids<<<(ncab + 255) / 256, 256, 0, c.stream>>>(w, c0, ncab, s->tmp);
+        TD_HIP(hipGetLastError());
+    }
+    int32_t *cd[5] = {c_from, c_to, c_clnt, c_onboard, c_start};
+    const int32_t *cs[5] = {w.c_from + c0, w.c_to + c0, s->tmp, w.c_onb + c0, w.c_start + c0};
+    int32_t *rd[5] = {d_cab, d_pick, d_pool_id, d_pool_plan, d_pool_cost};
+    const int32_t *rs[5] = {w.r_cab + r0, w.r_pick + r0, w.r_pid + r0, w.r_plan + r0, w.r_pcost + r0};
+    for (int q = 0; q < 5; q++)
+        if ((rc = get(cd[q], cs[q], (size_t)ncab)) || (rc = get(rd[q], rs[q], (size_t)nreq))) return rc;
+    TD_HIP(hipStreamSynchronize(c.stream));
+    return TD_OK;
+}
+
+extern "C" int td_simb_metrics(td_simb *s, int64_t *out)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !out) return fail(TD_EINVAL, "null argument");
+    int rc = read_head(s);
+    if (rc) return rc;
+    for (int b = 0; b < s->B; b++) {
+        const Ctl &h = h_ctl(s)[b];
+        int64_t *o = out + (size_t)TD_SIM_N_METRICS * b;
+        o[0] = h.dropped;
+        o[1] = h.pickup_time;
+        o[2] = h.pickup_numb;
+        o[3] = s->lcm_used[b];
+        o[4] = s->max_model[b];
+        o[5] = s->max_solver[b];
+        o[6] = s->max_pool_mem[b];
+        o[7] = s->max_pool[b];
+        o[8] = h.second;
+    }
+    return TD_OK;
+}

@@ -491,3 +491,161 @@ class DeviceSimulator:
         view.d_id = np.empty(self.n_req, np.int64)
         view.d_cab = self.state()["d_cab"]
         return Simulator.metrics_text(view, total_simul_time, max_solver_time, max_lcm_time, max_pool_time)
+
+
+def pack_worlds(demand_rows_list, n_cabs_list):
+    """The host side of td_simb_create: a list of demand tables (rows `(id, from, to, time, at)`, one table per world; a
+    table may be empty) and a list of fleet sizes -> (n_cabs[B], req_off[B+1], id, from, to, at), the tables concatenated
+    world after world as int32.  Ids must be unique and not negative within a world; two worlds may use the same ids."""
+    tables = list(demand_rows_list)
+    cabs = [int(c) for c in n_cabs_list]
+    if not tables:
+        raise ValueError("pack_worlds: a batch needs at least one world")
+    if len(tables) != len(cabs):
+        raise ValueError("pack_worlds: %d demand tables for %d fleet sizes" % (len(tables), len(cabs)))
+    off, parts = [0], []
+    for b, rows in enumerate(tables):
+        d = np.asarray(rows, dtype=np.int64)
+        if d.size == 0:
+            d = d.reshape(0, 5)
+        if d.ndim != 2 or d.shape[1] != 5:
+            raise ValueError("pack_worlds: world %d's demand table has shape %r, not (n, 5)" % (b, d.shape))
+        if cabs[b] < 1:
+            raise ValueError("pack_worlds: world %d has %d cabs, at least 1 is needed" % (b, cabs[b]))
+        ids = d[:, 0]
+        if ids.size and ids.min() < 0:
+            raise ValueError("pack_worlds: world %d has a negative request id" % b)
+        if np.unique(ids).size != ids.size:
+            raise ValueError("pack_worlds: request ids must be unique within world %d" % b)
+        if d.size and (d.max() > 2**31 - 1 or d.min() < -2**31):
+            raise ValueError("pack_worlds: world %d holds a value outside int32" % b)
+        parts.append(d)
+        off.append(off[-1] + d.shape[0])
+    if off[-1] > 2**31 - 1:
+        raise ValueError("pack_worlds: %d requests in all, more than int32 offsets address" % off[-1])
+    allrows = np.concatenate(parts, axis=0)
+    cols = [np.ascontiguousarray(allrows[:, k].astype(np.int32)) for k in (0, 1, 2, 4)]
+    return (np.asarray(cabs, np.int32), np.asarray(off, np.int32)) + tuple(cols)
+
+
+class DeviceSimulatorBatch:
+    """B independent worlds behind ONE handle (td_simb_*, csrc/td_simb.hip): the worlds share the city (n_stands, drop_time,
+    max_non_lcm, big_cost) and differ in fleet size and request table.  `tick` advances every world by one td_simb_step
+    (td_pool2_batched and td_tick_batched on the device lists); `begin` / `model` / `apply` split the tick for decisions
+    from any source.  Per world, lines, `m[b]`, `state(b)` and `metrics_text(b)` are those of `DeviceSimulator`."""
+
+    M_KEYS, CAB_KEYS, REQ_KEYS = DeviceSimulator.M_KEYS, DeviceSimulator.CAB_KEYS, DeviceSimulator.REQ_KEYS
+    format_line = staticmethod(DeviceSimulator.format_line)
+
+    def __init__(self, demand_rows_list, n_cabs_list, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None):
+        import ctypes
+        from . import _ffi
+        self._ffi, self._ct = _ffi, ctypes
+        self._h = None
+        cabs, off, rid, rfrom, rto, rat = pack_worlds(demand_rows_list, n_cabs_list)
+        self._lib = _ffi.lib()
+        self.batch = int(cabs.size)
+        self.n_cabs = [int(v) for v in cabs]
+        self.req_off = off
+        self.n_req = [int(off[b + 1] - off[b]) for b in range(self.batch)]
+        self.n_stands = int(N_STANDS if n_stands is None else n_stands)
+        self.drop_time = int(DROP_TIME if drop_time is None else drop_time)
+        self.max_non_lcm = int(MAX_NON_LCM if max_non_lcm is None else max_non_lcm)
+        self.big_cost = int(BIG_COST if big_cost is None else big_cost)
+        h = ctypes.c_void_p()
+        some = int(off[-1]) > 0
+        _ffi.check(self._lib.td_simb_create(self.batch, _ffi.addr(cabs), self.n_stands, self.drop_time, self.max_non_lcm, self.big_cost,
+                                            _ffi.addr(off), *[_ffi.addr(c) if some else None for c in (rid, rfrom, rto, rat)],
+                                            ctypes.byref(h)))
+        self._h = h
+        self._info = None
+        self.logs = [[] for _ in range(self.batch)]
+
+    def close(self):
+        if self._h is not None:
+            self._lib.td_simb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- the split tick
+    def begin(self, t):
+        """-> int32 [B, 4]: per world (has_demand, demand before pooling, supply, demand after pooling)"""
+        info = np.zeros((self.batch, 4), np.int32)
+        self._ffi.check(self._lib.td_simb_begin(self._h, int(t), self._ffi.addr(info)))
+        self._info = info
+        return info
+
+    def model(self):
+        """this tick's models: (cab_off, cab_to, dem_off, dem_from), ragged over the worlds (also after a `tick` that
+        td_simb_step refused: the tick is then begun and waits for `apply`)"""
+        cab_off, dem_off = np.zeros(self.batch + 1, np.int32), np.zeros(self.batch + 1, np.int32)
+        cab, dem = np.empty(max(sum(self.n_cabs), 1), np.int32), np.empty(max(sum(self.n_req), 1), np.int32)
+        self._ffi.check(self._lib.td_simb_model(self._h, *[self._ffi.addr(a) for a in (cab_off, cab, dem_off, dem)]))
+        return cab_off, cab[:cab_off[-1]], dem_off, dem[:dem_off[-1]]
+
+    def apply(self, decisions):
+        """decisions: per world None (nothing to apply) or (lcm_rows, lcm_cols, solved, row_to_col) -> OPT counts [B]"""
+        if len(decisions) != self.batch:
+            raise self._ffi.TdError("DeviceSimulatorBatch.apply: %d decisions for %d worlds" % (len(decisions), self.batch))
+        rows, cols, r2c, solved, p_off, r_off = [], [], [], [], [0], [0]
+        for d in decisions:
+            a, b, sv, r = ((), (), False, ()) if d is None else d
+            a, b, r = (self._ffi.as_i32(np.asarray(x).reshape(-1)) for x in (a, b, r))
+            if a.size != b.size:
+                raise self._ffi.TdError("lcm_rows and lcm_cols differ in length")
+            rows.append(a), cols.append(b), r2c.append(r), solved.append(int(bool(sv)))
+            p_off.append(p_off[-1] + a.size), r_off.append(r_off[-1] + r.size)
+        rows, cols, r2c = (np.ascontiguousarray(np.concatenate(x).astype(np.int32)) for x in (rows, cols, r2c))
+        p_off, r_off, solved = (np.asarray(x, np.int32) for x in (p_off, r_off, solved))
+        opt = np.zeros(self.batch, np.int32)
+        ad = self._ffi.addr
+        self._ffi.check(self._lib.td_simb_apply(self._h, ad(p_off), ad(rows) if rows.size else None, ad(cols) if cols.size else None,
+                                                ad(solved), ad(r_off), ad(r2c) if r2c.size else None, ad(opt)))
+        return opt
+
+    # ---- one tick of every world in one call
+    def tick(self, t):
+        """-> the B log lines of tick t (None for a world without demand), or None when no world has one"""
+        line = np.zeros((self.batch, 9), np.int32)
+        self._ffi.check(self._lib.td_simb_step(self._h, int(t), self._ffi.addr(line)))
+        self._info = None
+        if not line[:, 0].any():
+            return None
+        return [self.format_line(int(t), line[b]) for b in range(self.batch)]
+
+    def run(self, t_end=HOURS * 60):
+        for t in range(t_end):
+            lines = self.tick(t)
+            if lines is not None:
+                for b, line in enumerate(lines):
+                    if line is not None:
+                        self.logs[b].append(line)
+        return self.logs
+
+    # ---- read-outs
+    @property
+    def m(self):
+        out = np.zeros((self.batch, len(self.M_KEYS)), np.int64)
+        self._ffi.check(self._lib.td_simb_metrics(self._h, self._ffi.addr(out)))
+        return [{k: int(v) for k, v in zip(self.M_KEYS, row)} for row in out]
+
+    def state(self, b):
+        """the ten state arrays of world b under Simulator's attribute names (c_clnt holds request ids)"""
+        nc, nr = self.n_cabs[b], self.n_req[b]
+        arrs = [np.empty(max(nc, 1), np.int32) for _ in self.CAB_KEYS] + [np.empty(max(nr, 1), np.int32) for _ in self.REQ_KEYS]
+        self._ffi.check(self._lib.td_simb_state(self._h, int(b), *[self._ffi.addr(a) for a in arrs]))
+        out = {k: a[:nc] for k, a in zip(self.CAB_KEYS, arrs[:5])}
+        out.update({k: a[:nr] for k, a in zip(self.REQ_KEYS, arrs[5:])})
+        return out
+
+    def metrics_text(self, b, total_simul_time=0, max_solver_time=0, max_lcm_time=0, max_pool_time=0):
+        view = Simulator.__new__(Simulator)
+        view.m = self.m[b]
+        view.d_id = np.empty(self.n_req[b], np.int64)
+        view.d_cab = self.state(b)["d_cab"]
+        return Simulator.metrics_text(view, total_simul_time, max_solver_time, max_lcm_time, max_pool_time)

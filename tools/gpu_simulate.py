@@ -1,15 +1,32 @@
 """Full 120-tick replay of the reference's simulation input with every path operation on the GPU
 (dev tool; prints timing + the printMetrics block).  --world host (default): the Python world model around the GPU path;
---world device: the world in device memory too (DeviceSimulator = td_sim_step, one C-ABI call per tick)."""
+--world device: the world in device memory too (DeviceSimulator = td_sim_step, one C-ABI call per tick);
+--world device --cabs 900,1100,1300: the committed demand file once per fleet size as ONE batch of worlds
+(DeviceSimulatorBatch = td_simb_step, one C-ABI call per tick for all of them), each world's metrics block printed."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import taxidispatcher_amd as td
 from taxidispatcher_amd import simulator
 ap = argparse.ArgumentParser()
 ap.add_argument("--world", choices=("host", "device"), default="host")
+ap.add_argument("--cabs", default=None, help="comma-separated fleet sizes: one world per size, run as one batch (needs --world device)")
 args = ap.parse_args()
+if args.cabs and args.world != "device":
+    ap.error("--cabs needs --world device")
 td.init(0)
 rows = simulator.read_demand("tests/golden/taxi_demand.txt.gz")
+if args.world == "device" and args.cabs:
+    fleets = [int(v) for v in args.cabs.split(",")]
+    sim = simulator.DeviceSimulatorBatch([rows] * len(fleets), fleets)
+    t0 = time.time()
+    logs = sim.run(120)
+    dt = time.time() - t0
+    print("120 ticks of %d worlds in %.2f s; worlds and path on the GPU, one td_simb_step call per tick for all worlds" % (len(fleets), dt))
+    for b, n in enumerate(fleets):
+        print("\n=== world %d: %d cabs ===" % (b, n))
+        print("\n".join(logs[b][-2:]))
+        print(sim.metrics_text(b, total_simul_time=int(dt)))
+    sys.exit(0)
 if args.world == "device":
     sim = simulator.DeviceSimulator(rows)
     t0 = time.time()
