@@ -422,6 +422,11 @@ TD_API int td_pool2_batched(int batch, int n, const int32_t *off, const int32_t 
  *   pool[10000] simply overflows there).
  *   k = 2, 3 or 4 passengers (TD_EINVAL otherwise: with k = 1 the reference's duplicate test compares its 4 padded slots
  *   and keeps a single pool, which is not reproduced).
+ *   td_pool_n: n <= 2047 (TD_EINVAL above); TD_ERANGE when a happy plan costs more than 16383 (n_happy is still set).
+ *   td_pool_merge: n_requests <= 2047 (TD_EINVAL above).  Precondition on pools_in (host or device memory): the first k
+ *   fields of every record, the requests, lie in [0, n_requests).  It is checked on the device before the de-duplication
+ *   runs: an input with a request outside that range is refused with TD_EINVAL, td_last_error() names the first such record
+ *   and the id, *n_out = 0 and nothing is written to pools_out.
  */
 TD_API int td_pool_n(int k, int n, const int32_t *from, const int32_t *to, const int32_t *max_wait,
                      const int32_t *max_loss, const int32_t *dist, int S, int first0, int first1,

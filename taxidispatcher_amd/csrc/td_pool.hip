@@ -66,6 +66,7 @@ struct PnCtl {
     unsigned long long happy;   // happy plans found (may exceed the capacity: then the call fails)
     int err;                    // 1: cost does not fit the key
     int kept;
+    int bad;                    // td_pool_merge: n_in - (first record naming a request outside [0, n_requests)), 0: none
 };
 
 // happiness of all passengers + plan cost for pick-ups p and drop-off order q
@@ -113,14 +114,14 @@ __global__ __launch_bounds__(256) void k_pooln_enum(int n, const int32_t *__rest
         sl[i] = loss[i];
     }
     __syncthreads();
-    constexpr int NP = K == 1 ? 1 : (K == 2 ? 2 : (K == 3 ? 6 : 24));
+    static_assert(K == 2 || K == 3, "pools of four have k_pooln_enum4");
+    constexpr int NP = K == 2 ? 2 : 6;
     int p[4] = {0, 0, 0, 0};
     p[0] = first0 + blockIdx.y;
     if (p[0] >= first1 || 0 > sw[p[0]]) return;   // (pool_n.c:177 at level 0: an empty path against WAIT)
     const unsigned long long nn = (unsigned long long)n;
-    auto emit = [&](int p2, int p3) {
+    auto emit = [&](int p2) {
         p[2] = p2;
-        p[3] = p3;
         for (int qi = 0; qi < NP; qi++) {
             int q[4];
             pn_perm(K, qi, q);
@@ -129,39 +130,24 @@ __global__ __launch_bounds__(256) void k_pooln_enum(int n, const int32_t *__rest
                 const unsigned long long idx = atomicAdd(&ctl->happy, 1ull);
                 if (cost > PN_MAXCOST || cost < 0) atomicOr(&ctl->err, 1);
                 if (idx < cap) {
-                    const unsigned long long seq = ((((unsigned long long)p[0] * nn + (K > 1 ? p[1] : 0)) * nn + (K > 2 ? p2 : 0)) * nn +
-                                                    (K > 3 ? p3 : 0)) * 24ull + (unsigned long long)qi;
+                    const unsigned long long seq = (((unsigned long long)p[0] * nn + p[1]) * nn + p2) * nn * 24ull + (unsigned long long)qi;
                     keys[idx] = ((unsigned long long)cost << PN_SEQ_BITS) | seq;
                 }
             }
         }
     };
-    if constexpr (K == 1) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) emit(0, 0);
-        return;
+    const int p1 = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p1 >= n || p1 == p[0]) return;
+    p[1] = p1;
+    const int d01 = pn_d(dist, S, sf[p[0]], sf[p1]);
+    if (d01 > sw[p1]) return;           // pool_n.c:177-178
+    if constexpr (K == 2) {
+        emit(0);
     } else {
-        const int p1 = blockIdx.x * blockDim.x + threadIdx.x;
-        if (p1 >= n || p1 == p[0]) return;
-        p[1] = p1;
-        const int d01 = pn_d(dist, S, sf[p[0]], sf[p1]);
-        if (d01 > sw[p1]) return;           // pool_n.c:177-178
-        if constexpr (K == 2) {
-            emit(0, 0);
-        } else {
-            for (int p2 = 0; p2 < n; p2++) {
-                if (p2 == p[0] || p2 == p1) continue;
-                const int d012 = d01 + pn_d(dist, S, sf[p1], sf[p2]);
-                if (d012 > sw[p2]) continue;
-                if constexpr (K == 3) {
-                    emit(p2, 0);
-                } else {
-                    for (int p3 = 0; p3 < n; p3++) {
-                        if (p3 == p[0] || p3 == p1 || p3 == p2) continue;
-                        if (d012 + pn_d(dist, S, sf[p2], sf[p3]) > sw[p3]) continue;
-                        emit(p2, p3);
-                    }
-                }
-            }
+        for (int p2 = 0; p2 < n; p2++) {
+            if (p2 == p[0] || p2 == p1) continue;
+            if (d01 + pn_d(dist, S, sf[p1], sf[p2]) > sw[p2]) continue;
+            emit(p2);
         }
     }
 }
@@ -339,13 +325,18 @@ __global__ void k_pooln_emit(int k, int n, int nkept, const unsigned long long *
     }
 }
 
-// merge keys: (cost when sorting by cost) << 32 | input position
-__global__ void k_pool_merge_keys(int k, int n_in, const int32_t *__restrict__ recs, int sort_by_cost,
-                                  unsigned long long *__restrict__ keys)
+// merge keys: (cost when sorting by cost) << 32 | input position.  A record that names a request outside [0, n_requests)
+// would index the greedy's LDS tables out of bounds: the first such record is reported in ctl->bad (atomicMax of n_in - t)
+__global__ void k_pool_merge_keys(int k, int n_requests, int n_in, const int32_t *__restrict__ recs, int sort_by_cost,
+                                  unsigned long long *__restrict__ keys, PnCtl *__restrict__ ctl)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_in) return;
-    const unsigned long long c = sort_by_cost ? (unsigned long long)(uint32_t)recs[(size_t)t * (2 * k + 1) + 2 * k] : 0ull;
+    const int32_t *r = recs + (size_t)t * (size_t)(2 * k + 1);
+    bool bad = false;
+    for (int a = 0; a < k; a++) bad = bad || r[a] < 0 || r[a] >= n_requests;
+    if (bad) atomicMax(&ctl->bad, n_in - t);
+    const unsigned long long c = sort_by_cost ? (unsigned long long)(uint32_t)r[2 * k] : 0ull;
     keys[t] = (c << 32) | (unsigned long long)t;
 }
 
@@ -451,18 +442,11 @@ extern "C" int td_pool_n(int k, int n, const int32_t *from, const int32_t *to, c
 #define TD_PN(KV)                                                                                                        \
     k_pooln_enum<KV><<<g, 256, shm, c.stream>>>(n, d_arr[0], d_arr[1], d_arr[2], d_arr[3], (const int32_t *)d_dist, S, \
                                                first0, first1, (unsigned long long)max_happy, keys, ctl)
-        switch (k) {
-            case 1: TD_PN(1); break;
-            case 2: TD_PN(2); break;
-            case 3: TD_PN(3); break;
-            default:
-                if (n <= 65535 && first1 - first0 <= 65535)
-                    k_pooln_enum4<<<dim3((n + 255) / 256, n, first1 - first0), 256, 0, c.stream>>>(
-                        n, d_arr[0], d_arr[1], d_arr[2], d_arr[3], (const int32_t *)d_dist, S, first0, first1, (unsigned long long)max_happy, keys, ctl);
-                else
-                    TD_PN(4);
-                break;
-        }
+        if (k == 2) TD_PN(2);
+        else if (k == 3) TD_PN(3);
+        else   // n <= PN_MAXN: both grid dimensions fit
+            k_pooln_enum4<<<dim3((n + 255) / 256, n, first1 - first0), 256, 0, c.stream>>>(
+                n, d_arr[0], d_arr[1], d_arr[2], d_arr[3], (const int32_t *)d_dist, S, first0, first1, (unsigned long long)max_happy, keys, ctl);
 #undef TD_PN
         TD_HIP(hipGetLastError());
     }
@@ -497,9 +481,21 @@ extern "C" int td_pool_merge(int k, int n_requests, int n_in, const int32_t *poo
     if ((rc = ensure(g_pw.keys2, sizeof(unsigned long long) * (size_t)n_in))) return rc;
     if ((rc = ensure(g_pw.ctl, 256))) return rc;
     TD_HIP(hipMemsetAsync(g_pw.ctl.p, 0, sizeof(PnCtl), c.stream));
-    k_pool_merge_keys<<<(n_in + 255) / 256, 256, 0, c.stream>>>(k, n_in, (const int32_t *)d_in, sort_by_cost, (unsigned long long *)g_pw.keys.p);
+    k_pool_merge_keys<<<(n_in + 255) / 256, 256, 0, c.stream>>>(k, n_requests, n_in, (const int32_t *)d_in, sort_by_cost,
+                                                                (unsigned long long *)g_pw.keys.p, (PnCtl *)g_pw.ctl.p);
     TD_HIP(hipGetLastError());
     if ((rc = sort_keys((unsigned long long *)g_pw.keys.p, (unsigned long long *)g_pw.keys2.p, (size_t)n_in))) return rc;
+    // the greedy indexes LDS by request id: no launch before every id is known to be inside [0, n_requests)
+    TD_HIP(hipMemcpyAsync(c.pinned, g_pw.ctl.p, sizeof(PnCtl), hipMemcpyDeviceToHost, c.stream));
+    TD_HIP(hipStreamSynchronize(c.stream));
+    if (const int bad = ((const PnCtl *)c.pinned)->bad) {
+        const int rec = n_in - bad;
+        int32_t ids[4] = {0, 0, 0, 0};
+        TD_HIP(hipMemcpy(ids, (const int32_t *)d_in + (size_t)rec * (size_t)(2 * k + 1), sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost));
+        int a = 0;
+        while (a < k - 1 && ids[a] >= 0 && ids[a] < n_requests) a++;
+        return fail(TD_EINVAL, "td_pool_merge: record %d names request %d (field %d), outside [0, %d)", rec, ids[a], a, n_requests);
+    }
     return greedy_and_emit<false>(k, n_requests, (size_t)n_in, (const unsigned long long *)g_pw.keys2.p, (const int32_t *)d_in, max_pools,
                                   pools_out, n_out);
 }
