@@ -271,7 +271,8 @@ TD_API void td_tick_release_workspace(void);
 /* ---- a simulator world in device memory (Simulator.java:151-211, the whole tick loop) -----------------
  * The handle owns the request table (id, from, to, at, cab_assigned, picked_at, pool_id, pool_plan, pool_cost) and the
  * fleet (from, to, client, on_board, time_started) in HBM; they never leave the device.  Cab i starts at stand
- * i % n_stands (initSupply :565-573); distances are |a - b| on n_stands stands.  A tick is
+ * i % n_stands (initSupply :565-573); distances are |a - b| on n_stands stands (td_sim_create) or a stand-to-stand table
+ * (td_sim_create_dist, below).  A tick is
  *   td_sim_begin   checkIfCabAtDestination (:220-254), createTempDemand incl. the drop (:329-355), createTempSupply
  *                  (:358-372), findPool (td_pool2 on the device lists) and analyzePool (:760-784; skipped without supply).
  *                  info = {has_demand, demand before pooling, supply, demand after pooling}; has_demand == 0: the tick
@@ -283,8 +284,8 @@ TD_API void td_tick_release_workspace(void);
  *                  analyzeSolution :375-421.  *opt_count = the line's "OPT count", -1 when the LCM ran and solved == 0
  *                  (:188-189, the line has none).  A cab and a request occur in at most one pair, a request in at most
  *                  one row_to_col cell (what td_tick returns); a pair outside the model is TD_EINVAL and applies nothing.
- *   td_sim_step    begin + td_tick(dist NULL, fill big_cost, threshold drop_time, stop_size max_non_lcm) on the device
- *                  lists + apply.  line = {has line, demand, supply, LCM ran, pairs, sent to solver, demand and supply
+ *   td_sim_step    begin + td_tick(the world's table or NULL, fill big_cost, threshold drop_time, stop_size max_non_lcm) on
+ *                  the device lists + apply.  line = {has line, demand, supply, LCM ran, pairs, sent to solver, demand and supply
  *                  of the remainder, OPT count or -1}.
  * Per tick only the counters and the small lists (pairs, kept lists, row_to_col) cross PCIe.  Request ids must be unique
  * and not negative, stands lie in 0 .. n_stands - 1 (at most 2^18 stands), arrival times are not negative: td_sim_create
@@ -292,6 +293,20 @@ TD_API void td_tick_release_workspace(void);
  * Sequencing: ticks run forward (td_sim_begin with t <= the last begun tick is TD_EINVAL, and so is a begin while a tick
  * with demand waits for its apply); td_sim_model / td_sim_apply need a begun tick with has_demand == 1.  Handles are
  * independent worlds; td_workspace_bytes counts their memory until td_sim_destroy.
+ * td_sim_create_dist: the same world on a distance table dist[n_stands * n_stands], row-major, dist[from][to] = the ticks a cab
+ * needs from stand `from` to stand `to`; host or device memory; NULL is td_sim_create.  The handle COPIES the table (the caller
+ * may free or overwrite it after the call) and keeps the copy and two neighbour bit matrices built from it (2 * n_stands *
+ * ceil(n_stands / 32) words) until td_sim_destroy; td_workspace_bytes counts them.  The row is always the stand the cab is at
+ * or heads to, as Simulator.java reads dist[][]: a cab arrives when dist[from][to] == t - time_started; a request enters the
+ * temp demand iff some client-less cab has dist[cab.to][request.from] < drop_time, a standing client-less cab the temp supply
+ * iff some unassigned request has dist[cab.to][request.from] < drop_time; td_pool2 and td_tick get the table; a cab goes to a
+ * pick-up iff dist[cab.to][request.from] < drop_time and total_pickup_time grows by dist[cab.from][request.from].  The pooled
+ * cab's destination stays the reference's stand arithmetic (from +- pool cost against n_stands, :469-474), which means
+ * something on a line only; it is kept as it is.  Symmetry and the triangle inequality are not required.  TD_EINVAL (no
+ * handle): n_stands > 4096, a diagonal entry other than 0, any other entry outside 1 .. 0x1fffffff (a 0 between two stands
+ * would start a cab that never arrives; three entries must stay below td_pool2's INT_MAX marker).  The entries are checked on
+ * the device, on the handle's copy: a refused table has the handle allocated and freed again inside the call, so
+ * td_workspace_bytes is back at its earlier value when the call returns.  Every other td_sim_* call works on such a world unchanged.
  * td_sim_state: any pointer may be NULL; cab arrays [n_cabs] (client = the request id, -1 none), request arrays [n_req].
  * td_sim_metrics: Simulator.m in its order: total_dropped, total_pickup_time, total_pickup_numb, total_LCM_used,
  * max_model_size, max_solver_size, max_POOL_MEM_size, max_POOL_size, total_second_passengers. */
@@ -300,6 +315,10 @@ typedef struct td_sim td_sim;
 TD_API int td_sim_create(int n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost, int n_req,
                          const int32_t *req_id, const int32_t *req_from, const int32_t *req_to, const int32_t *req_at,
                          td_sim **out);
+TD_API int td_sim_create_dist(int n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost, int n_req,
+                              const int32_t *req_id, const int32_t *req_from, const int32_t *req_to, const int32_t *req_at,
+                              const int32_t *dist /* n_stands x n_stands, [from][to]; host or device; NULL: td_sim_create */,
+                              td_sim **out);
 TD_API int td_sim_destroy(td_sim *s);
 TD_API int td_sim_begin(td_sim *s, int t, int32_t info[4]);
 TD_API int td_sim_model(td_sim *s, int32_t *cab_to, int32_t *dem_from);

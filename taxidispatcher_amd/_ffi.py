@@ -69,6 +69,8 @@ SIGNATURES = {
     "td_tick_release_workspace": (None, []),
     "td_sim_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int, c_i32p, c_i32p,
                                      c_i32p, c_i32p, ctypes.POINTER(ctypes.c_void_p)]),
+    "td_sim_create_dist": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int, c_i32p,
+                                          c_i32p, c_i32p, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_void_p)]),
     "td_sim_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "td_sim_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p]),
     "td_sim_model": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p]),

@@ -22,6 +22,15 @@
 // reference's list order and the golden log depends on it.  The scan of the (few) workgroup counts is done by each
 // scatter workgroup for itself (a bounded reduction over the counts before it): no workgroup waits for another.
 // Counters are reduced per workgroup and added with one 64-bit atomic per workgroup.
+//
+// A world on a distance table (td_sim_create_dist): the handle owns a copy of the table and two neighbour bit matrices built
+// from it once (k_nb_build, which also validates the table).  The near test of createTempDemand / createTempSupply is then
+// one more kernel after each k_flags, k_near: near[s] = any(nb[s][q] & flags[q]), one wave per stand; the predicates read
+// one bit of it, and arrival / dispatch / analyzeSolution read one table cell (td_sim_core.h way()).  The direction rule:
+// the row of the table is always the cab's stand, dist[cab.to][request.from]:
+//   nb_dem[s] bit s'  <=>  dist[s'][s] < drop_time   (request at s, a cab heading to s': a COLUMN of the table)
+//   nb_sup[s] bit s'  <=>  dist[s][s'] < drop_time   (cab at s, a request starting at s': a ROW)
+// A line world (dist == nullptr) launches exactly what it launched before.
 #include <limits.h>
 
 #include <algorithm>
@@ -40,6 +49,9 @@ struct td_sim {
     Buf mem;                     // every device array of the handle
     Ctl *ctl = nullptr;
     uint32_t *bits_cab = nullptr, *bits_req = nullptr;
+    // a table world: the table (= w.dist), the neighbour bit matrices [n_stands][words], the near bitsets [words]
+    int32_t *dist = nullptr;
+    uint32_t *nb_dem = nullptr, *nb_sup = nullptr, *near_cab = nullptr, *near_req = nullptr;
     int32_t *blockcnt = nullptr;
     // temp lists: demand before pooling, supply, demand after pooling, kept lists
     int32_t *dem_idx, *dem_from, *dem_to;
@@ -159,14 +171,66 @@ __global__ __launch_bounds__(CB) void k_flags(int n, int n_stands, const int32_t
         if (s_bits[q]) atomicOr(&bits[q], s_bits[q]);
 }
 
-// createTempDemand's predicate (Simulator.java:329-355) on the table as the drop pass left it
+// the neighbour bit matrices of a distance table, one thread per (stand s, word q); the row read visits every cell of the
+// table exactly once, so the table is validated here: diagonal 0, every other entry in 1 .. MAX_DIST (error word 3)
+constexpr int32_t MAX_DIST = 0x1fffffff;   // three entries stay below td_pool2's INT_MAX diagonal marker
+constexpr int MAX_DIST_STANDS = 4096;
+
+__global__ __launch_bounds__(256) void k_nb_build(int n_stands, int words, int drop_time, const int32_t *__restrict__ dist,
+                                                  uint32_t *__restrict__ nb_dem, uint32_t *__restrict__ nb_sup, Ctl *ctl)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // n_stands * words <= 4096 * 128
+    if (i >= n_stands * words) return;
+    const int s = i / words, q = i - s * words;
+    uint32_t md = 0, ms = 0;
+    bool bad = false;
+    for (int b = 0; b < 32; b++) {
+        const int o = q * 32 + b;
+        if (o >= n_stands) break;
+        const int32_t out = dist[(int64_t)s * n_stands + o], in = dist[(int64_t)o * n_stands + s];
+        bad |= o == s ? out != 0 : (out < 1 || out > MAX_DIST);
+        if (out < drop_time) ms |= 1u << b;
+        if (in < drop_time) md |= 1u << b;
+    }
+    nb_dem[i] = md;
+    nb_sup[i] = ms;
+    if (bad) atomicMax(&ctl->err, 3);
+}
+
+// near[s] = any(nb[s][q] & flags[q]): one wave per stand, the lanes stride over the words (at most two strides: 128 words),
+// then a ballot.  A workgroup of 16 waves owns the 32 stands of ONE output word (two stands per wave) and writes it with a
+// plain store, so the near bitset needs no clearing and no global atomic.
+__global__ __launch_bounds__(CB) void k_near(int n_stands, int words, const uint32_t *__restrict__ nb, const uint32_t *__restrict__ flags,
+                                             uint32_t *__restrict__ near)
+{
+    __shared__ uint32_t s_word;
+    if (threadIdx.x == 0) s_word = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int j = 0; j < 2; j++) {
+        const int bit = 2 * wv + j, s = (int)blockIdx.x * 32 + bit;
+        if (s >= n_stands) break;   // the same for the whole wave
+        const uint32_t *row = nb + (size_t)s * words;
+        uint32_t acc = 0;
+        for (int q = lane; q < words; q += 64) acc |= row[q] & flags[q];
+        if (__ballot(acc != 0) != 0ull && lane == 0) atomicOr(&s_word, 1u << bit);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) near[blockIdx.x] = s_word;
+}
+
+__device__ __forceinline__ bool bit_of(const uint32_t *bits, int s) { return (bits[s >> 5] >> (s & 31)) & 1u; }
+
+// createTempDemand's predicate (Simulator.java:329-355) on the table as the drop pass left it.  near: the near bitset of a
+// table world (k_near on nb_dem), nullptr = the line's window over bits_cab
 struct DemPred {
     World w;
     int t;
-    const uint32_t *bits_cab;
+    const uint32_t *bits_cab, *near;
     __device__ bool operator()(int d) const
     {
-        return w.r_cab[d] == -1 && t >= w.r_at[d] && t - w.r_at[d] < w.drop_time && near_window(bits_cab, w.n_stands, w.drop_time, w.r_from[d]);
+        return w.r_cab[d] == -1 && t >= w.r_at[d] && t - w.r_at[d] < w.drop_time &&
+               (near ? bit_of(near, w.r_from[d]) : near_window(bits_cab, w.n_stands, w.drop_time, w.r_from[d]));
     }
 };
 struct DemEmit {
@@ -182,10 +246,11 @@ struct DemEmit {
 // createTempSupply (Simulator.java:358-372)
 struct SupPred {
     World w;
-    const uint32_t *bits_req;
+    const uint32_t *bits_req, *near;   // near: k_near on nb_sup, nullptr = the line
     __device__ bool operator()(int c) const
     {
-        return w.c_from[c] == w.c_to[c] && w.c_clnt[c] == -1 && near_window(bits_req, w.n_stands, w.drop_time, w.c_to[c]);
+        return w.c_from[c] == w.c_to[c] && w.c_clnt[c] == -1 &&
+               (near ? bit_of(near, w.c_to[c]) : near_window(bits_req, w.n_stands, w.drop_time, w.c_to[c]));
     }
 };
 struct SupEmit {
@@ -379,8 +444,8 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, int n_s, 
     if (s < n_s) {
         const int c = s < n_r2c ? r2c[s] : -1;
         if (c >= 0 && c < n_d) {
-            const int dist = iabs(sup_to[s] - d_from[c]);
-            const int cell = dist < w.drop_time ? dist : w.big_cost;   // the thresholded |a - b| model's cell
+            const int dist = way(w, sup_to[s], d_from[c]);
+            const int cell = dist < w.drop_time ? dist : w.big_cost;   // the thresholded model's cell
             if (cell < w.big_cost) {
                 count = 1;
                 const int idx = d_idx[c], cab = sup_cab[s], partner = d_partner[c];
@@ -469,16 +534,18 @@ int sim_begin(td_sim *s, int t, int32_t info[4])
     const size_t shm = sizeof(uint32_t) * (size_t)words;
     k_arrive<<<nblocks(w.n_cabs), CB, 0, c.stream>>>(w, t, s->ctl);
     k_flags<<<nblocks(w.n_cabs), CB, shm, c.stream>>>(w.n_cabs, w.n_stands, w.c_to, w.c_clnt, s->bits_cab);
+    if (s->dist) k_near<<<words, CB, 0, c.stream>>>(w.n_stands, words, s->nb_dem, s->bits_cab, s->near_cab);
     if (w.n_req > 0) {
-        const DemPred dp{w, t, s->bits_cab};
+        const DemPred dp{w, t, s->bits_cab, s->near_cab};
         k_dem_count<<<nblocks(w.n_req), CB, 0, c.stream>>>(dp, s->blockcnt, s->ctl);
         k_scatter<DemPred, DemEmit><<<nblocks(w.n_req), CB, 0, c.stream>>>(w.n_req, dp, DemEmit{w, s->dem_idx, s->dem_from, s->dem_to}, s->blockcnt,
                                                                          &s->ctl->n_dem);
         k_flags<<<nblocks(w.n_req), CB, shm, c.stream>>>(w.n_req, w.n_stands, w.r_from, w.r_cab, s->bits_req);
     }
+    if (s->dist) k_near<<<words, CB, 0, c.stream>>>(w.n_stands, words, s->nb_sup, s->bits_req, s->near_req);
     TD_HIP(hipGetLastError());
     // createTempSupply changes nothing, so it is queued before the demand count is known: one read-back for both
-    if ((rc = compact(s, w.n_cabs, SupPred{w, s->bits_req}, SupEmit{w, s->sup_cab, s->sup_to}, &s->ctl->n_sup))) return rc;
+    if ((rc = compact(s, w.n_cabs, SupPred{w, s->bits_req, s->near_req}, SupEmit{w, s->sup_cab, s->sup_to}, &s->ctl->n_sup))) return rc;
     Ctl h;
     if ((rc = read_ctl(s, &h))) return rc;
     if (h.err) return fail(TD_EINTERNAL, "td_sim: device error word %d", h.err);
@@ -499,7 +566,7 @@ int sim_begin(td_sim *s, int t, int32_t info[4])
     const int n = h.n_dem;
     if (n >= 2) {
         s->max_pool_mem = std::max(s->max_pool_mem, (int64_t)n * (n - 1));
-        if ((rc = td_pool2(n, s->dem_from, s->dem_to, nullptr, 0, s->pl_a, s->pl_b, s->pl_plan, s->pl_cost, &k))) return rc;
+        if ((rc = td_pool2(n, s->dem_from, s->dem_to, s->dist, s->dist ? w.n_stands : 0, s->pl_a, s->pl_b, s->pl_plan, s->pl_cost, &k))) return rc;
         s->max_pool = std::max(s->max_pool, (int64_t)k);
     }
     TD_HIP(hipMemsetAsync(s->isb, 0, sizeof(int32_t) * (size_t)n, c.stream));
@@ -576,10 +643,9 @@ int sim_apply(td_sim *s, int n_pairs, const int32_t *rows, const int32_t *cols, 
     return TD_OK;
 }
 
-}  // namespace
-
-extern "C" int td_sim_create(int n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost, int n_req, const int32_t *req_id,
-                             const int32_t *req_from, const int32_t *req_to, const int32_t *req_at, td_sim **out)
+// td_sim_create (dist == nullptr) and td_sim_create_dist
+int sim_create(int n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost, int n_req, const int32_t *req_id,
+               const int32_t *req_from, const int32_t *req_to, const int32_t *req_at, const int32_t *dist, td_sim **out)
 {
     TD_REQUIRE_INIT();
     Ctx &c = ctx();
@@ -588,6 +654,7 @@ extern "C" int td_sim_create(int n_cabs, int n_stands, int drop_time, int max_no
     if (n_cabs < 1 || n_stands < 1 || drop_time < 0 || max_non_lcm < 0 || big_cost < 0 || n_req < 0)
         return fail(TD_EINVAL, "td_sim_create: n_cabs and n_stands at least 1, nothing negative");
     if (n_stands > (1 << 18)) return fail(TD_EINVAL, "td_sim_create: at most %d stands (one bit per stand in LDS)", 1 << 18);
+    if (dist && n_stands > MAX_DIST_STANDS) return fail(TD_EINVAL, "td_sim_create_dist: at most %d stands with a distance table", MAX_DIST_STANDS);
     if (n_req && (!req_id || !req_from || !req_to || !req_at)) return fail(TD_EINVAL, "null request array");
     // the request file on the host once: ids unique and not negative, stands inside the line, arrival times not negative
     std::vector<int32_t> h((size_t)4 * n_req);
@@ -607,7 +674,8 @@ extern "C" int td_sim_create(int n_cabs, int n_stands, int drop_time, int max_no
     s->max_non_lcm = max_non_lcm;
     const size_t nr = (size_t)std::max(n_req, 1), nc = (size_t)n_cabs, cap = std::max(nr, nc), words = (size_t)(n_stands + 31) / 32;
     s->cap = (int)cap;
-    const size_t ints = 64 + 2 * words + (cap + CB - 1) / CB + 9 * nr + 5 * nc + 3 * nr + 2 * nc + 5 * nr + 2 * nc + 5 * nr + 2 * nr + 4 * (nr / 2 + 1) +
+    const size_t ns = (size_t)n_stands, table_ints = dist ? ns * ns + 2 * ns * words + 2 * words : 0;
+    const size_t ints = table_ints + 64 + 2 * words + (cap + CB - 1) / CB + 9 * nr + 5 * nc + 3 * nr + 2 * nc + 5 * nr + 2 * nc + 5 * nr + 2 * nr + 4 * (nr / 2 + 1) +
                         nc + nr + 3 * cap + cap + 64;
     int rc = ensure(s->mem, sizeof(int32_t) * ints);
     if (rc) {
@@ -622,7 +690,14 @@ extern "C" int td_sim_create(int n_cabs, int n_stands, int drop_time, int max_no
     };
     s->ctl = (Ctl *)take(64);
     s->bits_cab = (uint32_t *)take(words);
-    s->bits_req = (uint32_t *)take(words);
+    s->bits_req = (uint32_t *)take(words);   // must stay directly behind bits_cab: sim_begin clears both with ONE memset
+    if (dist) {
+        s->near_cab = (uint32_t *)take(words);
+        s->near_req = (uint32_t *)take(words);
+        s->nb_dem = (uint32_t *)take(ns * words);
+        s->nb_sup = (uint32_t *)take(ns * words);
+        s->dist = take(ns * ns);
+    }
     s->blockcnt = take((cap + CB - 1) / CB);
     World &w = s->w;
     w.n_cabs = n_cabs;
@@ -630,6 +705,7 @@ extern "C" int td_sim_create(int n_cabs, int n_stands, int drop_time, int max_no
     w.n_stands = n_stands;
     w.drop_time = drop_time;
     w.big_cost = big_cost;
+    w.dist = s->dist;
     int32_t *rid = take(nr), *rfrom = take(nr), *rto = take(nr), *rat = take(nr);
     w.r_id = rid;
     w.r_from = rfrom;
@@ -697,9 +773,39 @@ extern "C" int td_sim_create(int n_cabs, int n_stands, int drop_time, int max_no
     k_init_fleet<<<(n_cabs + 255) / 256, 256, 0, c.stream>>>(w);
     if (n_req) k_init_requests<<<(n_req + 255) / 256, 256, 0, c.stream>>>(w);
     if ((e = hipGetLastError()) != hipSuccess) return bail(hip_fail(e, "td_sim_create launch"));
+    if (dist) {
+        // the handle's own copy of the table, then its bit matrices; k_nb_build reports an invalid table in the error word
+        if ((e = hipMemcpyAsync(s->dist, dist, sizeof(int32_t) * ns * ns, is_device_ptr(dist) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                c.stream)) != hipSuccess)
+            return bail(hip_fail(e, "hipMemcpyAsync(distance table)"));
+        const int cells = n_stands * (int)words;
+        k_nb_build<<<(cells + 255) / 256, 256, 0, c.stream>>>(n_stands, (int)words, drop_time, s->dist, s->nb_dem, s->nb_sup, s->ctl);
+        if ((e = hipGetLastError()) != hipSuccess) return bail(hip_fail(e, "td_sim_create_dist launch"));
+    }
     if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return bail(hip_fail(e, "hipStreamSynchronize"));   // `h` leaves scope
+    if (dist) {
+        Ctl hc;
+        int rc = read_ctl(s, &hc);
+        if (rc) return bail(rc);
+        if (hc.err)
+            return bail(fail(TD_EINVAL, "td_sim_create_dist: the distance table needs a zero diagonal and every other entry in 1 .. %d", MAX_DIST));
+    }
     *out = s;
     return TD_OK;
+}
+
+}  // namespace
+
+extern "C" int td_sim_create(int n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost, int n_req, const int32_t *req_id,
+                             const int32_t *req_from, const int32_t *req_to, const int32_t *req_at, td_sim **out)
+{
+    return sim_create(n_cabs, n_stands, drop_time, max_non_lcm, big_cost, n_req, req_id, req_from, req_to, req_at, nullptr, out);
+}
+
+extern "C" int td_sim_create_dist(int n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost, int n_req, const int32_t *req_id,
+                                  const int32_t *req_from, const int32_t *req_to, const int32_t *req_at, const int32_t *dist, td_sim **out)
+{
+    return sim_create(n_cabs, n_stands, drop_time, max_non_lcm, big_cost, n_req, req_id, req_from, req_to, req_at, dist, out);
 }
 
 extern "C" int td_sim_destroy(td_sim *s)
@@ -763,8 +869,8 @@ extern "C" int td_sim_step(td_sim *s, int t, int32_t line[9])
     int64_t total = 0;
     int solved = 0;
     if (n_s > 0) {
-        // the arguments HipTickBackend.tick hands td_tick, with the position lists where they already are
-        if ((rc = td_tick(s->sup_to, n_s, s->d2_from, n_d, nullptr, 0, s->w.big_cost, s->w.drop_time, s->max_non_lcm, s->h_rows, s->h_cols, &k, &lm,
+        // the arguments HipTickBackend.tick hands td_tick, with the position lists (and the table) where they already are
+        if ((rc = td_tick(s->sup_to, n_s, s->d2_from, n_d, s->dist, s->dist ? s->w.n_stands : 0, s->w.big_cost, s->w.drop_time, s->max_non_lcm, s->h_rows, s->h_cols, &k, &lm,
                           s->h_kc, s->h_kd, &n_rest, s->h_r2c, &total)))
             return rc;
         const bool lcm = s->max_non_lcm < n;

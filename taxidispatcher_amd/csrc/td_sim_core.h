@@ -20,6 +20,8 @@ struct World {
     int32_t *r_cab, *r_pick, *r_pid, *r_plan, *r_pcost;
     // fleet (c_clnt = request INDEX, -1 = none)
     int32_t *c_from, *c_to, *c_clnt, *c_onb, *c_start;
+    // the city: a stand-to-stand table [from][to] of n_stands x n_stands entries, nullptr = the line (|a - b|)
+    const int32_t *dist;
 };
 
 // device counters: the sums of Simulator.m (64-bit), the error word, and this tick's list sizes
@@ -38,7 +40,10 @@ __host__ __device__ inline int cheat_a_bit(int frm, int cost, int n_stands)
 
 __host__ __device__ inline int iabs(int v) { return v < 0 ? -v : v; }
 
-// Simulator._near: any flagged stand within distance < drop_time of s (bits = one bit per stand)
+// the way from stand a to stand b (the row is always the stand the cab is at or heads to)
+__device__ __forceinline__ int way(const World &w, int a, int b) { return w.dist ? w.dist[(int64_t)a * w.n_stands + b] : iabs(a - b); }
+
+// Simulator._near on the line: any flagged stand within distance < drop_time of s (bits = one bit per stand)
 __device__ inline bool near_window(const uint32_t *bits, int n_stands, int drop_time, int s)
 {
     const int r = (drop_time - 1 < n_stands ? drop_time - 1 : n_stands);   // a wider window sees no more stands
@@ -58,7 +63,7 @@ __device__ inline bool near_window(const uint32_t *bits, int n_stands, int drop_
 __device__ inline int arrive_as(const World &w, int t, int c, int cab_no)
 {
     const int f = w.c_from[c], to = w.c_to[c];
-    if (f == to || iabs(f - to) != t - w.c_start[c]) return 0;
+    if (f == to || way(w, f, to) != t - w.c_start[c]) return 0;
     if (w.c_onb[c] == 0) {
         const int d = w.c_clnt[c];
         if (d < 0) return 0;
@@ -80,23 +85,26 @@ __device__ inline int arrive_as(const World &w, int t, int c, int cab_no)
 __device__ inline int arrive(const World &w, int t, int c) { return arrive_as(w, t, c, c); }
 
 // Simulator.java:424-490 _dispatch for cab `cab` (standing at sup_to) and the customer (request idx, pool partner / cost)
-__device__ inline void dispatch(const World &w, int t, int cab, int sup_to, int idx, int partner, int pcost, int &numb, int &ptime)
+__device__ __forceinline__ void dispatch(const World &w, int t, int cab, int sup_to, int idx, int partner, int pcost, int &numb, int &ptime)
 {
     const int cf = w.r_from[idx];
+    int dn = 0, dp = 0;   // added to the counters once, below: no store through either reference inside a branch
     if (sup_to == cf) {   // assignToCabAndGo
         w.c_from[cab] = cf;
         w.c_to[cab] = partner == -1 ? w.r_to[idx] : cheat_a_bit(cf, pcost, w.n_stands);
         w.c_clnt[cab] = idx;
         w.c_onb[cab] = 1;
         w.c_start[cab] = t;
-        numb++;
-    } else if (iabs(sup_to - cf) < w.drop_time) {   // goToPickup
+        dn = 1;
+    } else if (way(w, sup_to, cf) < w.drop_time) {   // goToPickup
         w.c_to[cab] = cf;
         w.c_clnt[cab] = idx;
         w.c_onb[cab] = 0;
         w.c_start[cab] = t;
-        ptime += iabs(w.c_from[cab] - cf);
+        dp = way(w, w.c_from[cab], cf);
     }
+    numb += dn;
+    ptime += dp;
 }
 
 }  // namespace tdsim

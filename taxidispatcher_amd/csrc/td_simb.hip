@@ -914,6 +914,7 @@ extern "C" int td_simb_create(int batch, const int32_t *n_cabs, int n_stands, in
     w.n_stands = n_stands;
     w.drop_time = drop_time;
     w.big_cost = big_cost;
+    w.dist = nullptr;   // the worlds of a batch live on the line
     int32_t *rid = take(nr), *rfrom = take(nr), *rto = take(nr), *rat = take(nr);
     w.r_id = rid;
     w.r_from = rfrom;

@@ -25,15 +25,46 @@ BIG_COST = 250000      # :114
 CLNT_A_ENDS, CLNT_B_ENDS = 0, 1   # :97-98
 
 
-class HipBackend:
-    """cost build / LCM / optimal assignment on the GPU through the C ABI."""
+MAX_DIST_STANDS = 4096       # a distance table has at most this many stands (td_sim_create_dist)
+MAX_DIST = 0x1fffffff        # and no larger entry: three of them stay below td_pool2's INT_MAX diagonal marker
 
-    def __init__(self):
+
+def check_dist(dist, n_stands=None):
+    """A stand-to-stand distance table as the simulator worlds accept it -> a C-contiguous int32 copy.  Square, integers,
+    1 .. MAX_DIST_STANDS stands (n_stands, when given), diagonal 0, every other entry in 1 .. MAX_DIST (a zero between two
+    stands would start a cab that never arrives: arrival is tested on a later tick).  Symmetry and the triangle
+    inequality are not required; dist[a][b] is the way FROM a TO b.  Raises ValueError."""
+    d = np.asarray(dist)
+    if d.ndim != 2 or d.shape[0] != d.shape[1]:
+        raise ValueError("distance table: shape %r is not square" % (d.shape,))
+    n = int(d.shape[0])
+    if n_stands is not None and n != int(n_stands):
+        raise ValueError("distance table: %d x %d for %d stands" % (n, n, int(n_stands)))
+    if not 1 <= n <= MAX_DIST_STANDS:
+        raise ValueError("distance table: %d stands, outside 1 .. %d" % (n, MAX_DIST_STANDS))
+    if d.dtype.kind not in "iu":
+        if d.dtype.kind != "f" or not np.array_equal(np.rint(d), d):
+            raise ValueError("distance table: entries must be integers")
+        d = np.rint(d)
+    d = d.astype(np.int64)
+    if np.diagonal(d).any():
+        raise ValueError("distance table: the diagonal must be 0")
+    off = d[~np.eye(n, dtype=bool)]
+    if off.size and (off.min() < 1 or off.max() > MAX_DIST):
+        raise ValueError("distance table: entries between different stands must lie in 1 .. %d" % MAX_DIST)
+    return np.ascontiguousarray(d.astype(np.int32))
+
+
+class HipBackend:
+    """cost build / LCM / optimal assignment on the GPU through the C ABI; dist: a stand-to-stand table (None = |a - b|)."""
+
+    def __init__(self, dist=None):
         from . import dispatch
         self.d = dispatch
+        self.dist = None if dist is None else check_dist(dist)
 
     def calculate_cost(self, cab_to, dem_from):
-        return self.d.cost_build(cab_to, dem_from, None, fill=BIG_COST, threshold=DROP_TIME)[1]
+        return self.d.cost_build(cab_to, dem_from, self.dist, fill=BIG_COST, threshold=DROP_TIME)[1]
 
     def lcm(self, cost):
         return self.d.LCM_simulator(cost, max_non_lcm=MAX_NON_LCM, big_cost=BIG_COST)
@@ -42,7 +73,7 @@ class HipBackend:
         return self.d.assign(cost)[0]
 
     def find_pool(self, frm, to):
-        return self.d.find_pool(frm, to, None)
+        return self.d.find_pool(frm, to, self.dist)
 
 
 class HipTickBackend(HipBackend):
@@ -51,7 +82,7 @@ class HipTickBackend(HipBackend):
     only applies the pairs and the solution to its world."""
 
     def tick(self, cab_to, dem_from):
-        return self.d.tick(np.asarray(cab_to, np.int32), np.asarray(dem_from, np.int32), None, big_cost=BIG_COST,
+        return self.d.tick(np.asarray(cab_to, np.int32), np.asarray(dem_from, np.int32), self.dist, big_cost=BIG_COST,
                            drop_time=DROP_TIME, max_non_lcm=MAX_NON_LCM)
 
 
@@ -59,20 +90,21 @@ class _RealCells:
     """cost[s][c] of a model that stayed on the device, as far as analyzeSolution reads it (Simulator.java:508-511: a
     cell is dist[cab.to][request.from] when that is below DROP_TIME, else big_cost)"""
 
-    def __init__(self, supply, demand):
-        self.supply, self.demand = supply, demand
+    def __init__(self, supply, demand, dist=None):
+        self.supply, self.demand, self.dist = supply, demand, dist
 
     def __getitem__(self, s):
         to = self.supply[s][2]
-        return _RealRow(to, self.demand)
+        return _RealRow(to, self.demand, self.dist)
 
 
 class _RealRow:
-    def __init__(self, to, demand):
-        self.to, self.demand = to, demand
+    def __init__(self, to, demand, dist=None):
+        self.to, self.demand, self.dist = to, demand, dist
 
     def __getitem__(self, c):
-        d = abs(self.to - self.demand[c][1])
+        frm = self.demand[c][1]
+        d = abs(self.to - frm) if self.dist is None else int(self.dist[self.to, frm])
         return d if d < DROP_TIME else BIG_COST
 
 
@@ -96,8 +128,14 @@ def cheat_a_bit(frm, cost):
 
 
 class Simulator:
-    def __init__(self, demand_rows, backend=None, n_cabs=N_CABS, on_solver_instance=None):
-        self.be = backend if backend is not None else HipBackend()
+    """dist: a stand-to-stand distance table (N_STANDS x N_STANDS, see check_dist; None = the line, |a - b|).  The row is
+    always the stand the cab is at or heads to: dist[cab][request].  The backend has to work on the same table
+    (HipBackend(dist=...)).  cheat_a_bit stays the reference's stand arithmetic (from +- cost against N_STANDS), which
+    means something on a line only; it is kept as it is, bug-compatible, in a table world too."""
+
+    def __init__(self, demand_rows, backend=None, n_cabs=N_CABS, on_solver_instance=None, dist=None):
+        self.dist = None if dist is None else check_dist(dist, N_STANDS).astype(np.int64)
+        self.be = backend if backend is not None else HipBackend(dist)
         self.on_solver_instance = on_solver_instance
         d = np.asarray(demand_rows, dtype=np.int64)
         self.d_id, self.d_from, self.d_to, self.d_time, self.d_at = (d[:, k].copy() for k in range(5))
@@ -121,9 +159,13 @@ class Simulator:
         self.log = []
 
     # ---- Simulator.java:220-254
+    def _way(self, a, b):
+        """the distance from stand(s) a to stand(s) b"""
+        return np.abs(a - b) if self.dist is None else self.dist[a, b]
+
     def check_if_cab_at_destination(self, t):
         moving = np.nonzero((self.c_from != self.c_to) &
-                            (np.abs(self.c_from - self.c_to) == t - self.c_start))[0]
+                            (self._way(self.c_from, self.c_to) == t - self.c_start))[0]
         for c in moving:
             if self.c_onboard[c] == 0:
                 d = self.id2idx.get(int(self.c_clnt[c]))
@@ -153,6 +195,18 @@ class Simulator:
         hi = np.minimum(N_STANDS - 1, s + (DROP_TIME - 1))
         return (cs[hi + 1] - cs[lo]) > 0
 
+    def _near_cabs(self, cab_flags):
+        """createTempDemand's side: near[s] = some flagged stand s' (a cab heads there) has dist[s'][s] < DROP_TIME"""
+        if self.dist is None:
+            return self._near(cab_flags)
+        return (self.dist[np.nonzero(cab_flags)[0], :] < DROP_TIME).any(axis=0)
+
+    def _near_requests(self, req_flags):
+        """createTempSupply's side: near[s] = some flagged stand s' (a request starts there) has dist[s][s'] < DROP_TIME"""
+        if self.dist is None:
+            return self._near(req_flags)
+        return (self.dist[:, np.nonzero(req_flags)[0]] < DROP_TIME).any(axis=1)
+
     # ---- Simulator.java:329-355
     def create_temp_demand(self, t):
         cand = np.nonzero((self.d_cab == -1) & (t >= self.d_at))[0]
@@ -162,7 +216,7 @@ class Simulator:
         keep = cand[t - self.d_at[cand] < DROP_TIME]
         free_to = np.zeros(N_STANDS, bool)
         free_to[self.c_to[self.c_clnt == -1]] = True
-        near = self._near(free_to)
+        near = self._near_cabs(free_to)
         keep = keep[near[self.d_from[keep]]]
         # TempDemand: id, from, to, pool_clnt_id, pool_plan, pool_cost
         return [[int(self.d_id[d]), int(self.d_from[d]), int(self.d_to[d]), -1, -1, 0] for d in keep]
@@ -171,7 +225,7 @@ class Simulator:
     def create_temp_supply(self):
         has_req = np.zeros(N_STANDS, bool)
         has_req[self.d_from[self.d_cab == -1]] = True     # ANY unassigned request, no time check
-        near = self._near(has_req)
+        near = self._near_requests(has_req)
         cabs = np.nonzero((self.c_from == self.c_to) & (self.c_clnt == -1) & near[self.c_to])[0]
         return [[int(c), int(self.c_from[c]), int(self.c_to[c])] for c in cabs]   # Supply: id, from, to
 
@@ -233,13 +287,13 @@ class Simulator:
         self.c_clnt[c] = cust[0]
         self.c_onboard[c] = 0
         self.c_start[c] = t
-        self.m["total_pickup_time"] += abs(int(self.c_from[c]) - int(self.c_to[c]))
+        self.m["total_pickup_time"] += int(self._way(int(self.c_from[c]), int(self.c_to[c])))
 
     def _dispatch(self, t, supply, cust):
         c = supply[0]   # cab id == cab index
         if supply[2] == cust[1]:
             self._assign_to_cab_and_go(t, c, cust)
-        elif abs(supply[2] - cust[1]) < DROP_TIME:
+        elif self._way(supply[2], cust[1]) < DROP_TIME:
             self._go_to_pickup(t, c, cust)
 
     # ---- Simulator.java:613-674
@@ -339,8 +393,8 @@ class Simulator:
             line += ". Sent to solver: demand=%d, supply=%d. " % (len(temp_demand), len(temp_supply))
         self.m["max_solver_size"] = max(self.m["max_solver_size"], res["n_rest"])
         r2c = res["row_to_col"]
-        # analyzeSolution reads cost[s][c] < big_cost (:378-383): a real cell of the thresholded |a - b| model
-        count = self.analyze_solution(t, r2c, _RealCells(temp_supply, temp_demand), temp_demand, temp_supply)
+        # analyzeSolution reads cost[s][c] < big_cost (:378-383): a real cell of the thresholded model
+        count = self.analyze_solution(t, r2c, _RealCells(temp_supply, temp_demand, self.dist), temp_demand, temp_supply)
         return line + "; OPT count=%d" % count
 
     # ---- Simulator.java:256-277 printMetrics (wall-clock lines are the caller's: pass them in)
@@ -373,14 +427,18 @@ class DeviceSimulator:
     """The same world in device memory behind the C ABI (td_sim_*, csrc/td_sim.hip): the cab and request tables never leave
     the GPU, a tick is ONE call (`tick` = td_sim_step: world kernels around td_pool2 and td_tick), and only the counters
     of the log line come back.  `begin` / `model` / `apply` split the tick so that the assignment decisions can come from
-    any source.  Log lines, `m` and `metrics_text` are those of `Simulator` with `HipTickBackend`."""
+    any source.  Log lines, `m` and `metrics_text` are those of `Simulator` with `HipTickBackend`.
+    dist: a stand-to-stand distance table as `Simulator` takes it (numpy array-like, or an int32 torch tensor on the device);
+    the handle keeps its own copy (td_sim_create_dist).  n_stands then defaults to the table's size.  A host table is
+    checked here (check_dist: ValueError); a device tensor is checked for shape and dtype only (ValueError) and its size,
+    diagonal and entries by td_sim_create_dist on the device, which raises TdError."""
 
     M_KEYS = ("total_dropped", "total_pickup_time", "total_pickup_numb", "total_LCM_used", "max_model_size", "max_solver_size",
               "max_POOL_MEM_size", "max_POOL_size", "total_second_passengers")
     CAB_KEYS = ("c_from", "c_to", "c_clnt", "c_onboard", "c_start")
     REQ_KEYS = ("d_cab", "d_pick", "d_pool_id", "d_pool_plan", "d_pool_cost")
 
-    def __init__(self, demand_rows, n_cabs=None, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None):
+    def __init__(self, demand_rows, n_cabs=None, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None):
         import ctypes
         from . import _ffi
         self._ffi, self._ct = _ffi, ctypes
@@ -389,14 +447,23 @@ class DeviceSimulator:
         d = np.asarray(demand_rows, dtype=np.int64).reshape(-1, 5)
         self.n_req = int(d.shape[0])
         self.n_cabs = int(N_CABS if n_cabs is None else n_cabs)
+        if dist is not None:
+            if getattr(dist, "is_cuda", False):      # a device table is checked by td_sim_create_dist
+                if str(dist.dtype) != "torch.int32" or dist.dim() != 2 or dist.shape[0] != dist.shape[1]:
+                    raise ValueError("distance table: a device tensor must be a square int32 table")
+            else:
+                dist = check_dist(dist)
+            if n_stands is not None and int(n_stands) != int(dist.shape[0]):
+                raise ValueError("distance table: %d x %d for n_stands=%d" % (dist.shape[0], dist.shape[0], int(n_stands)))
+            n_stands = int(dist.shape[0])
         self.n_stands = int(N_STANDS if n_stands is None else n_stands)
         self.drop_time = int(DROP_TIME if drop_time is None else drop_time)
         self.max_non_lcm = int(MAX_NON_LCM if max_non_lcm is None else max_non_lcm)
         self.big_cost = int(BIG_COST if big_cost is None else big_cost)
         cols = [_ffi.as_i32(d[:, k]) for k in (0, 1, 2, 4)]      # id, from, to, at
         h = ctypes.c_void_p()
-        _ffi.check(self._lib.td_sim_create(self.n_cabs, self.n_stands, self.drop_time, self.max_non_lcm, self.big_cost, self.n_req,
-                                           *[_ffi.addr(c) if self.n_req else None for c in cols], ctypes.byref(h)))
+        _ffi.check(self._lib.td_sim_create_dist(self.n_cabs, self.n_stands, self.drop_time, self.max_non_lcm, self.big_cost, self.n_req,
+                                                *[_ffi.addr(c) if self.n_req else None for c in cols], _ffi.addr(dist), ctypes.byref(h)))
         self._h = h
         self._cap = max(self.n_cabs, self.n_req, 1)
         self._info = None

@@ -2,19 +2,34 @@
 (dev tool; prints timing + the printMetrics block).  --world host (default): the Python world model around the GPU path;
 --world device: the world in device memory too (DeviceSimulator = td_sim_step, one C-ABI call per tick);
 --world device --cabs 900,1100,1300: the committed demand file once per fleet size as ONE batch of worlds
-(DeviceSimulatorBatch = td_simb_step, one C-ABI call per tick for all of them), each world's metrics block printed."""
+(DeviceSimulatorBatch = td_simb_step, one C-ABI call per tick for all of them), each world's metrics block printed.
+--dist FILE.npy: the city as a stand-to-stand distance table (a square integer array saved with numpy.save, [from][to]) for
+--world host and --world device; the stands of the demand file must lie inside it."""
 import argparse, os, sys, time
+import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import taxidispatcher_amd as td
 from taxidispatcher_amd import simulator
 ap = argparse.ArgumentParser()
 ap.add_argument("--world", choices=("host", "device"), default="host")
 ap.add_argument("--cabs", default=None, help="comma-separated fleet sizes: one world per size, run as one batch (needs --world device)")
+ap.add_argument("--dist", default=None, metavar="FILE.npy", help="a stand-to-stand distance table (numpy.save of a square integer array)")
 args = ap.parse_args()
 if args.cabs and args.world != "device":
     ap.error("--cabs needs --world device")
-td.init(0)
+if args.cabs and args.dist:
+    ap.error("--dist cannot be combined with --cabs: a batch of worlds (td_simb) lives on the line, it takes no distance table")
+dist = None
+if args.dist:
+    try:
+        dist = simulator.check_dist(np.load(args.dist))
+    except (OSError, ValueError) as e:
+        ap.error("--dist %s: %s" % (args.dist, e))
+    simulator.N_STANDS = int(dist.shape[0])      # the host world reads its stand count from the module
 rows = simulator.read_demand("tests/golden/taxi_demand.txt.gz")
+if dist is not None and rows[:, 1:3].max() >= dist.shape[0]:
+    ap.error("--dist %s: the demand file uses stand %d, the table has %d stands" % (args.dist, rows[:, 1:3].max(), dist.shape[0]))
+td.init(0)
 if args.world == "device" and args.cabs:
     fleets = [int(v) for v in args.cabs.split(",")]
     sim = simulator.DeviceSimulatorBatch([rows] * len(fleets), fleets)
@@ -28,7 +43,7 @@ if args.world == "device" and args.cabs:
         print(sim.metrics_text(b, total_simul_time=int(dt)))
     sys.exit(0)
 if args.world == "device":
-    sim = simulator.DeviceSimulator(rows)
+    sim = simulator.DeviceSimulator(rows, dist=dist)
     t0 = time.time()
     log = sim.run(120)
     dt = time.time() - t0
@@ -36,7 +51,7 @@ if args.world == "device":
     print("\n".join(log[-3:]))
     print(sim.metrics_text(total_simul_time=int(dt)))
     sys.exit(0)
-sim = simulator.Simulator(rows)
+sim = simulator.Simulator(rows, dist=dist)
 t0 = time.time()
 per = {"pool": 0.0, "cost": 0.0, "lcm": 0.0, "solve": 0.0}
 be = sim.be
