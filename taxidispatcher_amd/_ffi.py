@@ -81,6 +81,8 @@ SIGNATURES = {
     "td_sim_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "td_simb_create": (ctypes.c_int, [ctypes.c_int, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, c_i32p, c_i32p, c_i32p,
                                       c_i32p, c_i32p, ctypes.POINTER(ctypes.c_void_p)]),
+    "td_simb_create_dist": (ctypes.c_int, [ctypes.c_int, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, c_i32p, c_i32p,
+                                           c_i32p, c_i32p, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_void_p)]),
     "td_simb_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "td_simb_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p]),
     "td_simb_model": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p]),

@@ -24,7 +24,7 @@
 // Counters are reduced per workgroup and added with one 64-bit atomic per workgroup.
 //
 // A world on a distance table (td_sim_create_dist): the handle owns a copy of the table and two neighbour bit matrices built
-// from it once (k_nb_build, which also validates the table).  The near test of createTempDemand / createTempSupply is then
+// from it once (k_nb_build in td_sim_core.h, which also validates the table).  The near test of createTempDemand / createTempSupply is then
 // one more kernel after each k_flags, k_near: near[s] = any(nb[s][q] & flags[q]), one wave per stand; the predicates read
 // one bit of it, and arrival / dispatch / analyzeSolution read one table cell (td_sim_core.h way()).  The direction rule:
 // the row of the table is always the cab's stand, dist[cab.to][request.from]:
@@ -171,32 +171,6 @@ __global__ __launch_bounds__(CB) void k_flags(int n, int n_stands, const int32_t
         if (s_bits[q]) atomicOr(&bits[q], s_bits[q]);
 }
 
-// the neighbour bit matrices of a distance table, one thread per (stand s, word q); the row read visits every cell of the
-// table exactly once, so the table is validated here: diagonal 0, every other entry in 1 .. MAX_DIST (error word 3)
-constexpr int32_t MAX_DIST = 0x1fffffff;   // three entries stay below td_pool2's INT_MAX diagonal marker
-constexpr int MAX_DIST_STANDS = 4096;
-
-__global__ __launch_bounds__(256) void k_nb_build(int n_stands, int words, int drop_time, const int32_t *__restrict__ dist,
-                                                  uint32_t *__restrict__ nb_dem, uint32_t *__restrict__ nb_sup, Ctl *ctl)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // n_stands * words <= 4096 * 128
-    if (i >= n_stands * words) return;
-    const int s = i / words, q = i - s * words;
-    uint32_t md = 0, ms = 0;
-    bool bad = false;
-    for (int b = 0; b < 32; b++) {
-        const int o = q * 32 + b;
-        if (o >= n_stands) break;
-        const int32_t out = dist[(int64_t)s * n_stands + o], in = dist[(int64_t)o * n_stands + s];
-        bad |= o == s ? out != 0 : (out < 1 || out > MAX_DIST);
-        if (out < drop_time) ms |= 1u << b;
-        if (in < drop_time) md |= 1u << b;
-    }
-    nb_dem[i] = md;
-    nb_sup[i] = ms;
-    if (bad) atomicMax(&ctl->err, 3);
-}
-
 // near[s] = any(nb[s][q] & flags[q]): one wave per stand, the lanes stride over the words (at most two strides: 128 words),
 // then a ballot.  A workgroup of 16 waves owns the 32 stands of ONE output word (two stands per wave) and writes it with a
 // plain store, so the near bitset needs no clearing and no global atomic.
@@ -218,8 +192,6 @@ __global__ __launch_bounds__(CB) void k_near(int n_stands, int words, const uint
     __syncthreads();
     if (threadIdx.x == 0) near[blockIdx.x] = s_word;
 }
-
-__device__ __forceinline__ bool bit_of(const uint32_t *bits, int s) { return (bits[s >> 5] >> (s & 31)) & 1u; }
 
 // createTempDemand's predicate (Simulator.java:329-355) on the table as the drop pass left it.  near: the near bitset of a
 // table world (k_near on nb_dem), nullptr = the line's window over bits_cab
@@ -779,7 +751,7 @@ int sim_create(int n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t
                                 c.stream)) != hipSuccess)
             return bail(hip_fail(e, "hipMemcpyAsync(distance table)"));
         const int cells = n_stands * (int)words;
-        k_nb_build<<<(cells + 255) / 256, 256, 0, c.stream>>>(n_stands, (int)words, drop_time, s->dist, s->nb_dem, s->nb_sup, s->ctl);
+        k_nb_build<<<(cells + 255) / 256, 256, 0, c.stream>>>(n_stands, (int)words, drop_time, s->dist, s->nb_dem, s->nb_sup, &s->ctl->err);
         if ((e = hipGetLastError()) != hipSuccess) return bail(hip_fail(e, "td_sim_create_dist launch"));
     }
     if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return bail(hip_fail(e, "hipStreamSynchronize"));   // `h` leaves scope

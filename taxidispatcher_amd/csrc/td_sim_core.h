@@ -1,4 +1,4 @@
-// td_sim_core.h — the per-element rules of the device-resident simulator world (td_sim.hip), one place each.
+// td_sim_core.h — the per-element rules of the device-resident simulator worlds (td_sim.hip, td_simb.hip), one place each.
 //
 // Every rule is a statement-by-statement port of taxidispatcher_amd/simulator.py (the harness with Simulator.java's
 // semantics; SURVEY.md Appendix A lists the bug-compatible details).  Requests are addressed by their INDEX in the
@@ -56,6 +56,36 @@ __device__ inline bool near_window(const uint32_t *bits, int n_stands, int drop_
         if (bits[w] & m) return true;
     }
     return false;
+}
+
+__device__ __forceinline__ bool bit_of(const uint32_t *bits, int s) { return (bits[s >> 5] >> (s & 31)) & 1u; }
+
+// ---- a world on a distance table (td_sim_create_dist, td_simb_create_dist)
+constexpr int32_t MAX_DIST = 0x1fffffff;   // three entries stay below td_pool2's INT_MAX diagonal marker
+constexpr int MAX_DIST_STANDS = 4096;
+
+// the neighbour bit matrices of a distance table, one thread per (stand s, word q); the row read visits every cell of the
+// table exactly once, so the table is validated here: diagonal 0, every other entry in 1 .. MAX_DIST (error word 3).
+// static: td_sim.hip and td_simb.hip each hold their own instance of this one definition
+static __global__ __launch_bounds__(256) void k_nb_build(int n_stands, int words, int drop_time, const int32_t *__restrict__ dist,
+                                                         uint32_t *__restrict__ nb_dem, uint32_t *__restrict__ nb_sup, int32_t *err)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // n_stands * words <= 4096 * 128
+    if (i >= n_stands * words) return;
+    const int s = i / words, q = i - s * words;
+    uint32_t md = 0, ms = 0;
+    bool bad = false;
+    for (int b = 0; b < 32; b++) {
+        const int o = q * 32 + b;
+        if (o >= n_stands) break;
+        const int32_t out = dist[(int64_t)s * n_stands + o], in = dist[(int64_t)o * n_stands + s];
+        bad |= o == s ? out != 0 : (out < 1 || out > MAX_DIST);
+        if (out < drop_time) ms |= 1u << b;
+        if (in < drop_time) md |= 1u << b;
+    }
+    nb_dem[i] = md;
+    nb_sup[i] = ms;
+    if (bad) atomicMax(err, 3);
 }
 
 // Simulator.java:220-254 for ONE cab; returns 1 when a passenger was picked up.  c = the cab's row in the fleet table,

@@ -24,6 +24,13 @@
 // A world without demand in a tick has empty lists (its supply is not listed either); a world with demand and no supply keeps
 // its demand list as its model and is left out of the pool and tick calls (their lists pl_* / tk_* hold the worlds WITH
 // supply only).  The error word is one for the handle: a pair outside its world's model applies nothing in any world.
+//
+// A batch on a distance table (td_simb_create_dist): the worlds share ONE city, so the handle owns one copy of the table and
+// one pair of neighbour bit matrices (k_nb_build of td_sim_core.h, which also validates the table); the near bitsets are
+// per world, laid out like `bits`.  k_near_b after each k_flags is td_sim.hip's k_near with a world dimension: two launches
+// per tick whatever B is.  The predicates then read one bit, arrival / dispatch / analyzeSolution read one table cell
+// (way()), and the batched calls get the handle's table.  The direction rule is td_sim.hip's: the row of the table is
+// always the stand the cab is at or heads to.  A line batch (dist == nullptr) launches exactly what it launched before.
 #include <limits.h>
 
 #include <algorithm>
@@ -39,6 +46,11 @@ namespace {
 constexpr int SIMB_NMAX = 2048;   // largest model of td_tick_batched / td_pool2_batched
 constexpr int N_OFF = 7;          // offset arrays of the head block
 constexpr int N_PER = 4;          // per-world words of the head block
+#ifndef TD_NEAR_WPG
+#define TD_NEAR_WPG 4             // DESIGN.md 3.9 compares 4, 8 and 16
+#endif
+constexpr int NEAR_WPG = TD_NEAR_WPG;   // worlds one k_near_b workgroup serves with one read of its 32 matrix rows (at most 64)
+static_assert(NEAR_WPG >= 1 && NEAR_WPG <= 64, "k_near_b keeps world l's bits in lane l");
 }  // namespace
 
 // decisions of a tick: packed ragged arrays from the caller (stride == 0), or td_tick_batched's strided outputs
@@ -67,6 +79,9 @@ struct td_simb {
     int32_t *n_pools, *tk_np, *tk_lm, *tk_rest;
     int32_t *d_cab_off = nullptr, *d_req_off = nullptr;
     uint32_t *bits = nullptr;    // world b: cab bits at (2 b) * words, request bits at (2 b + 1) * words
+    // a table batch: the table (= w.dist), the neighbour bit matrices [n_stands][words] and the near bitsets, laid out like bits
+    int32_t *dist = nullptr;
+    uint32_t *nb_dem = nullptr, *nb_sup = nullptr, *near = nullptr;
     int32_t *cnt_a, *cnt_b;
     int32_t *dem_idx, *dem_from, *dem_to, *pl_from, *pl_to;
     int32_t *sup_cab, *sup_to;
@@ -224,15 +239,55 @@ __global__ __launch_bounds__(CB) void k_flags(const int32_t *__restrict__ off, i
         if (s_bits[q]) atomicOr(&out[q], s_bits[q]);
 }
 
-// predicates: (element in the concatenated index space, world)
+// near[b][which][q] bit j = any(nb[32 q + j][*] & flags_b[*]) for every world b: k_near of td_sim.hip with a world dimension.
+// Grid (words, ceil(B / NEAR_WPG)).  A workgroup of 16 waves owns the 32 stands of ONE output word (two stands per wave) for
+// NEAR_WPG worlds: it stages those worlds' flag words in LDS, every wave loads its stand's matrix row into registers once
+// (words <= 128: at most two words per lane) and then walks the worlds with one ballot each; lane l of the wave keeps the
+// wave's two bits of world l, so a wave ORs them into LDS once, and a world's word leaves with a plain store.  The matrix
+// is read ceil(B / NEAR_WPG) times, not B times; nothing needs clearing, there is no global atomic and no workgroup waits
+// for another.  Every loop is bounded by NEAR_WPG or words.  Dynamic LDS: (NEAR_WPG * words + NEAR_WPG) words.
+__global__ __launch_bounds__(CB) void k_near_b(int B, int n_stands, int words, const uint32_t *__restrict__ nb,
+                                               const uint32_t *__restrict__ bits, uint32_t *__restrict__ near, int which)
+{
+    extern __shared__ uint32_t s_near[];
+    uint32_t *s_flags = s_near, *s_out = s_near + NEAR_WPG * words;
+    const int b0 = (int)blockIdx.y * NEAR_WPG, nw = B - b0 < NEAR_WPG ? B - b0 : NEAR_WPG;   // 1 <= nw <= NEAR_WPG by the grid
+    for (int i = threadIdx.x; i < nw * words; i += CB) {
+        const int wl = i / words, q = i - wl * words;
+        s_flags[i] = bits[((size_t)2 * (b0 + wl) + which) * words + q];
+    }
+    if ((int)threadIdx.x < NEAR_WPG) s_out[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const bool in0 = lane < words, in1 = lane + 64 < words;
+    uint32_t mine = 0;   // lane wl: this wave's two bits of world wl
+    for (int j = 0; j < 2; j++) {
+        const int bit = 2 * wv + j, s = (int)blockIdx.x * 32 + bit;
+        if (s >= n_stands) break;   // the same for the whole wave
+        const uint32_t *row = nb + (size_t)s * words;
+        const uint32_t r0 = in0 ? row[lane] : 0u, r1 = in1 ? row[lane + 64] : 0u;
+        for (int wl = 0; wl < nw; wl++) {
+            const uint32_t *f = s_flags + wl * words;
+            const uint32_t acc = (in0 ? r0 & f[lane] : 0u) | (in1 ? r1 & f[lane + 64] : 0u);
+            if (__ballot(acc != 0) != 0ull && lane == wl) mine |= 1u << bit;
+        }
+    }
+    if (mine) atomicOr(&s_out[lane], mine);   // mine != 0 only in a lane below nw
+    __syncthreads();
+    if ((int)threadIdx.x < nw) near[((size_t)2 * (b0 + threadIdx.x) + which) * words + blockIdx.x] = s_out[threadIdx.x];
+}
+
+// predicates: (element in the concatenated index space, world).  near: the near bitsets of a table batch (k_near_b), nullptr =
+// the line's window over the flag bits
 struct DemPred {
     World w;
     int t, words;
-    const uint32_t *bits;
+    const uint32_t *bits, *near;
     __device__ bool operator()(int d, int b) const
     {
         return w.r_cab[d] == -1 && t >= w.r_at[d] && t - w.r_at[d] < w.drop_time &&
-               near_window(bits + (size_t)2 * b * words, w.n_stands, w.drop_time, w.r_from[d]);
+               (near ? bit_of(near + (size_t)2 * b * words, w.r_from[d])
+                     : near_window(bits + (size_t)2 * b * words, w.n_stands, w.drop_time, w.r_from[d]));
     }
 };
 // emitters: (position in the list, position in the list of the worlds with supply or -1, element, world)
@@ -253,11 +308,12 @@ struct DemEmit {
 struct SupPred {
     World w;
     int words;
-    const uint32_t *bits;
+    const uint32_t *bits, *near;
     __device__ bool operator()(int c, int b) const
     {
         return w.c_from[c] == w.c_to[c] && w.c_clnt[c] == -1 &&
-               near_window(bits + ((size_t)2 * b + 1) * words, w.n_stands, w.drop_time, w.c_to[c]);
+               (near ? bit_of(near + ((size_t)2 * b + 1) * words, w.c_to[c])
+                     : near_window(bits + ((size_t)2 * b + 1) * words, w.n_stands, w.drop_time, w.c_to[c]));
     }
 };
 struct SupEmit {
@@ -532,8 +588,8 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, SimbDec d
         const int c = l < nr ? dec.r2c[rb + l] : -1;
         if (c >= 0 && c < n_d) {
             const int e = d0 + c;
-            const int dist = iabs(l_to[s] - l_from[e]);
-            const int cell = dist < w.drop_time ? dist : w.big_cost;   // the thresholded |a - b| model's cell
+            const int dist = way(w, l_to[s], l_from[e]);
+            const int cell = dist < w.drop_time ? dist : w.big_cost;   // the thresholded model's cell
             if (cell < w.big_cost) {
                 count = 1;
                 const int idx = l_idx[e], cab = l_cab[s], partner = l_partner[e];
@@ -633,10 +689,14 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     const dim3 grid_c(gc, B), grid_r(gr, B);
     k_arrive<<<grid_c, CB, 0, c.stream>>>(w, s->d_cab_off, t, s->ctl);
     k_flags<<<grid_c, CB, shm, c.stream>>>(s->d_cab_off, w.n_stands, w.c_to, w.c_clnt, s->bits, 0);
-    const DemPred dp{w, t, s->words, s->bits};
+    const dim3 grid_n(s->words, (B + NEAR_WPG - 1) / NEAR_WPG);
+    const size_t shm_n = sizeof(uint32_t) * ((size_t)NEAR_WPG * s->words + NEAR_WPG);
+    if (s->dist) k_near_b<<<grid_n, CB, shm_n, c.stream>>>(B, w.n_stands, s->words, s->nb_dem, s->bits, s->near, 0);
+    const DemPred dp{w, t, s->words, s->bits, s->near};
     k_dem_count<<<grid_r, CB, 0, c.stream>>>(dp, s->d_req_off, s->cnt_a, s->ctl);
     k_flags<<<grid_r, CB, shm, c.stream>>>(s->d_req_off, w.n_stands, w.r_from, w.r_cab, s->bits, 1);
-    const SupPred sp{w, s->words, s->bits};
+    if (s->dist) k_near_b<<<grid_n, CB, shm_n, c.stream>>>(B, w.n_stands, s->words, s->nb_sup, s->bits, s->near, 1);
+    const SupPred sp{w, s->words, s->bits, s->near};
     k_count<SupPred><<<grid_c, CB, 0, c.stream>>>(s->d_cab_off, sp, s->cnt_b);
     k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, gr, s->cnt_b, gc, 1, nullptr, s->dem_off, s->sup_off, s->pl_off);
     k_scatter<DemPred, DemEmit><<<grid_r, CB, 0, c.stream>>>(s->d_req_off, dp, DemEmit{w, s->dem_idx, s->dem_from, s->dem_to, s->pl_from, s->pl_to},
@@ -663,7 +723,7 @@ int simb_begin(td_simb *s, int t, int32_t *info)
             if (s->n_sup[b] > 0 && s->n_dem[b] >= 2) s->max_pool_mem[b] = std::max(s->max_pool_mem[b], (int64_t)s->n_dem[b] * (s->n_dem[b] - 1));
         if (max_act <= SIMB_NMAX) {
             s->pool_h = std::max(1, max_act / 2);
-            if ((rc = td_pool2_batched(B, max_act, hp, s->pl_from, s->pl_to, nullptr, 0, 0.0, 0, s->pa, s->pb, s->pp, s->pc, s->n_pools, s->p_total)))
+            if ((rc = td_pool2_batched(B, max_act, hp, s->pl_from, s->pl_to, s->dist, s->dist ? w.n_stands : 0, 0.0, 0, s->pa, s->pb, s->pp, s->pc, s->n_pools, s->p_total)))
                 return rc;
         } else {
             // a world beyond the batched call's model size: td_pool2 world by world, plans packed at pl_off[b] / 2 (a world
@@ -673,7 +733,7 @@ int simb_begin(td_simb *s, int t, int32_t *info)
             for (int b = 0; b < B; b++) {
                 const int m = hp[b + 1] - hp[b], q = hp[b] >> 1;
                 np[b] = 0;
-                if (m >= 2 && (rc = td_pool2(m, s->pl_from + hp[b], s->pl_to + hp[b], nullptr, 0, s->pa + q, s->pb + q, s->pp + q, s->pc + q, &np[b])))
+                if (m >= 2 && (rc = td_pool2(m, s->pl_from + hp[b], s->pl_to + hp[b], s->dist, s->dist ? w.n_stands : 0, s->pa + q, s->pb + q, s->pp + q, s->pc + q, &np[b])))
                     return rc;
             }
             TD_HIP(hipMemcpyAsync(s->n_pools, np, sizeof(int32_t) * B, hipMemcpyHostToDevice, c.stream));
@@ -804,9 +864,10 @@ int check_offsets(const td_simb *s, const char *what, const std::vector<int32_t>
 
 }  // namespace
 
-extern "C" int td_simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost,
-                              const int32_t *req_off, const int32_t *req_id, const int32_t *req_from, const int32_t *req_to,
-                              const int32_t *req_at, td_simb **out)
+// td_simb_create (dist == nullptr) and td_simb_create_dist
+static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost, const int32_t *req_off,
+                       const int32_t *req_id, const int32_t *req_from, const int32_t *req_to, const int32_t *req_at, const int32_t *dist,
+                       td_simb **out)
 {
     TD_REQUIRE_INIT();
     Ctx &c = ctx();
@@ -816,6 +877,7 @@ extern "C" int td_simb_create(int batch, const int32_t *n_cabs, int n_stands, in
     if (!n_cabs || !req_off) return fail(TD_EINVAL, "td_simb_create: null n_cabs / req_off");
     if (n_stands < 1 || drop_time < 0 || max_non_lcm < 0 || big_cost < 0) return fail(TD_EINVAL, "td_simb_create: n_stands at least 1, nothing negative");
     if (n_stands > (1 << 18)) return fail(TD_EINVAL, "td_simb_create: at most %d stands (one bit per stand in LDS)", 1 << 18);
+    if (dist && n_stands > MAX_DIST_STANDS) return fail(TD_EINVAL, "td_simb_create_dist: at most %d stands with a distance table", MAX_DIST_STANDS);
     if (max_non_lcm > 1024)
         return fail(TD_EINVAL, "td_simb_create: max_non_lcm = %d > 1024 (the remainder td_tick_batched hands its solver)", max_non_lcm);
     const int B = batch;
@@ -872,7 +934,8 @@ extern "C" int td_simb_create(int batch, const int32_t *n_cabs, int n_stands, in
     s->pool_cap = std::max(nb * (size_t)s->hcap, nr / 2 + 1);
     const size_t tk_cap = nb * (size_t)s->ncap;
     s->head_ints = 16 * nb + 16 + (size_t)N_OFF * (nb + 1) + (size_t)N_PER * nb;
-    const size_t ints = s->head_ints + 2 * (nb + 1) + 2 * words * nb + 2 * n_cnt + 9 * nr + 5 * nc   // head, offsets, bits, counts, tables
+    const size_t ns = (size_t)n_stands, table_ints = dist ? ns * ns + 2 * ns * words + 2 * words * nb : 0;   // table, matrices, near bitsets
+    const size_t ints = table_ints + s->head_ints + 2 * (nb + 1) + 2 * words * nb + 2 * n_cnt + 9 * nr + 5 * nc   // head, offsets, bits, counts, tables
                         + 5 * nr + 2 * nc + 6 * nr + 2 * nc + 5 * nr + 2 * nr                        // dem / pl, sup, d2 / tk, ks, kd, isb / ainfo
                         + 4 * s->pool_cap + 4 * nb + nc + nr                                         // plans, two int64 [B], pair maps
                         + 3 * in_cap + 2 * (nb + 1) + nb + 3 * tk_cap + std::max<size_t>(max_cabs, 1) + 64;
@@ -914,7 +977,13 @@ extern "C" int td_simb_create(int batch, const int32_t *n_cabs, int n_stands, in
     w.n_stands = n_stands;
     w.drop_time = drop_time;
     w.big_cost = big_cost;
-    w.dist = nullptr;   // the worlds of a batch live on the line
+    if (dist) {   // one city for the whole batch
+        s->near = (uint32_t *)take(2 * words * nb);
+        s->nb_dem = (uint32_t *)take(ns * words);
+        s->nb_sup = (uint32_t *)take(ns * words);
+        s->dist = take(ns * ns);
+    }
+    w.dist = s->dist;   // nullptr: the worlds of the batch live on the line
     int32_t *rid = take(nr), *rfrom = take(nr), *rto = take(nr), *rat = take(nr);
     w.r_id = rid;
     w.r_from = rfrom;
@@ -1012,9 +1081,37 @@ extern "C" int td_simb_create(int batch, const int32_t *n_cabs, int n_stands, in
     for (const Up &u : ups)
         if (u.n && (e = hipMemcpyAsync(u.dst, u.src, sizeof(int32_t) * u.n, hipMemcpyHostToDevice, c.stream)) != hipSuccess)
             return bail(hip_fail(e, "hipMemcpyAsync(td_simb tables)"));
+    if (dist) {
+        // the handle's own copy of the table, then its bit matrices; k_nb_build reports an invalid table in the error word
+        if ((e = hipMemcpyAsync(s->dist, dist, sizeof(int32_t) * ns * ns, is_device_ptr(dist) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                c.stream)) != hipSuccess)
+            return bail(hip_fail(e, "hipMemcpyAsync(distance table)"));
+        const int cells = n_stands * s->words;
+        k_nb_build<<<(cells + 255) / 256, 256, 0, c.stream>>>(n_stands, s->words, drop_time, s->dist, s->nb_dem, s->nb_sup, s->gerr);
+        if ((e = hipGetLastError()) != hipSuccess) return bail(hip_fail(e, "td_simb_create_dist launch"));
+    }
     if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return bail(hip_fail(e, "hipStreamSynchronize"));   // `h` leaves scope
+    if (dist) {
+        if ((rc = read_head(s))) return bail(rc);
+        if (*h_of(s, s->gerr))
+            return bail(fail(TD_EINVAL, "td_simb_create_dist: the distance table needs a zero diagonal and every other entry in 1 .. %d", MAX_DIST));
+    }
     *out = s;
     return TD_OK;
+}
+
+extern "C" int td_simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost,
+                              const int32_t *req_off, const int32_t *req_id, const int32_t *req_from, const int32_t *req_to,
+                              const int32_t *req_at, td_simb **out)
+{
+    return simb_create(batch, n_cabs, n_stands, drop_time, max_non_lcm, big_cost, req_off, req_id, req_from, req_to, req_at, nullptr, out);
+}
+
+extern "C" int td_simb_create_dist(int batch, const int32_t *n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t big_cost,
+                                   const int32_t *req_off, const int32_t *req_id, const int32_t *req_from, const int32_t *req_to,
+                                   const int32_t *req_at, const int32_t *dist, td_simb **out)
+{
+    return simb_create(batch, n_cabs, n_stands, drop_time, max_non_lcm, big_cost, req_off, req_id, req_from, req_to, req_at, dist, out);
 }
 
 extern "C" int td_simb_destroy(td_simb *s)
@@ -1102,7 +1199,7 @@ extern "C" int td_simb_step(td_simb *s, int t, int32_t *line)
     }
     if (n > 0) {
         // the arguments HipTickBackend.tick hands td_tick, for every world with supply at once; the lists stay where they are
-        if ((rc = td_tick_batched(B, n, h_of(s, s->sup_off), s->sup_to, h_of(s, s->tk_off), s->tk_from, nullptr, 0, s->w.big_cost, s->w.drop_time,
+        if ((rc = td_tick_batched(B, n, h_of(s, s->sup_off), s->sup_to, h_of(s, s->tk_off), s->tk_from, s->dist, s->dist ? s->w.n_stands : 0, s->w.big_cost, s->w.drop_time,
                                   s->max_non_lcm, s->tk_rows, s->tk_cols, s->tk_np, s->tk_lm, nullptr, nullptr, s->tk_rest, s->tk_r2c, s->tk_total,
                                   nullptr)))
             return rc;

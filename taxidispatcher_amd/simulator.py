@@ -599,17 +599,37 @@ class DeviceSimulatorBatch:
     """B independent worlds behind ONE handle (td_simb_*, csrc/td_simb.hip): the worlds share the city (n_stands, drop_time,
     max_non_lcm, big_cost) and differ in fleet size and request table.  `tick` advances every world by one td_simb_step
     (td_pool2_batched and td_tick_batched on the device lists); `begin` / `model` / `apply` split the tick for decisions
-    from any source.  Per world, lines, `m[b]`, `state(b)` and `metrics_text(b)` are those of `DeviceSimulator`."""
+    from any source.  Per world, lines, `m[b]`, `state(b)` and `metrics_text(b)` are those of `DeviceSimulator`.
+    dist: ONE stand-to-stand distance table for the whole batch, as `DeviceSimulator` takes it (numpy array-like, or an int32
+    torch tensor on the device); the handle keeps its own copy (td_simb_create_dist).  n_stands then defaults to the table's
+    size.  A host table is checked here (check_dist), and so are its size against n_stands and the request stands against
+    the table: ValueError, before the library is touched.  A device tensor is checked for shape and dtype only; its size,
+    diagonal and entries by td_simb_create_dist on the device, which raises TdError."""
 
     M_KEYS, CAB_KEYS, REQ_KEYS = DeviceSimulator.M_KEYS, DeviceSimulator.CAB_KEYS, DeviceSimulator.REQ_KEYS
     format_line = staticmethod(DeviceSimulator.format_line)
 
-    def __init__(self, demand_rows_list, n_cabs_list, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None):
+    def __init__(self, demand_rows_list, n_cabs_list, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None):
         import ctypes
         from . import _ffi
         self._ffi, self._ct = _ffi, ctypes
         self._h = None
         cabs, off, rid, rfrom, rto, rat = pack_worlds(demand_rows_list, n_cabs_list)
+        if dist is not None:
+            if getattr(dist, "is_cuda", False):      # a device table is checked by td_simb_create_dist
+                if str(dist.dtype) != "torch.int32" or dist.dim() != 2 or dist.shape[0] != dist.shape[1]:
+                    raise ValueError("distance table: a device tensor must be a square int32 table")
+            else:
+                dist = check_dist(dist)
+            if n_stands is not None and int(n_stands) != int(dist.shape[0]):
+                raise ValueError("distance table: %d x %d for n_stands=%d" % (dist.shape[0], dist.shape[0], int(n_stands)))
+            n_stands = int(dist.shape[0])
+            for what, col in (("from", rfrom), ("to", rto)):
+                bad = np.nonzero((col < 0) | (col >= n_stands))[0]
+                if bad.size:
+                    b = int(np.searchsorted(off, bad[0], side="right")) - 1
+                    raise ValueError("distance table: world %d, request %d: %s stand %d outside the %d x %d table"
+                                     % (b, int(bad[0] - off[b]), what, int(col[bad[0]]), n_stands, n_stands))
         self._lib = _ffi.lib()
         self.batch = int(cabs.size)
         self.n_cabs = [int(v) for v in cabs]
@@ -621,9 +641,12 @@ class DeviceSimulatorBatch:
         self.big_cost = int(BIG_COST if big_cost is None else big_cost)
         h = ctypes.c_void_p()
         some = int(off[-1]) > 0
-        _ffi.check(self._lib.td_simb_create(self.batch, _ffi.addr(cabs), self.n_stands, self.drop_time, self.max_non_lcm, self.big_cost,
-                                            _ffi.addr(off), *[_ffi.addr(c) if some else None for c in (rid, rfrom, rto, rat)],
-                                            ctypes.byref(h)))
+        args = [self.batch, _ffi.addr(cabs), self.n_stands, self.drop_time, self.max_non_lcm, self.big_cost, _ffi.addr(off)]
+        args += [_ffi.addr(c) if some else None for c in (rid, rfrom, rto, rat)]
+        if dist is None:
+            _ffi.check(self._lib.td_simb_create(*args, ctypes.byref(h)))
+        else:
+            _ffi.check(self._lib.td_simb_create_dist(*args, _ffi.addr(dist), ctypes.byref(h)))
         self._h = h
         self._info = None
         self.logs = [[] for _ in range(self.batch)]

@@ -4,7 +4,8 @@
 --world device --cabs 900,1100,1300: the committed demand file once per fleet size as ONE batch of worlds
 (DeviceSimulatorBatch = td_simb_step, one C-ABI call per tick for all of them), each world's metrics block printed.
 --dist FILE.npy: the city as a stand-to-stand distance table (a square integer array saved with numpy.save, [from][to]) for
---world host and --world device; the stands of the demand file must lie inside it."""
+--world host and --world device, a batch of worlds (--cabs) included: the worlds of a batch share the one table
+(td_simb_create_dist); the stands of the demand file must lie inside it."""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,8 +18,6 @@ ap.add_argument("--dist", default=None, metavar="FILE.npy", help="a stand-to-sta
 args = ap.parse_args()
 if args.cabs and args.world != "device":
     ap.error("--cabs needs --world device")
-if args.cabs and args.dist:
-    ap.error("--dist cannot be combined with --cabs: a batch of worlds (td_simb) lives on the line, it takes no distance table")
 dist = None
 if args.dist:
     try:
@@ -32,7 +31,7 @@ if dist is not None and rows[:, 1:3].max() >= dist.shape[0]:
 td.init(0)
 if args.world == "device" and args.cabs:
     fleets = [int(v) for v in args.cabs.split(",")]
-    sim = simulator.DeviceSimulatorBatch([rows] * len(fleets), fleets)
+    sim = simulator.DeviceSimulatorBatch([rows] * len(fleets), fleets, dist=dist)
     t0 = time.time()
     logs = sim.run(120)
     dt = time.time() - t0
