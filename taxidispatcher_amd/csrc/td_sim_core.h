@@ -1,4 +1,5 @@
 // td_sim_core.h — the per-element rules of the device-resident simulator worlds (td_sim.hip, td_simb.hip), one place each.
+// The kernels that apply them, and the host helpers of both handles, are in td_sim_world.h.
 //
 // Every rule is a statement-by-statement port of taxidispatcher_amd/simulator.py (the harness with Simulator.java's
 // semantics; SURVEY.md Appendix A lists the bug-compatible details).  Requests are addressed by their INDEX in the
@@ -24,12 +25,14 @@ struct World {
     const int32_t *dist;
 };
 
-// device counters: the sums of Simulator.m (64-bit), the error word, and this tick's list sizes
+// device counters of one world: the sums of Simulator.m (64-bit), an error word (td_sim's; a batch has one for the handle)
+// and this tick's OPT count.  The list sizes are offset arrays of the handles.
 struct Ctl {
     long long dropped, pickup_time, pickup_numb, second;
-    int32_t err;        // 1: internal, 2: a pair or plan index handed in lies outside its list
-    int32_t n_dem, n_sup, n_dem2, n_ks, n_kd, opt_count, pad;
+    int32_t err;        // 1: internal, 2: a pair or plan index handed in lies outside its list, 3: an invalid distance table
+    int32_t opt_count, pad[6];
 };
+static_assert(sizeof(Ctl) == 64, "both handles lay a Ctl out as 16 ints");
 
 // Simulator.java:469-474
 __host__ __device__ inline int cheat_a_bit(int frm, int cost, int n_stands)
@@ -111,8 +114,6 @@ __device__ inline int arrive_as(const World &w, int t, int c, int cab_no)
     w.c_start[c] = -1;
     return 0;
 }
-
-__device__ inline int arrive(const World &w, int t, int c) { return arrive_as(w, t, c, c); }
 
 // Simulator.java:424-490 _dispatch for cab `cab` (standing at sup_to) and the customer (request idx, pool partner / cost)
 __device__ __forceinline__ void dispatch(const World &w, int t, int cab, int sup_to, int idx, int partner, int pcost, int &numb, int &ptime)

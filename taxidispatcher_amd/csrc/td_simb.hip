@@ -1,4 +1,7 @@
-// td_simb.hip — B independent simulator worlds in HBM behind one handle (td_simb_*): td_sim.hip with a world dimension.
+// td_simb.hip — B independent simulator worlds in HBM behind one handle (td_simb_*).  The world kernels, predicates and
+// emitters are td_sim_world.h's, shared with td_sim.hip; this file holds what B worlds need of their own: the handle and
+// its head block, k_offsets, the scatter behind it, where the batched calls leave plans and decisions (SimbPlans,
+// SimbDec), and the host flow.
 //
 // Layout.  The B fleets are ONE cab table and the B request tables ONE request table (world after world; cab_off / req_off
 // say where a world begins).  c_clnt and the pool partner stay indices into the concatenated request table; the cab number
@@ -27,17 +30,13 @@
 //
 // A batch on a distance table (td_simb_create_dist): the worlds share ONE city, so the handle owns one copy of the table and
 // one pair of neighbour bit matrices (k_nb_build of td_sim_core.h, which also validates the table); the near bitsets are
-// per world, laid out like `bits`.  k_near_b after each k_flags is td_sim.hip's k_near with a world dimension: two launches
+// per world, laid out like `bits`.  k_near_b after each k_flags serves NEAR_WPG worlds per workgroup: two launches
 // per tick whatever B is.  The predicates then read one bit, arrival / dispatch / analyzeSolution read one table cell
 // (way()), and the batched calls get the handle's table.  The direction rule is td_sim.hip's: the row of the table is
 // always the stand the cab is at or heads to.  A line batch (dist == nullptr) launches exactly what it launched before.
 #include <limits.h>
 
-#include <algorithm>
-#include <vector>
-
-#include "td_common.h"
-#include "td_sim_core.h"
+#include "td_sim_world.h"
 
 using namespace td;
 using namespace tdsim;
@@ -46,11 +45,6 @@ namespace {
 constexpr int SIMB_NMAX = 2048;   // largest model of td_tick_batched / td_pool2_batched
 constexpr int N_OFF = 7;          // offset arrays of the head block
 constexpr int N_PER = 4;          // per-world words of the head block
-#ifndef TD_NEAR_WPG
-#define TD_NEAR_WPG 4             // DESIGN.md 3.9 compares 4, 8 and 16
-#endif
-constexpr int NEAR_WPG = TD_NEAR_WPG;   // worlds one k_near_b workgroup serves with one read of its 32 matrix rows (at most 64)
-static_assert(NEAR_WPG >= 1 && NEAR_WPG <= 64, "k_near_b keeps world l's bits in lane l");
 }  // namespace
 
 // decisions of a tick: packed ragged arrays from the caller (stride == 0), or td_tick_batched's strided outputs
@@ -59,6 +53,39 @@ struct SimbDec {
     const int32_t *pair_off, *r2c_off, *solved;
     const int32_t *n_pairs, *n_rest, *last_min;
     int stride;
+    __device__ __forceinline__ void pairs(int b, int *base, int *cnt) const
+    {
+        if (stride) {
+            *base = b * stride;
+            *cnt = n_pairs[b];
+        } else {
+            *base = pair_off[b];
+            *cnt = pair_off[b + 1] - *base;
+        }
+    }
+    // row_to_col of world b: where it begins and how many entries count (0 when the world was not solved)
+    __device__ __forceinline__ void r2c_of(int b, bool lcm, int big_cost, int *base, int *nr, bool *sol) const
+    {
+        if (stride) {
+            *base = b * stride;
+            *sol = n_rest[b] > 0 && !(lcm && last_min[b] == big_cost);
+            *nr = *sol ? n_rest[b] : 0;
+        } else {
+            *base = r2c_off[b];
+            *sol = solved[b] != 0;
+            *nr = *sol ? r2c_off[b + 1] - *base : 0;
+        }
+    }
+};
+
+// this tick's plan lists: world b's at b * pool_h (td_pool2_batched), or packed at pl_off[b] / 2 (td_pool2 world by world);
+// pl_off delimits the customers that were pooled, the demand of the worlds with supply
+struct SimbPlans {
+    int pool_h, ragged;
+    const int32_t *pl_off, *n_pools;
+    __device__ __forceinline__ int n_act(int b) const { return pl_off[b + 1] - pl_off[b]; }
+    __device__ __forceinline__ int count(int b) const { return n_pools[b]; }
+    __device__ __forceinline__ int base(int b) const { return ragged ? pl_off[b] >> 1 : b * pool_h; }
 };
 
 struct td_simb {
@@ -107,307 +134,6 @@ struct td_simb {
 };
 
 namespace {
-
-template <class T>
-__device__ __forceinline__ T wave_sum(T v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
-
-// sum over the workgroup, returned to every thread (s_red: one slot per wave)
-template <class T>
-__device__ __forceinline__ T block_sum(T v, T *s_red)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    v = wave_sum(v);
-    if (lane == 0) s_red[wv] = v;
-    __syncthreads();
-    T tot = 0;
-    for (int q = 0; q < nw; q++) tot += s_red[q];
-    __syncthreads();
-    return tot;
-}
-
-// rank of this thread among the flagged threads of the workgroup (ascending thread order), *tot = how many
-__device__ __forceinline__ int block_rank(bool f, int *s_w, int *tot)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    const unsigned long long m = __ballot(f);
-    const int before = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_w[wv] = __popcll(m);
-    __syncthreads();
-    int off = 0, t = 0;
-    for (int q = 0; q < nw; q++) {
-        if (q < wv) off += s_w[q];
-        t += s_w[q];
-    }
-    __syncthreads();
-    *tot = t;
-    return off + before;
-}
-
-// exclusive scan of v over the workgroup (full waves), *tot = the sum
-__device__ __forceinline__ int block_excl_scan(int v, int *s_w, int *tot)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    int off = 0, t = 0;
-    for (int q = 0; q < nw; q++) {
-        if (q < wv) off += s_w[q];
-        t += s_w[q];
-    }
-    __syncthreads();
-    *tot = t;
-    return off + inc - v;
-}
-
-// the handle's error word as ONE value for the whole workgroup
-__device__ __forceinline__ int block_err(const int32_t *gerr)
-{
-    __shared__ int s_e;
-    if (threadIdx.x == 0) s_e = *gerr;
-    __syncthreads();
-    return s_e;
-}
-
-// does world b's model go through the LCM (analyzePairs)?  Without supply there is no model at all.
-__device__ __forceinline__ bool world_lcm(int n_s, int n_d, int max_non_lcm) { return n_s > 0 && (n_s > n_d ? n_s : n_d) > max_non_lcm; }
-
-__device__ __forceinline__ void dec_pairs(const SimbDec &d, int b, int *base, int *cnt)
-{
-    if (d.stride) {
-        *base = b * d.stride;
-        *cnt = d.n_pairs[b];
-    } else {
-        *base = d.pair_off[b];
-        *cnt = d.pair_off[b + 1] - *base;
-    }
-}
-
-// row_to_col of world b: where it begins and how many entries count (0 when the world was not solved)
-__device__ __forceinline__ void dec_r2c(const SimbDec &d, int b, bool lcm, int big_cost, int *base, int *nr, bool *solved)
-{
-    if (d.stride) {
-        *base = b * d.stride;
-        *solved = d.n_rest[b] > 0 && !(lcm && d.last_min[b] == big_cost);
-        *nr = *solved ? d.n_rest[b] : 0;
-    } else {
-        *base = d.r2c_off[b];
-        *solved = d.solved[b] != 0;
-        *nr = *solved ? d.r2c_off[b + 1] - *base : 0;
-    }
-}
-
-__global__ __launch_bounds__(CB) void k_arrive(World w, const int32_t *__restrict__ cab_off, int t, Ctl *ctl)
-{
-    __shared__ int s_red[16];
-    const int b = blockIdx.y, lo = cab_off[b], n = cab_off[b + 1] - lo, l = blockIdx.x * CB + threadIdx.x;
-    const int got = l < n ? arrive_as(w, t, lo + l, l) : 0;
-    const int tot = block_sum(got, s_red);
-    if (threadIdx.x == 0) {
-        if (blockIdx.x == 0) ctl[b].opt_count = 0;   // this tick's OPT count starts from zero
-        if (tot) atomicAdd((unsigned long long *)&ctl[b].pickup_numb, (unsigned long long)tot);
-    }
-}
-
-// world b's bitset `which` |= some element i of the world with who[i] == -1 has stand[i] == s
-__global__ __launch_bounds__(CB) void k_flags(const int32_t *__restrict__ off, int n_stands, const int32_t *__restrict__ stand,
-                                              const int32_t *__restrict__ who, uint32_t *__restrict__ bits, int which)
-{
-    extern __shared__ uint32_t s_bits[];
-    const int words = (n_stands + 31) / 32;
-    const int b = blockIdx.y, lo = off[b], n = off[b + 1] - lo, l = blockIdx.x * CB + threadIdx.x;
-    if ((int)blockIdx.x * CB >= n) return;   // the whole workgroup lies behind the world's segment
-    for (int i = threadIdx.x; i < words; i += CB) s_bits[i] = 0;
-    __syncthreads();
-    if (l < n && who[lo + l] == -1) {
-        const int s = stand[lo + l];
-        atomicOr(&s_bits[s >> 5], 1u << (s & 31));
-    }
-    __syncthreads();
-    uint32_t *out = bits + ((size_t)2 * b + which) * words;
-    for (int q = threadIdx.x; q < words; q += CB)
-        if (s_bits[q]) atomicOr(&out[q], s_bits[q]);
-}
-
-// near[b][which][q] bit j = any(nb[32 q + j][*] & flags_b[*]) for every world b: k_near of td_sim.hip with a world dimension.
-// Grid (words, ceil(B / NEAR_WPG)).  A workgroup of 16 waves owns the 32 stands of ONE output word (two stands per wave) for
-// NEAR_WPG worlds: it stages those worlds' flag words in LDS, every wave loads its stand's matrix row into registers once
-// (words <= 128: at most two words per lane) and then walks the worlds with one ballot each; lane l of the wave keeps the
-// wave's two bits of world l, so a wave ORs them into LDS once, and a world's word leaves with a plain store.  The matrix
-// is read ceil(B / NEAR_WPG) times, not B times; nothing needs clearing, there is no global atomic and no workgroup waits
-// for another.  Every loop is bounded by NEAR_WPG or words.  Dynamic LDS: (NEAR_WPG * words + NEAR_WPG) words.
-__global__ __launch_bounds__(CB) void k_near_b(int B, int n_stands, int words, const uint32_t *__restrict__ nb,
-                                               const uint32_t *__restrict__ bits, uint32_t *__restrict__ near, int which)
-{
-    extern __shared__ uint32_t s_near[];
-    uint32_t *s_flags = s_near, *s_out = s_near + NEAR_WPG * words;
-    const int b0 = (int)blockIdx.y * NEAR_WPG, nw = B - b0 < NEAR_WPG ? B - b0 : NEAR_WPG;   // 1 <= nw <= NEAR_WPG by the grid
-    for (int i = threadIdx.x; i < nw * words; i += CB) {
-        const int wl = i / words, q = i - wl * words;
-        s_flags[i] = bits[((size_t)2 * (b0 + wl) + which) * words + q];
-    }
-    if ((int)threadIdx.x < NEAR_WPG) s_out[threadIdx.x] = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const bool in0 = lane < words, in1 = lane + 64 < words;
-    uint32_t mine = 0;   // lane wl: this wave's two bits of world wl
-    for (int j = 0; j < 2; j++) {
-        const int bit = 2 * wv + j, s = (int)blockIdx.x * 32 + bit;
-        if (s >= n_stands) break;   // the same for the whole wave
-        const uint32_t *row = nb + (size_t)s * words;
-        const uint32_t r0 = in0 ? row[lane] : 0u, r1 = in1 ? row[lane + 64] : 0u;
-        for (int wl = 0; wl < nw; wl++) {
-            const uint32_t *f = s_flags + wl * words;
-            const uint32_t acc = (in0 ? r0 & f[lane] : 0u) | (in1 ? r1 & f[lane + 64] : 0u);
-            if (__ballot(acc != 0) != 0ull && lane == wl) mine |= 1u << bit;
-        }
-    }
-    if (mine) atomicOr(&s_out[lane], mine);   // mine != 0 only in a lane below nw
-    __syncthreads();
-    if ((int)threadIdx.x < nw) near[((size_t)2 * (b0 + threadIdx.x) + which) * words + blockIdx.x] = s_out[threadIdx.x];
-}
-
-// predicates: (element in the concatenated index space, world).  near: the near bitsets of a table batch (k_near_b), nullptr =
-// the line's window over the flag bits
-struct DemPred {
-    World w;
-    int t, words;
-    const uint32_t *bits, *near;
-    __device__ bool operator()(int d, int b) const
-    {
-        return w.r_cab[d] == -1 && t >= w.r_at[d] && t - w.r_at[d] < w.drop_time &&
-               (near ? bit_of(near + (size_t)2 * b * words, w.r_from[d])
-                     : near_window(bits + (size_t)2 * b * words, w.n_stands, w.drop_time, w.r_from[d]));
-    }
-};
-// emitters: (position in the list, position in the list of the worlds with supply or -1, element, world)
-struct DemEmit {
-    World w;
-    int32_t *idx, *from, *to, *pl_from, *pl_to;
-    __device__ void operator()(int o, int o2, int d, int) const
-    {
-        idx[o] = d;
-        from[o] = w.r_from[d];
-        to[o] = w.r_to[d];
-        if (o2 >= 0) {
-            pl_from[o2] = w.r_from[d];
-            pl_to[o2] = w.r_to[d];
-        }
-    }
-};
-struct SupPred {
-    World w;
-    int words;
-    const uint32_t *bits, *near;
-    __device__ bool operator()(int c, int b) const
-    {
-        return w.c_from[c] == w.c_to[c] && w.c_clnt[c] == -1 &&
-               (near ? bit_of(near + ((size_t)2 * b + 1) * words, w.c_to[c])
-                     : near_window(bits + ((size_t)2 * b + 1) * words, w.n_stands, w.drop_time, w.c_to[c]));
-    }
-};
-struct SupEmit {
-    World w;
-    int32_t *cab, *to;
-    __device__ void operator()(int o, int, int c, int) const
-    {
-        cab[o] = c;
-        to[o] = w.c_to[c];
-    }
-};
-struct PoolPred {
-    const int32_t *isb;
-    __device__ bool operator()(int d, int) const { return !isb[d]; }
-};
-struct PoolEmit {
-    int pool_h, ragged;
-    const int32_t *dem_off, *pl_off, *n_pools, *dem_idx, *dem_from, *ainfo, *pl_b, *pl_plan, *pl_cost;
-    int32_t *idx, *from, *partner, *plan, *cost, *tk_from;
-    __device__ void operator()(int o, int o2, int d, int b) const
-    {
-        idx[o] = dem_idx[d];
-        from[o] = dem_from[d];
-        const int p = ainfo[d];
-        const bool a = p >= 0 && p < n_pools[b];
-        const int q = (ragged ? pl_off[b] >> 1 : b * pool_h) + (a ? p : 0);
-        const int pb = a ? pl_b[q] : -1;   // k_pool_mark raised the error word for a plan outside the list; never index by it
-        partner[o] = pb >= 0 && pb < dem_off[b + 1] - dem_off[b] ? dem_idx[dem_off[b] + pb] : -1;
-        plan[o] = a ? pl_plan[q] : -1;
-        cost[o] = a ? pl_cost[q] : 0;
-        if (o2 >= 0) tk_from[o2] = dem_from[d];
-    }
-};
-// the cabs / requests of an LCM world that are in no pair (analyzePairs' supply2 / demand2)
-struct KeptPred {
-    const int32_t *pair_of, *sup_off, *d2_off;
-    int max_non_lcm;
-    __device__ bool operator()(int i, int b) const
-    {
-        return world_lcm(sup_off[b + 1] - sup_off[b], d2_off[b + 1] - d2_off[b], max_non_lcm) && pair_of[i] == NONE;
-    }
-};
-struct KeptSupEmit {
-    const int32_t *cab, *to;
-    int32_t *cab2, *to2;
-    __device__ void operator()(int o, int, int s, int) const
-    {
-        cab2[o] = cab[s];
-        to2[o] = to[s];
-    }
-};
-struct KeptDemEmit {
-    const int32_t *idx, *from, *partner, *plan, *cost;
-    int32_t *idx2, *from2, *partner2, *plan2, *cost2;
-    __device__ void operator()(int o, int, int d, int) const
-    {
-        idx2[o] = idx[d];
-        from2[o] = from[d];
-        partner2[o] = partner[d];
-        plan2[o] = plan[d];
-        cost2[o] = cost[d];
-    }
-};
-
-// the request pass of createTempDemand: drop what waited DROP_TIME (cab_assigned = -2), count the kept per workgroup
-__global__ __launch_bounds__(CB) void k_dem_count(DemPred pred, const int32_t *__restrict__ req_off, int32_t *__restrict__ cnt, Ctl *ctl)
-{
-    __shared__ int s_red[16];
-    const World &w = pred.w;
-    const int b = blockIdx.y, lo = req_off[b], n = req_off[b + 1] - lo, l = blockIdx.x * CB + threadIdx.x;
-    int drop = 0, keep = 0;
-    if (l < n) {
-        const int d = lo + l;
-        if (w.r_cab[d] == -1 && pred.t >= w.r_at[d] && pred.t - w.r_at[d] >= w.drop_time) {
-            w.r_cab[d] = -2;
-            drop = 1;
-        }
-        keep = pred(d, b) ? 1 : 0;
-    }
-    const int nd = block_sum(drop, s_red), nk = block_sum(keep, s_red);
-    if (threadIdx.x == 0) {
-        cnt[b * gridDim.x + blockIdx.x] = nk;
-        if (nd) atomicAdd((unsigned long long *)&ctl[b].dropped, (unsigned long long)nd);
-    }
-}
-
-template <class P>
-__global__ __launch_bounds__(CB) void k_count(const int32_t *__restrict__ off, P pred, int32_t *__restrict__ cnt)
-{
-    __shared__ int s_red[16];
-    const int b = blockIdx.y, lo = off[b], n = off[b + 1] - lo, l = blockIdx.x * CB + threadIdx.x;
-    const int nk = block_sum((l < n && pred(lo + l, b)) ? 1 : 0, s_red);
-    if (threadIdx.x == 0) cnt[b * gridDim.x + blockIdx.x] = nk;
-}
 
 // ONE workgroup: per-workgroup counts -> per-world totals -> offset arrays (exclusive scans over the worlds, B in slices of CB).
 //   off_a = the list counted in cnt_a; off_b (cnt_b non-null) = the list counted in cnt_b.
@@ -472,174 +198,7 @@ __global__ __launch_bounds__(CB) void k_scatter(const int32_t *__restrict__ off,
     if (f && pos < cap) emit(off_out[b] + pos, two ? off_out2[b] + pos : -1, lo + l, b);
 }
 
-__global__ __launch_bounds__(256) void k_pool_mark(int pool_h, int ragged, const int32_t *__restrict__ dem_off, const int32_t *__restrict__ pl_off,
-                                                   const int32_t *__restrict__ n_pools, const int32_t *__restrict__ pl_a,
-                                                   const int32_t *__restrict__ pl_b, int32_t *__restrict__ isb, int32_t *__restrict__ ainfo,
-                                                   int32_t *gerr)
-{
-    const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n_act = pl_off[b + 1] - pl_off[b];   // 0 for a world without supply: it has no pool
-    if (p >= n_pools[b] || p >= n_act / 2) return;
-    const int q = (ragged ? pl_off[b] >> 1 : b * pool_h) + p;
-    const int a = pl_a[q], c = pl_b[q];
-    if (a < 0 || a >= n_act || c < 0 || c >= n_act) {
-        atomicMax(gerr, 1);
-        return;
-    }
-    isb[dem_off[b] + c] = 1;
-    atomicMin(&ainfo[dem_off[b] + a], p);   // the first plan of an A customer (plans are disjoint anyway)
-}
-
-// by_cab / by_clnt of analyzePairs (Simulator.java:613-674) in every LCM world: the FIRST pair of a cab / of a request
-__global__ __launch_bounds__(256) void k_pair_map(SimbDec dec, int max_non_lcm, const int32_t *__restrict__ sup_off,
-                                                  const int32_t *__restrict__ d2_off, int32_t *__restrict__ pair_cab,
-                                                  int32_t *__restrict__ pair_dem, int32_t *gerr)
-{
-    const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n_s = sup_off[b + 1] - sup_off[b], n_d = d2_off[b + 1] - d2_off[b];
-    if (!world_lcm(n_s, n_d, max_non_lcm)) return;
-    int base, cnt;
-    dec_pairs(dec, b, &base, &cnt);
-    if (p >= cnt) return;
-    const int r = dec.rows[base + p], c = dec.cols[base + p];
-    if (r < 0 || r >= n_s || c < 0 || c >= n_d) {
-        atomicMax(gerr, 2);
-        return;
-    }
-    atomicMin(&pair_cab[sup_off[b] + r], p);
-    atomicMin(&pair_dem[d2_off[b] + c], p);
-}
-
-// analyzePairs: thread l < n_s of a world is the cab loop, the rest the request loop (td_sim.hip's k_apply_pairs per world)
-__global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, SimbDec dec, int max_non_lcm, const int32_t *__restrict__ cab_off,
-                                                    const int32_t *__restrict__ sup_off, const int32_t *__restrict__ d2_off,
-                                                    const int32_t *__restrict__ pair_cab, const int32_t *__restrict__ pair_dem,
-                                                    const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
-                                                    const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_partner,
-                                                    const int32_t *__restrict__ d_cost, Ctl *ctl, const int32_t *gerr)
-{
-    __shared__ int s_red[16];
-    if (block_err(gerr)) return;
-    const int b = blockIdx.y, s0 = sup_off[b], n_s = sup_off[b + 1] - s0, d0 = d2_off[b], n_d = d2_off[b + 1] - d0;
-    if (!world_lcm(n_s, n_d, max_non_lcm) || (int)blockIdx.x * CB >= n_s + n_d) return;
-    int base, cnt;
-    dec_pairs(dec, b, &base, &cnt);
-    const int l = blockIdx.x * CB + threadIdx.x;
-    int numb = 0, ptime = 0, second = 0;
-    if (l < n_s) {
-        const int p = pair_cab[s0 + l];
-        if (p != NONE) {
-            const int d = d0 + dec.cols[base + p];
-            dispatch(w, t, sup_cab[s0 + l], sup_to[s0 + l], d_idx[d], d_partner[d], d_cost[d], numb, ptime);
-        }
-    } else if (l < n_s + n_d) {
-        const int d = d0 + l - n_s, p = pair_dem[d];
-        if (p != NONE) {   // the request side is not guarded by the distance
-            const int cab = sup_cab[s0 + dec.rows[base + p]] - cab_off[b], idx = d_idx[d];
-            w.r_cab[idx] = cab;
-            w.r_pick[idx] = t;
-            if (d_partner[d] > -1) {
-                w.r_cab[d_partner[d]] = cab;   // assignPooled; pool info is NOT copied into the table on this path
-                second = 1;
-                numb = 1;
-            }
-        }
-    }
-    const int tn = block_sum(numb, s_red), tp = block_sum(ptime, s_red), ts = block_sum(second, s_red);
-    if (threadIdx.x == 0) {
-        if (tn) atomicAdd((unsigned long long *)&ctl[b].pickup_numb, (unsigned long long)tn);
-        if (tp) atomicAdd((unsigned long long *)&ctl[b].pickup_time, (unsigned long long)tp);
-        if (ts) atomicAdd((unsigned long long *)&ctl[b].second, (unsigned long long)ts);
-    }
-}
-
-// analyzeSolution (Simulator.java:375-421): one thread per cab of the solver's model of world b: the kept lists where the
-// LCM ran, else the whole model
-__global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, SimbDec dec, int max_non_lcm, const int32_t *__restrict__ cab_off,
-                                                       const int32_t *__restrict__ sup_off, const int32_t *__restrict__ d2_off,
-                                                       const int32_t *__restrict__ ks_off, const int32_t *__restrict__ kd_off,
-                                                       const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
-                                                       const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_from,
-                                                       const int32_t *__restrict__ d_partner, const int32_t *__restrict__ d_plan,
-                                                       const int32_t *__restrict__ d_cost, const int32_t *__restrict__ ks_cab,
-                                                       const int32_t *__restrict__ ks_to, const int32_t *__restrict__ kd_idx,
-                                                       const int32_t *__restrict__ kd_from, const int32_t *__restrict__ kd_partner,
-                                                       const int32_t *__restrict__ kd_plan, const int32_t *__restrict__ kd_cost, Ctl *ctl,
-                                                       const int32_t *gerr)
-{
-    __shared__ int s_red[16];
-    if (block_err(gerr)) return;
-    const int b = blockIdx.y;
-    const int n_s0 = sup_off[b + 1] - sup_off[b], n_d0 = d2_off[b + 1] - d2_off[b];
-    if (n_s0 == 0 || (int)blockIdx.x * CB >= n_s0) return;
-    const bool lcm = world_lcm(n_s0, n_d0, max_non_lcm);
-    int rb, nr;
-    bool solved;
-    dec_r2c(dec, b, lcm, w.big_cost, &rb, &nr, &solved);
-    if (lcm && !solved) return;
-    const int s0 = lcm ? ks_off[b] : sup_off[b], n_s = lcm ? ks_off[b + 1] - s0 : n_s0;
-    const int d0 = lcm ? kd_off[b] : d2_off[b], n_d = lcm ? kd_off[b + 1] - d0 : n_d0;
-    const int32_t *l_cab = lcm ? ks_cab : sup_cab, *l_to = lcm ? ks_to : sup_to, *l_idx = lcm ? kd_idx : d_idx, *l_from = lcm ? kd_from : d_from;
-    const int32_t *l_partner = lcm ? kd_partner : d_partner, *l_plan = lcm ? kd_plan : d_plan, *l_cost = lcm ? kd_cost : d_cost;
-    const int l = blockIdx.x * CB + threadIdx.x;
-    int count = 0, numb = 0, ptime = 0, second = 0;
-    if (l < n_s) {
-        const int s = s0 + l;
-        const int c = l < nr ? dec.r2c[rb + l] : -1;
-        if (c >= 0 && c < n_d) {
-            const int e = d0 + c;
-            const int dist = way(w, l_to[s], l_from[e]);
-            const int cell = dist < w.drop_time ? dist : w.big_cost;   // the thresholded model's cell
-            if (cell < w.big_cost) {
-                count = 1;
-                const int idx = l_idx[e], cab = l_cab[s], partner = l_partner[e];
-                w.r_cab[idx] = cab - cab_off[b];
-                w.r_pick[idx] = t;
-                if (partner > -1) {
-                    w.r_cab[partner] = cab - cab_off[b];
-                    second = 1;
-                    w.r_pid[idx] = w.r_id[partner];   // pool info reaches the table on the OPT path only (:391-396)
-                    w.r_plan[idx] = l_plan[e];
-                    w.r_pcost[idx] = l_cost[e];
-                    numb = 1;
-                }
-                dispatch(w, t, cab, l_to[s], idx, partner, l_cost[e], numb, ptime);
-            }
-        }
-    }
-    const int tc = block_sum(count, s_red), tn = block_sum(numb, s_red), tp = block_sum(ptime, s_red), ts = block_sum(second, s_red);
-    if (threadIdx.x == 0) {
-        if (tc) atomicAdd(&ctl[b].opt_count, tc);
-        if (tn) atomicAdd((unsigned long long *)&ctl[b].pickup_numb, (unsigned long long)tn);
-        if (tp) atomicAdd((unsigned long long *)&ctl[b].pickup_time, (unsigned long long)tp);
-        if (ts) atomicAdd((unsigned long long *)&ctl[b].second, (unsigned long long)ts);
-    }
-}
-
-// Simulator.c_clnt holds the request id; cabs [lo, lo + n)
-__global__ __launch_bounds__(256) void k_client_ids(World w, int lo, int n, int32_t *__restrict__ out)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    const int d = w.c_clnt[lo + c];
-    out[c] = d < 0 ? -1 : w.r_id[d];
-}
-
 inline int nchunks(int n) { return std::max(1, (n + CB - 1) / CB); }
-
-int put(int32_t *dst, const int32_t *src, size_t n)
-{
-    if (!n) return TD_OK;
-    TD_HIP(hipMemcpyAsync(dst, src, sizeof(int32_t) * n, is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx().stream));
-    return TD_OK;
-}
-
-int get(int32_t *dst, const int32_t *src, size_t n)
-{
-    if (!n || !dst) return TD_OK;
-    TD_HIP(hipMemcpyAsync(dst, src, sizeof(int32_t) * n, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx().stream));
-    return TD_OK;
-}
 
 // host copy of n values (host or device source)
 int host_copy(const int32_t *src, size_t n, std::vector<int32_t> &h)
@@ -687,17 +246,18 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     const size_t shm = sizeof(uint32_t) * (size_t)s->words;
     const int gc = nchunks(s->max_cabs), gr = nchunks(s->max_req);
     const dim3 grid_c(gc, B), grid_r(gr, B);
-    k_arrive<<<grid_c, CB, 0, c.stream>>>(w, s->d_cab_off, t, s->ctl);
-    k_flags<<<grid_c, CB, shm, c.stream>>>(s->d_cab_off, w.n_stands, w.c_to, w.c_clnt, s->bits, 0);
-    const dim3 grid_n(s->words, (B + NEAR_WPG - 1) / NEAR_WPG);
-    const size_t shm_n = sizeof(uint32_t) * ((size_t)NEAR_WPG * s->words + NEAR_WPG);
+    const SegOff cabs{s->d_cab_off}, reqs{s->d_req_off};
+    k_arrive<<<grid_c, CB, 0, c.stream>>>(w, cabs, t, s->ctl);
+    k_flags<<<grid_c, CB, shm, c.stream>>>(cabs, w.n_stands, w.c_to, w.c_clnt, s->bits, 0);
+    const dim3 grid_n = near_grid(B, s->words);
+    const size_t shm_n = near_lds(s->words);
     if (s->dist) k_near_b<<<grid_n, CB, shm_n, c.stream>>>(B, w.n_stands, s->words, s->nb_dem, s->bits, s->near, 0);
     const DemPred dp{w, t, s->words, s->bits, s->near};
-    k_dem_count<<<grid_r, CB, 0, c.stream>>>(dp, s->d_req_off, s->cnt_a, s->ctl);
-    k_flags<<<grid_r, CB, shm, c.stream>>>(s->d_req_off, w.n_stands, w.r_from, w.r_cab, s->bits, 1);
+    k_dem_count<<<grid_r, CB, 0, c.stream>>>(dp, reqs, s->cnt_a, s->ctl);
+    k_flags<<<grid_r, CB, shm, c.stream>>>(reqs, w.n_stands, w.r_from, w.r_cab, s->bits, 1);
     if (s->dist) k_near_b<<<grid_n, CB, shm_n, c.stream>>>(B, w.n_stands, s->words, s->nb_sup, s->bits, s->near, 1);
     const SupPred sp{w, s->words, s->bits, s->near};
-    k_count<SupPred><<<grid_c, CB, 0, c.stream>>>(s->d_cab_off, sp, s->cnt_b);
+    k_count<SegOff, SupPred><<<grid_c, CB, 0, c.stream>>>(cabs, sp, s->cnt_b);
     k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, gr, s->cnt_b, gc, 1, nullptr, s->dem_off, s->sup_off, s->pl_off);
     k_scatter<DemPred, DemEmit><<<grid_r, CB, 0, c.stream>>>(s->d_req_off, dp, DemEmit{w, s->dem_idx, s->dem_from, s->dem_to, s->pl_from, s->pl_to},
                                                            s->cnt_a, s->dem_off, s->pl_off);
@@ -742,17 +302,18 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     const size_t nd_tot = (size_t)hd[B];
     TD_HIP(hipMemsetAsync(s->isb, 0, sizeof(int32_t) * nd_tot, c.stream));
     TD_HIP(hipMemsetAsync(s->ainfo, 0x7f, sizeof(int32_t) * nd_tot, c.stream));
+    const SimbPlans pl{s->pool_h, s->pool_ragged, s->pl_off, s->n_pools};
+    const SegOff dem{s->dem_off};
     if (max_act >= 2)
-        k_pool_mark<<<dim3((max_act / 2 + 255) / 256, B), 256, 0, c.stream>>>(s->pool_h, s->pool_ragged, s->dem_off, s->pl_off, s->n_pools, s->pa, s->pb,
-                                                                             s->isb, s->ainfo, s->gerr);
+        k_pool_mark<<<dim3((max_act / 2 + 255) / 256, B), 256, 0, c.stream>>>(pl, dem, s->pa, s->pb, s->isb, s->ainfo, s->gerr);
     const dim3 grid_d(nchunks(max_dem), B);
     const PoolPred pp{s->isb};
-    k_count<PoolPred><<<grid_d, CB, 0, c.stream>>>(s->dem_off, pp, s->cnt_a);
+    k_count<SegOff, PoolPred><<<grid_d, CB, 0, c.stream>>>(dem, pp, s->cnt_a);
     k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, (int)grid_d.x, nullptr, 0, 0, s->sup_off, s->d2_off, nullptr, s->tk_off);
-    k_scatter<PoolPred, PoolEmit><<<grid_d, CB, 0, c.stream>>>(
+    k_scatter<PoolPred, PoolEmit<SimbPlans, SegOff>><<<grid_d, CB, 0, c.stream>>>(
         s->dem_off, pp,
-        PoolEmit{s->pool_h, s->pool_ragged, s->dem_off, s->pl_off, s->n_pools, s->dem_idx, s->dem_from, s->ainfo, s->pb, s->pp, s->pc, s->d2_idx,
-                 s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->tk_from},
+        PoolEmit<SimbPlans, SegOff>{pl, dem, s->dem_idx, s->dem_from, s->ainfo, s->pb, s->pp, s->pc, s->d2_idx, s->d2_from, s->d2_partner,
+                                    s->d2_plan, s->d2_cost, s->tk_from},
         s->cnt_a, s->d2_off, s->tk_off);
     TD_HIP(hipGetLastError());
     if ((rc = read_head(s))) return rc;
@@ -797,26 +358,27 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
         }
     }
     const int32_t *hs = h_of(s, s->sup_off), *h2 = h_of(s, s->d2_off);
+    const SegOff cabs{s->d_cab_off}, sup{s->sup_off}, d2{s->d2_off};
     if (any_lcm) {
         TD_HIP(hipMemsetAsync(s->pair_cab, 0x7f, sizeof(int32_t) * (size_t)hs[B], c.stream));
         TD_HIP(hipMemsetAsync(s->pair_dem, 0x7f, sizeof(int32_t) * (size_t)h2[B], c.stream));
         if (max_pairs > 0)
-            k_pair_map<<<dim3((max_pairs + 255) / 256, B), 256, 0, c.stream>>>(dec, mnl, s->sup_off, s->d2_off, s->pair_cab, s->pair_dem, s->gerr);
-        k_apply_pairs<<<dim3(nchunks(max_sd), B), CB, 0, c.stream>>>(w, t, dec, mnl, s->d_cab_off, s->sup_off, s->d2_off, s->pair_cab, s->pair_dem,
-                                                                   s->sup_cab, s->sup_to, s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, s->gerr);
+            k_pair_map<<<dim3((max_pairs + 255) / 256, B), 256, 0, c.stream>>>(dec, mnl, sup, d2, s->pair_cab, s->pair_dem, s->gerr);
+        k_apply_pairs<<<dim3(nchunks(max_sd), B), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, s->pair_cab, s->pair_dem, s->sup_cab, s->sup_to,
+                                                                   s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, s->gerr);
         const dim3 grid_s(nchunks(max_s), B), grid_d(nchunks(max_d), B);
-        const KeptPred ps{s->pair_cab, s->sup_off, s->d2_off, mnl}, pd{s->pair_dem, s->sup_off, s->d2_off, mnl};
-        k_count<KeptPred><<<grid_s, CB, 0, c.stream>>>(s->sup_off, ps, s->cnt_a);
-        k_count<KeptPred><<<grid_d, CB, 0, c.stream>>>(s->d2_off, pd, s->cnt_b);
+        const KeptPred<SegOff> ps{s->pair_cab, sup, d2, mnl}, pd{s->pair_dem, sup, d2, mnl};
+        k_count<SegOff, KeptPred<SegOff>><<<grid_s, CB, 0, c.stream>>>(sup, ps, s->cnt_a);
+        k_count<SegOff, KeptPred<SegOff>><<<grid_d, CB, 0, c.stream>>>(d2, pd, s->cnt_b);
         k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, (int)grid_s.x, s->cnt_b, (int)grid_d.x, 0, nullptr, s->ks_off, s->kd_off, nullptr);
-        k_scatter<KeptPred, KeptSupEmit><<<grid_s, CB, 0, c.stream>>>(s->sup_off, ps, KeptSupEmit{s->sup_cab, s->sup_to, s->ks_cab, s->ks_to}, s->cnt_a,
-                                                                    s->ks_off, nullptr);
-        k_scatter<KeptPred, KeptDemEmit><<<grid_d, CB, 0, c.stream>>>(
+        k_scatter<KeptPred<SegOff>, KeptSupEmit><<<grid_s, CB, 0, c.stream>>>(s->sup_off, ps, KeptSupEmit{s->sup_cab, s->sup_to, s->ks_cab, s->ks_to},
+                                                                            s->cnt_a, s->ks_off, nullptr);
+        k_scatter<KeptPred<SegOff>, KeptDemEmit><<<grid_d, CB, 0, c.stream>>>(
             s->d2_off, pd, KeptDemEmit{s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost},
             s->cnt_b, s->kd_off, nullptr);
     }
     if (any_sup)
-        k_apply_solution<<<dim3(nchunks(max_s), B), CB, 0, c.stream>>>(w, t, dec, mnl, s->d_cab_off, s->sup_off, s->d2_off, s->ks_off, s->kd_off, s->sup_cab,
+        k_apply_solution<<<dim3(nchunks(max_s), B), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, SegOff{s->ks_off}, SegOff{s->kd_off}, s->sup_cab,
                                                                      s->sup_to, s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->ks_cab,
                                                                      s->ks_to, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, s->gerr);
     TD_HIP(hipGetLastError());
@@ -899,20 +461,14 @@ static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_
     const int n_req = ho[B], nc_tot = cab_off[B];
     if (n_req && (!req_id || !req_from || !req_to || !req_at)) return fail(TD_EINVAL, "null request array");
     // the request files on the host once: ids unique within a world and not negative, stands inside the line, times not negative
-    std::vector<int32_t> h((size_t)4 * n_req);
-    const int32_t *src[4] = {req_id, req_from, req_to, req_at};
-    for (int q = 0; q < 4 && n_req; q++) TD_HIP(hipMemcpy(h.data() + (size_t)q * n_req, src[q], sizeof(int32_t) * (size_t)n_req, hipMemcpyDefault));
+    std::vector<int32_t> h;
+    if ((rc = load_requests(n_req, req_id, req_from, req_to, req_at, h))) return rc;
     for (int b = 0; b < B; b++) {
-        for (int i = ho[b]; i < ho[b + 1]; i++) {
-            const int32_t id = h[i], f = h[(size_t)n_req + i], to = h[(size_t)2 * n_req + i], at = h[(size_t)3 * n_req + i];
-            if (id < 0 || f < 0 || f >= n_stands || to < 0 || to >= n_stands || at < 0)
-                return fail(TD_EINVAL, "td_simb_create: world %d, request %d (id %d, from %d, to %d, at %d) is outside the world", b, i - ho[b], id, f,
-                            to, at);
-        }
-        std::vector<int32_t> ids(h.begin() + ho[b], h.begin() + ho[b + 1]);
-        std::sort(ids.begin(), ids.end());
-        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end())
-            return fail(TD_EINVAL, "td_simb_create: request ids must be unique within world %d", b);
+        const int i = bad_request(h, n_req, n_stands, ho[b], ho[b + 1]);
+        if (i >= 0)
+            return fail(TD_EINVAL, "td_simb_create: world %d, request %d (id %d, from %d, to %d, at %d) is outside the world", b, i - ho[b], h[i],
+                        h[(size_t)n_req + i], h[(size_t)2 * n_req + i], h[(size_t)3 * n_req + i]);
+        if (!ids_unique(h, ho[b], ho[b + 1])) return fail(TD_EINVAL, "td_simb_create: request ids must be unique within world %d", b);
     }
     td_simb *s = new td_simb();
     s->B = B;
@@ -1081,21 +637,10 @@ static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_
     for (const Up &u : ups)
         if (u.n && (e = hipMemcpyAsync(u.dst, u.src, sizeof(int32_t) * u.n, hipMemcpyHostToDevice, c.stream)) != hipSuccess)
             return bail(hip_fail(e, "hipMemcpyAsync(td_simb tables)"));
-    if (dist) {
-        // the handle's own copy of the table, then its bit matrices; k_nb_build reports an invalid table in the error word
-        if ((e = hipMemcpyAsync(s->dist, dist, sizeof(int32_t) * ns * ns, is_device_ptr(dist) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                c.stream)) != hipSuccess)
-            return bail(hip_fail(e, "hipMemcpyAsync(distance table)"));
-        const int cells = n_stands * s->words;
-        k_nb_build<<<(cells + 255) / 256, 256, 0, c.stream>>>(n_stands, s->words, drop_time, s->dist, s->nb_dem, s->nb_sup, s->gerr);
-        if ((e = hipGetLastError()) != hipSuccess) return bail(hip_fail(e, "td_simb_create_dist launch"));
-    }
+    if (dist && (rc = table_upload("td_simb_create_dist launch", dist, n_stands, s->words, drop_time, s->dist, s->nb_dem, s->nb_sup, s->gerr)))
+        return bail(rc);
     if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return bail(hip_fail(e, "hipStreamSynchronize"));   // `h` leaves scope
-    if (dist) {
-        if ((rc = read_head(s))) return bail(rc);
-        if (*h_of(s, s->gerr))
-            return bail(fail(TD_EINVAL, "td_simb_create_dist: the distance table needs a zero diagonal and every other entry in 1 .. %d", MAX_DIST));
-    }
+    if (dist && ((rc = read_head(s)) || (rc = table_verdict("td_simb_create_dist", *h_of(s, s->gerr))))) return bail(rc);
     *out = s;
     return TD_OK;
 }
@@ -1236,22 +781,9 @@ extern "C" int td_simb_state(td_simb *s, int world, int32_t *c_from, int32_t *c_
     TD_REQUIRE_INIT();
     if (!s) return fail(TD_EINVAL, "null handle");
     if (world < 0 || world >= s->B) return fail(TD_EINVAL, "td_simb_state: world %d outside 0 .. %d", world, s->B - 1);
-    Ctx &c = ctx();
-    const World &w = s->w;
     const int c0 = s->cab_off[world], ncab = s->cab_off[world + 1] - c0, r0 = s->req_off[world], nreq = s->req_off[world + 1] - r0;
-    int rc;
-    if (c_clnt) {
-        k_client_ids<<<(ncab + 255) / 256, 256, 0, c.stream>>>(w, c0, ncab, s->tmp);
-        TD_HIP(hipGetLastError());
-    }
-    int32_t *cd[5] = {c_from, c_to, c_clnt, c_onboard, c_start};
-    const int32_t *cs[5] = {w.c_from + c0, w.c_to + c0, s->tmp, w.c_onb + c0, w.c_start + c0};
-    int32_t *rd[5] = {d_cab, d_pick, d_pool_id, d_pool_plan, d_pool_cost};
-    const int32_t *rs[5] = {w.r_cab + r0, w.r_pick + r0, w.r_pid + r0, w.r_plan + r0, w.r_pcost + r0};
-    for (int q = 0; q < 5; q++)
-        if ((rc = get(cd[q], cs[q], (size_t)ncab)) || (rc = get(rd[q], rs[q], (size_t)nreq))) return rc;
-    TD_HIP(hipStreamSynchronize(c.stream));
-    return TD_OK;
+    int32_t *cd[5] = {c_from, c_to, c_clnt, c_onboard, c_start}, *rd[5] = {d_cab, d_pick, d_pool_id, d_pool_plan, d_pool_cost};
+    return state_out(s->w, c0, ncab, r0, nreq, s->tmp, cd, rd);
 }
 
 extern "C" int td_simb_metrics(td_simb *s, int64_t *out)
@@ -1260,18 +792,7 @@ extern "C" int td_simb_metrics(td_simb *s, int64_t *out)
     if (!s || !out) return fail(TD_EINVAL, "null argument");
     int rc = read_head(s);
     if (rc) return rc;
-    for (int b = 0; b < s->B; b++) {
-        const Ctl &h = h_ctl(s)[b];
-        int64_t *o = out + (size_t)TD_SIM_N_METRICS * b;
-        o[0] = h.dropped;
-        o[1] = h.pickup_time;
-        o[2] = h.pickup_numb;
-        o[3] = s->lcm_used[b];
-        o[4] = s->max_model[b];
-        o[5] = s->max_solver[b];
-        o[6] = s->max_pool_mem[b];
-        o[7] = s->max_pool[b];
-        o[8] = h.second;
-    }
+    for (int b = 0; b < s->B; b++)
+        fill_metrics(h_ctl(s)[b], s->lcm_used[b], s->max_model[b], s->max_solver[b], s->max_pool_mem[b], s->max_pool[b], out + (size_t)TD_SIM_N_METRICS * b);
     return TD_OK;
 }
