@@ -611,7 +611,15 @@ TD_API int td_profile_reset(void);
  * (many constant columns, see DESIGN.md "rectangular models"),
  * [8]=1 when the matrix was recognised as a line metric: sorted matching, proven by the certificate pass
  * (then [0..6] are 0 except [4]=4, [7]=1 when it was the transpose that was recognised (constant trailing columns),
- * [9] = number of constant rows of the unbalanced model; see DESIGN.md "line-metric instances") */
+ * [9] = number of constant rows of the unbalanced model; see DESIGN.md "line-metric instances").
+ * [11] = lcm_path, the path the last td_lcm / td_pool2 took, as a bit set (DESIGN.md section 3 has the thresholds):
+ *     1  level lists (otherwise the row-scan loop)        2  lists built with one workgroup per row (n <= 4096)
+ *     4  loop: narrow byte copy made (n >= 128)           8  loop: row keys held in LDS
+ *    16  lists: value range hinted by the caller (td_tick)
+ *    32  redone with the measured range after a wrong hint (the other bits are those of the second run)
+ *    64  pairs returned through the pinned block          128  called as td_pool2
+ *   Word [11] is set to 0 when td_lcm / td_pool2 is entered and filled in before it returns; it is defined only right
+ *   after such a call.  Other calls may clear it (td_assign zeroes all 16 words on its line-metric path). */
 TD_API int td_last_stats(int64_t *out, int n);
 
 #ifdef __cplusplus

@@ -258,6 +258,9 @@ __global__ __launch_bounds__(1024) void k_lcm_loop(int n, const int32_t *__restr
 constexpr int LV_MAX = 256;   // (pool-of-two costs are sums of three distances: up to ~150 levels on 50 stands)
 static int g_lcm_lists = getenv("TD_LCM_LISTS") ? atoi(getenv("TD_LCM_LISTS")) : 1;   // 0: always the row-scan loop
 
+// td_last_stats word 11 (lcm_path): which of the paths below answered the last td_lcm / td_pool2 (the header lists the bits)
+enum : int64_t { LP_LISTS = 1, LP_ROWS4 = 2, LP_NARROW = 4, LP_RB_LDS = 8, LP_HINTED = 16, LP_REDONE = 32, LP_PINNED = 64, LP_POOL2 = 128 };
+
 struct LcmsInfo {
     long long count;   // candidate cells
     int vmin, vmax;
@@ -716,6 +719,8 @@ static int lcm_impl(int n, const int32_t *cost, int32_t mask, int32_t threshold,
 {
     TD_REQUIRE_INIT();
     Ctx &c = ctx();
+    c.stats[11] = 0;
+    int64_t path = 0;
     if (n < 0 || max_pairs < 0) return fail(TD_EINVAL, "negative size");
     if (n_pairs) *n_pairs = 0;
     if (total) *total = 0;
@@ -777,6 +782,7 @@ static int lcm_impl(int n, const int32_t *cost, int32_t mask, int32_t threshold,
         }
         if (info.count > 0 && info.count <= (1ll << 28) && (int64_t)info.vmax - info.vmin < LV_MAX) {
             fast = true;
+            path |= LP_LISTS | (n <= 4096 ? LP_ROWS4 : 0) | (hinted ? LP_HINTED : 0);
             const int nlev = info.vmax - info.vmin + 1;
             const int nw32 = (n + 31) / 32;
             if ((rc = ensure(c.lcm_a, sizeof(int) * (size_t)nlev * n))) return rc;
@@ -825,6 +831,7 @@ static int lcm_impl(int n, const int32_t *cost, int32_t mask, int32_t threshold,
             k_lcm_narrow<<<std::min(n, c.n_cu * 8), 256, 0, c.stream>>>(n, pitch, d_cost, cand_limit, d_base, (uint8_t *)c.cc.p);
         int T = std::min(1024, std::max(64, ((n + 63) / 64) * 64));
         const int rb_in_lds = ((size_t)n * 8 + shm_mask) <= 96 * 1024;
+        path |= (narrow ? LP_NARROW : 0) | (rb_in_lds ? LP_RB_LDS : 0);
         const size_t shm = shm_mask + (rb_in_lds ? (size_t)n * 8 : 0);
         if (shm > 48 * 1024)
             (void)hipFuncSetAttribute((const void *)k_lcm_loop, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
@@ -842,9 +849,12 @@ static int lcm_impl(int n, const int32_t *cost, int32_t mask, int32_t threshold,
         TD_HIP(hipMemcpyAsync((char *)c.pinned + 8192, d_rows, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost, c.stream));
     TD_HIP(hipStreamSynchronize(c.stream));
     if (hinted && fast && ((const int *)c.pinned)[104 / 4] == bad_tag) {   // the hint was wrong: the lists are void
-        return lcm_impl(n, cost, mask, threshold, stop_value_on, stop_value, stop_size, sum_below, max_pairs, rows, cols, n_pairs, total,
-                        last_min, INT_MAX, INT_MIN);
+        rc = lcm_impl(n, cost, mask, threshold, stop_value_on, stop_value, stop_size, sum_below, max_pairs, rows, cols, n_pairs, total,
+                      last_min, INT_MAX, INT_MIN);
+        c.stats[11] |= LP_REDONE;
+        return rc;
     }
+    if (via_pinned) path |= LP_PINNED;
     LcmOut o = *(const LcmOut *)c.pinned;
     if (fast && o.last_min == INT_MAX) o.last_min = stop_value_on ? stop_value : mask;   // nothing left to look at
     if (o.n_pairs > 0 && via_pinned) {
@@ -861,6 +871,7 @@ static int lcm_impl(int n, const int32_t *cost, int32_t mask, int32_t threshold,
     if (n_pairs) *n_pairs = o.n_pairs;
     if (total) *total = o.total;
     if (last_min) *last_min = o.last_min;
+    c.stats[11] = path;
     return TD_OK;
 }
 
@@ -1247,6 +1258,8 @@ extern "C" int td_pool2(int n, const int32_t *from, const int32_t *to, const int
 {
     TD_REQUIRE_INIT();
     Ctx &c = ctx();
+    c.stats[11] = 0;
+    int64_t path = LP_POOL2;
     if (n_pairs) *n_pairs = 0;
     if (n < 0) return fail(TD_EINVAL, "n < 0");
     if (n < 2) return TD_OK;
@@ -1317,6 +1330,7 @@ extern "C" int td_pool2(int n, const int32_t *from, const int32_t *to, const int
         }
         if (info.count > 0 && info.count <= (1ll << 28) && (int64_t)info.vmax - info.vmin < LV_MAX) {
             fast = true;
+            path |= LP_LISTS;
             const int nlev = info.vmax - info.vmin + 1;
             const int nw32 = (n + 31) / 32;
             if ((rc = ensure(c.lcm_a, sizeof(int) * (size_t)nlev * n))) return rc;
@@ -1347,6 +1361,7 @@ extern "C" int td_pool2(int n, const int32_t *from, const int32_t *to, const int
         if (narrow) k_lcm_narrow<<<std::min(n, c.n_cu * 8), 256, 0, c.stream>>>(n, pitch, pc, cand_limit, d_base, (uint8_t *)c.cc.p);
         int T = std::min(1024, std::max(64, ((n + 63) / 64) * 64));
         const int rb_in_lds = ((size_t)n * 8 + shm_mask) <= 96 * 1024;
+        path |= (narrow ? LP_NARROW : 0) | (rb_in_lds ? LP_RB_LDS : 0);
         const size_t shm = shm_mask + (rb_in_lds ? (size_t)n * 8 : 0);
         if (shm > 48 * 1024)
             (void)hipFuncSetAttribute((const void *)k_lcm_loop, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
@@ -1371,6 +1386,7 @@ extern "C" int td_pool2(int n, const int32_t *from, const int32_t *to, const int
         TD_HIP(hipStreamSynchronize(c.stream));
     }
     if (n_pairs) *n_pairs = k;
+    c.stats[11] = path;
     return TD_OK;
 }
 

@@ -338,24 +338,13 @@ def test_lcm_randomized_differential(td):
 
 
 def _sorted_cell_greedy(c, threshold):
-    """Test-local restatement of the thresholded lowest-cost method for SPARSE candidates:
-    cells at or below the threshold in (value, row, col) order, taken when row and column are
-    free (what repeated np.argmin + masking does, greedy_opt.py:61-82). The oracle's O(n^2) scan
-    per pick is too slow at n = 20000; this one is checked against it at small n below."""
-    n = c.shape[0]
+    """The thresholded lowest-cost method for SPARSE candidates (greedy_opt.py:61-82): sparse_greedy of
+    tests/lcm_path_cases.py on the cells at or below the threshold.  The oracle's O(n^2) scan per pick is too slow at
+    n = 20000; this one is checked against it at small n below and in test_lcm_paths_cpu.py."""
+    from lcm_path_cases import sparse_greedy
     r, k = np.nonzero(c <= threshold)
-    v = c[r, k]
-    order = np.lexsort((k, r, v))
-    rt, ct = np.zeros(n, bool), np.zeros(n, bool)
-    rows, cols, tot = [], [], 0
-    for i in order:
-        a, b = r[i], k[i]
-        if not rt[a] and not ct[b]:
-            rt[a] = ct[b] = True
-            rows.append(a)
-            cols.append(b)
-            tot += int(v[i])
-    return tot, np.array(rows, np.int32), np.array(cols, np.int32)
+    tot, rows, cols, _ = sparse_greedy(c.shape[0], r, k, c[r, k], dict(mask=BIG, threshold=threshold, sum_below=BIG), fill=BIG)
+    return tot, rows, cols
 
 
 def test_lcm_large_hashed_tables(td):
