@@ -329,6 +329,52 @@ TD_API int td_sim_state(td_sim *s, int32_t *c_from, int32_t *c_to, int32_t *c_cl
                         int32_t *d_cab, int32_t *d_pick, int32_t *d_pool_id, int32_t *d_pool_plan, int32_t *d_pool_cost);
 TD_API int td_sim_metrics(td_sim *s, int64_t out[TD_SIM_N_METRICS]);
 
+/* ---- the event log of a world: Simulator.java's second file, simulog.txt (csrc/td_sim_world.h) ----------
+ * A record is 8 int32 words {t, world, kind, method, customer, cab, aux, 0}: world = 0 in td_sim; customer = a request ID;
+ * cab = the cab number (world-local in td_simb); method = 0 none, 1 LCM, 2 OPT; a word the kind does not use is -1 (method:
+ * 0).  Kinds and the Java line that writes them:
+ *    1 PICKED_UP       :233      customer, cab             7 POOL_PAIR       :746      customer = custA, aux = custB (ids)
+ *    2 CAB_FREE        :251      cab, aux = stand          8 ASSIGNED_PICKED :448-465  customer, cab, method, aux = the pooled
+ *    3 DROPPED         :339      customer                                               other customer's id or -1
+ *    4 TEMP_DEMAND     :331/352  aux = entries; every      9 HEADING         :486-487  customer, cab, method
+ *                                tick and world           10 ASSIGNED_LCM    :654      customer, cab
+ *    5 TEMP_DEMAND_ID  :347      customer, list order     11 POOLED_SECOND   :432-433  customer = the second passenger, cab,
+ *    6 POOL            :742/756  aux = plans kept; once                                 method
+ *                                where findPool ran (demand and supply both non-empty)
+ * Order: ticks as they ran; within a tick world 0's records, then world 1's ...; within a tick and world the order in which
+ * Simulator.java writes: 1 / 2 by cab; every 3 by request, 4, its 5s; 6, its 7s in plan order; analyzePairs' cab loop (8 / 9,
+ * LCM) in supply order; its request loop (10, then that request's 11, LCM) in demand order; analyzeSolution in supply order
+ * (a cab's 11 first, then its 8 / 9, OPT).  The device delivers this order; nothing is sorted.
+ *   td_sim_log     kinds: bit k set = kind k is recorded; capacity = records the log holds.  Allocates the log and its staging
+ *                  (td_workspace_bytes counts them until td_sim_destroy or td_sim_log(s, 0, 0), which switches logging off,
+ *                  frees them and discards what is buffered); a second call replaces the log.  Neither the log nor the handle
+ *                  grows afterwards.  TD_EINVAL: bits outside 1 .. 11, kinds != 0 with capacity outside 1 .. 2^31 - 1, a call
+ *                  while a tick with demand waits for its apply.  Logging is off until this call and then costs nothing: a
+ *                  tick launches the kernels it always launched, in instantiations without logging code.
+ *   td_sim_events  copies every buffered record, oldest first, to records (host or device memory), sets *n, sets *lost (may
+ *                  be NULL) to the records that did not fit since the last successful call, and empties the log.  More than
+ *                  max_records buffered: TD_EINVAL, *n = the number buffered, nothing is copied or removed.  Without logging
+ *                  *n = 0, *lost = 0.  A full log drops further records and counts them; what it keeps is a prefix of the
+ *                  full sequence.  After any td_sim_* call returns the log holds every record of the work done so far (begin,
+ *                  apply and step alike; a drain between td_simb_begin and td_simb_apply delivers begin's records of every
+ *                  world, the apply's follow world by world).  Logging never changes the world.
+ * td_simb_log / td_simb_events: the same for a batch; the log is one for the handle. */
+#define TD_EV_PICKED_UP 1
+#define TD_EV_CAB_FREE 2
+#define TD_EV_DROPPED 3
+#define TD_EV_TEMP_DEMAND 4
+#define TD_EV_TEMP_DEMAND_ID 5
+#define TD_EV_POOL 6
+#define TD_EV_POOL_PAIR 7
+#define TD_EV_ASSIGNED_PICKED 8
+#define TD_EV_HEADING 9
+#define TD_EV_ASSIGNED_LCM 10
+#define TD_EV_POOLED_SECOND 11
+#define TD_EV_ALL 0xffeu
+#define TD_EV_WORDS 8
+TD_API int td_sim_log(td_sim *s, uint32_t kinds, int64_t capacity);
+TD_API int td_sim_events(td_sim *s, int64_t max_records, int32_t *records, int64_t *n, int64_t *lost);
+
 /* ---- B simulator worlds behind ONE handle (a sweep over fleet sizes / request files of one city) -----------------------
  * td_simb is td_sim with a world dimension: B independent worlds in device memory, advanced one tick at a time by one call
  * for all of them; the number of launches and read-backs of a call does not depend on B (csrc/td_simb.hip).
@@ -399,6 +445,10 @@ TD_API int td_simb_state(td_simb *s, int world, int32_t *c_from, int32_t *c_to, 
                          int32_t *c_start, int32_t *d_cab, int32_t *d_pick, int32_t *d_pool_id, int32_t *d_pool_plan,
                          int32_t *d_pool_cost);
 TD_API int td_simb_metrics(td_simb *s, int64_t *out);
+/* the batch's event log: td_sim_log / td_sim_events above with a world word; ONE log for the handle, within a tick world 0's
+ * records first; the number of launches the log adds to a tick (three kernels, two fills) does not depend on B */
+TD_API int td_simb_log(td_simb *s, uint32_t kinds, int64_t capacity);
+TD_API int td_simb_events(td_simb *s, int64_t max_records, int32_t *records, int64_t *n, int64_t *lost);
 
 /* ---- f-3 pool of two (the step right before the path in every tick) -------------------
  * Replaces findPool: Simulator.java:681-758 (and pool.c:64-131): every ordered pair (A, B) of

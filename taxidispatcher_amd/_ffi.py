@@ -79,6 +79,8 @@ SIGNATURES = {
     "td_sim_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p]),
     "td_sim_state": (ctypes.c_int, [ctypes.c_void_p] + [c_i32p] * 10),
     "td_sim_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "td_sim_log": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int64]),
+    "td_sim_events": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_i32p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "td_simb_create": (ctypes.c_int, [ctypes.c_int, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, c_i32p, c_i32p, c_i32p,
                                       c_i32p, c_i32p, ctypes.POINTER(ctypes.c_void_p)]),
     "td_simb_create_dist": (ctypes.c_int, [ctypes.c_int, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, c_i32p, c_i32p,
@@ -90,6 +92,8 @@ SIGNATURES = {
     "td_simb_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p]),
     "td_simb_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [c_i32p] * 10),
     "td_simb_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "td_simb_log": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int64]),
+    "td_simb_events": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_i32p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "td_pool2": (ctypes.c_int, [ctypes.c_int, c_i32p, c_i32p, c_i32p, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p,
                                 ctypes.POINTER(ctypes.c_int32)]),
     "td_match_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),

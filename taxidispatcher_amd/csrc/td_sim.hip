@@ -40,6 +40,11 @@
 //   nb_dem[s] bit s'  <=>  dist[s'][s] < drop_time   (request at s, a cab heading to s': a COLUMN of the table)
 //   nb_sup[s] bit s'  <=>  dist[s][s'] < drop_time   (cab at s, a request starting at s': a ROW)
 // A line world (dist == nullptr) launches exactly what it launched before.
+//
+// The event log (td_sim_log / td_sim_events): off by default, and then every kernel above runs in its EvOff
+// instantiation and nothing else is queued.  With the log on, k_arrive, k_dem_count, k_apply_pairs and k_apply_solution write
+// their records into fixed staging slots, and the call that ends a tick queues ONE ordered flush (td_sim_world.h: k_ev_count,
+// k_ev_offsets, k_ev_scatter) that appends the tick's records to the log in Simulator.java's write order.
 #include <limits.h>
 
 #include "td_sim_world.h"
@@ -85,6 +90,8 @@ struct td_sim {
     int last_t = -1;
     bool begun = false;          // a tick with demand waits for td_sim_apply
     int n_dem = 0, n_sup = 0, n_dem2 = 0;
+    int n_pool = 0;              // this tick's plans (the event log reads them where td_pool2 left them)
+    EvLog ev;                    // td_sim_log
     // the host side of Simulator.m
     int64_t lcm_used = 0, max_model = 0, max_solver = 0, max_pool_mem = 0, max_pool = 0;
 };
@@ -188,6 +195,27 @@ int read_head(td_sim *s, Head *out)
     return TD_OK;
 }
 
+// the event log: this tick's records, sections `phase`, behind the log.  The host has every list size.
+int sim_ev_flush(td_sim *s, int phase)
+{
+    const World &w = s->w;
+    const EvLog &e = s->ev;
+    const Seg1 cabs{w.n_cabs, nullptr}, reqs{w.n_req, nullptr}, dem{s->n_dem, nullptr}, sup{s->n_sup, nullptr}, d2{s->n_dem2, nullptr};
+    const EvSrc<Seg1, Plans1> src{w, cabs, reqs, dem, sup, d2, Plans1{s->n_pool, s->n_dem}, s->max_non_lcm, s->last_t, phase, e.kinds,
+                                  e.st_arr, e.st_drop, e.st_pairs, e.st_sol, s->dem_idx, s->pl_a, s->pl_b};
+    const size_t vmax = (size_t)w.n_cabs + w.n_req + 2 + s->n_dem + s->n_pool + 2 * ((size_t)s->n_sup + s->n_dem2) + 2 * (size_t)s->n_sup;
+    return ev_flush(s->ev, src, 1, vmax);
+}
+
+// a tick is over (nothing to apply, or applied): what the log has not seen of it goes there
+int sim_ev_tick_done(td_sim *s)
+{
+    if (!s->ev.kinds) return TD_OK;
+    const int phase = s->ev.begin_flushed ? 2 : 3;
+    s->ev.begin_flushed = false;
+    return sim_ev_flush(s, phase);
+}
+
 int sim_begin(td_sim *s, int t, int32_t info[4])
 {
     Ctx &c = ctx();
@@ -200,12 +228,20 @@ int sim_begin(td_sim *s, int t, int32_t info[4])
     TD_HIP(hipMemsetAsync(s->bits, 0, sizeof(uint32_t) * 2 * (size_t)words, c.stream));
     const size_t shm = sizeof(uint32_t) * (size_t)words;
     const Seg1 cabs{w.n_cabs, nullptr}, reqs{w.n_req, nullptr};
-    k_arrive<<<nblocks(w.n_cabs), CB, 0, c.stream>>>(w, cabs, t, s->ctl);
+    const bool log = s->ev.kinds != 0;
+    s->n_pool = 0;
+    if (log)
+        k_arrive<<<nblocks(w.n_cabs), CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOn{s->ev.st_arr});
+    else
+        k_arrive<<<nblocks(w.n_cabs), CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOff{});
     k_flags<<<nblocks(w.n_cabs), CB, shm, c.stream>>>(cabs, w.n_stands, w.c_to, w.c_clnt, s->bits, 0);
     if (s->dist) k_near_b<<<near_grid(1, words), CB, near_lds(words), c.stream>>>(1, w.n_stands, words, s->nb_dem, s->bits, s->near, 0);
     if (w.n_req > 0) {
         const DemPred dp{w, t, words, s->bits, s->near};
-        k_dem_count<<<nblocks(w.n_req), CB, 0, c.stream>>>(dp, reqs, s->blockcnt, s->ctl);
+        if (log)
+            k_dem_count<<<nblocks(w.n_req), CB, 0, c.stream>>>(dp, reqs, s->blockcnt, s->ctl, EvOn{s->ev.st_drop});
+        else
+            k_dem_count<<<nblocks(w.n_req), CB, 0, c.stream>>>(dp, reqs, s->blockcnt, s->ctl, EvOff{});
         k_scatter<DemPred, DemEmit><<<nblocks(w.n_req), CB, 0, c.stream>>>(
             w.n_req, dp, DemEmit{w, s->dem_idx, s->dem_from, s->dem_to, nullptr, nullptr}, s->blockcnt, &s->head->n_dem);
         k_flags<<<nblocks(w.n_req), CB, shm, c.stream>>>(reqs, w.n_stands, w.r_from, w.r_cab, s->bits, 1);
@@ -220,7 +256,7 @@ int sim_begin(td_sim *s, int t, int32_t info[4])
     s->last_t = t;
     s->n_dem = h.n_dem;
     s->n_sup = s->n_dem2 = 0;
-    if (h.n_dem == 0) return TD_OK;   // Simulator.java:160: nothing to do in this tick
+    if (h.n_dem == 0) return sim_ev_tick_done(s);   // Simulator.java:160: nothing to do in this tick
     s->n_sup = h.n_sup;
     s->n_dem2 = h.n_dem;
     s->begun = true;
@@ -236,6 +272,7 @@ int sim_begin(td_sim *s, int t, int32_t info[4])
         s->max_pool_mem = std::max(s->max_pool_mem, (int64_t)n * (n - 1));
         if ((rc = td_pool2(n, s->dem_from, s->dem_to, s->dist, s->dist ? w.n_stands : 0, s->pl_a, s->pl_b, s->pl_plan, s->pl_cost, &k))) return rc;
         s->max_pool = std::max(s->max_pool, (int64_t)k);
+        s->n_pool = k;
     }
     TD_HIP(hipMemsetAsync(s->isb, 0, sizeof(int32_t) * (size_t)n, c.stream));
     TD_HIP(hipMemsetAsync(s->ainfo, 0x7f, sizeof(int32_t) * (size_t)n, c.stream));
@@ -264,8 +301,10 @@ int sim_apply(td_sim *s, int n_pairs, const int32_t *rows, const int32_t *cols, 
     *opt_count = 0;
     if (n_s == 0) {   // no supply: analyzeSolution walks an empty list, the line ends in "; OPT count=0"
         s->begun = false;
-        return TD_OK;
+        return sim_ev_tick_done(s);
     }
+    const bool log = s->ev.kinds != 0;
+    if (log && (rc = ev_clear_apply(s->ev, (size_t)n_s, (size_t)n_d))) return rc;
     const bool lcm = n > mnl;
     if (lcm && !solved) *opt_count = -1;
     const int nr = solved ? n_r2c : 0;
@@ -277,8 +316,14 @@ int sim_apply(td_sim *s, int n_pairs, const int32_t *rows, const int32_t *cols, 
         TD_HIP(hipMemsetAsync(s->pair_cab, 0x7f, sizeof(int32_t) * (size_t)n_s, c.stream));
         TD_HIP(hipMemsetAsync(s->pair_dem, 0x7f, sizeof(int32_t) * (size_t)n_d, c.stream));
         if (n_pairs > 0) k_pair_map<<<(n_pairs + 255) / 256, 256, 0, c.stream>>>(dec, mnl, sup, d2, s->pair_cab, s->pair_dem, gerr);
-        k_apply_pairs<<<nblocks(n_s + n_d), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, s->pair_cab, s->pair_dem, s->sup_cab,
-                                                             s->sup_to, s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, gerr);
+        auto pairs = [&](auto ev) {
+            k_apply_pairs<<<nblocks(n_s + n_d), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, s->pair_cab, s->pair_dem, s->sup_cab,
+                                                                 s->sup_to, s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, gerr, ev);
+        };
+        if (log)
+            pairs(EvOn{s->ev.st_pairs});
+        else
+            pairs(EvOff{});
         TD_HIP(hipGetLastError());
         if ((rc = compact(s, n_s, KeptPred<Seg1>{s->pair_cab, sup, d2, mnl}, KeptSupEmit{s->sup_cab, s->sup_to, s->ks_cab, s->ks_to},
                           &s->head->n_ks)))
@@ -293,9 +338,15 @@ int sim_apply(td_sim *s, int n_pairs, const int32_t *rows, const int32_t *cols, 
         if ((rc = put(s->in_r2c, r2c, (size_t)nr))) return rc;
         // the kernel takes the kept lists where the LCM ran (their sizes are on the device), else the whole model
         const Seg1 ks{0, &s->head->n_ks}, kd{0, &s->head->n_kd};
-        k_apply_solution<<<nblocks(n_s), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, ks, kd, s->sup_cab, s->sup_to, s->d2_idx, s->d2_from,
-                                                          s->d2_partner, s->d2_plan, s->d2_cost, s->ks_cab, s->ks_to, s->kd_idx, s->kd_from,
-                                                          s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, gerr);
+        auto solution = [&](auto ev) {
+            k_apply_solution<<<nblocks(n_s), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, ks, kd, s->sup_cab, s->sup_to, s->d2_idx, s->d2_from,
+                                                              s->d2_partner, s->d2_plan, s->d2_cost, s->ks_cab, s->ks_to, s->kd_idx, s->kd_from,
+                                                              s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, gerr, ev);
+        };
+        if (log)
+            solution(EvOn{s->ev.st_sol});
+        else
+            solution(EvOff{});
         TD_HIP(hipGetLastError());
     }
     Head h;
@@ -313,7 +364,7 @@ int sim_apply(td_sim *s, int n_pairs, const int32_t *rows, const int32_t *cols, 
         *opt_count = h.ctl.opt_count;
         s->max_solver = std::max(s->max_solver, (int64_t)(lcm ? std::max(h.n_ks, h.n_kd) : n));
     }
-    return TD_OK;
+    return sim_ev_tick_done(s);
 }
 
 // td_sim_create (dist == nullptr) and td_sim_create_dist
@@ -473,6 +524,7 @@ extern "C" int td_sim_destroy(td_sim *s)
     if (!s) return TD_OK;
     if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
     buf_free(s->mem);
+    ev_off(s->ev);
     if (s->pin) (void)hipHostFree(s->pin);
     delete s;
     return TD_OK;
@@ -564,4 +616,28 @@ extern "C" int td_sim_metrics(td_sim *s, int64_t out[TD_SIM_N_METRICS])
     if (rc) return rc;
     fill_metrics(h.ctl, s->lcm_used, s->max_model, s->max_solver, s->max_pool_mem, s->max_pool, out);
     return TD_OK;
+}
+
+extern "C" int td_sim_log(td_sim *s, uint32_t kinds, int64_t capacity)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (kinds & ~TD_EV_ALL) return fail(TD_EINVAL, "td_sim_log: kinds = 0x%x has bits outside 1 .. 11", kinds);
+    if (kinds && (capacity <= 0 || capacity > INT_MAX)) return fail(TD_EINVAL, "td_sim_log: capacity = %lld outside 1 .. 2^31 - 1", (long long)capacity);
+    if (s->begun) return fail(TD_EINVAL, "td_sim_log: tick %d still waits for td_sim_apply", s->last_t);
+    const size_t nc = (size_t)s->w.n_cabs, nr = (size_t)s->w.n_req;
+    return ev_setup(s->ev, kinds, capacity, 1, nc, nr, nc + nr + 2 + nr + nr / 2 + 2 * (nc + nr) + 2 * nc);
+}
+
+extern "C" int td_sim_events(td_sim *s, int64_t max_records, int32_t *records, int64_t *n, int64_t *lost)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !n) return fail(TD_EINVAL, "null argument");
+    if (max_records < 0) return fail(TD_EINVAL, "td_sim_events: negative max_records");
+    int rc;
+    if (s->ev.kinds && s->begun && !s->ev.begin_flushed) {   // a tick waits for its apply: what it has written so far
+        if ((rc = sim_ev_flush(s, 1))) return rc;
+        s->ev.begin_flushed = true;
+    }
+    return ev_drain(s->ev, "td_sim_events", max_records, records, n, lost);
 }

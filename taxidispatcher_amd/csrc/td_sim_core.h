@@ -8,6 +8,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "taxidispatcher_amd.h"
+
 namespace tdsim {
 
 constexpr int CB = 1024;                 // workgroup of every compaction pass: 16 waves, one element per thread
@@ -33,6 +35,24 @@ struct Ctl {
     int32_t opt_count, pad[6];
 };
 static_assert(sizeof(Ctl) == 64, "both handles lay a Ctl out as 16 ints");
+
+// ---- the event log (td_sim_log / td_simb_log).  Every record a rule can write has a fixed slot in a staging
+// array of its phase; a slot is four words {kind | method << 8, customer id, cab number, aux}, kind 0 = no record.  The rules
+// take an emitter: EvOff is empty and compiles to nothing (the instantiation every handle uses until *_log switches logging
+// on), EvOn writes the slot with one 16-byte vector store.
+constexpr int EV_LCM = 1, EV_OPT = 2;   // the record's method word (0: the kind has none)
+struct EvOff {
+    static constexpr bool on = false;
+    __device__ __forceinline__ void put(int, int, int, int, int, int) const {}
+};
+struct EvOn {
+    static constexpr bool on = true;
+    int4 *st;
+    __device__ __forceinline__ void put(int slot, int kind, int method, int customer, int cab, int aux) const
+    {
+        st[slot] = make_int4(kind | method << 8, customer, cab, aux);
+    }
+};
 
 // Simulator.java:469-474
 __host__ __device__ inline int cheat_a_bit(int frm, int cost, int n_stands)
@@ -92,14 +112,18 @@ static __global__ __launch_bounds__(256) void k_nb_build(int n_stands, int words
 }
 
 // Simulator.java:220-254 for ONE cab; returns 1 when a passenger was picked up.  c = the cab's row in the fleet table,
-// cab_no = the number the request table stores for it (the same thing in one world; world-local in a batch of worlds)
-__device__ inline int arrive_as(const World &w, int t, int c, int cab_no)
+// cab_no = the number the request table stores for it (the same thing in one world; world-local in a batch of worlds).
+// The cab's record (:233 picked up, :251 free, or none) goes to `slot` of ev: every cab writes its slot in every tick.
+template <class EV>
+__device__ inline int arrive_as(const World &w, int t, int c, int cab_no, const EV &ev, int slot)
 {
     const int f = w.c_from[c], to = w.c_to[c];
+    ev.put(slot, 0, 0, -1, -1, -1);
     if (f == to || way(w, f, to) != t - w.c_start[c]) return 0;
     if (w.c_onb[c] == 0) {
         const int d = w.c_clnt[c];
         if (d < 0) return 0;
+        if constexpr (EV::on) ev.put(slot, TD_EV_PICKED_UP, 0, w.r_id[d], cab_no, -1);
         w.r_cab[d] = cab_no;
         w.r_pick[d] = t;
         w.c_from[c] = w.r_from[d];
@@ -112,11 +136,15 @@ __device__ inline int arrive_as(const World &w, int t, int c, int cab_no)
     w.c_clnt[c] = -1;
     w.c_onb[c] = 0;
     w.c_start[c] = -1;
+    ev.put(slot, TD_EV_CAB_FREE, 0, -1, cab_no, to);
     return 0;
 }
 
-// Simulator.java:424-490 _dispatch for cab `cab` (standing at sup_to) and the customer (request idx, pool partner / cost)
-__device__ __forceinline__ void dispatch(const World &w, int t, int cab, int sup_to, int idx, int partner, int pcost, int &numb, int &ptime)
+// Simulator.java:424-490 _dispatch for cab `cab` (standing at sup_to) and the customer (request idx, pool partner / cost).
+// The record (:448-465 or :486-487, with `method`) goes to `slot` of ev; cab_no is the cab's number as the log prints it.
+template <class EV>
+__device__ __forceinline__ void dispatch(const World &w, int t, int cab, int sup_to, int idx, int partner, int pcost, int &numb, int &ptime,
+                                         const EV &ev, int slot, int method, int cab_no)
 {
     const int cf = w.r_from[idx];
     int dn = 0, dp = 0;   // added to the counters once, below: no store through either reference inside a branch
@@ -127,12 +155,14 @@ __device__ __forceinline__ void dispatch(const World &w, int t, int cab, int sup
         w.c_onb[cab] = 1;
         w.c_start[cab] = t;
         dn = 1;
+        if constexpr (EV::on) ev.put(slot, TD_EV_ASSIGNED_PICKED, method, w.r_id[idx], cab_no, partner == -1 ? -1 : w.r_id[partner]);
     } else if (way(w, sup_to, cf) < w.drop_time) {   // goToPickup
         w.c_to[cab] = cf;
         w.c_clnt[cab] = idx;
         w.c_onb[cab] = 0;
         w.c_start[cab] = t;
         dp = way(w, w.c_from[cab], cf);
+        if constexpr (EV::on) ev.put(slot, TD_EV_HEADING, method, w.r_id[idx], cab_no, -1);
     }
     numb += dn;
     ptime += dp;

@@ -114,14 +114,15 @@ struct SegOff {
     }
 };
 
-template <class S>
-__global__ __launch_bounds__(CB) void k_arrive(World w, S cabs, int t, Ctl *ctl)
+// ev: the event log's emitter (td_sim_core.h): EvOff, or EvOn on the arrival stage, slot = the cab's row
+template <class S, class EV>
+__global__ __launch_bounds__(CB) void k_arrive(World w, S cabs, int t, Ctl *ctl, EV ev)
 {
     __shared__ int s_red[16];
     const int b = blockIdx.y, l = blockIdx.x * CB + threadIdx.x;
     int lo, n;
     cabs(b, &lo, &n);
-    const int got = l < n ? arrive_as(w, t, lo + l, l) : 0;
+    const int got = l < n ? arrive_as(w, t, lo + l, l, ev, lo + l) : 0;
     const int tot = block_sum(got, s_red);
     if (threadIdx.x == 0) {
         if (blockIdx.x == 0) ctl[b].opt_count = 0;   // this tick's OPT count starts from zero
@@ -306,9 +307,10 @@ struct KeptDemEmit {
     }
 };
 
-// the request pass of createTempDemand: drop what waited DROP_TIME (cab_assigned = -2), count the kept per workgroup
-template <class S>
-__global__ __launch_bounds__(CB) void k_dem_count(DemPred pred, S reqs, int32_t *__restrict__ cnt, Ctl *ctl)
+// the request pass of createTempDemand: drop what waited DROP_TIME (cab_assigned = -2), count the kept per workgroup.
+// ev: EvOff, or EvOn on the drop stage, slot = the request's row (every request writes its slot: :339 or none)
+template <class S, class EV>
+__global__ __launch_bounds__(CB) void k_dem_count(DemPred pred, S reqs, int32_t *__restrict__ cnt, Ctl *ctl, EV ev)
 {
     __shared__ int s_red[16];
     const World &w = pred.w;
@@ -322,6 +324,7 @@ __global__ __launch_bounds__(CB) void k_dem_count(DemPred pred, S reqs, int32_t 
             w.r_cab[d] = -2;
             drop = 1;
         }
+        if constexpr (EV::on) ev.put(d, drop ? TD_EV_DROPPED : 0, 0, drop ? w.r_id[d] : -1, -1, -1);
         keep = pred(d, b) ? 1 : 0;
     }
     const int nd = block_sum(drop, s_red), nk = block_sum(keep, s_red);
@@ -388,12 +391,14 @@ __global__ __launch_bounds__(256) void k_pair_map(D dec, int max_non_lcm, S sup,
 // analyzePairs: thread l < n_s of a world is the cab loop, the rest the request loop.  A cab and a request occur in at most
 // one pair, so the two loops write disjoint state (fleet / request table) and share only the counters.  The cab number a
 // request stores is world-local: cab minus where the world's fleet begins.
-template <class D, class S>
+// ev: EvOff, or EvOn on the pairs stage (cleared by the host before the launch): thread l of world b owns slots
+// 2 (s0 + d0 + l) and + 1, so the cab loop's records precede the request loop's and :654 precedes the same request's :432.
+template <class D, class S, class EV>
 __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, int max_non_lcm, S cabs, S sup, S d2,
                                                     const int32_t *__restrict__ pair_cab, const int32_t *__restrict__ pair_dem,
                                                     const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
                                                     const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_partner,
-                                                    const int32_t *__restrict__ d_cost, Ctl *ctl, const int32_t *gerr)
+                                                    const int32_t *__restrict__ d_cost, Ctl *ctl, const int32_t *gerr, EV ev)
 {
     __shared__ int s_red[16];
     if (block_err(gerr)) return;
@@ -406,12 +411,13 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, int m
     int base, cnt;
     dec.pairs(b, &base, &cnt);
     const int l = blockIdx.x * CB + threadIdx.x;
+    const int slot = 2 * (s0 + d0 + l);
     int numb = 0, ptime = 0, second = 0;
     if (l < n_s) {
         const int p = pair_cab[s0 + l];
         if (p != NONE) {
             const int d = d0 + dec.cols[base + p];
-            dispatch(w, t, sup_cab[s0 + l], sup_to[s0 + l], d_idx[d], d_partner[d], d_cost[d], numb, ptime);
+            dispatch(w, t, sup_cab[s0 + l], sup_to[s0 + l], d_idx[d], d_partner[d], d_cost[d], numb, ptime, ev, slot, EV_LCM, sup_cab[s0 + l] - c0);
         }
     } else if (l < n_s + n_d) {
         const int d = d0 + l - n_s, p = pair_dem[d];
@@ -419,10 +425,12 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, int m
             const int cab = sup_cab[s0 + dec.rows[base + p]] - c0, idx = d_idx[d];
             w.r_cab[idx] = cab;
             w.r_pick[idx] = t;
+            if constexpr (EV::on) ev.put(slot, TD_EV_ASSIGNED_LCM, 0, w.r_id[idx], cab, -1);
             if (d_partner[d] > -1) {
                 w.r_cab[d_partner[d]] = cab;   // assignPooled; pool info is NOT copied into the table on this path
                 second = 1;
                 numb = 1;
+                if constexpr (EV::on) ev.put(slot + 1, TD_EV_POOLED_SECOND, EV_LCM, w.r_id[d_partner[d]], cab, -1);
             }
         }
     }
@@ -437,7 +445,9 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, int m
 // analyzeSolution (Simulator.java:375-421): one thread per cab of the solver's model of world b: the kept lists where the
 // LCM ran, else the whole model.  A supply entry's from == to holds by construction (createTempSupply admits only standing
 // cabs and the lists are copies), so that test is not repeated.
-template <class D, class S>
+// ev: EvOff, or EvOn on the solution stage (cleared by the host before the launch): cab l of world b's model owns slots
+// 2 (s0 + l) and + 1 with s0 = where the world's SUPPLY list begins (a kept list is no longer): :432 first, then :448 / :486.
+template <class D, class S, class EV>
 __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, int max_non_lcm, S cabs, S sup, S d2, S ks, S kd,
                                                        const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
                                                        const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_from,
@@ -446,7 +456,7 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, in
                                                        const int32_t *__restrict__ ks_to, const int32_t *__restrict__ kd_idx,
                                                        const int32_t *__restrict__ kd_from, const int32_t *__restrict__ kd_partner,
                                                        const int32_t *__restrict__ kd_plan, const int32_t *__restrict__ kd_cost, Ctl *ctl,
-                                                       const int32_t *gerr)
+                                                       const int32_t *gerr, EV ev)
 {
     __shared__ int s_red[16];
     if (block_err(gerr)) return;
@@ -461,6 +471,7 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, in
     bool solved;
     dec.r2c_of(b, lcm, w.big_cost, &rb, &nr, &solved);
     if (lcm && !solved) return;
+    const int slot0 = 2 * s0;
     if (lcm) {   // the kept lists: their sizes are on the device in both handles
         ks(b, &s0, &n_s);
         kd(b, &d0, &n_d);
@@ -488,8 +499,9 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, in
                     w.r_plan[idx] = l_plan[e];
                     w.r_pcost[idx] = l_cost[e];
                     numb = 1;
+                    if constexpr (EV::on) ev.put(slot0 + 2 * l, TD_EV_POOLED_SECOND, EV_OPT, w.r_id[partner], cab - c0, -1);
                 }
-                dispatch(w, t, cab, l_to[s], idx, partner, l_cost[e], numb, ptime);
+                dispatch(w, t, cab, l_to[s], idx, partner, l_cost[e], numb, ptime, ev, slot0 + 2 * l + 1, EV_OPT, cab - c0);
             }
         }
     }
@@ -500,6 +512,126 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, in
         if (tp) atomicAdd((unsigned long long *)&ctl[b].pickup_time, (unsigned long long)tp);
         if (ts) atomicAdd((unsigned long long *)&ctl[b].second, (unsigned long long)ts);
     }
+}
+
+// ---- the event log: one tick's records of world b as ONE virtual slot sequence, in the order Simulator.java writes them:
+//   A  n_cabs   the arrival stage (k_arrive)          E  0 / 1      the pool header, where findPool ran
+//   B  n_req    the drop stage (k_dem_count)          F  plans      the plan list of findPool, as the pool call left it
+//   C  1        the tempDemand header                 G  2 (ns+nd)  the pairs stage (k_apply_pairs), LCM worlds
+//   D  n_dem    the demand list before pooling        H  2 ns       the solution stage (k_apply_solution)
+// C .. F are not staged: they are read from the lists where they lie.  phase bit 0 = A .. F (td_*_begin's), bit 1 = G, H.
+template <class S, class PL>
+struct EvSrc {
+    World w;
+    S cabs, reqs, dem, sup, d2;
+    PL pl;
+    int max_non_lcm, t, phase;
+    uint32_t kinds;
+    const int4 *st_arr, *st_drop, *st_pairs, *st_sol;
+    const int32_t *dem_idx, *pl_a, *pl_b;
+    // slot v of world b -> its kind (0: no record, a masked kind, or v behind the sequence); *o = {kind | method << 8, customer, cab, aux}
+    __device__ int read(int b, int v, int4 *o) const
+    {
+        int c0, nc, r0, nr, e0, ne, s0, ns, d0, nd;
+        cabs(b, &c0, &nc);
+        reqs(b, &r0, &nr);
+        dem(b, &e0, &ne);
+        sup(b, &s0, &ns);
+        d2(b, &d0, &nd);
+        const bool p1 = phase & 1, p2 = phase & 2, pooled = ne > 0 && ns > 0;
+        int np = 0;   // plans: never more than the pooled customers allow, whatever the count word says
+        if (pooled) np = min(max(pl.count(b), 0), pl.n_act(b) / 2);
+        const int nA = p1 ? nc : 0, nB = p1 ? nr : 0, nC = p1 ? 1 : 0, nD = p1 ? ne : 0, nE = p1 && pooled ? 1 : 0, nF = p1 ? np : 0;
+        const int nG = p2 && ne > 0 && world_lcm(ns, nd, max_non_lcm) ? 2 * (ns + nd) : 0, nH = p2 && pooled ? 2 * ns : 0;
+        int4 r = make_int4(0, -1, -1, -1);
+        int u = v;
+        if (u < nA) {
+            r = st_arr[c0 + u];
+        } else if ((u -= nA) < nB) {
+            r = st_drop[r0 + u];
+        } else if ((u -= nB) < nC) {
+            r.x = TD_EV_TEMP_DEMAND;
+            r.w = ne;
+        } else if ((u -= nC) < nD) {
+            r.x = TD_EV_TEMP_DEMAND_ID;
+            r.y = w.r_id[dem_idx[e0 + u]];
+        } else if ((u -= nD) < nE) {
+            r.x = TD_EV_POOL;
+            r.w = np;
+        } else if ((u -= nE) < nF) {
+            const int q = pl.base(b) + u, a = pl_a[q], c = pl_b[q], n_act = pl.n_act(b);
+            r.x = TD_EV_POOL_PAIR;
+            r.y = a >= 0 && a < n_act ? w.r_id[dem_idx[e0 + a]] : -1;   // k_pool_mark raised the error word for such a plan
+            r.w = c >= 0 && c < n_act ? w.r_id[dem_idx[e0 + c]] : -1;
+        } else if ((u -= nF) < nG) {
+            r = st_pairs[2 * (s0 + d0) + u];
+        } else if ((u -= nG) < nH) {
+            r = st_sol[2 * s0 + u];
+        }
+        *o = r;
+        const int kind = r.x & 255;
+        return (kinds >> kind) & 1u ? kind : 0;   // bit 0 is never set
+    }
+};
+
+// the log's device words: records held, records that did not fit since the last drain, where this flush appends
+struct EvCtl {
+    long long n, lost, base, pad;
+};
+
+template <class SRC>
+__global__ __launch_bounds__(CB) void k_ev_count(SRC src, int32_t *__restrict__ cnt)
+{
+    __shared__ int s_red[16];
+    int4 r;
+    const int nk = block_sum(src.read(blockIdx.y, blockIdx.x * CB + threadIdx.x, &r) ? 1 : 0, s_red);
+    if (threadIdx.x == 0) cnt[blockIdx.y * gridDim.x + blockIdx.x] = nk;
+}
+
+// ONE workgroup: per-workgroup counts -> where each world's records begin within this flush (B in slices of CB), then the
+// log's words: the flush appends at lg->base, as much of it as fits is counted in, the rest is counted as lost
+__global__ __launch_bounds__(CB) void k_ev_offsets(int B, const int32_t *__restrict__ cnt, int nc, int32_t *__restrict__ woff, EvCtl *lg,
+                                                   long long cap)
+{
+    __shared__ int s_w[16];
+    int run = 0;
+    for (int b0 = 0; b0 < B; b0 += CB) {
+        const int b = b0 + threadIdx.x;
+        int na = 0;
+        if (b < B)
+            for (int j = 0; j < nc; j++) na += cnt[b * nc + j];
+        int ta;
+        const int ea = block_excl_scan(na, s_w, &ta);
+        if (b < B) woff[b] = run + ea;
+        run += ta;
+    }
+    if (threadIdx.x == 0) {
+        const long long base = lg->n, room = cap - base, kept = run < room ? run : room;
+        lg->base = base;
+        lg->n = base + kept;
+        lg->lost += run - kept;
+    }
+}
+
+// log[base + the world's offset + the counts of the world's earlier chunks + rank] = the record; nothing at or behind cap
+template <class SRC>
+__global__ __launch_bounds__(CB) void k_ev_scatter(SRC src, const int32_t *__restrict__ cnt, const int32_t *__restrict__ woff,
+                                                   const EvCtl *__restrict__ lg, long long cap, int4 *__restrict__ log)
+{
+    __shared__ int s_red[16];
+    const int b = blockIdx.y;
+    int part = 0;
+    for (int j = threadIdx.x; j < (int)blockIdx.x; j += CB) part += cnt[b * gridDim.x + j];
+    const int before = block_sum(part, s_red);
+    int4 r;
+    const int kind = src.read(b, blockIdx.x * CB + threadIdx.x, &r);
+    int tot;
+    const int rank = block_rank(kind != 0, s_red, &tot);
+    if (!kind) return;
+    const long long pos = lg->base + woff[b] + before + rank;
+    if (pos < 0 || pos >= cap) return;
+    log[2 * pos] = make_int4(src.t, b, kind, (r.x >> 8) & 255);
+    log[2 * pos + 1] = make_int4(r.y, r.z, r.w, 0);
 }
 
 // Simulator.c_clnt holds the request id; cabs [lo, lo + n)
@@ -571,6 +703,99 @@ inline int table_upload(const char *launch, const int32_t *dist, int n_stands, i
 inline int table_verdict(const char *who, int err)
 {
     return err ? td::fail(TD_EINVAL, "%s: the distance table needs a zero diagonal and every other entry in 1 .. %d", who, MAX_DIST) : TD_OK;
+}
+
+// ---- the event log's host side, one per handle.  Everything *_log allocates is in `mem`.
+struct EvLog {
+    uint32_t kinds = 0;          // 0: logging is off
+    long long cap = 0;           // records the log holds
+    td::Buf mem;
+    EvCtl *ctl = nullptr;
+    int4 *log = nullptr, *st_arr = nullptr, *st_drop = nullptr, *st_pairs = nullptr, *st_sol = nullptr;
+    int32_t *cnt = nullptr, *woff = nullptr;
+    int chunks = 0;              // workgroups per world the count array has room for
+    bool begin_flushed = false;  // the begun tick's sections A .. F are in the log already (a drain before its apply)
+};
+
+inline int ev_off(EvLog &ev)
+{
+    if (ev.mem.p && td::ctx().inited) (void)hipStreamSynchronize(td::ctx().stream);
+    td::buf_free(ev.mem);
+    ev = EvLog();
+    return TD_OK;
+}
+
+// td_sim_log / td_simb_log after their argument checks: B worlds, nc cabs and nr requests in all, at most vmax slots per world
+inline int ev_setup(EvLog &ev, uint32_t kinds, int64_t capacity, int B, size_t nc, size_t nr, size_t vmax)
+{
+    ev_off(ev);
+    if (!kinds) return TD_OK;
+    const size_t chunks = (vmax + CB - 1) / CB, slots = nc + nr + 2 * (nc + nr) + 2 * nc;
+    const size_t ints = 8 + 8 * (size_t)capacity + 4 * slots + (size_t)B * chunks + (size_t)B + 16;
+    int rc = td::ensure(ev.mem, sizeof(int32_t) * ints);
+    if (rc) return rc;
+    int32_t *p = (int32_t *)ev.mem.p;
+    ev.ctl = (EvCtl *)p;
+    ev.log = (int4 *)(p + 8);
+    ev.st_arr = ev.log + 2 * (size_t)capacity;
+    ev.st_drop = ev.st_arr + nc;
+    ev.st_pairs = ev.st_drop + nr;
+    ev.st_sol = ev.st_pairs + 2 * (nc + nr);
+    ev.cnt = (int32_t *)(ev.st_sol + 2 * nc);
+    ev.woff = ev.cnt + (size_t)B * chunks;
+    ev.chunks = (int)chunks;
+    ev.cap = capacity;
+    hipError_t e = hipMemsetAsync(ev.ctl, 0, sizeof(EvCtl), td::ctx().stream);
+    if (e != hipSuccess) {
+        ev_off(ev);
+        return td::hip_fail(e, "hipMemsetAsync(event log)");
+    }
+    ev.kinds = kinds;
+    return TD_OK;
+}
+
+// the pairs and solution stages start a td_*_apply empty, as far as this tick's lists reach (n_sup, n_d2: the totals)
+inline int ev_clear_apply(EvLog &ev, size_t n_sup, size_t n_d2)
+{
+    const hipStream_t st = td::ctx().stream;
+    if (n_sup + n_d2) TD_HIP(hipMemsetAsync(ev.st_pairs, 0, sizeof(int4) * 2 * (n_sup + n_d2), st));
+    if (n_sup) TD_HIP(hipMemsetAsync(ev.st_sol, 0, sizeof(int4) * 2 * n_sup, st));
+    return TD_OK;
+}
+
+// appends the records src yields, in order, to the log: count, offsets, scatter; vmax = the longest world's slot sequence
+template <class SRC>
+int ev_flush(EvLog &ev, const SRC &src, int B, size_t vmax)
+{
+    const hipStream_t st = td::ctx().stream;
+    const int chunks = (int)std::min<size_t>(std::max<size_t>((vmax + CB - 1) / CB, 1), (size_t)ev.chunks);
+    const dim3 grid(chunks, B);
+    k_ev_count<<<grid, CB, 0, st>>>(src, ev.cnt);
+    k_ev_offsets<<<1, CB, 0, st>>>(B, ev.cnt, chunks, ev.woff, ev.ctl, ev.cap);
+    k_ev_scatter<<<grid, CB, 0, st>>>(src, ev.cnt, ev.woff, ev.ctl, ev.cap, ev.log);
+    TD_HIP(hipGetLastError());
+    return TD_OK;
+}
+
+// td_sim_events / td_simb_events once every record of the work done so far is queued for the log
+inline int ev_drain(EvLog &ev, const char *who, int64_t max_records, int32_t *records, int64_t *n, int64_t *lost)
+{
+    const hipStream_t st = td::ctx().stream;
+    *n = 0;
+    if (lost) *lost = 0;
+    if (!ev.kinds) return TD_OK;
+    long long h[2];
+    TD_HIP(hipMemcpyAsync(h, ev.ctl, sizeof(h), hipMemcpyDeviceToHost, st));
+    TD_HIP(hipStreamSynchronize(st));
+    *n = h[0];
+    if (h[0] > max_records) return td::fail(TD_EINVAL, "%s: %lld records are buffered, max_records = %lld", who, h[0], (long long)max_records);
+    if (h[0] && !records) return td::fail(TD_EINVAL, "%s: null records", who);
+    int rc = get(records, (const int32_t *)ev.log, (size_t)h[0] * 8);
+    if (rc) return rc;
+    TD_HIP(hipMemsetAsync(ev.ctl, 0, sizeof(EvCtl), st));
+    TD_HIP(hipStreamSynchronize(st));
+    if (lost) *lost = h[1];
+    return TD_OK;
 }
 
 // td_sim_state / td_simb_state: cabs [c0, c0 + ncab) and requests [r0, r0 + nreq) of the tables, five arrays each (a null

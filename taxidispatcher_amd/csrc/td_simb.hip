@@ -34,6 +34,9 @@
 // per tick whatever B is.  The predicates then read one bit, arrival / dispatch / analyzeSolution read one table cell
 // (way()), and the batched calls get the handle's table.  The direction rule is td_sim.hip's: the row of the table is
 // always the stand the cab is at or heads to.  A line batch (dist == nullptr) launches exactly what it launched before.
+//
+// The event log (td_simb_log / td_simb_events) is td_sim's with the world dimension of the grid: one flush per
+// tick over all worlds, three launches whatever B is, world 0's records first.  Off by default: the EvOff instantiations.
 #include <limits.h>
 
 #include "td_sim_world.h"
@@ -130,6 +133,7 @@ struct td_simb {
     int pool_ragged = 0;         // this tick's plans lie at pl_off[b] / 2 (the per-world td_pool2 path) instead of b * pool_h
     int pool_h = 1;
     std::vector<int32_t> n_dem, n_sup, n_d2;
+    EvLog ev;                    // td_simb_log
     std::vector<int64_t> lcm_used, max_model, max_solver, max_pool_mem, max_pool;
 };
 
@@ -233,6 +237,30 @@ int clear_err(td_simb *s)
     return TD_OK;
 }
 
+// the event log: this tick's records, sections `phase`, behind the log: world after world, whatever B is
+int simb_ev_flush(td_simb *s, int phase)
+{
+    const EvLog &e = s->ev;
+    const EvSrc<SegOff, SimbPlans> src{s->w, SegOff{s->d_cab_off}, SegOff{s->d_req_off}, SegOff{s->dem_off}, SegOff{s->sup_off}, SegOff{s->d2_off},
+                                       SimbPlans{s->pool_h, s->pool_ragged, s->pl_off, s->n_pools}, s->max_non_lcm, s->last_t, phase, e.kinds,
+                                       e.st_arr, e.st_drop, e.st_pairs, e.st_sol, s->dem_idx, s->pa, s->pb};
+    size_t vmax = 0;
+    for (int b = 0; b < s->B; b++) {
+        const size_t nc = (size_t)(s->cab_off[b + 1] - s->cab_off[b]), nr = (size_t)(s->req_off[b + 1] - s->req_off[b]), ns = (size_t)s->n_sup[b];
+        vmax = std::max(vmax, nc + nr + 2 + s->n_dem[b] + s->n_dem[b] / 2 + 2 * (ns + s->n_d2[b]) + 2 * ns);
+    }
+    return ev_flush(s->ev, src, s->B, vmax);
+}
+
+// a tick is over (no world has anything to apply, or applied): what the log has not seen of it goes there
+int simb_ev_tick_done(td_simb *s)
+{
+    if (!s->ev.kinds) return TD_OK;
+    const int phase = s->ev.begin_flushed ? 2 : 3;
+    s->ev.begin_flushed = false;
+    return simb_ev_flush(s, phase);
+}
+
 int simb_begin(td_simb *s, int t, int32_t *info)
 {
     Ctx &c = ctx();
@@ -247,13 +275,20 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     const int gc = nchunks(s->max_cabs), gr = nchunks(s->max_req);
     const dim3 grid_c(gc, B), grid_r(gr, B);
     const SegOff cabs{s->d_cab_off}, reqs{s->d_req_off};
-    k_arrive<<<grid_c, CB, 0, c.stream>>>(w, cabs, t, s->ctl);
+    const bool log = s->ev.kinds != 0;
+    if (log)
+        k_arrive<<<grid_c, CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOn{s->ev.st_arr});
+    else
+        k_arrive<<<grid_c, CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOff{});
     k_flags<<<grid_c, CB, shm, c.stream>>>(cabs, w.n_stands, w.c_to, w.c_clnt, s->bits, 0);
     const dim3 grid_n = near_grid(B, s->words);
     const size_t shm_n = near_lds(s->words);
     if (s->dist) k_near_b<<<grid_n, CB, shm_n, c.stream>>>(B, w.n_stands, s->words, s->nb_dem, s->bits, s->near, 0);
     const DemPred dp{w, t, s->words, s->bits, s->near};
-    k_dem_count<<<grid_r, CB, 0, c.stream>>>(dp, reqs, s->cnt_a, s->ctl);
+    if (log)
+        k_dem_count<<<grid_r, CB, 0, c.stream>>>(dp, reqs, s->cnt_a, s->ctl, EvOn{s->ev.st_drop});
+    else
+        k_dem_count<<<grid_r, CB, 0, c.stream>>>(dp, reqs, s->cnt_a, s->ctl, EvOff{});
     k_flags<<<grid_r, CB, shm, c.stream>>>(reqs, w.n_stands, w.r_from, w.r_cab, s->bits, 1);
     if (s->dist) k_near_b<<<grid_n, CB, shm_n, c.stream>>>(B, w.n_stands, s->words, s->nb_sup, s->bits, s->near, 1);
     const SupPred sp{w, s->words, s->bits, s->near};
@@ -275,7 +310,7 @@ int simb_begin(td_simb *s, int t, int32_t *info)
         max_dem = std::max(max_dem, s->n_dem[b]);
         max_act = std::max(max_act, hp[b + 1] - hp[b]);
     }
-    if (hd[B] == 0) return TD_OK;   // Simulator.java:160 in every world: nothing to do in this tick
+    if (hd[B] == 0) return simb_ev_tick_done(s);   // Simulator.java:160 in every world: nothing to do in this tick
     s->begun = true;
     // findPool for the worlds with supply, the plans stay on the device
     if (max_act >= 2) {
@@ -359,13 +394,21 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
     }
     const int32_t *hs = h_of(s, s->sup_off), *h2 = h_of(s, s->d2_off);
     const SegOff cabs{s->d_cab_off}, sup{s->sup_off}, d2{s->d2_off};
+    const bool log = s->ev.kinds != 0;
+    if (log && (rc = ev_clear_apply(s->ev, (size_t)hs[B], (size_t)h2[B]))) return rc;
     if (any_lcm) {
         TD_HIP(hipMemsetAsync(s->pair_cab, 0x7f, sizeof(int32_t) * (size_t)hs[B], c.stream));
         TD_HIP(hipMemsetAsync(s->pair_dem, 0x7f, sizeof(int32_t) * (size_t)h2[B], c.stream));
         if (max_pairs > 0)
             k_pair_map<<<dim3((max_pairs + 255) / 256, B), 256, 0, c.stream>>>(dec, mnl, sup, d2, s->pair_cab, s->pair_dem, s->gerr);
-        k_apply_pairs<<<dim3(nchunks(max_sd), B), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, s->pair_cab, s->pair_dem, s->sup_cab, s->sup_to,
-                                                                   s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, s->gerr);
+        auto pairs = [&](auto ev) {
+            k_apply_pairs<<<dim3(nchunks(max_sd), B), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, s->pair_cab, s->pair_dem, s->sup_cab, s->sup_to,
+                                                                       s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, s->gerr, ev);
+        };
+        if (log)
+            pairs(EvOn{s->ev.st_pairs});
+        else
+            pairs(EvOff{});
         const dim3 grid_s(nchunks(max_s), B), grid_d(nchunks(max_d), B);
         const KeptPred<SegOff> ps{s->pair_cab, sup, d2, mnl}, pd{s->pair_dem, sup, d2, mnl};
         k_count<SegOff, KeptPred<SegOff>><<<grid_s, CB, 0, c.stream>>>(sup, ps, s->cnt_a);
@@ -377,10 +420,16 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
             s->d2_off, pd, KeptDemEmit{s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost},
             s->cnt_b, s->kd_off, nullptr);
     }
-    if (any_sup)
+    auto solution = [&](auto ev) {
         k_apply_solution<<<dim3(nchunks(max_s), B), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, SegOff{s->ks_off}, SegOff{s->kd_off}, s->sup_cab,
                                                                      s->sup_to, s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->ks_cab,
-                                                                     s->ks_to, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, s->gerr);
+                                                                     s->ks_to, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, s->gerr,
+                                                                     ev);
+    };
+    if (any_sup && log)
+        solution(EvOn{s->ev.st_sol});
+    else if (any_sup)
+        solution(EvOff{});
     TD_HIP(hipGetLastError());
     if ((rc = read_head(s))) return rc;
     const int err = *h_of(s, s->gerr);
@@ -406,7 +455,7 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
         opt_count[b] = h_ctl(s)[b].opt_count;
         s->max_solver[b] = std::max(s->max_solver[b], (int64_t)(lcm ? std::max(hks[b + 1] - hks[b], hkd[b + 1] - hkd[b]) : n));
     }
-    return TD_OK;
+    return simb_ev_tick_done(s);
 }
 
 // offsets [B + 1] from the caller: start at 0, never decrease, world b's segment at most cap(b) long
@@ -664,6 +713,7 @@ extern "C" int td_simb_destroy(td_simb *s)
     if (!s) return TD_OK;
     if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
     buf_free(s->mem);
+    ev_off(s->ev);
     if (s->pin) (void)hipHostFree(s->pin);
     delete s;
     return TD_OK;
@@ -795,4 +845,28 @@ extern "C" int td_simb_metrics(td_simb *s, int64_t *out)
     for (int b = 0; b < s->B; b++)
         fill_metrics(h_ctl(s)[b], s->lcm_used[b], s->max_model[b], s->max_solver[b], s->max_pool_mem[b], s->max_pool[b], out + (size_t)TD_SIM_N_METRICS * b);
     return TD_OK;
+}
+
+extern "C" int td_simb_log(td_simb *s, uint32_t kinds, int64_t capacity)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (kinds & ~TD_EV_ALL) return fail(TD_EINVAL, "td_simb_log: kinds = 0x%x has bits outside 1 .. 11", kinds);
+    if (kinds && (capacity <= 0 || capacity > INT_MAX)) return fail(TD_EINVAL, "td_simb_log: capacity = %lld outside 1 .. 2^31 - 1", (long long)capacity);
+    if (s->begun) return fail(TD_EINVAL, "td_simb_log: tick %d still waits for td_simb_apply", s->last_t);
+    const size_t nc = (size_t)s->max_cabs, nr = (size_t)s->max_req;
+    return ev_setup(s->ev, kinds, capacity, s->B, (size_t)s->nc_tot, (size_t)s->nr_tot, nc + nr + 2 + nr + nr / 2 + 2 * (nc + nr) + 2 * nc);
+}
+
+extern "C" int td_simb_events(td_simb *s, int64_t max_records, int32_t *records, int64_t *n, int64_t *lost)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !n) return fail(TD_EINVAL, "null argument");
+    if (max_records < 0) return fail(TD_EINVAL, "td_simb_events: negative max_records");
+    int rc;
+    if (s->ev.kinds && s->begun && !s->ev.begin_flushed) {   // a tick waits for its apply: what it has written so far
+        if ((rc = simb_ev_flush(s, 1))) return rc;
+        s->ev.begin_flushed = true;
+    }
+    return ev_drain(s->ev, "td_simb_events", max_records, records, n, lost);
 }

@@ -25,6 +25,14 @@ BIG_COST = 250000      # :114
 CLNT_A_ENDS, CLNT_B_ENDS = 0, 1   # :97-98
 
 
+# the event log, Simulator.java's simulog.txt: a record is (t, world, kind, method, customer id, cab, aux, 0); a word the kind
+# does not use is -1 (method: 0).  The kinds, with the Java line that writes them (include/taxidispatcher_amd.h, TD_EV_*)
+(EV_PICKED_UP, EV_CAB_FREE, EV_DROPPED, EV_TEMP_DEMAND, EV_TEMP_DEMAND_ID, EV_POOL, EV_POOL_PAIR, EV_ASSIGNED_PICKED, EV_HEADING,
+ EV_ASSIGNED_LCM, EV_POOLED_SECOND) = range(1, 12)
+EV_KINDS = tuple(range(1, 12))
+EV_LCM, EV_OPT = 1, 2                    # the method word
+EV_METHOD = {EV_LCM: "LCM", EV_OPT: "OPT"}
+
 MAX_DIST_STANDS = 4096       # a distance table has at most this many stands (td_sim_create_dist)
 MAX_DIST = 0x1fffffff        # and no larger entry: three of them stay below td_pool2's INT_MAX diagonal marker
 
@@ -133,7 +141,9 @@ class Simulator:
     (HipBackend(dist=...)).  cheat_a_bit stays the reference's stand arithmetic (from +- cost against N_STANDS), which
     means something on a line only; it is kept as it is, bug-compatible, in a table world too."""
 
-    def __init__(self, demand_rows, backend=None, n_cabs=N_CABS, on_solver_instance=None, dist=None):
+    def __init__(self, demand_rows, backend=None, n_cabs=N_CABS, on_solver_instance=None, dist=None, events=False):
+        self._events_on = bool(events)
+        self.events = []         # events=True: the records of simulog.txt (format_events), in the order the Java writes them
         self.dist = None if dist is None else check_dist(dist, N_STANDS).astype(np.int64)
         self.be = backend if backend is not None else HipBackend(dist)
         self.on_solver_instance = on_solver_instance
@@ -158,6 +168,10 @@ class Simulator:
                       total_second_passengers=0)
         self.log = []
 
+    def _ev(self, t, kind, method=0, customer=-1, cab=-1, aux=-1):
+        if self._events_on:
+            self.events.append((int(t), 0, kind, method, int(customer), int(cab), int(aux), 0))
+
     # ---- Simulator.java:220-254
     def _way(self, a, b):
         """the distance from stand(s) a to stand(s) b"""
@@ -173,6 +187,7 @@ class Simulator:
                     continue
                 self.d_cab[d] = c
                 self.d_pick[d] = t
+                self._ev(t, EV_PICKED_UP, customer=self.d_id[d], cab=c)                       # :233
                 self.m["total_pickup_numb"] += 1
                 self.c_from[c] = self.d_from[d]
                 self.c_to[c] = self.d_to[d] if self.d_pool_id[d] == -1 else cheat_a_bit(int(self.d_from[d]),
@@ -185,6 +200,7 @@ class Simulator:
                 self.c_clnt[c] = -1
                 self.c_onboard[c] = 0
                 self.c_start[c] = -1
+                self._ev(t, EV_CAB_FREE, cab=c, aux=self.c_to[c])                             # :251
 
     @staticmethod
     def _near(stand_flags):
@@ -213,11 +229,16 @@ class Simulator:
         drop = cand[t - self.d_at[cand] >= DROP_TIME]
         self.d_cab[drop] = -2
         self.m["total_dropped"] += int(drop.size)
+        for d in drop:
+            self._ev(t, EV_DROPPED, customer=self.d_id[d])                                    # :339
         keep = cand[t - self.d_at[cand] < DROP_TIME]
         free_to = np.zeros(N_STANDS, bool)
         free_to[self.c_to[self.c_clnt == -1]] = True
         near = self._near_cabs(free_to)
         keep = keep[near[self.d_from[keep]]]
+        self._ev(t, EV_TEMP_DEMAND, aux=keep.size)                                            # :331 / :352, also an empty list
+        for d in keep:
+            self._ev(t, EV_TEMP_DEMAND_ID, customer=self.d_id[d])                             # :347
         # TempDemand: id, from, to, pool_clnt_id, pool_plan, pool_cost
         return [[int(self.d_id[d]), int(self.d_from[d]), int(self.d_to[d]), -1, -1, 0] for d in keep]
 
@@ -230,9 +251,10 @@ class Simulator:
         return [[int(c), int(self.c_from[c]), int(self.c_to[c])] for c in cabs]   # Supply: id, from, to
 
     # ---- Simulator.java:681-758 (every ordered pair is admitted: plan1 = plan2 = true at :691)
-    def find_pool(self, temp_demand):
+    def find_pool(self, temp_demand, t=None):
         n = len(temp_demand)
         if n < 2:
+            self._ev(t, EV_POOL, aux=0)                                                       # :742 / :756, no pair
             return []
         frm = np.array([r[1] for r in temp_demand], np.int64)
         to = np.array([r[2] for r in temp_demand], np.int64)
@@ -240,6 +262,9 @@ class Simulator:
         # pool of two on the backend (td_pool2 on the GPU; the tests' comparator restates it on the host)
         out = self.be.find_pool(frm, to)
         self.m["max_POOL_size"] = max(self.m["max_POOL_size"], len(out))
+        self._ev(t, EV_POOL, aux=len(out))                                                    # :742 / :756
+        for p in out:
+            self._ev(t, EV_POOL_PAIR, customer=temp_demand[p[0]][0], aux=temp_demand[p[1]][0])   # :746
         return out
 
     # ---- Simulator.java:760-784
@@ -268,33 +293,36 @@ class Simulator:
                                                  np.array([d[1] for d in temp_demand], np.int32)))
 
     # ---- Simulator.java:424-490
-    def _assign_pooled(self, customer, cab):
+    def _assign_pooled(self, customer, cab, t=None, method=0):
         d2 = self.id2idx.get(int(customer))
         if d2 is not None:
             self.d_cab[d2] = cab
+            self._ev(t, EV_POOLED_SECOND, method, customer=customer, cab=cab)                 # :432-433
             self.m["total_second_passengers"] += 1
 
-    def _assign_to_cab_and_go(self, t, c, cust):
+    def _assign_to_cab_and_go(self, t, c, cust, method=0):
         self.c_from[c] = cust[1]
         self.c_to[c] = cust[2] if cust[3] == -1 else cheat_a_bit(int(self.c_from[c]), cust[5])
         self.c_clnt[c] = cust[0]
         self.c_onboard[c] = 1
         self.c_start[c] = t
         self.m["total_pickup_numb"] += 1
+        self._ev(t, EV_ASSIGNED_PICKED, method, customer=cust[0], cab=c, aux=cust[3])          # :448-465
 
-    def _go_to_pickup(self, t, c, cust):
+    def _go_to_pickup(self, t, c, cust, method=0):
         self.c_to[c] = cust[1]
         self.c_clnt[c] = cust[0]
         self.c_onboard[c] = 0
         self.c_start[c] = t
+        self._ev(t, EV_HEADING, method, customer=cust[0], cab=c)                              # :486-487
         self.m["total_pickup_time"] += int(self._way(int(self.c_from[c]), int(self.c_to[c])))
 
-    def _dispatch(self, t, supply, cust):
+    def _dispatch(self, t, supply, cust, method=0):
         c = supply[0]   # cab id == cab index
         if supply[2] == cust[1]:
-            self._assign_to_cab_and_go(t, c, cust)
+            self._assign_to_cab_and_go(t, c, cust, method)
         elif self._way(supply[2], cust[1]) < DROP_TIME:
-            self._go_to_pickup(t, c, cust)
+            self._go_to_pickup(t, c, cust, method)
 
     # ---- Simulator.java:613-674
     def analyze_pairs(self, t, pairs, temp_demand, temp_supply):
@@ -306,7 +334,7 @@ class Simulator:
         supply2, demand2 = [], []
         for s, sup in enumerate(temp_supply):
             if s in by_cab:
-                self._dispatch(t, sup, temp_demand[by_cab[s]])
+                self._dispatch(t, sup, temp_demand[by_cab[s]], EV_LCM)
             else:
                 supply2.append(list(sup))
         for d, cust in enumerate(temp_demand):
@@ -314,9 +342,10 @@ class Simulator:
                 c2 = self.id2idx[cust[0]]
                 cab_id = temp_supply[by_clnt[d]][0]
                 self.d_cab[c2] = cab_id
+                self._ev(t, EV_ASSIGNED_LCM, customer=cust[0], cab=cab_id)                    # :654
                 self.d_pick[c2] = t
                 if cust[3] > -1:
-                    self._assign_pooled(cust[3], cab_id)
+                    self._assign_pooled(cust[3], cab_id, t, EV_LCM)
                     self.m["total_pickup_numb"] += 1
                 # NOTE: pool info is NOT copied into demand[] on the LCM path (only :391-396 does)
             else:
@@ -335,10 +364,10 @@ class Simulator:
                 self.d_cab[d] = sup[0]
                 self.d_pick[d] = t
                 if cust[3] > -1:
-                    self._assign_pooled(cust[3], sup[0])
+                    self._assign_pooled(cust[3], sup[0], t, EV_OPT)
                     self.d_pool_id[d], self.d_pool_plan[d], self.d_pool_cost[d] = cust[3], cust[4], cust[5]
                     self.m["total_pickup_numb"] += 1
-                self._dispatch(t, sup, cust)
+                self._dispatch(t, sup, cust, EV_OPT)
         return total
 
     # ---- one tick of Simulator.java:151-211 ; returns the simulog_solv line (or None)
@@ -354,7 +383,7 @@ class Simulator:
         if temp_supply and hasattr(self.be, "tick"):
             return self._tick_one_call(t, line, temp_demand, temp_supply)
         if temp_supply:
-            temp_demand = self.analyze_pool(self.find_pool(temp_demand), temp_demand)
+            temp_demand = self.analyze_pool(self.find_pool(temp_demand, t), temp_demand)
             cost = self.calculate_cost(temp_demand, temp_supply)
             self.m["max_model_size"] = max(self.m["max_model_size"], cost.shape[0])
             if cost.shape[0] > MAX_NON_LCM:
@@ -375,7 +404,7 @@ class Simulator:
 
     # ---- the same tick (Simulator.java:163-208) with the whole path behind ONE backend call (td_tick)
     def _tick_one_call(self, t, line, temp_demand, temp_supply):
-        temp_demand = self.analyze_pool(self.find_pool(temp_demand), temp_demand)
+        temp_demand = self.analyze_pool(self.find_pool(temp_demand, t), temp_demand)
         n = max(len(temp_demand), len(temp_supply))
         self.m["max_model_size"] = max(self.m["max_model_size"], n)
         res = self.be.tick([s[2] for s in temp_supply], [d[1] for d in temp_demand])
@@ -423,7 +452,95 @@ class Simulator:
         return self.log
 
 
-class DeviceSimulator:
+def event_kinds_mask(events):
+    """events: True (every kind) or an iterable of kinds 1 .. 11 -> td_sim_log's bit set; None / False -> 0"""
+    if events is None or events is False:
+        return 0
+    if events is True:
+        return sum(1 << k for k in EV_KINDS)
+    mask = 0
+    for k in events:
+        if int(k) not in EV_KINDS:
+            raise ValueError("event kind %r outside 1 .. 11" % (k,))
+        mask |= 1 << int(k)
+    return mask
+
+
+def format_events(records, world=None):
+    """The lines of simulog.txt, byte for byte Simulator.java's strings (without the newline), from event records in log order:
+    an (n, 8) array or a sequence of 8-word records.  world: format the records of this world only (a batch's records are
+    formatted world by world); None takes every record.  A tempDemand / pool header collects the list records that follow it
+    within its tick; a header whose list records were masked out or lost is the bare header, and a list record without its
+    header gives no line."""
+    lines = []
+    open_kind, open_t = 0, None
+    for r in np.asarray(records, dtype=np.int64).reshape(-1, 8).tolist():
+        t, w, kind, method, cust, cab, aux = r[:7]
+        if world is not None and w != world:
+            continue
+        head = "Time %d. " % t
+        if kind in (EV_TEMP_DEMAND_ID, EV_POOL_PAIR):
+            if open_kind == kind - 1 and open_t == t:
+                lines[-1] += "%d, " % cust if kind == EV_TEMP_DEMAND_ID else "%d(%d), " % (cust, aux)
+            continue
+        open_kind, open_t = (kind, t) if kind in (EV_TEMP_DEMAND, EV_POOL) else (0, None)
+        if kind == EV_PICKED_UP:
+            lines.append(head + "Customer %d picked up by Cab %d" % (cust, cab))                    # :233
+        elif kind == EV_CAB_FREE:
+            lines.append(head + "Cab %d is free at stand %d" % (cab, aux))                          # :251
+        elif kind == EV_DROPPED:
+            lines.append(head + "Customer %d dropped" % cust)                                       # :339
+        elif kind == EV_TEMP_DEMAND:
+            lines.append(head + "tempDemand: ")                                                     # :331
+        elif kind == EV_POOL:
+            lines.append(head + "Customers in pool: ")                                              # :742
+        elif kind == EV_ASSIGNED_PICKED:                                                            # :448-463
+            lines.append(head + "Customer %d assigned to and picked up by Cab %d" % (cust, cab)
+                         + (" (POOL: the other Customer %d)" % aux if aux != -1 else "") + " (method %s)" % EV_METHOD[method])
+        elif kind == EV_HEADING:                                                                    # :486-487
+            lines.append(head + "Customer %d assigned to Cab %d, cab is heading to the customer (method %s)" % (cust, cab, EV_METHOD[method]))
+        elif kind == EV_ASSIGNED_LCM:
+            lines.append(head + "Customer %d assigned by LCM to Cab %d" % (cust, cab))              # :654
+        elif kind == EV_POOLED_SECOND:                                                              # :432-433
+            lines.append(head + "Customer %d assigned in a pool as second passenger to Cab %d (method %s)" % (cust, cab, EV_METHOD[method]))
+        else:
+            raise ValueError("event record of kind %d" % kind)
+    return lines
+
+
+class _DeviceEvents:
+    """the event log of a device handle (td_sim_log / td_sim_events or their td_simb twins), shared by both classes"""
+
+    def _events_init(self, log_fn, events_fn, events, capacity, default_capacity):
+        self._ev_fn = events_fn
+        self.events_lost = 0         # records that did not fit the log, the running total
+        self.event_kinds = event_kinds_mask(events)
+        self.event_capacity = 0
+        if self.event_kinds:
+            self.event_capacity = int(default_capacity if capacity is None else capacity)
+            self._ffi.check(log_fn(self._h, self.event_kinds, self.event_capacity))
+
+    def events(self, max_records=None):
+        """drains the log -> an (n, 8) int32 array of records, oldest first ((0, 8) without logging); `events_lost` grows by
+        what did not fit since the last drain.  max_records: take at most so many; more in the log raises TdError and
+        leaves the log as it is."""
+        ct = self._ct
+        n, lost = ct.c_int64(0), ct.c_int64(0)
+        if max_records is None:      # ask for the number first: max_records = 0 succeeds only on an empty log
+            rc = self._ev_fn(self._h, 0, None, ct.byref(n), ct.byref(lost))
+            if rc == 0:
+                self.events_lost += lost.value
+                return np.zeros((0, 8), np.int32)
+            if n.value <= 0:
+                self._ffi.check(rc)
+            max_records = n.value
+        out = np.empty((max(int(max_records), 1), 8), np.int32)
+        self._ffi.check(self._ev_fn(self._h, int(max_records), self._ffi.addr(out), ct.byref(n), ct.byref(lost)))
+        self.events_lost += lost.value
+        return out[:n.value].copy()
+
+
+class DeviceSimulator(_DeviceEvents):
     """The same world in device memory behind the C ABI (td_sim_*, csrc/td_sim.hip): the cab and request tables never leave
     the GPU, a tick is ONE call (`tick` = td_sim_step: world kernels around td_pool2 and td_tick), and only the counters
     of the log line come back.  `begin` / `model` / `apply` split the tick so that the assignment decisions can come from
@@ -431,14 +548,19 @@ class DeviceSimulator:
     dist: a stand-to-stand distance table as `Simulator` takes it (numpy array-like, or an int32 torch tensor on the device);
     the handle keeps its own copy (td_sim_create_dist).  n_stands then defaults to the table's size.  A host table is
     checked here (check_dist: ValueError); a device tensor is checked for shape and dtype only (ValueError) and its size,
-    diagonal and entries by td_sim_create_dist on the device, which raises TdError."""
+    diagonal and entries by td_sim_create_dist on the device, which raises TdError.
+    events: True or an iterable of event kinds (EV_*) switches the event log on (td_sim_log); `events()` drains it,
+    `format_events` makes simulog.txt's lines of it.  event_capacity: the records the log holds; the default,
+    4 * (n_cabs + n_req) + 64, holds any one tick of the world (a tick writes at most 3 n_cabs + 3.5 n_req + 2 records), so
+    a caller that drains after every tick loses nothing."""
 
     M_KEYS = ("total_dropped", "total_pickup_time", "total_pickup_numb", "total_LCM_used", "max_model_size", "max_solver_size",
               "max_POOL_MEM_size", "max_POOL_size", "total_second_passengers")
     CAB_KEYS = ("c_from", "c_to", "c_clnt", "c_onboard", "c_start")
     REQ_KEYS = ("d_cab", "d_pick", "d_pool_id", "d_pool_plan", "d_pool_cost")
 
-    def __init__(self, demand_rows, n_cabs=None, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None):
+    def __init__(self, demand_rows, n_cabs=None, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None, events=None,
+                 event_capacity=None):
         import ctypes
         from . import _ffi
         self._ffi, self._ct = _ffi, ctypes
@@ -468,6 +590,7 @@ class DeviceSimulator:
         self._cap = max(self.n_cabs, self.n_req, 1)
         self._info = None
         self.log = []
+        self._events_init(self._lib.td_sim_log, self._lib.td_sim_events, events, event_capacity, 4 * (self.n_cabs + self.n_req) + 64)
 
     def close(self):
         if self._h is not None:
@@ -595,7 +718,7 @@ def pack_worlds(demand_rows_list, n_cabs_list):
     return (np.asarray(cabs, np.int32), np.asarray(off, np.int32)) + tuple(cols)
 
 
-class DeviceSimulatorBatch:
+class DeviceSimulatorBatch(_DeviceEvents):
     """B independent worlds behind ONE handle (td_simb_*, csrc/td_simb.hip): the worlds share the city (n_stands, drop_time,
     max_non_lcm, big_cost) and differ in fleet size and request table.  `tick` advances every world by one td_simb_step
     (td_pool2_batched and td_tick_batched on the device lists); `begin` / `model` / `apply` split the tick for decisions
@@ -604,12 +727,16 @@ class DeviceSimulatorBatch:
     torch tensor on the device); the handle keeps its own copy (td_simb_create_dist).  n_stands then defaults to the table's
     size.  A host table is checked here (check_dist), and so are its size against n_stands and the request stands against
     the table: ValueError, before the library is touched.  A device tensor is checked for shape and dtype only; its size,
-    diagonal and entries by td_simb_create_dist on the device, which raises TdError."""
+    diagonal and entries by td_simb_create_dist on the device, which raises TdError.
+    events / event_capacity: as `DeviceSimulator` takes them; ONE log for the handle (td_simb_log), a record's second word is
+    its world, and within a tick world 0's records come first.  The default capacity, 4 * (all cabs + all requests) + 64 * B,
+    holds any one tick of the batch."""
 
     M_KEYS, CAB_KEYS, REQ_KEYS = DeviceSimulator.M_KEYS, DeviceSimulator.CAB_KEYS, DeviceSimulator.REQ_KEYS
     format_line = staticmethod(DeviceSimulator.format_line)
 
-    def __init__(self, demand_rows_list, n_cabs_list, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None):
+    def __init__(self, demand_rows_list, n_cabs_list, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None,
+                 events=None, event_capacity=None):
         import ctypes
         from . import _ffi
         self._ffi, self._ct = _ffi, ctypes
@@ -650,6 +777,8 @@ class DeviceSimulatorBatch:
         self._h = h
         self._info = None
         self.logs = [[] for _ in range(self.batch)]
+        self._events_init(self._lib.td_simb_log, self._lib.td_simb_events, events, event_capacity,
+                          4 * (sum(self.n_cabs) + sum(self.n_req)) + 64 * self.batch)
 
     def close(self):
         if self._h is not None:

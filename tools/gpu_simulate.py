@@ -5,7 +5,10 @@
 (DeviceSimulatorBatch = td_simb_step, one C-ABI call per tick for all of them), each world's metrics block printed.
 --dist FILE.npy: the city as a stand-to-stand distance table (a square integer array saved with numpy.save, [from][to]) for
 --world host and --world device, a batch of worlds (--cabs) included: the worlds of a batch share the one table
-(td_simb_create_dist); the stands of the demand file must lie inside it."""
+(td_simb_create_dist); the stands of the demand file must lie inside it.
+--events FILE: the run's event log, Simulator.java's simulog.txt, written to FILE (every world: the host world records it
+itself, a device world through td_sim_log / td_sim_events, drained after every tick); with --cabs a,b,c one file per world,
+FILE with the world's number put before its extension (simulog.0.txt, simulog.1.txt, ...)."""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,6 +18,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--world", choices=("host", "device"), default="host")
 ap.add_argument("--cabs", default=None, help="comma-separated fleet sizes: one world per size, run as one batch (needs --world device)")
 ap.add_argument("--dist", default=None, metavar="FILE.npy", help="a stand-to-stand distance table (numpy.save of a square integer array)")
+ap.add_argument("--events", default=None, metavar="FILE", help="write the event log (simulog.txt) of the run to FILE")
 args = ap.parse_args()
 if args.cabs and args.world != "device":
     ap.error("--cabs needs --world device")
@@ -29,12 +33,44 @@ rows = simulator.read_demand("tests/golden/taxi_demand.txt.gz")
 if dist is not None and rows[:, 1:3].max() >= dist.shape[0]:
     ap.error("--dist %s: the demand file uses stand %d, the table has %d stands" % (args.dist, rows[:, 1:3].max(), dist.shape[0]))
 td.init(0)
+
+
+def write_events(path, records, world=None):
+    with open(path, "w") as f:
+        f.writelines(l + "\n" for l in simulator.format_events(records, world=world))
+    print("wrote %s" % path)
+
+
+def run_logged(sim, ticks):
+    """sim.run(ticks) with the event log drained after every tick -> the records, (n, 8)"""
+    parts = []
+    for t in range(ticks):
+        out = sim.tick(t)
+        if isinstance(sim, simulator.DeviceSimulatorBatch):
+            for b, line in enumerate(out or []):
+                if line is not None:
+                    sim.logs[b].append(line)
+        elif out is not None:
+            sim.log.append(out)
+        parts.append(sim.events())
+    if sim.events_lost:
+        print("event log: %d records lost" % sim.events_lost)
+    return np.concatenate(parts)
+
+
 if args.world == "device" and args.cabs:
     fleets = [int(v) for v in args.cabs.split(",")]
-    sim = simulator.DeviceSimulatorBatch([rows] * len(fleets), fleets, dist=dist)
+    sim = simulator.DeviceSimulatorBatch([rows] * len(fleets), fleets, dist=dist, events=True if args.events else None)
     t0 = time.time()
-    logs = sim.run(120)
+    if args.events:
+        records, logs = run_logged(sim, 120), sim.logs
+    else:
+        logs = sim.run(120)
     dt = time.time() - t0
+    if args.events:
+        stem, ext = os.path.splitext(args.events)
+        for b in range(len(fleets)):
+            write_events("%s.%d%s" % (stem, b, ext), records, world=b)
     print("120 ticks of %d worlds in %.2f s; worlds and path on the GPU, one td_simb_step call per tick for all worlds" % (len(fleets), dt))
     for b, n in enumerate(fleets):
         print("\n=== world %d: %d cabs ===" % (b, n))
@@ -42,15 +78,20 @@ if args.world == "device" and args.cabs:
         print(sim.metrics_text(b, total_simul_time=int(dt)))
     sys.exit(0)
 if args.world == "device":
-    sim = simulator.DeviceSimulator(rows, dist=dist)
+    sim = simulator.DeviceSimulator(rows, dist=dist, events=True if args.events else None)
     t0 = time.time()
-    log = sim.run(120)
+    if args.events:
+        records, log = run_logged(sim, 120), sim.log
+    else:
+        log = sim.run(120)
     dt = time.time() - t0
+    if args.events:
+        write_events(args.events, records)
     print("120 ticks in %.2f s (reference: 2603 s, README.md:45); world and path on the GPU, one td_sim_step call per tick" % dt)
     print("\n".join(log[-3:]))
     print(sim.metrics_text(total_simul_time=int(dt)))
     sys.exit(0)
-sim = simulator.Simulator(rows, dist=dist)
+sim = simulator.Simulator(rows, dist=dist, events=bool(args.events))
 t0 = time.time()
 per = {"pool": 0.0, "cost": 0.0, "lcm": 0.0, "solve": 0.0}
 be = sim.be
@@ -62,6 +103,8 @@ be.find_pool = timed("pool", be.find_pool); be.calculate_cost = timed("cost", be
 be.lcm = timed("lcm", be.lcm); be.solve = timed("solve", be.solve)
 log = sim.run(120)
 dt = time.time() - t0
+if args.events:
+    write_events(args.events, sim.events)
 print("120 ticks in %.2f s (reference: 2603 s, README.md:45); path time on GPU incl. PCIe: %s" % (dt, {k: round(v, 3) for k, v in per.items()}))
 print("\n".join(log[-3:]))
 print(sim.metrics_text(total_simul_time=int(dt)))
