@@ -33,7 +33,7 @@ def build(force=False, verbose=False):
         hipcc = "hipcc"
     flags = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden",
              "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"),
-             "-DTD_BUILDING=1", "-DTD_NT=%s" % os.environ.get("TD_NT", "2"),
+             "-DTD_BUILDING=1",
              "-DTD_SX_G=%s" % os.environ.get("TD_SX_G", "8"), "-DTD_SX_NG=%s" % os.environ.get("TD_SX_NG", "2"),
              "-DTD_SX_TX=%s" % os.environ.get("TD_SX_TX", "128")]
     # one object per source, compiled side by side (no device symbol crosses a file), then one link; an object is

@@ -202,7 +202,6 @@ int g_warm_minfree = 32;    // TD_WARM_MINFREE  free rows after the eps = 0 roun
 int g_warm_min_n = 512;     // TD_WARM_MIN_N    no warm start for smaller models
 int g_sapx = 1;             // TD_SAPX          cooperative multi-workgroup serial finisher (k_sapx)
 int g_sapx_min = 8;         // TD_SAPX_MIN      fewest workgroups (256 chunks each) for which it is used
-int g_sapx_slim_chunks = INT_MAX; // TD_SAPX_SLIM  1- / 2-byte rows with at least this many 16-byte chunks: 64-thread column slices in k_sapx.  OFF: measured at n = 65 536 (perf.jl rows, 7 searches, 14 steps) 64 slim workgroups take 1.41 ms against 0.71 ms for 16 wide ones — the barrier and the publish phase grow with the workgroup count faster than the relax shrinks
 int g_sapx_rows = 24;       // TD_SAPX_ROWS     ... half of that when at least this many rows are left for it
 int g_sap512 = 1;           // TD_SAP512        512-thread generic finisher (double register budget) for n <= 8192
 int g_psap_worth = 4;       // TD_PSAP_WORTH    rows a batch must commit on average for another group to be launched
@@ -224,7 +223,6 @@ long long g_forest_wx = 16; // TD_FOREST_WX     how far above the smallest free-
 int g_blocks = -1;          // TD_BLOCKS        block-local start of the 1-byte attempt (td_blocks.h): diagonal blocks of the matrix; 0: off, -1: by size (td_assign: off below TD_BLOCKS_MIN_N)
 int g_blocks_min_n = 12288; // TD_BLOCKS_MIN_N  smallest n td_assign starts block-locally by itself (perf.jl solve, n = 12 288 / 16 384 / 32 768 / 65 536: 0.61 / 0.76 / 2.26 / 7.5 -> 0.41 / 0.52 / 1.69 / 6.2 ms)
 int g_zs_rounds = 4;        // TD_ZS_ROUNDS     local bidding rounds of phase A after round 0
-int g_zs_sep = 0;           // TD_ZS_SEP        rows of <= 16 384 columns: round 0 of phase A as its own launch behind the plain compress pass.  OFF: measured slower (td_assign n = 16 384 0.487 -> 0.543 ms: the plain 256 x 16 pass takes 0.29 ms in this sequence, the pass that also writes the bids 0.243)
 int g_hop_passes = 2;       // TD_HOP_PASSES    two-hop passes at the end of phase A (the second one takes the rows the first pass's greedy left: 4 of 183 at n = 16 384)
 int g_hop_max_rows = HOP_FMAX;   // TD_HOP_MAX_ROWS  a block with more free rows than this is left to the rounds
 int g_lazy_cc = 1;          // TD_LAZY_CC       td_assign, block-local start: the compress pass stores the diagonal slices of the narrow copy only; the rest is written (k_compress_rest) only if phase A + the two-hop pass over the whole matrix leave rows
@@ -239,7 +237,6 @@ double g_core_eps = 1.0;    // TD_CORE_EPS
 int g_rand_test = 1;        // TD_RAND_TEST     row-correlation test (k_row_corr): random-like matrices get the short eps ladder (TD_RAND_DIV) and TD_RAND_ROUNDS eps = 0 rounds after it
 int g_rand_div = 8192;      // TD_RAND_DIV
 int g_rand_rounds = 48;     // TD_RAND_ROUNDS
-int g_rand_repeat = 1;      // TD_RAND_REPEAT   blocks of TD_RAND_ROUNDS eps = 0 rounds after the warm start
 double g_rand_corr = 0.12;  // TD_RAND_CORR     mean |r| over 64 sampled row pairs below which the matrix counts as random-like (random: ~0.05; metric structure: 0.3 - 0.9)
 int g_core_patience = 6;    // TD_CORE_PATIENCE groups of 8 rounds a phase on trusted lists may take before the lists are dropped for good
 int g_solver_eps = 0;       // TD_SOLVER=eps    literal eps-scaling auction (comparison mode)
@@ -273,7 +270,6 @@ void read_tunables()
     if (const char *e = getenv("TD_WARM_MINFREE")) g_warm_minfree = std::max(1, atoi(e));
     if (const char *e = getenv("TD_WARM_MIN_N")) g_warm_min_n = std::max(0, atoi(e));
     if (const char *e = getenv("TD_SAPX_MIN")) g_sapx_min = std::max(1, atoi(e));
-    if (const char *e = getenv("TD_SAPX_SLIM")) g_sapx_slim_chunks = std::max(64, atoi(e));
     if (const char *e = getenv("TD_SAPX_ROWS")) g_sapx_rows = std::max(1, atoi(e));
     if (const char *e = getenv("TD_PSAP_WORTH")) g_psap_worth = std::max(1, atoi(e));
     if (const char *e = getenv("TD_SPECULATE")) g_speculate = atoi(e) != 0;
@@ -313,11 +309,9 @@ void read_tunables()
     if (const char *e = getenv("TD_RAND_DIV")) g_rand_div = std::max(1, atoi(e));
     if (const char *e = getenv("TD_RAND_ROUNDS")) g_rand_rounds = std::max(1, std::min(48, atoi(e)));
     if (const char *e = getenv("TD_RAND_CORR")) g_rand_corr = atof(e);
-    if (const char *e = getenv("TD_RAND_REPEAT")) g_rand_repeat = std::max(1, atoi(e));
     if (const char *e = getenv("TD_BLOCKS")) g_blocks = std::max(-1, std::min(HOP_BMAX, atoi(e)));
     if (const char *e = getenv("TD_BLOCKS_MIN_N")) g_blocks_min_n = std::max(0, atoi(e));
     if (const char *e = getenv("TD_ZS_ROUNDS")) g_zs_rounds = std::max(0, std::min(32, atoi(e)));
-    if (const char *e = getenv("TD_ZS_SEP")) g_zs_sep = atoi(e) != 0;
     if (const char *e = getenv("TD_HOP_PASSES")) g_hop_passes = std::max(0, std::min(8, atoi(e)));
     if (const char *e = getenv("TD_HOP_MAX_ROWS")) g_hop_max_rows = std::max(1, atoi(e));
     if (const char *e = getenv("TD_HOP_GLOBAL")) g_hop_global = atoi(e) != 0;
@@ -382,16 +376,10 @@ __device__ __forceinline__ void unpack<u32n>(const uint4 &v, uint32_t *o)
     o[3] = v.w;
 }
 
-// 16-byte streaming load: TD_NT bit 2 makes the bidding kernels' row stream nontemporal
+// 16-byte load of a chunk of the row that k_bid streams
 __device__ __forceinline__ uint4 load16_stream(const void *p)
 {
-#if defined(TD_NT) && (TD_NT & 4)
-    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-    const v4u t = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p));
-    return make_uint4(t.x, t.y, t.z, t.w);
-#else
     return *reinterpret_cast<const uint4 *>(p);
-#endif
 }
 
 template <typename T>
@@ -528,10 +516,7 @@ __device__ __forceinline__ void shape_decide(int n, int *__restrict__ ctl);
 // BID0: the row is in registers with its minimum known, so the bid of round 0 (all prices 0: the first minimum in
 // the row's rotated chunk order, raised by second smallest - smallest) is written here and the round's own pass over
 // the narrow matrix (k_bid, round 0) is not launched — the same key, bit for bit.
-// LH > 0: the LAST LH of a thread's VPT 16-byte pieces wait in LDS instead of registers between the load and the store
-// phase (65 536-column rows: 1024 threads x 16 pieces hit the 128-VGPR cap of a 16-wave workgroup and spilled 200 bytes per
-// lane — scratch traffic of the order of the row itself; 8 pieces in registers + 8 x 16 KiB in LDS do not spill).
-template <typename CT, int VPT, int THREADS, bool BID0 = false, int LH = 0>
+template <typename CT, int VPT, int THREADS, bool BID0 = false>
 __global__ __launch_bounds__(THREADS) void k_compress_reg(
     int n, int nrows, int nchunks, const int32_t *__restrict__ cost, CT *__restrict__ cc, int32_t *__restrict__ rowmin, int *__restrict__ ctl,
     int *__restrict__ rconst, const long long *__restrict__ skip, unsigned long long *__restrict__ bid = nullptr, int row0 = 0,
@@ -599,23 +584,17 @@ __global__ __launch_bounds__(THREADS) void k_compress_reg(
             }
         }
     };
-    constexpr int VR = VPT - LH;   // pieces that stay in registers
-    extern __shared__ int4 s_rowh[];   // [LH][THREADS]: every thread reads back what it wrote itself
     for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
         const int4 *s4 = reinterpret_cast<const int4 *>(cost + (int64_t)row * n);
         int4 v[VPT];
 #pragma unroll
         for (int k = 0; k < VPT; k++) {
             const int q = k * THREADS + tid;
-#if defined(TD_NT) && (TD_NT & 2)
-            if (q < nq) {
+            if (q < nq) {   // nontemporal: the int32 row is read once
                 typedef int v4i __attribute__((ext_vector_type(4)));
                 const v4i t4 = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(s4) + q);
                 v[k] = make_int4(t4.x, t4.y, t4.z, t4.w);
             }
-#else
-            if (q < nq) v[k] = s4[q];
-#endif
         }
         int mn = INT_MAX, mx = INT_MIN;
 #pragma unroll
@@ -625,11 +604,6 @@ __global__ __launch_bounds__(THREADS) void k_compress_reg(
                 mn = min(min(mn, v[k].x), min(v[k].y, min(v[k].z, v[k].w)));
                 mx = max(max(mx, v[k].x), max(v[k].y, max(v[k].z, v[k].w)));
             }
-        }
-        if constexpr (LH > 0) {   // park the upper pieces in LDS: their registers are free for the scan below
-#pragma unroll
-            for (int k = VR; k < VPT; k++)
-                if (k * THREADS + tid < nq) s_rowh[(k - VR) * THREADS + tid] = v[k];
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -673,12 +647,7 @@ __global__ __launch_bounds__(THREADS) void k_compress_reg(
         for (int k = 0; k < VPT; k++) {
             const int q = k * THREADS + tid;
             if (q < nq) {
-                int4 x4;
-                if constexpr (LH > 0) {
-                    if (k >= VR) x4 = s_rowh[(k - VR) * THREADS + tid];
-                    else x4 = v[k];
-                } else
-                    x4 = v[k];
+                const int4 x4 = v[k];
                 const uint32_t a = (uint32_t)(x4.x - mn), b = (uint32_t)(x4.y - mn), c = (uint32_t)(x4.z - mn),
                                d = (uint32_t)(x4.w - mn);
                 if constexpr (sizeof(CT) == 1) {
@@ -1321,109 +1290,16 @@ __global__ __launch_bounds__(256) void k_compress_tr(int n, int npad, const int3
 }
 
 // The same pass for 1-byte cells with an escape (u8e): every cell is `esc_raw` (the fill value, code 254) or lies in
-// base .. base + 253, else CTL_FLAG is raised and the host redoes the pass with 4-byte cells.  A workgroup takes 64 of
-// the caller's columns x TR8_ROWS rows (512): the codes are staged transposed in LDS (row pitch TR8_ROWS + 4 bytes, an odd
-// number of dwords: the 64 lanes of a wave hit 64 different banks), then every transposed row leaves as one contiguous piece.
-template <int TR8_ROWS>
-__global__ __launch_bounds__(256) void k_compress_tr8(int n, int npad, const int32_t *__restrict__ in, uint8_t *__restrict__ out, int base,
-                                                      int esc_raw, int *__restrict__ colmin, int *__restrict__ colmax, int *__restrict__ ctl)
-{
-    constexpr int TR8_LP = TR8_ROWS + 4;
-    static_assert(TR8_ROWS % 256 == 0, "a transposed row leaves as TR8_ROWS / 256 dwords per lane");
-    extern __shared__ __attribute__((aligned(16))) unsigned char tb[];   // [64][TR8_LP]
-    __shared__ int s_mn[64], s_mx[64];
-    const int bx = blockIdx.x * 64, ry0 = blockIdx.y * TR8_ROWS;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid < 64) {
-        s_mn[tid] = INT_MAX;
-        s_mx[tid] = INT_MIN;
-    }
-    __syncthreads();
-    // Load phase: lane (cg = lane % 16, rs = lane / 16) of wave w reads 16 bytes = columns 4cg .. 4cg+3 of row 16p + 4w + rs
-    // (a wave reads 4 full 256-byte row pieces per instruction, 8 instructions in flight).  The four lanes cg, cg+16,
-    // cg+32, cg+48 hold a 4 x 4 block (4 rows x 4 columns): each packs its row's codes into one dword, fetches the
-    // other three by shuffles and writes ONE dword = 4 consecutive rows of column 4cg + rs — a conflict-free
-    // ds_write_b32 (dword address (4cg + rs) * 257 + row / 4: 64 different banks over the wave).
-    const int cg = lane & 15, rs = lane >> 4;
-    int mn[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX}, mx[4] = {INT_MIN, INT_MIN, INT_MIN, INT_MIN};
-    bool bad = false;
-    const int jc0 = bx + 4 * cg;
-    const bool vec = (n % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) & 15) == 0);   // the caller's matrix: a 4-byte-aligned base takes the scalar loads
-    constexpr int U = 8;
-    for (int p0 = 0; p0 < TR8_ROWS / 16; p0 += U) {
-        int4 v[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int r = 16 * (p0 + u) + 4 * wv + rs, i = ry0 + r;
-            if (i < n && vec && jc0 + 3 < n)
-                v[u] = *reinterpret_cast<const int4 *>(in + (int64_t)i * n + jc0);
-            else {
-                int t4[4];
-#pragma unroll
-                for (int x = 0; x < 4; x++) t4[x] = (i < n && jc0 + x < n) ? in[(int64_t)i * n + jc0 + x] : esc_raw;
-                v[u] = make_int4(t4[0], t4[1], t4[2], t4[3]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int r = 16 * (p0 + u) + 4 * wv + rs, i = ry0 + r;
-            const int vv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-            uint32_t packed = 0;
-#pragma unroll
-            for (int x = 0; x < 4; x++) {
-                uint32_t code = 0xFFu;
-                if (i < n && jc0 + x < n) {
-                    mn[x] = min(mn[x], vv[x]);
-                    mx[x] = max(mx[x], vv[x]);
-                    const int d = vv[x] - base;
-                    if (vv[x] == esc_raw)
-                        code = U8E_ESC;
-                    else {
-                        code = (uint32_t)d & 0xFFu;
-                        bad = bad || d < 0 || d > 253;
-                    }
-                }
-                packed |= code << (8 * x);
-            }
-            // 4 x 4 transpose over the lanes cg + 16 * q: my dword = byte `rs` of the packed rows q = 0 .. 3
-            uint32_t mine = 0;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const uint32_t pq = (uint32_t)__shfl((int)packed, cg + 16 * q);
-                mine |= ((pq >> (8 * rs)) & 0xFFu) << (8 * q);
-            }
-            const int rbase = 16 * (p0 + u) + 4 * wv;   // the four rows of this block
-            *reinterpret_cast<uint32_t *>(tb + (size_t)(4 * cg + rs) * TR8_LP + rbase) = mine;
-        }
-    }
-#pragma unroll
-    for (int x = 0; x < 4; x++)
-        if (mn[x] <= mx[x]) {
-            atomicMin(&s_mn[4 * cg + x], mn[x]);
-            atomicMax(&s_mx[4 * cg + x], mx[x]);
-        }
-    __syncthreads();
-    // wave wv writes the transposed rows wv * 16 .. + 15: lane l holds the dwords l, l + 64, .. of the row
-    for (int k = 0; k < 16; k++) {
-        const int rr = wv * 16 + k, jj = bx + rr;
-        if (jj >= n) break;
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(tb + (size_t)rr * TR8_LP);
-#pragma unroll
-        for (int q = 0; q < TR8_ROWS / 256; q++) {
-            const int dw = lane + 64 * q, b = ry0 + 4 * dw;
-            if (b < npad) *reinterpret_cast<uint32_t *>(out + (size_t)jj * npad + b) = src[dw];
-        }
-    }
-    if (tid < 64 && bx + tid < n && s_mn[tid] <= s_mx[tid]) {
-        atomicMin(&colmin[bx + tid], s_mn[tid]);
-        atomicMax(&colmax[bx + tid], s_mx[tid]);
-    }
-    if (bad) atomicOr(&ctl[CTL_FLAG], 1);
-}
-
-// The same pass with WIDE tiles: 256 of the caller's columns x TR8W_ROWS rows per workgroup.  Wave w takes the column group
-// [64w, 64w + 64): one instruction of the four waves together reads 4 rows x 1 KiB CONTIGUOUS (the narrow tile read 256-byte
-// pieces at a 64 KiB stride: 3.8 TB/s of traffic), every transposed row leaves as TR8W_ROWS contiguous bytes.
+// base .. base + 253, else CTL_FLAG is raised and the host redoes the pass with 4-byte cells.  A workgroup takes 256 of
+// the caller's columns x TR8W_ROWS rows (128): the codes are staged transposed in LDS (row pitch TR8W_ROWS + 4 bytes, an
+// odd number of dwords: the 64 lanes of a wave hit 64 different banks), then every transposed row leaves as TR8W_ROWS
+// contiguous bytes.
+// Load phase: wave w takes the column group [64w, 64w + 64); its lane (cg = lane % 16, rs = lane / 16) reads 16 bytes =
+// columns 4cg .. 4cg+3 of the group in row 4p + rs, so one instruction of the four waves together reads 4 rows x 1 KiB
+// CONTIGUOUS, 8 instructions in flight.  The four lanes cg, cg+16, cg+32, cg+48 hold a 4 x 4 block (4 rows x 4 columns):
+// each packs its row's codes into one dword, fetches the other three by shuffles and writes ONE dword = 4 consecutive
+// rows of column 64w + 4cg + rs — a conflict-free ds_write_b32.  (Narrower tiles read shorter pieces at the matrix's row
+// stride: 64 columns gave 256-byte pieces 64 KiB apart and 3.8 TB/s of traffic)
 template <int TR8W_ROWS, bool GEN = false>
 __global__ __launch_bounds__(256) void k_compress_tr8w(int n, int npad, const int32_t *__restrict__ in, uint8_t *__restrict__ out, int base,
                                                        int esc_raw, int *__restrict__ colmin, int *__restrict__ colmax, int *__restrict__ ctl,
@@ -3222,11 +3098,10 @@ struct td_shard {
     Buf gpos;                  // td_build_assign's position arrays / distance table on the device
     bool tick_sized = false;   // td_tick's remainder (hinted, n < 2048): the rounds leave a dozen rows, the serial workgroup is through before a speculative batch + its commit are — no read-back of the free-row count to decide that
     int zs_V = 0;              // diagonal blocks of the whole matrix the 1-byte attempt may start in (0: off)
-    bool zs_done = false;      // the compress pass prepared the block-local start (wrote the zero-slice bids of phase A's round 0, or left them to k_zs_bid: zs_round0): sv_phase_a is due
+    bool zs_done = false;      // the compress pass prepared the block-local start (wrote the zero-slice bids of phase A's round 0): sv_phase_a is due
     bool lazy_cc = false;      // td_assign: the block-local start may leave the narrow copy with the diagonal slices only (k_compress_reg diag_only)
     bool cc_partial = false;   // ... and this attempt's copy IS partial: whoever needs whole rows calls sv_complete_cc first
     int cc_rpb = 0;
-    bool zs_round0 = false;    // ... round 0 of phase A is still to be bid (rows of <= 16 384 columns: the plain compress pass + one k_zs_bid round over 1/8 of every row beat the pass that also scans for the bids, 216 + ~10 against 243 us)
     bool began = false;        // the state (prices, owners, row_to_col, bid keys) has been initialised for the current compressed copy
     bool state_ready = false;  // sharded solve: the state was initialised in front of the compress pass and phase A has run on it (td_shard_begin must not redo it)
     bool ctl_clear = false;    // the control words were cleared by a kernel queued in front of the next compress pass (the line probe): no memset
@@ -3289,7 +3164,6 @@ int sv_compress_t(Solver &sv, bool *fits, bool speculate = false)
     sv.bid0_done = false;
     sv.state_ready = false;
     sv.zs_done = false;
-    sv.zs_round0 = false;
     sv.began = false;
     sv.cc_partial = false;
     if (nrows > 0) {
@@ -3307,25 +3181,15 @@ int sv_compress_t(Solver &sv, bool *fits, bool speculate = false)
             const int rpb = n / sv.zs_V;
             if (sv.row0 % rpb == 0 && nrows % rpb == 0 && nrows / rpb <= HOP_BMAX) zs_rpb = rpb;
         }
-        // block-local start of rows that fit the 256-thread pass (n <= 16 384): round 0 of phase A as its own k_zs_bid launch
-        // (it reads 1/V of every row: 32 MB at n = 16 384) behind the PLAIN pass, which is 27 us faster than the one that
-        // scans the narrow words for the bids; wider rows keep the fused pass (their plain pass is no faster: spills)
-        const bool zs_sep = zs_rpb > 0 && g_zs_sep && nq <= 256 * 16;
-        if (zs_sep) {
-            sv.zs_done = true;
-            sv.zs_round0 = true;
-        }
-        const bool bid0_kernel = bid0 && !zs_sep;
         // the narrow cells outside the diagonal slices are only read if phase A leaves rows: do not write them until then
         // (7/8 of the 0.25 GiB copy at n = 16 384)
-        const int diag = (sizeof(CT) == 1 && sv.lazy_cc && g_lazy_cc && bid0_kernel && zs_rpb > 0 && sv.d_cost && !sv.gen) ? 1 : 0;
+        const int diag = (sizeof(CT) == 1 && sv.lazy_cc && g_lazy_cc && bid0 && zs_rpb > 0 && sv.d_cost && !sv.gen) ? 1 : 0;
         // (two restructurings of the diag_only pass were built and measured at n = 16 384, both SLOWER than this pass's
         // 215 us: one WAVE per row with only the slice waiting in registers — no LDS, no barrier — 284 - 390 us, slower the
         // more waves stream at once; the next row's loads issued before the barrier, so that every workgroup has a row
         // in flight all the time, 267 - 288 us.  More bytes in flight do not help this pass)
-        static const int gbm = getenv("TD_BID0_GRID") ? atoi(getenv("TD_BID0_GRID")) : 0;
-        const int gb = std::max(1, std::min(nrows, c.n_cu * (gbm > 0 ? gbm : std::max(1, g_cgrid / 2))));   // 512-thread workgroups of the BID0 pass
-        if (bid0_kernel) {
+        const int gb = std::max(1, std::min(nrows, c.n_cu * std::max(1, g_cgrid / 2)));   // 512-thread workgroups of the BID0 pass
+        if (bid0) {
             using PT = typename Tr<CT>::PT;
             const int npad = nchunks * E;
             const PT padkey = (PT)(Tr<CT>::BIG << 1) | (PT)1;
@@ -3355,48 +3219,23 @@ int sv_compress_t(Solver &sv, bool *fits, bool speculate = false)
             else if (nq <= 512) { TD_CR(2); }
             else if (nq <= 1024) { TD_CR(4); }
             else if (nq <= 2048) { TD_CR(8); }
-            else if (bid0_kernel) {
+            else if (bid0) {
                 // 512 threads x 8 pieces: half the row registers per thread, so that the zero-byte scan fits without giving up waves
                 if constexpr (sizeof(CT) == 1) {
-                    static const int shape = getenv("TD_BID0_SHAPE") ? atoi(getenv("TD_BID0_SHAPE")) : 0;
-                    if (shape == 1)
-                        k_compress_reg<CT, 4, 1024, true><<<gb, 1024, 0, c.stream>>>(n, nrows, nchunks, sv.d_cost, cc, rm, ctl, rcs, sv.skip, bidp,
-                                                                                    sv.row0, defer_r2c, tickets, zs_rpb, diag);
-                    else
-                        k_compress_reg<CT, 8, 512, true><<<gb, 512, 0, c.stream>>>(n, nrows, nchunks, sv.d_cost, cc, rm, ctl, rcs, sv.skip, bidp,
-                                                                                   sv.row0, defer_r2c, tickets, zs_rpb, diag);
+                    k_compress_reg<CT, 8, 512, true><<<gb, 512, 0, c.stream>>>(n, nrows, nchunks, sv.d_cost, cc, rm, ctl, rcs, sv.skip, bidp,
+                                                                               sv.row0, defer_r2c, tickets, zs_rpb, diag);
                     sv.zs_done = zs_rpb > 0;
                     sv.cc_partial = diag != 0;
                     sv.cc_rpb = zs_rpb;
                 }
-            } else {
-                static const int cshape = getenv("TD_CREG_SHAPE") ? atoi(getenv("TD_CREG_SHAPE")) : 0;
-                if (cshape == 1)
-                    k_compress_reg<CT, 8, 512><<<gb, 512, 0, c.stream>>>(n, nrows, nchunks, sv.d_cost, cc, rm, ctl, rcs, sv.skip);
-                else if (cshape == 2)
-                    k_compress_reg<CT, 4, 1024><<<gb, 1024, 0, c.stream>>>(n, nrows, nchunks, sv.d_cost, cc, rm, ctl, rcs, sv.skip);
-                else { TD_CR(16); }
-            }
+            } else { TD_CR(16); }
 #undef TD_CR
         } else if (g_creg && vec && nq <= 1024 * 16) {
             const int g4 = std::max(1, std::min(nrows, c.n_cu * 2));
-            static const int clds = getenv("TD_CLDS") ? atoi(getenv("TD_CLDS")) : 0;   // pieces per thread parked in LDS (0: all in registers).  Measured at n = 65 536: 0 / 8 / 4 -> 4.046 / 4.032 / 4.637 ms: the 52 bytes per lane the register shape spills are not what holds the pass at 5.3 TB/s of traffic
-            if (bid0_kernel) {
-                if constexpr (sizeof(CT) == 1)
-                {
-                    if (clds == 8) {
-                        const int shm = 8 * 1024 * 16;
-                        (void)hipFuncSetAttribute((const void *)k_compress_reg<CT, 16, 1024, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-                        k_compress_reg<CT, 16, 1024, true, 8><<<g4, 1024, shm, c.stream>>>(n, nrows, nchunks, sv.d_cost, cc, rm, ctl, rcs, sv.skip, bidp,
-                                                                                          sv.row0, defer_r2c, tickets, zs_rpb, diag);
-                    } else if (clds == 4) {
-                        const int shm = 4 * 1024 * 16;
-                        (void)hipFuncSetAttribute((const void *)k_compress_reg<CT, 16, 1024, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-                        k_compress_reg<CT, 16, 1024, true, 4><<<g4, 1024, shm, c.stream>>>(n, nrows, nchunks, sv.d_cost, cc, rm, ctl, rcs, sv.skip, bidp,
-                                                                                          sv.row0, defer_r2c, tickets, zs_rpb, diag);
-                    } else
-                        k_compress_reg<CT, 16, 1024, true><<<g4, 1024, 0, c.stream>>>(n, nrows, nchunks, sv.d_cost, cc, rm, ctl, rcs, sv.skip, bidp,
-                                                                                      sv.row0, defer_r2c, tickets, zs_rpb, diag);
+            if (bid0) {
+                if constexpr (sizeof(CT) == 1) {
+                    k_compress_reg<CT, 16, 1024, true><<<g4, 1024, 0, c.stream>>>(n, nrows, nchunks, sv.d_cost, cc, rm, ctl, rcs, sv.skip, bidp,
+                                                                                  sv.row0, defer_r2c, tickets, zs_rpb, diag);
                     sv.zs_done = zs_rpb > 0;
                     sv.cc_partial = diag != 0;
                     sv.cc_rpb = zs_rpb;
@@ -3458,34 +3297,16 @@ int sv_compress_fused(Solver &sv, bool *fits, int64_t *range, bool cells8 = fals
         k_fill_i32<<<(n + 255) / 256, 256, 0, c.stream>>>(colmin, n, INT_MAX);
         k_fill_i32<<<(n + 255) / 256, 256, 0, c.stream>>>(colmax, n, INT_MIN);
         if (cells8) {
-            static const int tr8_rows = getenv("TD_TR8_ROWS") ? atoi(getenv("TD_TR8_ROWS")) : 512;   // rows per tile: 512 = 33 KB of LDS, 4 workgroups per CU (g3 N = 16 384: compress 0.33 ms; 1024 rows, 2 per CU: 0.35 - 0.38; 256: 0.36)
-#define TD_TR8(R)                                                                                                                          \
-    do {                                                                                                                                   \
-        const size_t shm = (size_t)64 * (R + 4);                                                                                           \
-        (void)hipFuncSetAttribute((const void *)k_compress_tr8<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                  \
-        k_compress_tr8<R><<<dim3((n + 63) / 64, (n + R - 1) / R), 256, shm, c.stream>>>(n, npad, sv.d_cost, (uint8_t *)sv.cc.p, 0, esc_raw, \
-                                                                                       colmin, colmax, ctl);                              \
-    } while (0)
-            static const int tr8_wide = getenv("TD_TR8_WIDE") ? atoi(getenv("TD_TR8_WIDE")) : 128;   // > 0: 256-column tiles of this many rows (128 / 256; g3 N = 16 384 step: 64-column tiles 0.838, 256 x 128 0.821, 256 x 256 0.841 ms — the tile shape is not what holds this pass at 3.8 TB/s of traffic)
-#define TD_TR8W(R)                                                                                                                           \
-    do {                                                                                                                                     \
-        const size_t shm = (size_t)256 * (R + 4);                                                                                            \
-        (void)hipFuncSetAttribute((const void *)k_compress_tr8w<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                   \
-        k_compress_tr8w<R><<<dim3((n + 255) / 256, (n + R - 1) / R), 256, shm, c.stream>>>(n, npad, sv.d_cost, (uint8_t *)sv.cc.p, 0, esc_raw, \
-                                                                                          colmin, colmax, ctl);                             \
-    } while (0)
+            // 256 columns x 128 rows per workgroup: 33 KB of LDS
+            const size_t shm = (size_t)256 * (128 + 4);
+            const dim3 g8((n + 255) / 256, (n + 127) / 128);
             if (sv.gen) {   // cells made from the position arrays (td_build_assign)
-                const size_t shm = (size_t)256 * (128 + 4);
                 (void)hipFuncSetAttribute((const void *)k_compress_tr8w<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-                k_compress_tr8w<128, true><<<dim3((n + 255) / 256, (n + 127) / 128), 256, shm, c.stream>>>(n, npad, nullptr, (uint8_t *)sv.cc.p, 0, esc_raw,
-                                                                                                          colmin, colmax, ctl, sv.gsrc);
-            } else if (tr8_wide == 128) TD_TR8W(128);
-            else if (tr8_wide == 256) TD_TR8W(256);
-            else if (tr8_rows == 256) TD_TR8(256);
-            else if (tr8_rows == 512) TD_TR8(512);
-            else TD_TR8(1024);
-#undef TD_TR8W
-#undef TD_TR8
+                k_compress_tr8w<128, true><<<g8, 256, shm, c.stream>>>(n, npad, nullptr, (uint8_t *)sv.cc.p, 0, esc_raw, colmin, colmax, ctl, sv.gsrc);
+            } else {
+                (void)hipFuncSetAttribute((const void *)k_compress_tr8w<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+                k_compress_tr8w<128><<<g8, 256, shm, c.stream>>>(n, npad, sv.d_cost, (uint8_t *)sv.cc.p, 0, esc_raw, colmin, colmax, ctl);
+            }
         } else if (sv.gen && n > 4096)
             k_compress_tr<8, true><<<dim3((n + 63) / 64, (n + 511) / 512), 256, 0, c.stream>>>(n, npad, nullptr, (uint32_t *)sv.cc.p, 0, colmin, colmax, ctl, sv.gsrc);
         else if (sv.gen)
@@ -3582,9 +3403,6 @@ int sv_hop_t(Solver &sv, int rpb, int ncols_blk, int col_lo, int nb, bool window
 // Phase A of a 1-byte attempt whose compress pass wrote the zero-slice bids (sv.zs_done): everything local to this
 // shard's diagonal blocks, no price moves.  Leaves the ordinary state (owner / r2c / packed prices with the owned bit)
 // for the global rounds; the free rows it left are counted in HopCtl::left.
-template <typename CT>
-int sv_begin_t(Solver &sv);
-
 int sv_phase_a(Solver &sv, int hop_passes)
 {
     Ctx &c = ctx();
@@ -3603,13 +3421,7 @@ int sv_phase_a(Solver &sv, int hop_passes)
         k_zs_assign<<<ga, 256, 0, c.stream>>>(col_lo, col_hi, nrows, sv.row0, bid, (int32_t *)sv.price.p, (int *)sv.owner.p, (int *)sv.r2c.p,
                                               (uint8_t *)sv.ob.p, ctl);
     };
-    if (sv.zs_round0) {   // round 0 as its own launch behind the plain compress pass (the same bids as the fused pass writes, bit for bit)
-        if (!sv.began && (rc = sv_begin_t<uint8_t>(sv))) return rc;   // (a shard: td_shard_begin comes after the exchange)
-        k_zs_bid<<<std::min(nrows, c.n_cu * 16), 256, 0, c.stream>>>(nrows, sv.row0, sv.nchunks, rpb, (const uint8_t *)sv.cc.p,
-                                                                     (const uint8_t *)sv.ob.p, (const int *)sv.r2c.p, bid, ctl, 0, 0);
-        sv.zs_round0 = false;
-    }
-    assign();   // round 0
+    assign();   // round 0: its bids were written by the compress pass
     for (int r = 1; r <= g_zs_rounds; r++) {
         k_zs_bid<<<std::min(nrows, c.n_cu * 16), 256, 0, c.stream>>>(nrows, sv.row0, sv.nchunks, rpb, (const uint8_t *)sv.cc.p,
                                                                      (const uint8_t *)sv.ob.p, (const int *)sv.r2c.p, bid, ctl, r, g_tie_evict);
@@ -3753,21 +3565,13 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
             void *kargs[] = {&a_n, &a_nch, &a_tab, &a_pk, &a_owner, &a_r2c, &g_pcp, &g_base, &g_root, &g_col, &a_ctl, &fs, &a_w0, &a_wx, &a_pcl};
             const size_t dyn = std::max<size_t>(2 * n4, a_pcl ? 6 * n4 : 0);   // forest row list (u16) / predecessor columns + owners (u16) of workgroup 0 at an END
             hipError_t le;
-            static const int force_cw = getenv("TD_FOREST_CW") ? atoi(getenv("TD_FOREST_CW")) : 0;
-            static const int force_tb = getenv("TD_FOREST_TB") ? atoi(getenv("TD_FOREST_TB")) : 1024;
 #define TD_FO_LAUNCH(CWV, TBV)                                                                                                        \
     do {                                                                                                                              \
         (void)hipFuncSetAttribute((const void *)k_forest<CT, CWV, TBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);        \
         le = hipLaunchCooperativeKernel((const void *)k_forest<CT, CWV, TBV>, dim3((n + CWV - 1) / CWV), dim3(TBV), kargs, dyn, c.stream); \
     } while (0)
-            if (n <= 16384 && force_cw != 128) {
-                if (force_tb >= 1024) TD_FO_LAUNCH(64, 1024);
-                else if (force_tb >= 512) TD_FO_LAUNCH(64, 512);
-                else TD_FO_LAUNCH(64, 256);
-            } else {
-                if (force_tb >= 512) TD_FO_LAUNCH(128, 512);
-                else TD_FO_LAUNCH(128, 256);
-            }
+            if (n <= 16384) TD_FO_LAUNCH(64, 1024);
+            else TD_FO_LAUNCH(128, 512);
 #undef TD_FO_LAUNCH
             if (le == hipSuccess) {
                 TD_HIP(hipGetLastError());
@@ -3857,15 +3661,12 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
 #define TD_SX_TX 128
 #endif
         constexpr int TXsel = (sizeof(CT) == 4) ? TD_SX_TX : 256;
-        // narrow cells of a very wide matrix (1-byte rows at n = 65 536: 4096 chunks): 64-thread column slices, so that 64
-        // CUs instead of 16 pull the published rows (a step of ~70 rows x 64 KiB took 27 us through 16 CUs)
-        const bool slim = sizeof(CT) < 4 && nchunks >= g_sapx_slim_chunks;
-        const int KX = slim ? (nchunks + 63) / 64 : (nchunks + TXsel - 1) / TXsel;
+        const int KX = (nchunks + TXsel - 1) / TXsel;
         const bool lean8 = IsLean8<CT>::value && CH == 1 && g_sap8;
         bool launched_x = false;
         // from 8 x 256 chunks on always; from 4 x 256 on when many rows are left (|a-b| n = 6000: 190 -> 109 ms with 62 rows;
         // uniform 0..10^6 n = 4096 with 10 rows: 9.8 -> 12.1 ms, so not for a handful)
-        const bool big = slim || KX * TXsel >= g_sapx_min * 256 || (KX * TXsel >= g_sapx_min * 128 && nfree_left >= g_sapx_rows);
+        const bool big = KX * TXsel >= g_sapx_min * 256 || (KX * TXsel >= g_sapx_min * 128 && nfree_left >= g_sapx_rows);
         if (g_sapx && !lean8 && big && KX <= SX_KMAX) {
             Ctx &c = ctx();
             using PT = typename Tr<CT>::PT;
@@ -3881,14 +3682,7 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
             void *kargs[] = {&a_n, &a_nch, &a_tab, &a_pk, &a_owner, &a_r2c, &a_pred, &a_list, &a_ctl, &a_sh};
             // 4-byte cells: 4 row groups per workgroup (1024 threads, 4 waves per SIMD in the relax phase)
             constexpr int NGsel = (sizeof(CT) == 4) ? TD_SX_NG : 1;
-            hipError_t le;
-            if constexpr (sizeof(CT) < 4) {
-                if (slim)
-                    le = hipLaunchCooperativeKernel((const void *)k_sapx<CT, 64, 1>, dim3(KX), dim3(64), kargs, 0, c.stream);
-                else
-                    le = hipLaunchCooperativeKernel((const void *)k_sapx<CT, TXsel, NGsel>, dim3(KX), dim3(TXsel * NGsel), kargs, 0, c.stream);
-            } else
-                le = hipLaunchCooperativeKernel((const void *)k_sapx<CT, TXsel, NGsel>, dim3(KX), dim3(TXsel * NGsel), kargs, 0, c.stream);
+            const hipError_t le = hipLaunchCooperativeKernel((const void *)k_sapx<CT, TXsel, NGsel>, dim3(KX), dim3(TXsel * NGsel), kargs, 0, c.stream);
             if (le == hipSuccess) launched_x = true;
             else (void)hipGetLastError();
         }
@@ -4714,10 +4508,6 @@ restart:
             if ((rc = warm(g_warm_bits))) return rc;
             if (random_like) round_cap = std::max(round_cap, g_rand_rounds);   // (cheap here: a few hundred bidders; halves what is left for the forest)
             if ((rc = rounds(false))) return rc;
-            for (int rep = 1; random_like && rep < g_rand_repeat; rep++) {   // more blocks of eps = 0 rounds (the per-round progress words are reused)
-                TD_HIP(hipMemsetAsync((int *)sv.misc.p + CTL_PROG, 0, sizeof(int) * 64, c.stream));
-                if ((rc = rounds(false))) return rc;
-            }
         }
         ShardTab tab{};
         tab.p[0] = sv.cc.p;

@@ -30,7 +30,6 @@
 // barrier (monotonic counter, release / acquire fences at agent scope, bounded spin -> abort).
 
 constexpr int FO_CAP = 4;      // entries a workgroup publishes per level
-constexpr int FO_T = 256;      // threads per workgroup
 constexpr int FO_GMAX = 256;   // workgroups (one per CU)
 constexpr int FO_RELMAX = 16;  // trees released per END
 constexpr int FO_EMAX = FO_GMAX * FO_CAP;
