@@ -223,6 +223,39 @@ TD_API int td_tick_batched(int batch, int n, const int32_t *cab_off, const int32
                            int32_t *kept_cabs, int32_t *kept_dems, int32_t *n_rest, int32_t *row_to_col,
                            int64_t *total, int64_t *dual_bound);
 
+/* ---- the split heuristic of MANY cases in one call (split.py:61-119 as a whole) -----------------------------------------
+ * B ragged cases as above (offsets, positions, one shared table or NULL = |a - b|, host or device memory, synchronous,
+ * batch == 0 is a no-op); n bounds every case's max(n_s, n_d), n <= 1024 (the fifth model can be a whole case).  Cells are
+ * dist[cab_to][dem_from], no threshold.
+ *   Ranges: split_size = size / parts; range r is stands [r*split_size, (r+1)*split_size) for every r*split_size < size, so a
+ *   size that parts does not divide gives more than parts ranges, the last one short (the reference's `while start<size`).
+ *   A cab belongs to the range of its cab_to, a request to that of its dem_from; order within a region is the case's order.
+ *   Region with cabs and requests: the optimum of its square model padded with fill.  A pair on a real cell is served; with
+ *   more cabs than requests the cabs on dummy columns go to the rest, with more requests the requests on dummy rows do.
+ *   Region with requests only / without requests: all of them / all its cabs go to the rest.
+ *   Fifth solve: the optimum over the rest cabs and rest requests, each in the case's order; only real cells are summed.
+ *   A case with no cabs or no requests has no solve at all (split.py:62-64): total 0, every cab -1, n_rest 0 / 0.
+ * Outputs: cab_req[cab_off[c] + i]: the index, within case c's request list, of the request cab i serves, or -1;
+ *   cab_stage (same shape, may be NULL): 0 served inside its region, 1 by the fifth solve, -1 not served; total[c]: the split
+ *   total; rest_total[c] (may be NULL): the fifth solve's part of it; n_rest[2c], n_rest[2c + 1] (may be NULL): the sizes of
+ *   the rest lists; dual_gap[c] (may be NULL): the sum over every model solved for the case of total - dual_bound as the
+ *   solver's dual pass reports them: 0 certifies every model of the case.  Which cab of a region stays over is the solver's
+ *   choice among equal optima, so totals of two different solvers need not agree; a region's own sum always does.
+ * Five launches whatever B is (partition, the region models, collection, the fifth models, sums: csrc/td_batch.hip), no
+ * host read-back between them, one synchronisation at the end.
+ * TD_EINVAL, with every output left unwritten: n > 1024 or a case larger than n, bad offsets, parts outside [1, 32],
+ *   size < parts, S < size with a table, a position outside [0, size), a table entry used as a cell outside [0, fill),
+ *   fill < 1, on the line size - 1 >= fill, null cab_req / total or inputs.  Positions and table entries are checked on the
+ *   device.  TD_EINTERNAL (outputs unwritten as well) if a model hit a defensive loop cap.
+ * When to use which (measured on MI355X): the whole heuristic is one call wherever the two-call route
+ * (two td_build_assign_batched calls with a host pass that cuts the lists and collects the unserved) was measured: 1000 cases of
+ * 10 per side on 20 stands 0.97 against 23.3 ms, 1000 cases of 400 / 400 on 4000 stands 9.2 against 39.4 ms.  No shape was found
+ * where the two calls win; regions alone, with nothing left over to solve, remain td_build_assign_batched. */
+TD_API int td_split_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab_to,
+                            const int32_t *dem_off, const int32_t *dem_from, const int32_t *dist, int S,
+                            int size, int parts, int32_t fill, int32_t *cab_req, int32_t *cab_stage,
+                            int64_t *total, int64_t *rest_total, int32_t *n_rest, int64_t *dual_gap);
+
 /* Row-sharded LCM: rank r owns cost rows [row0, row0 + nrows).  Per pick every shard
  * reports its smallest live cell {value, global row, column} (value = INT64_MAX: none), the caller
  * takes the minimum in the reference's order (value, row, column) over all shards — one all-gather of

@@ -54,6 +54,8 @@ SIGNATURES = {
     "td_tick_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int32,
                                        ctypes.c_int32, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p,
                                        c_i32p, c_i32p]),
+    "td_split_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
     "td_lcm_shard_create":(ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p, ctypes.c_int, ctypes.c_int32,
                                            ctypes.POINTER(ctypes.c_void_p)]),
     "td_lcm_shard_destroy": (ctypes.c_int, [ctypes.c_void_p]),

@@ -1,7 +1,8 @@
 // td_batch.hip — many small independent models in one call: optimal assignment (td_assign_batched) and the LCM greedy
 // (td_lcm_batched) of B square models of size <= 1024, one workgroup per model; and the same solve and LCM for B ragged
 // dispatch models made from cab / request positions (td_build_assign_batched, td_tick_batched: cells through PosCells, no
-// cost matrix).  gfx950 only.
+// cost matrix); and split.py's whole heuristic for B ragged cases (td_split_batched: partition into stand ranges, the region
+// models, the left-overs' fifth model, the sums).  gfx950 only.
 //
 // Nothing here waits on another workgroup: a model's whole solve lives in one workgroup's LDS and registers (no
 // cross-workgroup atomics, no spins), and a grid-stride loop over the models covers batches larger than the grid.
@@ -922,6 +923,326 @@ void launch_tick_lcm_t(int batch, int n_out, int nl, const PosIn &in, int S, int
 #undef TD_TICK_LCM_ARGS
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// td_split_batched (split.py:61-119): the stand ranges of every case are solved as region models, whoever they leave
+// over is solved once more per case.  Both solves are k_assign_pos_batched launches; the three kernels below partition a
+// case into its regions, collect the left-overs and sum up.  One workgroup per case (grid-stride beyond SPLIT_GRID),
+// every loop bounded by the case's counts or the number of ranges, no atomic on global memory except the error word.
+// ---------------------------------------------------------------------------------------------------------------------
+enum { ERR_POS = 16, ERR_CELL = 32 };   // further bits of the error word: a position outside [0, size), a cell outside [0, fill)
+constexpr int SPLIT_GRID = 2048;
+constexpr int SPLIT_RMAX = 64;          // parts <= 32 gives at most 2 * parts - 1 ranges
+
+__device__ __forceinline__ int32_t pos_dist(const int32_t *dist, int S, int a, int b)
+{
+    return dist ? dist[(int64_t)a * S + b] : (a > b ? a - b : b - a);
+}
+
+// sum of v over the workgroup (any number of full waves); s_sum int64[4]
+__device__ __forceinline__ int64_t block_sum_i64(int64_t v, int64_t *s_sum)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    v = wave_sum_i64(v);
+    if (lane == 0) s_sum[w] = v;
+    __syncthreads();
+    int64_t t = 0;
+    for (int q = 0; q < nw; q++) t += s_sum[q];
+    __syncthreads();
+    return t;
+}
+
+// rank of this thread among the threads with f set, in thread order, and their number (block_rank of td_sim_world.h)
+__device__ __forceinline__ int split_rank(bool f, int *s_w, int *tot)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    const unsigned long long m = __ballot(f);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_w[w] = __popcll(m);
+    __syncthreads();
+    int off = 0, t = 0;
+    for (int q = 0; q < nw; q++) {
+        if (q < w) off += s_w[q];
+        t += s_w[q];
+    }
+    __syncthreads();
+    *tot = t;
+    return off + before;
+}
+
+// true when a cell of the a x b model over the LDS position lists is outside [0, fill)
+__device__ __forceinline__ bool split_cells_bad(const int32_t *pa, int na, const int32_t *pb, int nb, const int32_t *dist, int S,
+                                                int32_t fill)
+{
+    bool bad = false;
+    for (int q = threadIdx.x; q < na * nb; q += blockDim.x) {
+        const int32_t v = dist[(int64_t)pa[q / nb] * S + pb[q % nb]];
+        bad |= (uint32_t)v >= (uint32_t)fill;
+    }
+    return bad;
+}
+
+// launch 1: checks the positions of case c and sorts its cabs (by cab_to) and requests (by dem_from) into range order,
+// stably: scab / sdem get the positions, scab_idx / sdem_idx the index within the case.  Region model m = c * R + r starts
+// at roff_c[m] / roff_d[m] (absolute, inside the case's segment) and has rcnt[2m] / rcnt[2m + 1] rows / columns: 0 / 0 for
+// a region with one side empty, which the solver reads as "no solve".  With a table, every cell of a region model is checked.
+__global__ __launch_bounds__(256) void k_split_part(int batch, int R, int ss, int size, const int32_t *__restrict__ cab_off,
+                                                    const int32_t *__restrict__ cab, const int32_t *__restrict__ dem_off,
+                                                    const int32_t *__restrict__ dem, const int32_t *__restrict__ dist, int S,
+                                                    int32_t fill, int32_t *__restrict__ roff_c, int32_t *__restrict__ roff_d,
+                                                    int32_t *__restrict__ rcnt, int32_t *__restrict__ scab,
+                                                    int32_t *__restrict__ scab_idx, int32_t *__restrict__ sdem,
+                                                    int32_t *__restrict__ sdem_idx, int32_t *__restrict__ cnt2,
+                                                    int *__restrict__ err)
+{
+    __shared__ int32_t s_rng[2][BATCH_NMAX];   // range of each cab / request, case order
+    __shared__ int32_t s_srt[2][BATCH_NMAX];   // positions in region order
+    __shared__ int s_hist[2][SPLIT_RMAX], s_start[2][SPLIT_RMAX + 1];
+    __shared__ int s_bad;
+    const int tid = threadIdx.x, T = blockDim.x;
+    for (int c = blockIdx.x; c < batch; c += gridDim.x) {
+        const int c0 = cab_off[c], d0 = dem_off[c];
+        const int ns = cab_off[c + 1] - c0, nd = dem_off[c + 1] - d0;
+        if (ns > BATCH_NMAX || nd > BATCH_NMAX) {   // validated on the host; never index LDS past its arrays
+            if (tid == 0) {
+                atomicOr(err, ERR_SIZE);
+                cnt2[2 * c] = cnt2[2 * c + 1] = 0;
+                for (int r = 0; r < R; r++) rcnt[2 * (c * R + r)] = rcnt[2 * (c * R + r) + 1] = 0;
+            }
+            continue;
+        }
+        __syncthreads();   // the previous case's LDS is no longer read
+        if (tid < SPLIT_RMAX) s_hist[0][tid] = s_hist[1][tid] = 0;
+        if (tid == 0) s_bad = 0;
+        __syncthreads();
+        for (int side = 0; side < 2; side++) {
+            const int m = side ? nd : ns;
+            const int32_t *src = side ? dem + d0 : cab + c0;
+            for (int i = tid; i < m; i += T) {
+                const int p = src[i];
+                const bool ok = (uint32_t)p < (uint32_t)size;
+                const int r = ok ? p / ss : 0;
+                if (!ok) s_bad = 1;
+                s_rng[side][i] = r;
+                atomicAdd(&s_hist[side][r], 1);
+            }
+        }
+        __syncthreads();
+        if (tid < 2) {
+            int at = 0;
+            for (int r = 0; r < R; r++) {
+                s_start[tid][r] = at;
+                at += s_hist[tid][r];
+            }
+            s_start[tid][R] = at;
+        }
+        __syncthreads();
+        const bool bad = s_bad != 0, empty = ns == 0 || nd == 0;
+        for (int side = 0; side < 2; side++) {
+            const int m = side ? nd : ns, base = side ? d0 : c0;
+            const int32_t *src = side ? dem : cab;
+            int32_t *dst = side ? sdem : scab, *idx = side ? sdem_idx : scab_idx;
+            for (int i = tid; i < m; i += T) {
+                const int r = s_rng[side][i];
+                int rank = 0;
+                for (int j = 0; j < i; j++) rank += s_rng[side][j] == r ? 1 : 0;
+                const int at = s_start[side][r] + rank;
+                const int32_t p = src[base + i];
+                s_srt[side][at] = p;
+                dst[base + at] = p;
+                idx[base + at] = i;
+            }
+        }
+        if (tid < R) {
+            const int m = c * R + tid, hc = s_hist[0][tid], hd = s_hist[1][tid];
+            const bool solve = !bad && !empty && hc > 0 && hd > 0;
+            roff_c[m] = c0 + s_start[0][tid];
+            roff_d[m] = d0 + s_start[1][tid];
+            rcnt[2 * m] = solve ? hc : 0;
+            rcnt[2 * m + 1] = solve ? hd : 0;
+        }
+        if (tid == 0) cnt2[2 * c] = cnt2[2 * c + 1] = 0;   // the fifth solve reads them even when launch 3 stops at a refused input
+        if (c == batch - 1 && tid == 0) {
+            roff_c[batch * R] = c0 + ns;
+            roff_d[batch * R] = d0 + nd;
+        }
+        if (bad && tid == 0) atomicOr(err, ERR_POS);
+        __syncthreads();   // s_srt is complete
+        if (dist && !bad && !empty) {
+            bool cb = false;
+            for (int r = 0; r < R; r++) {
+                const int hc = s_hist[0][r], hd = s_hist[1][r];
+                if (hc > 0 && hd > 0) cb |= split_cells_bad(s_srt[0] + s_start[0][r], hc, s_srt[1] + s_start[1][r], hd, dist, S, fill);
+            }
+            if (cb) atomicOr(err, ERR_CELL);
+        }
+    }
+}
+
+// launch 3: reads the region models' row_to_col.  A pair on a real cell is served (stage 0): ws_req[cab] = the request,
+// both in case indices, and its distance joins sum0[c]; gap0[c] = the regions' total - dual_bound.  Every other cab and
+// request of the case goes to the rest lists in case order (ballot + popcount ranks): positions to rcab / rdem, case
+// indices to rcab_idx / rdem_idx, at the case's own offsets; nrest = their sizes, cnt2 = the same when both are non-empty
+// (else 0 / 0: no fifth solve).  A case with no cabs or no requests has no solve and no lists (split.py:62-64).
+__global__ __launch_bounds__(256) void k_split_rest(int batch, int R, int n_out, const int32_t *__restrict__ cab_off,
+                                                    const int32_t *__restrict__ cab, const int32_t *__restrict__ dem_off,
+                                                    const int32_t *__restrict__ dem, const int32_t *__restrict__ dist, int S,
+                                                    int32_t fill, const int32_t *__restrict__ roff_c,
+                                                    const int32_t *__restrict__ roff_d, const int32_t *__restrict__ rcnt,
+                                                    const int32_t *__restrict__ scab, const int32_t *__restrict__ scab_idx,
+                                                    const int32_t *__restrict__ sdem, const int32_t *__restrict__ sdem_idx,
+                                                    const int32_t *__restrict__ r2c1, const int64_t *__restrict__ tot1,
+                                                    const int64_t *__restrict__ dual1, int32_t *__restrict__ ws_req,
+                                                    int32_t *__restrict__ rcab, int32_t *__restrict__ rcab_idx,
+                                                    int32_t *__restrict__ rdem, int32_t *__restrict__ rdem_idx,
+                                                    int32_t *__restrict__ cnt2, int32_t *__restrict__ nrest,
+                                                    int64_t *__restrict__ sum0, int64_t *__restrict__ gap0, int *err)
+{
+    __shared__ int32_t s_req[BATCH_NMAX];     // cab -> request served in its region, or -1
+    __shared__ int32_t s_dsv[BATCH_NMAX];     // request served in its region
+    __shared__ int32_t s_rp[2][BATCH_NMAX];   // positions of the rest lists
+    __shared__ int64_t s_sum[4];
+    __shared__ int s_w[4], s_err;
+    const int tid = threadIdx.x, T = blockDim.x;
+    if (tid == 0) s_err = *(volatile int *)err;   // one read per workgroup: another workgroup may set a bit meanwhile
+    __syncthreads();
+    if (s_err) return;   // an earlier launch refused the input: nothing below is needed
+    for (int c = blockIdx.x; c < batch; c += gridDim.x) {
+        const int c0 = cab_off[c], d0 = dem_off[c];
+        const int ns = cab_off[c + 1] - c0, nd = dem_off[c + 1] - d0;
+        if (ns > BATCH_NMAX || nd > BATCH_NMAX) continue;   // k_split_part has set the error word
+        __syncthreads();   // the previous case's LDS is no longer read
+        for (int i = tid; i < ns; i += T) s_req[i] = -1;
+        for (int j = tid; j < nd; j += T) s_dsv[j] = 0;
+        __syncthreads();
+        if (ns == 0 || nd == 0) {
+            for (int i = tid; i < ns; i += T) ws_req[c0 + i] = -1;
+            if (tid == 0) {
+                cnt2[2 * c] = cnt2[2 * c + 1] = 0;
+                nrest[2 * c] = nrest[2 * c + 1] = 0;
+                sum0[c] = 0;
+                gap0[c] = 0;
+            }
+            continue;
+        }
+        int64_t sum = 0, gap = 0;
+        for (int r = 0; r < R; r++) {
+            const int m = c * R + r, nsr = rcnt[2 * m], ndr = rcnt[2 * m + 1];
+            if (nsr == 0) continue;   // uniform
+            const int rc = roff_c[m], rd = roff_d[m];
+            for (int i = tid; i < nsr; i += T) {
+                const int j = r2c1[(int64_t)m * n_out + i];
+                if ((uint32_t)j < (uint32_t)ndr) {   // a real cell; a dummy column leaves the cab to the rest
+                    const int ci = scab_idx[rc + i], dj = sdem_idx[rd + j];
+                    s_req[ci] = dj;
+                    s_dsv[dj] = 1;
+                    sum += pos_dist(dist, S, scab[rc + i], sdem[rd + j]);
+                }
+            }
+            if (tid == 0) gap += tot1[m] - dual1[m];
+        }
+        __syncthreads();
+        int kc = 0, kd = 0;
+        for (int base = 0; base < ns; base += T) {
+            const int i = base + tid;
+            const bool f = i < ns && s_req[i] < 0;
+            int tot;
+            const int at = kc + split_rank(f, s_w, &tot);
+            if (f) {
+                const int32_t p = cab[c0 + i];
+                rcab[c0 + at] = p;
+                rcab_idx[c0 + at] = i;
+                s_rp[0][at] = p;
+            }
+            kc += tot;
+        }
+        for (int base = 0; base < nd; base += T) {
+            const int j = base + tid;
+            const bool f = j < nd && !s_dsv[j];
+            int tot;
+            const int at = kd + split_rank(f, s_w, &tot);
+            if (f) {
+                const int32_t p = dem[d0 + j];
+                rdem[d0 + at] = p;
+                rdem_idx[d0 + at] = j;
+                s_rp[1][at] = p;
+            }
+            kd += tot;
+        }
+        for (int i = tid; i < ns; i += T) ws_req[c0 + i] = s_req[i];
+        sum = block_sum_i64(sum, s_sum);   // its barriers also complete s_rp
+        if (dist && split_cells_bad(s_rp[0], kc, s_rp[1], kd, dist, S, fill)) atomicOr(err, ERR_CELL);
+        if (tid == 0) {
+            const bool solve = kc > 0 && kd > 0;
+            cnt2[2 * c] = solve ? kc : 0;
+            cnt2[2 * c + 1] = solve ? kd : 0;
+            nrest[2 * c] = kc;
+            nrest[2 * c + 1] = kd;
+            sum0[c] = sum;
+            gap0[c] = gap;
+        }
+    }
+}
+
+// launch 5: the fifth models' row_to_col back to case indices (stage 1), their real-cell sums, and the caller's outputs.
+// Nothing is written when the error word is set: a refused call leaves every output as it was.
+__global__ __launch_bounds__(256) void k_split_final(int batch, int n_out, const int32_t *__restrict__ cab_off,
+                                                     const int32_t *__restrict__ dem_off, const int32_t *__restrict__ dist, int S,
+                                                     const int32_t *__restrict__ ws_req, const int32_t *__restrict__ rcab,
+                                                     const int32_t *__restrict__ rcab_idx, const int32_t *__restrict__ rdem,
+                                                     const int32_t *__restrict__ rdem_idx, const int32_t *__restrict__ cnt2,
+                                                     const int32_t *__restrict__ nrest, const int64_t *__restrict__ sum0,
+                                                     const int64_t *__restrict__ gap0, const int32_t *__restrict__ r2c2,
+                                                     const int64_t *__restrict__ tot2, const int64_t *__restrict__ dual2,
+                                                     int32_t *__restrict__ cab_req, int32_t *__restrict__ cab_stage,
+                                                     int64_t *__restrict__ total, int64_t *__restrict__ rest_total,
+                                                     int32_t *__restrict__ n_rest, int64_t *__restrict__ dual_gap,
+                                                     const int *__restrict__ err)
+{
+    __shared__ int32_t s_req[BATCH_NMAX], s_stage[BATCH_NMAX];
+    __shared__ int64_t s_sum[4];
+    const int tid = threadIdx.x, T = blockDim.x;
+    if (*err) return;   // uniform: nothing in this launch writes the word
+    for (int c = blockIdx.x; c < batch; c += gridDim.x) {
+        const int c0 = cab_off[c], d0 = dem_off[c];
+        const int ns = cab_off[c + 1] - c0;
+        __syncthreads();   // the previous case's LDS is no longer read
+        for (int i = tid; i < ns; i += T) {
+            const int v = ws_req[c0 + i];
+            s_req[i] = v;
+            s_stage[i] = v >= 0 ? 0 : -1;
+        }
+        __syncthreads();
+        const int kc = cnt2[2 * c], kd = cnt2[2 * c + 1];
+        int64_t sum = 0;
+        for (int i = tid; i < kc; i += T) {
+            const int j = r2c2[(int64_t)c * n_out + i];
+            if ((uint32_t)j < (uint32_t)kd) {
+                const int ci = rcab_idx[c0 + i];
+                s_req[ci] = rdem_idx[d0 + j];
+                s_stage[ci] = 1;
+                sum += pos_dist(dist, S, rcab[c0 + i], rdem[d0 + j]);
+            }
+        }
+        sum = block_sum_i64(sum, s_sum);
+        for (int i = tid; i < ns; i += T) {
+            cab_req[c0 + i] = s_req[i];
+            if (cab_stage) cab_stage[c0 + i] = s_stage[i];
+        }
+        if (tid == 0) {
+            total[c] = sum0[c] + sum;
+            if (rest_total) rest_total[c] = sum;
+            if (n_rest) {
+                n_rest[2 * c] = nrest[2 * c];
+                n_rest[2 * c + 1] = nrest[2 * c + 1];
+            }
+            if (dual_gap) dual_gap[c] = gap0[c] + tot2[c] - dual2[c];
+        }
+    }
+}
+
+Buf g_sp;                       // td_split_batched's device workspace (grow-only)
+std::vector<char> g_sp_host;    // its host destinations land here first: a refused call leaves the caller's arrays unwritten
+
 }  // namespace
 
 void td::pool2_greedy_launch(int batch, int n, const int32_t *d_ns, const int32_t *d_cost, int32_t *rows, int32_t *cols, int32_t *n_pairs)
@@ -1067,10 +1388,94 @@ int td_tick_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab
     return outputs_finish("td_tick_batched", o, 10, err_off);
 }
 
+int td_split_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab_to, const int32_t *dem_off, const int32_t *dem_from,
+                     const int32_t *dist, int S, int size, int parts, int32_t fill, int32_t *cab_req, int32_t *cab_stage,
+                     int64_t *total, int64_t *rest_total, int32_t *n_rest, int64_t *dual_gap)
+{
+    TD_REQUIRE_INIT();
+    const char *fn = "td_split_batched";
+    if (parts < 1 || parts > 32) return fail(TD_EINVAL, "%s: parts = %d outside [1, 32]", fn, parts);
+    if (size < parts) return fail(TD_EINVAL, "%s: size = %d < parts = %d", fn, size, parts);
+    if (dist && S < size) return fail(TD_EINVAL, "%s: the table has S = %d stands, fewer than size = %d", fn, S, size);
+    if (dist && fill < 1) return fail(TD_EINVAL, "%s: fill = %d < 1", fn, (int)fill);
+    if (!dist && (int64_t)size - 1 >= (int64_t)fill)
+        return fail(TD_EINVAL, "%s: the distance %d of the line's ends is not below fill = %d", fn, size - 1, (int)fill);
+    PosIn in;
+    int rc = pos_args(fn, batch, n, BATCH_NMAX, cab_off, cab_to, dem_off, dem_from, dist, S, &in);
+    if (rc) return rc;
+    if (batch == 0) return TD_OK;
+    if (!cab_req || !total) return fail(TD_EINVAL, "%s: null cab_req / total", fn);
+    const int ss = size / parts, R = (size + ss - 1) / ss, nl = in.nmax;
+    if (R >= SPLIT_RMAX) return fail(TD_EINTERNAL, "%s: %d ranges", fn, R);   // parts <= 32 gives at most 63
+    if ((int64_t)batch * R > INT_MAX / 2) return fail(TD_EINVAL, "%s: %d cases of %d ranges are more than 2^30 region models", fn, batch, R);
+    const size_t B = (size_t)batch, M = B * (size_t)R, nc = (size_t)g_off[0][batch], nd = (size_t)g_off[1][batch];
+    // workspace: the int64 arrays first, every array 256-byte aligned
+    size_t at = 0;
+    auto take = [&at](size_t bytes) {
+        const size_t o = at;
+        at += align256(bytes);
+        return o;
+    };
+    const size_t o_tot1 = take(8 * M), o_dual1 = take(8 * M), o_tot2 = take(8 * B), o_dual2 = take(8 * B), o_sum0 = take(8 * B),
+                 o_gap0 = take(8 * B), o_roffc = take(4 * (M + 1)), o_roffd = take(4 * (M + 1)), o_rcnt = take(8 * M),
+                 o_scab = take(4 * nc), o_scabi = take(4 * nc), o_sdem = take(4 * nd), o_sdemi = take(4 * nd),
+                 o_r2c1 = take(4 * M * (size_t)nl), o_wsreq = take(4 * nc), o_rcab = take(4 * nc), o_rcabi = take(4 * nc),
+                 o_rdem = take(4 * nd), o_rdemi = take(4 * nd), o_cnt2 = take(8 * B), o_nrest = take(8 * B),
+                 o_r2c2 = take(4 * B * (size_t)nl);
+    if ((rc = ensure(g_sp, at + 256))) return rc;
+    char *w = (char *)g_sp.p;
+    int64_t *tot1 = (int64_t *)(w + o_tot1), *dual1 = (int64_t *)(w + o_dual1), *tot2 = (int64_t *)(w + o_tot2),
+            *dual2 = (int64_t *)(w + o_dual2), *sum0 = (int64_t *)(w + o_sum0), *gap0 = (int64_t *)(w + o_gap0);
+    int32_t *roff_c = (int32_t *)(w + o_roffc), *roff_d = (int32_t *)(w + o_roffd), *rcnt = (int32_t *)(w + o_rcnt),
+            *scab = (int32_t *)(w + o_scab), *scab_idx = (int32_t *)(w + o_scabi), *sdem = (int32_t *)(w + o_sdem),
+            *sdem_idx = (int32_t *)(w + o_sdemi), *r2c1 = (int32_t *)(w + o_r2c1), *ws_req = (int32_t *)(w + o_wsreq),
+            *rcab = (int32_t *)(w + o_rcab), *rcab_idx = (int32_t *)(w + o_rcabi), *rdem = (int32_t *)(w + o_rdem),
+            *rdem_idx = (int32_t *)(w + o_rdemi), *cnt2 = (int32_t *)(w + o_cnt2), *nrest = (int32_t *)(w + o_nrest),
+            *r2c2 = (int32_t *)(w + o_r2c2);
+    Out o[6] = {{cab_req, sizeof(int32_t) * nc},   {cab_stage, sizeof(int32_t) * nc}, {total, sizeof(int64_t) * B},
+                {rest_total, sizeof(int64_t) * B}, {n_rest, sizeof(int32_t) * 2 * B}, {dual_gap, sizeof(int64_t) * B}};
+    size_t err_off;
+    if ((rc = outputs_prepare(o, 6, &err_off))) return rc;
+    int *d_err = (int *)((char *)g_out.p + err_off);
+    Ctx &c = ctx();
+    const int T = nl <= 64 ? 64 : 256, grid = std::min(batch, SPLIT_GRID);
+    k_split_part<<<grid, T, 0, c.stream>>>(batch, R, ss, size, in.cab_off, in.cab, in.dem_off, in.dem, in.dist, S, fill, roff_c, roff_d,
+                                           rcnt, scab, scab_idx, sdem, sdem_idx, cnt2, d_err);
+    PosIn rin = in;
+    rin.cab_off = roff_c;
+    rin.dem_off = roff_d;
+    launch_pos_assign((int)M, nl, nl, rin, scab, sdem, rcnt, S, fill, -1, r2c1, tot1, dual1, d_err);
+    k_split_rest<<<grid, T, 0, c.stream>>>(batch, R, nl, in.cab_off, in.cab, in.dem_off, in.dem, in.dist, S, fill, roff_c, roff_d, rcnt,
+                                           scab, scab_idx, sdem, sdem_idx, r2c1, tot1, dual1, ws_req, rcab, rcab_idx, rdem, rdem_idx,
+                                           cnt2, nrest, sum0, gap0, d_err);
+    launch_pos_assign(batch, nl, nl, in, rcab, rdem, cnt2, S, fill, -1, r2c2, tot2, dual2, d_err);
+    k_split_final<<<grid, T, 0, c.stream>>>(batch, nl, in.cab_off, in.dem_off, in.dist, S, ws_req, rcab, rcab_idx, rdem, rdem_idx, cnt2,
+                                            nrest, sum0, gap0, r2c2, tot2, dual2, (int32_t *)o[0].dptr(), (int32_t *)o[1].dptr(),
+                                            (int64_t *)o[2].dptr(), (int64_t *)o[3].dptr(), (int32_t *)o[4].dptr(),
+                                            (int64_t *)o[5].dptr(), d_err);
+    TD_HIP(hipGetLastError());
+    // host destinations: through g_sp_host (same layout as g_out), handed over only when the call succeeded
+    g_sp_host.resize(err_off);
+    for (int i = 0; i < 6; i++)
+        if (o[i].user && !o[i].dev && o[i].bytes)
+            TD_HIP(hipMemcpyAsync(g_sp_host.data() + o[i].off, (char *)g_out.p + o[i].off, o[i].bytes, hipMemcpyDeviceToHost, c.stream));
+    TD_HIP(hipMemcpyAsync(c.pinned, d_err, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    TD_HIP(hipStreamSynchronize(c.stream));
+    const int e = *(int *)c.pinned;
+    if (e & ERR_POS) return fail(TD_EINVAL, "%s: a cab_to / dem_from position outside [0, %d)", fn, size);
+    if (e & ERR_CELL) return fail(TD_EINVAL, "%s: a table entry used as a cell is outside [0, fill = %d)", fn, (int)fill);
+    if (e)
+        return fail(TD_EINTERNAL, "%s: a model hit a defensive loop cap (error word 0x%x: 1 search steps, 2 augmenting path, "
+                    "4 label range, 8 model size)", fn, e);
+    for (int i = 0; i < 6; i++)
+        if (o[i].user && !o[i].dev && o[i].bytes) memcpy(o[i].user, g_sp_host.data() + o[i].off, o[i].bytes);
+    return TD_OK;
+}
+
 }  // extern "C"
 
 void td::batch_release_workspace()
 {
-    Buf *bs[] = {&g_out, &g_ws, &g_in[0], &g_in[1], &g_in[2], &g_in[3], &g_in[4]};
+    Buf *bs[] = {&g_out, &g_ws, &g_sp, &g_in[0], &g_in[1], &g_in[2], &g_in[3], &g_in[4]};
     for (Buf *b : bs) buf_free(*b);
 }

@@ -24,6 +24,9 @@ Reference map (file:line in boguszjelinski/taxidispatcher):
     build_assign_batched  build_assign of many ragged position models per call (split.py's regions, zones of one tick)
     tick_batched          tick() of many ragged position models per call (Simulator.java:163-208 per zone / per seed)
     match_batched         maximum-weight matching of many general graphs per call (the optimum behind pool_opt_min.py)
+    split_batched         split.py:61-119 as a whole, for many cases per call (td_split_batched)
+    solve_split           split.py:61-119 for one case, the reference's call shape  -> total
+    split_gap             split.py's main (optimum, split total, LCM) as library calls
     pool2_batched         greedy (pool_opt_min.py:81-102) or optimal (:114-122) pools of two of many ragged models per call
     find_pool_optimal     find_pool's format, optimal pools
     pool_gap              pool_opt_min.py as two calls
@@ -664,6 +667,87 @@ def tick_batched(cab_tos, dem_froms, distances=None, big_cost=BIG_COST, drop_tim
                     "kept_dems": kd[b, :n_d - kk], "n_rest": nr, "row_to_col": r2c[b, :nr if solved else 0], "total": int(total[b]),
                     "solved": solved, "dual_bound": int(dual[b])})
     return out
+
+
+# ----------------------------------------------------------------------------------------
+# the split heuristic as a whole (td_split_batched)
+# ----------------------------------------------------------------------------------------
+def split_batched(cab_tos, dem_froms, size, parts=4, distances=None, fill=BIG_COST):
+    """td_split_batched: split.py:61-119 of B ragged cases in one call: the stand ranges of `size` stands in `parts` parts
+    (size / parts stands each, a short extra range when parts does not divide size) solved as region models, then one solve
+    per case over whoever the regions left over.  cab_tos / dem_froms: see pack_ragged; one shared distance table (None:
+    |a - b|).  Returns a dict: cab_req int32[all cabs] (the index within the case's request list of the request a cab serves,
+    or -1; case c's cabs at cab_off[c] : cab_off[c + 1]), cab_stage (0 region, 1 fifth solve, -1 not served), total int64[B],
+    rest_total int64[B] (the fifth solve's part), n_rest int32[B, 2] (rest cabs, rest requests), dual_gap int64[B] (0 certifies
+    every model of the case), cab_off int64[B + 1]."""
+    lib = _ffi.lib()
+    cv, co, dv, do, batch, n = pack_ragged(cab_tos, dem_froms)
+    ch = np.asarray(co.detach().cpu().numpy() if hasattr(co, "detach") else co, np.int64)
+    dptr, S, keep = _dist_arg(distances)
+    nc = int(ch[-1])
+    req, stage = _out((nc,), np.int32), _out((nc,), np.int32)
+    total, rest, gap = (_out((batch,), np.int64) for _ in range(3))
+    n_rest = _out((batch, 2), np.int32)
+    _ffi.check(lib.td_split_batched(batch, n, _ffi.addr(co), _ffi.addr(cv), _ffi.addr(do), _ffi.addr(dv), dptr, S, int(size), int(parts),
+                                    int(fill), _ffi.addr(req), _ffi.addr(stage), _ffi.addr(total), _ffi.addr(rest), _ffi.addr(n_rest),
+                                    _ffi.addr(gap)))
+    del keep
+    return {"cab_req": req, "cab_stage": stage, "total": total, "rest_total": rest, "n_rest": n_rest, "dual_gap": gap, "cab_off": ch}
+
+
+def solve_split(distances, demand, cabs, size, parts=4):
+    """split.py:61-119 for one case in the reference's call shape: demand / cabs are (id, from, to) records, a cab stands at
+    its `to`, a request at its `from`.  Returns the split total, or None when either list is empty (split.py:62-64)."""
+    demand, cabs = list(demand), list(cabs)
+    if not demand or not cabs:
+        return None
+    _, d_frm, _ = _records(demand)
+    _, _, c_to = _records(cabs)
+    return int(split_batched([c_to], [d_frm], size, parts, distances)["total"][0])
+
+
+def _rand_positions(rng, numb, size, cases, column):
+    """rand_list (split.py:41-52) for `cases` lists: numb draws of (from, to) in [0, size), a record with from == to is dropped;
+    returns the kept records' `column` (0 = from, 1 = to) per list"""
+    ft = rng.integers(0, size, (cases, numb, 2))
+    keep = ft[:, :, 0] != ft[:, :, 1]
+    return [ft[c, keep[c], column].astype(np.int32) for c in range(cases)]
+
+
+def split_gap(n_stands=20, n_size=10, cases=1000, seed=None, parts=4):
+    """split.py's main as library calls, for `cases` random cases on the line of n_stands stands: the unsplit optimum
+    (build_assign_batched), the split total (split_batched) and split.py:161-175's LCM (LCM_batched over chunks of cases whose
+    cost slab stays below 256 MiB), each summed over real cells only.  Returns (optima, split_totals, lcm_totals int64[cases],
+    split gap, LCM gap), a gap being 100 * (sum x - sum opt) / sum opt.  Raises when a split total is below its optimum."""
+    rng = np.random.default_rng(seed)
+    dems = _rand_positions(rng, n_size, n_stands, cases, 0)
+    cabs = _rand_positions(rng, n_size, n_stands, cases, 1)
+    n_s = np.array([c.size for c in cabs], np.int64)
+    n_d = np.array([d.size for d in dems], np.int64)
+    nb = np.maximum(n_s, n_d)
+    _, padded = build_assign_batched(cabs, dems)
+    opt = np.where((n_s > 0) & (n_d > 0), padded - np.abs(n_s - n_d) * BIG_COST, 0)   # dummy cells count fill in td_build_assign
+    split = split_batched(cabs, dems, n_stands, parts)["total"].astype(np.int64)
+    bad = np.nonzero(split < opt)[0]
+    if bad.size:
+        raise _ffi.TdError("split total below the optimum in %d cases (first: %d: %d < %d)"
+                           % (bad.size, int(bad[0]), int(split[bad[0]]), int(opt[bad[0]])))
+    n = int(nb.max()) if cases else 0
+    lcm = np.zeros(cases, np.int64)
+    chunk = max(1, (256 * 2**20 - 1) // max(1, 4 * n * n))
+    for lo in range(0, cases if n else 0, chunk):
+        hi = min(cases, lo + chunk)
+        pc = np.zeros((hi - lo, n), np.int32)
+        pd = np.zeros((hi - lo, n), np.int32)
+        for k in range(lo, hi):
+            pc[k - lo, :n_s[k]] = cabs[k]
+            pd[k - lo, :n_d[k]] = dems[k]
+        real = (np.arange(n)[None, :, None] < n_s[lo:hi, None, None]) & (np.arange(n)[None, None, :] < n_d[lo:hi, None, None])
+        slab = np.where(real, np.abs(pc[:, :, None] - pd[:, None, :]), BIG_COST).astype(np.int32)
+        lcm[lo:hi] = LCM_batched(slab, nb[lo:hi].astype(np.int32), mask=BIG_COST, threshold=-1, sum_below=BIG_COST)[0]
+    so = float(opt.sum())
+    gaps = tuple(100.0 * (float(x.sum()) - so) / so if so else 0.0 for x in (split, lcm))
+    return opt, split, lcm, gaps[0], gaps[1]
 
 
 # ----------------------------------------------------------------------------------------
