@@ -556,6 +556,42 @@ TD_API int td_pool_n(int k, int n, const int32_t *from, const int32_t *to, const
 TD_API int td_pool_merge(int k, int n_requests, int n_in, const int32_t *pools_in /* n_in * (2k+1) */,
                          int sort_by_cost, int max_pools, int32_t *pools_out, int32_t *n_out);
 
+/* ---- f-4 for MANY models per call ------------------------------------------------------
+ * td_pool_n_batched: B ragged models, model b = requests [off[b], off[b+1]) of the concatenated from / to / max_wait /
+ *   max_loss arrays (request indices in the output are positions within the model), one shared table (dist S x S, or NULL
+ *   = |a - b|).  n: the output stride, every model size n_b <= n <= 512 (a larger model stays td_pool_n over slices).
+ *   Arrays may be host or device memory (outputs too); the call is synchronous; batch == 0 is a no-op.  One workgroup per
+ *   model enumerates, selects and writes the records (csrc/td_pool_batch.hip): no launch, sort or host synchronisation per
+ *   model.
+ *   Model b is exactly td_pool_n(k, n_b, ..., first0, first1, ...) on its own requests: the same wait rule (the level-0 test
+ *   0 > max_wait[p0] included), the same happiness test in double with 1 + loss / 100.0, the same cost, the same order
+ *   (stable by cost, the reference's enumeration order among equal costs) and the same de-duplication.  first == NULL:
+ *   every request may be the first pick-up; else first[2b], first[2b+1] is model b's first-pick-up slice, clamped to
+ *   [0, n_b] as td_pool_n clamps it: findpool.c's 8 children are 8 models of one batch (the same demand, 8 slices).  An
+ *   empty slice or n_b < k gives 0 pools and 0 happy plans.
+ *   pools: records of 2k+1 ints (pick-ups, drop-offs, cost), model b's from b * (n / k) * (2k + 1); a model keeps at most
+ *   n_b / k pools, so nothing is truncated; nothing is written behind a model's n_pools[b] records; may be NULL when
+ *   n / k == 0.  n_pools[B];  n_happy[B] (may be NULL): happy plans before de-duplication;  total[B] (may be NULL): the sum
+ *   of the listed costs.
+ *   max_happy: the most happy plans one model may have (<= 0: 65536; at most 2^22).  Plan storage is (workgroups in flight)
+ *   x max_happy 8-byte keys, workgroups in flight = min(1024, 1 GiB / (8 max_happy)) whatever the batch: grow-only, counted
+ *   by td_workspace_bytes, released by td_shutdown; inputs and results are staged in one block that grows in 4 MiB steps.
+ *   TD_EINVAL, every output unwritten: k outside 2..4, batch < 0, n outside [0, 512], off[0] != 0, a decreasing offset, a
+ *   model larger than n, a null required array, dist with S <= 0, max_happy > 2^22, and, with a table, a from / to outside
+ *   [0, S) (checked on the device; td_last_error() names the first such model).  TD_ERANGE when some model has more than
+ *   max_happy happy plans (the message names the first such model and its count; n_happy[] is still written for every
+ *   model, nothing else is), or when a happy plan's cost is negative or above 16383 (td_pool_n's limit; nothing is written).
+ *   When to use which: td_pool_n_batched for many models of at most 512 requests each.  Measured on one MI355X (host clock,
+ *   host arrays): 1000 models x 100 requests take 3.80 / 4.13 / 8.90 ms at k = 2 / 3 / 4 against 104 / 163 / 833 ms for a loop
+ *   of td_pool_n (27x / 39x / 94x); 1000 x 40: 29x / 36x / 70x; 64 x 256: 9.8x / 5.1x / 3.4x; findpool.c's 8 children of the
+ *   committed fixture demands (40..400 requests) as one batch: 2.1x .. 11.2x.  No measured shape has the loop ahead.  td_pool_n remains the call for one model,
+ *   for any model above 512 requests and for more than 2^22 happy plans per slice.
+ */
+TD_API int td_pool_n_batched(int k, int batch, int n, const int32_t *off,
+                             const int32_t *from, const int32_t *to, const int32_t *max_wait, const int32_t *max_loss,
+                             const int32_t *dist, int S, const int32_t *first /* [2*batch] or NULL */,
+                             int64_t max_happy, int32_t *pools, int32_t *n_pools, int64_t *n_happy, int64_t *total);
+
 /* ---- a-7 objective evaluation  (greedy_opt.py:21-29 count_sum) ---------------------- */
 TD_API int td_count_sum(int n, const int32_t *cost, const int32_t *row_to_col, int64_t big_cost,
                  int64_t *sum, int32_t *n_real);

@@ -97,6 +97,8 @@ void pool2_greedy_launch(int batch, int n, const int32_t *d_ns, const int32_t *d
 void match_release_workspace();
 // td_pool.hip: frees td_pool_n / td_pool_merge's workspace (td_shutdown)
 void pool_release_workspace();
+// td_pool_batch.hip: frees td_pool_n_batched's key slab and staging (td_shutdown)
+void pool_batch_release_workspace();
 void prof_begin(int k);
 void prof_end(int k);
 void prof_flush();

@@ -28,39 +28,11 @@
 #include <hipcub/hipcub.hpp>
 
 #include "td_common.h"
+#include "td_pool_core.h"
 
 using namespace td;
 
 namespace {
-
-constexpr int PN_MAXN = 2047;          // 4 * 11 bits + 5 bits of drop-off order < 2^50
-constexpr int PN_SEQ_BITS = 50;
-constexpr unsigned long long PN_SEQ_MASK = (1ull << PN_SEQ_BITS) - 1ull;
-constexpr int PN_MAXCOST = (1 << 14) - 1;
-
-// the k! drop-off orders in lexicographic order (the recursion order of pool_n.c:140-153), 2 bits per slot
-__host__ __device__ inline int pn_perm(int k, int qi, int *q)
-{
-    // generate the qi-th permutation of 0..k-1 in lexicographic order
-    int avail[4] = {0, 1, 2, 3};
-    int f = 1;
-    for (int i = 2; i < k; i++) f *= i;   // (k-1)!
-    int left = k;
-    for (int i = 0; i < k; i++) {
-        const int idx = qi / f;
-        qi -= idx * f;
-        q[i] = avail[idx];
-        for (int j = idx; j < left - 1; j++) avail[j] = avail[j + 1];
-        left--;
-        if (left > 1) f /= left;
-    }
-    return 0;
-}
-
-__device__ __forceinline__ int pn_d(const int32_t *dist, int S, int a, int b)
-{
-    return dist ? dist[(int64_t)a * S + b] : (a > b ? a - b : b - a);
-}
 
 struct PnCtl {
     unsigned long long happy;   // happy plans found (may exceed the capacity: then the call fails)
@@ -68,35 +40,6 @@ struct PnCtl {
     int kept;
     int bad;                    // td_pool_merge: n_in - (first record naming a request outside [0, n_requests)), 0: none
 };
-
-// happiness of all passengers + plan cost for pick-ups p and drop-off order q
-template <int K>
-__device__ __forceinline__ bool pn_check(const int *p, const int *q, const int32_t *sf, const int32_t *st,
-                                         const int32_t *sl, const int32_t *dist, int S, int *cost_out)
-{
-    int pick[K];   // pick[i] = d(from p[i], from p[i+1]); suffix sums give "rest of the pick-up path"
-    int ptot = 0;
-#pragma unroll
-    for (int i = 0; i < K - 1; i++) {
-        pick[i] = pn_d(dist, S, sf[p[i]], sf[p[i + 1]]);
-        ptot += pick[i];
-    }
-    const int first = pn_d(dist, S, sf[p[K - 1]], st[p[q[0]]]);
-    int drop = 0;
-    bool happy = true;
-#pragma unroll
-    for (int d = 0; d < K; d++) {
-        if (d > 0) drop += pn_d(dist, S, st[p[q[d - 1]]], st[p[q[d]]]);
-        int c = first + drop;
-#pragma unroll
-        for (int ph = 0; ph < K - 1; ph++) c += (ph >= q[d]) ? pick[ph] : 0;
-        const int x = p[q[d]];
-        const double lim = (double)pn_d(dist, S, sf[x], st[x]) * (1 + sl[x] / 100.0);
-        if ((double)c > lim) happy = false;
-    }
-    *cost_out = ptot + first + drop;
-    return happy;
-}
 
 template <int K>
 __global__ __launch_bounds__(256) void k_pooln_enum(int n, const int32_t *__restrict__ from, const int32_t *__restrict__ to,

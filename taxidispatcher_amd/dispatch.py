@@ -30,6 +30,8 @@ Reference map (file:line in boguszjelinski/taxidispatcher):
     pool2_batched         greedy (pool_opt_min.py:81-102) or optimal (:114-122) pools of two of many ragged models per call
     find_pool_optimal     find_pool's format, optimal pools
     pool_gap              pool_opt_min.py as two calls
+    pool_n_batched        pool_n.c (pools of 2..4) of many models of at most 512 requests per call
+    find_pool_fanout      findpool.c as two calls: the 8 children as one batch, then the merge
 """
 import ctypes
 
@@ -416,6 +418,63 @@ def merge_pools(k, n_requests, lists):
     _ffi.check(lib.td_pool_merge(int(k), int(n_requests), int(allp.shape[0]), _ffi.addr(allp) if allp.size else None,
                                  1 if k == 4 else 0, cap, _ffi.addr(out), ctypes.byref(m)))
     return out[:m.value].copy()
+
+
+POOL_N_BATCHED_NMAX = 512   # largest model of pool_n_batched
+
+
+def pack_pool_n(demands, firsts=None):
+    """pool_n_batched's packing: a list of demand row arrays (id, from, to, max_wait, max_loss) -> (off int32[B + 1], from,
+    to, max_wait, max_loss int32[all requests], first int32[B, 2] or None, batch, n = the largest model).  firsts: per model
+    None (every request may be the first pick-up) or a (first0, first1) slice."""
+    rows = [_ffi.as_i32(np.asarray(d).reshape(len(d), -1)) if len(d) else np.zeros((0, 5), np.int32) for d in demands]
+    for b, d in enumerate(rows):
+        if d.shape[1] < 5:
+            raise _ffi.TdError("model %d: demand rows are (id, from, to, max_wait, max_loss)" % b)
+    batch = len(rows)
+    sizes = np.array([d.shape[0] for d in rows], np.int64)
+    off = np.zeros(batch + 1, np.int32)
+    off[1:] = np.cumsum(sizes)
+    allr = np.concatenate(rows, 0) if batch else np.zeros((0, 5), np.int32)
+    frm, to, wait, loss = (np.ascontiguousarray(allr[:, c]) for c in (1, 2, 3, 4))
+    first = None
+    if firsts is not None:
+        if len(firsts) != batch:
+            raise _ffi.TdError("%d first-pick-up slices for %d models" % (len(firsts), batch))
+        first = np.zeros((batch, 2), np.int32)
+        for b, f in enumerate(firsts):
+            first[b] = (0, sizes[b]) if f is None else (int(f[0]), int(f[1]))
+    return off, frm, to, wait, loss, first, batch, int(sizes.max()) if batch else 0
+
+
+def pool_n_batched(k, demands, distances=None, firsts=None, max_happy=0):
+    """td_pool_n_batched: pool_n.c for B models in one call, one shared distance table (None: |a - b|).  demands: a list of
+    row arrays (id, from, to, max_wait, max_loss) as find_pool_n takes, each of at most 512 requests; firsts: per model None or
+    its first-pick-up slice (first0, first1).  Returns (a list of int32 arrays [m_b, 2k+1] of pick-ups, drop-offs, cost in the
+    reference's output order, request indices being positions within the model; int64[B] happy plans per model)."""
+    lib = _ffi.lib()
+    if not 2 <= int(k) <= 4:
+        raise _ffi.TdError("pool size %d (2..4)" % int(k))
+    off, frm, to, wait, loss, first, batch, n = pack_pool_n(demands, firsts)
+    dptr, S, keep = _dist_arg(distances)
+    per = n // int(k)
+    pools = _out((batch, per, 2 * int(k) + 1), np.int32)
+    m, nh = _out((batch,), np.int32), _out((batch,), np.int64)
+    _ffi.check(lib.td_pool_n_batched(int(k), batch, n, _ffi.addr(off), _ffi.addr(frm), _ffi.addr(to), _ffi.addr(wait), _ffi.addr(loss),
+                                     dptr, S, _ffi.addr(first), int(max_happy), _ffi.addr(pools), _ffi.addr(m), _ffi.addr(nh), None))
+    del keep
+    return [pools[b, :int(m[b])].copy() for b in range(batch)], nh
+
+
+def find_pool_fanout(k, demand, distances=None, children=8):
+    """findpool.c as two calls: its `children` first-pick-up slices (pool_n.c:243-246) as one batch of `children` models of
+    the same demand, then the merge (findpool.c:73-98,166-172).  Returns the merged int32 array [m, 2k+1]."""
+    d = np.asarray(demand).reshape(len(demand), -1)
+    n = int(d.shape[0])
+    step = n // children + 1
+    firsts = [(step * c, min(n, step * c + step)) for c in range(children)]
+    lists, _ = pool_n_batched(k, [d] * children, distances, firsts)
+    return merge_pools(k, n, lists)
 
 
 def count_sum(nn, cost, res, big_cost=BIG_COST):
