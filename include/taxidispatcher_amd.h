@@ -738,7 +738,18 @@ TD_API int td_profile_reset(void);
  *    32  redone with the measured range after a wrong hint (the other bits are those of the second run)
  *    64  pairs returned through the pinned block          128  called as td_pool2
  *   Word [11] is set to 0 when td_lcm / td_pool2 is entered and filled in before it returns; it is defined only right
- *   after such a call.  Other calls may clear it (td_assign zeroes all 16 words on its line-metric path). */
+ *   after such a call.  Other calls may clear it (td_assign zeroes all 16 words on its line-metric path).
+ * [12] = line_path, what the last td_assign's line-metric attempt did, as a bit set (DESIGN.md 2.9 has the constants):
+ *     1  the probe was launched                           2  verdict 1 (balanced) on the matrix that was finished
+ *     4  the caller's matrix got verdict 2 (constant trailing columns) and the attempt went on on the transpose
+ *     8  verdict 3: the unbalanced plan (constant rows)  16  q was taken from the second row asked (row 0 saw no difference)
+ *    32  rows 0 and 1 coincide: i2 came from the search over the sampled rows
+ *    64  ... and that search found it only on column q  128  column keys negated
+ *   256  certificate pass with 16-byte loads            512  64-bit prices (a price left +-2^30)
+ *  1024  accepted (always equal to word [8])
+ *   Word [12] is set to 0 when td_assign is entered, filled in as the attempt proceeds and kept when the general solver
+ *   takes over, so a refusal can be read too.  After a transposed retry bits 2, 8 and 16..512 describe the probe and the
+ *   finish on the transpose.  The sharded entry points (td_line_shard_*) do not set it. */
 TD_API int td_last_stats(int64_t *out, int n);
 
 #ifdef __cplusplus

@@ -4144,6 +4144,7 @@ int assign_impl(Solver &sv, int n, const int32_t *cost, int32_t *row_to_col, int
     g_hint.valid = false;
     TD_REQUIRE_INIT();
     Ctx &c = ctx();
+    c.stats[12] = 0;   // line_path: filled in as the line attempt proceeds, kept when the general solver takes over
     read_tunables();
     if (n < 0) return fail(TD_EINVAL, "n < 0");
     if (n == 0) {  // solver.py:12  "if n==0: return 0, []"
@@ -4204,6 +4205,7 @@ int assign_impl(Solver &sv, int n, const int32_t *cost, int32_t *row_to_col, int
         // (one-trip sequence: the probe also clears the control words for the compress pass queued behind it)
         if ((rc = line_probe_launch(n, sv.d_cost, &sv.skip, g_one_trip ? (int *)sv.misc.p : nullptr, CTL_ALL))) return rc;
         line_pending = true;
+        c.stats[12] = LP_PROBE;
         sv.ctl_clear = g_one_trip != 0;
     }
     c.stats[8] = 0;
@@ -4328,13 +4330,18 @@ restart:
                     if ((rc = line_probe_wait(&mode, &kd))) return rc;
                     if (getenv("TD_DEBUG")) fprintf(stderr, "[td] line probe on the transpose: verdict %d, %d constant rows\n", mode, kd);
                     line_t = true;
+                    c.stats[12] |= LP_TRANSPOSE;
                 }
                 if (mode == 1 || mode == 3) {
-                    if ((rc = line_finish(n, mode == 3 ? kd : 0, line_t ? (const int32_t *)sv.tbuf.p : sv.d_cost, &res, &tot, &accepted)))
+                    int fin = 0;
+                    if ((rc = line_finish(n, mode == 3 ? kd : 0, line_t ? (const int32_t *)sv.tbuf.p : sv.d_cost, &res, &tot, &accepted, &fin)))
                         return rc;
+                    c.stats[12] |= (mode == 1 ? LP_BALANCED : LP_UNBAL) | fin;
                 }
                 if (accepted) {
+                    const int64_t line_path = c.stats[12] | LP_ACCEPTED;
                     for (int k = 0; k < 16; k++) c.stats[k] = 0;
+                    c.stats[12] = line_path;
                     c.stats[4] = 4;
                     c.stats[7] = line_t ? 1 : 0;
                     c.stats[8] = 1;

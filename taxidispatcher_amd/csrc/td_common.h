@@ -63,11 +63,15 @@ int to_device(const void *src, size_t bytes, Buf &stage, const void **out);
 //   line_probe_wait    waits for the probe alone (its call number in the pinned verdict block, not the stream) and returns its verdict:
 //                      0 refused, 1 plausible, 2 constant trailing columns (retry on the transpose),
 //                      3 plausible with *k constant rows (the unbalanced model)
-//   line_finish        keys, sort, prices, certificate pass; *accepted = 1: *r2c_dev / *total are proven optimal
+//   line_finish        keys, sort, prices, certificate pass; *accepted = 1: *r2c_dev / *total are proven optimal;
+//                      *path = the LP_QROW2 .. LP_WIDE bits of the probe and of this finish, accepted or not
+// td_last_stats word 12 (line_path): what the last td_assign's line attempt did (the public header lists the bits)
+enum { LP_PROBE = 1, LP_BALANCED = 2, LP_TRANSPOSE = 4, LP_UNBAL = 8, LP_QROW2 = 16, LP_I2SEARCH = 32, LP_I2COLQ = 64, LP_REV = 128,
+       LP_VEC = 256, LP_WIDE = 512, LP_ACCEPTED = 1024 };
 int line_probe_launch(int n, const int32_t *d_cost, const long long **skip_dev, int *clear_words = nullptr, int nclear = 0);
 int line_probe_wait(int *mode, int *k, int *suspicious = nullptr /* the 1-byte attempt is void: the probe made the queued pass a no-op */,
                     int *shape3 = nullptr /* int[4]: estimated constant columns / rows, row 0 too wide for one byte, value of the last column */);
-int line_finish(int n, int k, const int32_t *d_cost, const int32_t **r2c_dev, int64_t *total, int *accepted);
+int line_finish(int n, int k, const int32_t *d_cost, const int32_t **r2c_dev, int64_t *total, int *accepted, int *path);
 void line_release_workspace();
 // td_assign.hip: a hint for the NEXT td_assign call of this process (consumed by it): the matrix is a model padded with
 // `const_cols` dummy requests and `const_rows` dummy cabs of value `fill` (td_tick knows this from its position arrays)

@@ -37,7 +37,8 @@ namespace {
 
 // LC_PLAUS: 0 refused; 1 balanced line metric plausible; 2 constant trailing COLUMNS (retry on the transpose);
 //           3 plausible with LC_K constant rows (the unbalanced model: fewer cabs than requests)
-enum { LC_P = 0, LC_Q, LC_I1, LC_I2, LC_PLAUS, LC_REV, LC_FAIL, LC_FITS32, LC_TOTAL, LC_K, LC_FILL, LC_SKIP, LC_WORDS };
+// LC_PATH:  the probe's branches as td_last_stats word 12 names them (LP_QROW2, LP_I2SEARCH, LP_I2COLQ)
+enum { LC_P = 0, LC_Q, LC_I1, LC_I2, LC_PLAUS, LC_REV, LC_FAIL, LC_FITS32, LC_TOTAL, LC_K, LC_FILL, LC_SKIP, LC_PATH, LC_WORDS };
 constexpr int VERDICT_SEQ = 7;  // word of the probe's verdict block (pinned host memory) that takes the call number, last
 constexpr int LINE_KMAX = 256;  // most constant rows the unbalanced plan is made for: k prefix-min scans of n by one workgroup and O(k n) scratch (k = 256, n = 16 384: ~4 ms and 100 MB against > 400 ms for the general solver; 32 until round 3)
 
@@ -101,6 +102,7 @@ __global__ __launch_bounds__(1024) void k_line_probe(int n, const int32_t *__res
     for (int k = threadIdx.x; k < nclear; k += blockDim.x) clear_words[k] = 0;
     __shared__ ArgMax sh[16];
     __shared__ int s_cnt;
+    __shared__ int s_path;   // LC_PATH, kept by thread 0 alone (in LDS: the kernel has no register to spare)
     const int t = threadIdx.x, T = blockDim.x;
     const int p = 0, i1 = 0;
     const int step = n > 1024 ? n / 1024 : 1;
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(1024) void k_line_probe(int n, const int32_t *__res
     const long long B0 = c[(size_t)(n - 1) * n], B1 = c[n - 1];
     int mode = 0, rev = 0, q = -1, rq = 0, i2 = -1, kdummy = 0;
     int bad_a = 0, bad_b = 0, rowvar = 0, colvar = 0, far = 0;
-    if (t == 0) s_cnt = 0;
+    if (t == 0) s_cnt = 0, s_path = 0;
     if (t < n) {
         const long long xx = c[t], yy = c[(size_t)n + t];
         bad_a = !span_ok(xx, yy, Ea);
@@ -215,6 +217,7 @@ __global__ __launch_bounds__(1024) void k_line_probe(int n, const int32_t *__res
             }
             r = block_argmax(x, sh);
             if (r.v != 0) q = r.i;
+            if (t == 0) s_path |= LP_QROW2;
         }
         if (cols_ok && q >= 0) {
             if (w0 != u0 || c[(size_t)n + q] != c[q])
@@ -232,6 +235,7 @@ __global__ __launch_bounds__(1024) void k_line_probe(int n, const int32_t *__res
                     }
                     r = block_argmax(x, sh);
                     if (r.v != 0) i2 = r.i;
+                    if (t == 0) s_path |= attempt == 0 ? LP_I2SEARCH : LP_I2COLQ;
                 }
                 if (i2 >= 0) {
                     const long long uu = c[(size_t)i1 * n + p], ww = c[(size_t)i2 * n + p];
@@ -290,6 +294,7 @@ __global__ __launch_bounds__(1024) void k_line_probe(int n, const int32_t *__res
         ctl[LC_TOTAL] = 0;
         ctl[LC_K] = kdummy;
         ctl[LC_FILL] = B0;
+        ctl[LC_PATH] = s_path;
         ctl[LC_SKIP] = (mode != 0 || suspicious) ? 1 : 0;   // the speculative 1-byte compress pass queued behind this probe is void either way
         host_verdict[3] = est_cc;
         host_verdict[4] = est_cr;
@@ -921,8 +926,9 @@ int line_probe_wait(int *mode, int *k, int *suspicious, int *shape3)
 
 // The sorted matching on the n x n device matrix (after a "plausible" probe; k > 0: the last k rows of the sorted
 // order are constant rows, verdict 3). *accepted = 1: *r2c_dev points at the library's device copy of row_to_col
-// and *total is its cost, proven optimal by the certificate pass.
-int line_finish(int n, int k, const int32_t *d_cost, const int32_t **r2c_dev, int64_t *total, int *accepted)
+// and *total is its cost, proven optimal by the certificate pass.  *path: the probe's and this finish's bits of
+// td_last_stats word 12 (LP_QROW2 .. LP_WIDE), accepted or not.
+int line_finish(int n, int k, const int32_t *d_cost, const int32_t **r2c_dev, int64_t *total, int *accepted, int *path)
 {
     Ctx &c = ctx();
     *accepted = 0;
@@ -939,6 +945,7 @@ int line_finish(int n, int k, const int32_t *d_cost, const int32_t **r2c_dev, in
     long long *ctl = (long long *)g_lw.ctl.p;
     auto *kin = (unsigned long long *)g_lw.kin.p, *kout = (unsigned long long *)g_lw.kout.p;
     int *vin = (int *)g_lw.vin.p, *vout = (int *)g_lw.vout.p;
+    bool vec_loads = false;
     {
         ProfScope ps(TD_K_LINE);
         k_line_keys<<<std::max(1, std::min(c.n_cu * 4, (2 * n + 255) / 256)), 256, 0, c.stream>>>(n, d_cost, ctl, kin, vin);
@@ -974,6 +981,7 @@ int line_finish(int n, int k, const int32_t *d_cost, const int32_t **r2c_dev, in
         const int ngroups = (n + R - 1) / R;
         const int grid = std::max(1, std::min(ngroups, c.n_cu * 16));
         const bool vec = (n % 4 == 0) && (((uintptr_t)d_cost & 15) == 0);
+        vec_loads = vec;
         if (vec)
             k_line_cert<R, true><<<grid, 256, 0, c.stream>>>(n, n, d_cost, (const long long *)g_lw.v64.p, (const int32_t *)g_lw.v32.p,
                                                              (const int *)g_lw.r2c.p, ctl);
@@ -985,6 +993,8 @@ int line_finish(int n, int k, const int32_t *d_cost, const int32_t **r2c_dev, in
     TD_HIP(hipMemcpyAsync(c.pinned, ctl, LC_WORDS * sizeof(long long), hipMemcpyDeviceToHost, c.stream));
     TD_HIP(hipStreamSynchronize(c.stream));
     const long long *h = (const long long *)c.pinned;
+    *path = ((int)h[LC_PATH] & (LP_QROW2 | LP_I2SEARCH | LP_I2COLQ)) | (h[LC_REV] ? LP_REV : 0) | (vec_loads ? LP_VEC : 0) |
+            (h[LC_FITS32] ? 0 : LP_WIDE);
     if (h[LC_FAIL] == 0) {
         *accepted = 1;
         *total = h[LC_TOTAL];

@@ -388,19 +388,29 @@ def _line_instance(n, seed, spread=10):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,world,spread", [(2048, 4, 10), (1001, 3, 10), (513, 8, 1), (4096, 1, 1000), (96, 5, 10)])
+@pytest.mark.parametrize("n,world,spread", [(2048, 4, 10), (1001, 3, 10), (513, 8, 1), (4096, 1, 1000), (96, 5, 10), (16385, 3, 10)])
 def test_line_sharded_in_process_equals_sorted_matching(td, n, world, spread):
     """the line-metric path over row shards (td_line_shard_*), `world` shards driven in one process:
     the total is the sorted matching's (== the oracle's optimum), every shard certifies its rows, the local
-    row_to_col pieces form a permutation; ragged shards, n % 4 != 0 (scalar certificate loads), duplicate positions."""
+    row_to_col pieces form a permutation; ragged shards, n % 4 != 0 (scalar certificate loads), duplicate positions.
+    n = 16385: phase 3 runs k_line_scan on the shards' workspace, here through the second trip of its base loop
+    (16384 elements a base); that matrix is built on the device and the matched cells are gathered there."""
     import torch
     from oracle import oracle
     from taxidispatcher_amd import sharded
-    cost, a, b = _line_instance(n, 21, spread)
+    if n <= 8192:
+        cost, a, b = _line_instance(n, 21, spread)
+        full = torch.from_numpy(cost).cuda()
+    else:
+        rng = np.random.default_rng(21)
+        a, b = rng.integers(0, spread * n, n), rng.integers(0, spread * n, n)
+        full = torch.empty((n, n), dtype=torch.int32, device="cuda")
+        ta, tb = torch.as_tensor(a, device="cuda"), torch.as_tensor(b, device="cuda")
+        for r0 in range(0, n, 2048):     # |a_i - b_j| in int64, then the cast, a block of rows at a time
+            full[r0:r0 + 2048] = (ta[r0:r0 + 2048, None] - tb[None, :]).abs().to(torch.int32)
     ref = int(np.abs(np.sort(a) - np.sort(b)).sum())     # an optimal matching of points on a line does not cross
     if n <= 1001:
         assert ref == oracle.assign(cost)[0]
-    full = torch.from_numpy(cost).cuda()
     shards = []
     try:
         for r in range(world):
@@ -415,7 +425,10 @@ def test_line_sharded_in_process_equals_sorted_matching(td, n, world, spread):
     r2c = np.concatenate(parts)
     assert total == ref
     assert sorted(r2c.tolist()) == list(range(n))
-    assert int(cost[np.arange(n), r2c].sum()) == ref
+    matched = full[torch.arange(n, device="cuda"), torch.as_tensor(r2c, device="cuda").long()]
+    assert int(matched.sum(dtype=torch.int64).item()) == ref
+    del full, matched
+    torch.cuda.empty_cache()
 
 
 @pytest.mark.gpu

@@ -67,7 +67,7 @@ def solve_section(cases):
             cost = int(c[ar, torch.as_tensor(r, device="cuda").long().clamp(0, n - 1)].sum().item())
             out["%s_%d_%s" % (name, n, "dev" if dev_out else "host")] = {
                 "total": int(total.value), "dual": int(dual.value), "sha1": hashlib.sha1(r.tobytes()).hexdigest(),
-                "stats": sorted([k, int(v)] for k, v in td.last_stats().items() if k != "lcm_path"), "is_permutation": perm, "cost_of_r2c": cost}
+                "stats": sorted([k, int(v)] for k, v in td.last_stats().items() if k not in ("lcm_path", "line_path")), "is_permutation": perm, "cost_of_r2c": cost}
         del c
     return out
 

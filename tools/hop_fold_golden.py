@@ -77,7 +77,7 @@ def solve_section(sec, cases):
             r2c = torch.full((n,), -7, dtype=torch.int32, device="cuda") if dev_out else np.full(n, -7, np.int32)
             _ffi.check(lib.td_assign(n, _ffi.addr(c), _ffi.addr(r2c), ctypes.byref(total), ctypes.byref(dual)))
             r = r2c.cpu().numpy() if dev_out else r2c
-            out[key] = record(torch, c, n, r, total.value, dual.value, sorted([k, int(v)] for k, v in td.last_stats().items() if k != "lcm_path"))
+            out[key] = record(torch, c, n, r, total.value, dual.value, sorted([k, int(v)] for k, v in td.last_stats().items() if k not in ("lcm_path", "line_path")))
         if sec == "shards":   # the same matrix through the shard API, every shard in this process
             from taxidispatcher_amd import sharded
             sys.stderr.write("== %s/%d_%s_%d_api\n" % (sec, idx, name, n))
