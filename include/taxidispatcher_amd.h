@@ -119,11 +119,13 @@ TD_API int td_assign(int n, const int32_t *cost, int32_t *row_to_col, int64_t *t
  * returns the previous setting. */
 TD_API int td_set_line_metric(int on);
 
-/* ---- handle-scoped solvers ("the library must be re-entrant per handle") -----------------------------
+/* ---- handle-scoped solvers --------------------------------------------------------------------------
  * td_assign / td_build_assign solve in the library's default workspace.  A td_solver owns a workspace of its own (grow-only,
  * released by td_solver_destroy), so one process can keep several — e.g. one sized for N = 65 536 and one for ticks — without
- * one call regrowing what the other needs.  Same arguments, results and errors as td_assign / td_build_assign; calls are
- * synchronous and one at a time, like the reference (strictly single-threaded). */
+ * one call regrowing what the other needs.  Same arguments, results and errors as td_assign / td_build_assign.  A handle
+ * owns its workspace and nothing else: the stream, the pinned read-back block and td_last_stats belong to the library
+ * context, so calls are synchronous and ONE AT A TIME PER PROCESS, whichever handles they go to (the reference is
+ * strictly single-threaded).  Handles are not a way to solve from two threads at once. */
 typedef struct td_solver td_solver;
 TD_API int td_solver_create(td_solver **out);
 TD_API int td_solver_destroy(td_solver *h);
@@ -671,7 +673,8 @@ TD_API int td_shard_row_to_col(td_shard *s, int32_t *r2c_local);
  * summary[0..5] = {all ranks fit, all ran phase A, free rows left in total, constant rows, largest row range, rank 0's segment
  * word 6 (free for the caller: solve_sharded carries the line-metric attempt's plausibility word there)}.
  * The ordinary rounds (td_shard_bid / _apply / _rounds) and td_shard_finish take what is still free; when
- * summary[2] == 0 the solve is complete.  flags bit 2 (flags = 7): the compress pass stores the 1-byte cells of the
+ * summary[2] == 0 the solve is complete, except that td_shard_place_const is still due when summary[3] > 0 (the constant
+ * rows sat out phase A).  flags bit 2 (flags = 7): the compress pass stores the 1-byte cells of the
  * diagonal slices only (all that phase A reads: 1/8 of the narrow copy); the library writes the other cells by itself
  * the first time a call needs whole rows (td_shard_bid / _rounds, td_shard_cc — where the pointers td_shard_finish reads
  * through come from —, the dual bound of td_shard_total) — never, when phase A leaves nothing.  td_assign starts the same way for n >= 12 288 (td_set_blocks),

@@ -3118,8 +3118,7 @@ struct td_shard {
 namespace {
 
 using Solver = td_shard;
-Solver g_default;  // td_assign's workspace, kept across calls
-Solver *g_active = &g_default;   // the workspace the next td_assign / td_build_assign call solves in (a td_solver_* call switches it for its duration)
+Solver g_default;  // td_assign / td_build_assign / td_tick's workspace, kept across calls (a td_solver handle has its own)
 
 int sv_prepare(Solver &sv, int n, int row0, int nrows, const int32_t *cost)
 {
@@ -4062,96 +4061,627 @@ int sv_end_gated(Solver &sv, bool want_dual, int *r2c_out)
 
 }  // namespace
 
-// td_tick knows the model it hands over (how many dummy requests / cabs pad it, the fill value): the next td_assign call
-// skips the line probe and the speculative 1-byte attempt and goes straight to the fused pass when the shape rule says so
+// =====================================================================================
+// td_assign: the host driver (DESIGN.md 2.15 lists the steps in order)
+// =====================================================================================
 namespace {
+
+// What a caller that made the model itself knows about it (td_build_assign, td_tick): the matrix is a model padded with
+// `const_cols` dummy requests and `const_rows` dummy cabs of value `fill`.  The solve then skips the line probe and the
+// speculative 1-byte attempt and goes straight to the fused pass when the shape rule says so.  A default-constructed
+// hint is "no hint".
 struct AssignHint {
     bool valid = false;
     int const_cols = 0, const_rows = 0, fill = 0;
     bool tick = false;   // td_tick's remainder: its own round count, no speculative batches (tick-sized tuning)
     bool gen = false;    // the cells come from position arrays (src), `cost` is a placeholder
     CellSrc src;
-} g_hint;
-}  // namespace
-void td::assign_hint_padded(int const_cols, int const_rows, int32_t fill)
+};
+
+// the margin of the shape rule: that many more constant columns than constant rows (k_init_state's shape probe has the same)
+int fuse_margin(int n) { return n / 256 > 32 ? n / 256 : 32; }
+
+// the shape rule on a model whose padding the caller knows: the fused transposing compress pass at once
+bool fuse_rule(int n, int const_cols, int const_rows, int64_t fill)
 {
-    g_hint = AssignHint();
-    g_hint.valid = true;
-    g_hint.const_cols = const_cols;
-    g_hint.const_rows = const_rows;
-    g_hint.fill = fill;
-    g_hint.tick = true;
+    return g_fuse_t && g_shape && !g_solver_eps && n >= 64 && const_cols >= 16 && const_cols - const_rows >= fuse_margin(n) && fill >= 255 &&
+           fill <= NP_RANGE;
 }
 
-// Cost build + optimal assignment from DEVICE position arrays without the int32 matrix where the model allows it: a model
-// padded with dummy requests (n_s - n_d beyond the shape rule's margin: every Simulator.java / simulate.py tick) goes
-// through the fused transposing compress pass with its cells made on the fly (CellSrc), k_final sums them the same way;
-// any other shape is built into a library buffer and handed to td_assign as it is.
-int td::build_assign_device(const int32_t *d_cab, int n_s, const int32_t *d_dem, int n_d, const int32_t *d_dist, int S, int32_t fill,
-                            int32_t threshold, bool tick, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
+// what the width loop does after a step
+enum class Next {
+    go_on,            // the next step of this width
+    solved,           // tot / dual and the result arrays stand: deliver
+    next_width,       // this width is void or was skipped
+    rerun_compress,   // the compress pass of this width was a no-op behind the line probe: run it now
+    transpose,        // the shape probe asks for the transposed formulation
+    restart,          // the speculative fused pass was refused: the general path from the first width
+    delivered         // the line attempt's answer was accepted and has been handed out
+};
+
+constexpr size_t R2C_PIN_OFF = 8192;   // a small host row_to_col in the pinned block: clear of the control words (0..), the totals (1024) and the probe verdict (4096)
+
+// one td_assign call: what the steps below share
+struct Call {
+    Ctx &c;
+    const int n;
+    const AssignHint &hint;
+    int32_t *const row_to_col;
+    int64_t *const total, *const dual_bound;
+    // the whole call
+    bool line_pending = false;    // the line probe is queued, its verdict not read yet
+    bool early_check = false;     // the 1-byte attempt is likely void: one look at its flags before the rounds are queued
+    bool r2c_in_pinned = false;   // a host row_to_col rode along with the read-back
+    bool r2c_on_device = false;   // k_final has stored the result into the caller's device row_to_col
+    bool transposed = false, np_failed = false, no_fuse = false, fused_spec = false;
+    int max_rounds = 0;
+    int64_t range_hint = -1, hinted_range = -1, tot = 0, dual = 0;
+    // one orientation, one width of it
+    int orient = 0, bpc = 0, round_cap = 0;
+    int64_t known_range = -1, warm_rounds = 0;
+    bool spec = false, fits = false, all_placed = false, random_like = false;
+};
+
+int go(Next &next, Next to) { return next = to, TD_OK; }
+
+void deliver_totals(const Call &cl, int64_t tot, int64_t dual)
 {
-    read_tunables();
-    const int n = std::max(n_s, n_d);
-    Solver &sv = *g_active;
-    int rc;
-    if ((rc = ensure(sv.misc, 4096))) return rc;
-    const int const_cols = n - n_d, const_rows = n - n_s;
-    const int margin = n / 256 > 32 ? n / 256 : 32;
-    const bool fuse = g_fuse_gen && g_fuse_t && g_shape && !g_solver_eps && n >= 64 && const_cols >= 16 && const_cols - const_rows >= margin &&
-                      fill >= 255 && (int64_t)fill <= NP_RANGE;
-    if (!fuse) {
-        if ((rc = ensure(sv.genbuf, sizeof(int32_t) * (size_t)n * n))) return rc;
-        if ((rc = td::cost_build_async(d_cab, n_s, d_dem, n_d, d_dist, S, fill, threshold, (int32_t *)sv.genbuf.p))) return rc;
-        if (tick) td::assign_hint_padded(const_cols, const_rows, fill);
-        return td_assign(n, (const int32_t *)sv.genbuf.p, row_to_col, total, dual_bound);
+    if (cl.total) *cl.total = tot;
+    if (cl.dual_bound) *cl.dual_bound = dual;
+}
+
+// row_to_col (unless it is with the caller already), total and dual bound of a solved call
+int deliver(Solver &sv, Call &cl)
+{
+    const size_t bytes = sizeof(int32_t) * (size_t)cl.n;
+    cl.c.stats[7] = cl.transposed ? 1 : 0;
+    if (cl.r2c_in_pinned) {
+        memcpy(cl.row_to_col, (const char *)cl.c.pinned + R2C_PIN_OFF, bytes);
+    } else if (!cl.r2c_on_device) {   // (else k_final stored it, and the stream has been synchronised)
+        // transposed solve: its columns are the caller's rows, owner[] is the caller's row_to_col
+        TD_HIP(hipMemcpyAsync(cl.row_to_col, cl.transposed ? sv.owner.p : sv.r2c.p, bytes,
+                              is_device_ptr(cl.row_to_col) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cl.c.stream));
+        TD_HIP(hipStreamSynchronize(cl.c.stream));
     }
-    g_hint = AssignHint();
-    g_hint.valid = true;
-    g_hint.const_cols = const_cols;
-    g_hint.const_rows = const_rows;
-    g_hint.fill = fill;
-    g_hint.tick = tick;
-    g_hint.gen = true;
-    g_hint.src.cab_to = d_cab;
-    g_hint.src.dem_from = d_dem;
-    g_hint.src.dist = d_dist;
-    g_hint.src.n_s = n_s;
-    g_hint.src.n_d = n_d;
-    g_hint.src.S = S;
-    g_hint.src.fill = fill;
-    g_hint.src.thr = threshold;
-    return td_assign(n, (const int32_t *)sv.misc.p /* placeholder: no matrix exists */, row_to_col, total, dual_bound);
+    deliver_totals(cl, cl.tot, cl.dual);
+    return TD_OK;
 }
 
-// =====================================================================================
-// td_assign
-// =====================================================================================
-namespace {
-int assign_impl(Solver &sv, int n, const int32_t *cost, int32_t *row_to_col, int64_t *total, int64_t *dual_bound);
-}  // namespace
-
-extern "C" int td_assign(int n, const int32_t *cost, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
+// n == 0 (solver.py:12  "if n==0: return 0, []") and n == 1 (after sv_prepare: the one cell is on the device)
+int assign_trivial(Solver &sv, const Call &cl)
 {
-    return assign_impl(*g_active, n, cost, row_to_col, total, dual_bound);
+    if (cl.n == 0) {
+        deliver_totals(cl, 0, 0);
+        return TD_OK;
+    }
+    TD_HIP(hipMemcpyAsync(cl.c.pinned, sv.d_cost, sizeof(int32_t), hipMemcpyDeviceToHost, cl.c.stream));
+    TD_HIP(hipStreamSynchronize(cl.c.stream));
+    const int64_t tot = ((int32_t *)cl.c.pinned)[0];
+    int32_t zero = 0;
+    if (is_device_ptr(cl.row_to_col)) {
+        TD_HIP(hipMemcpyAsync(cl.row_to_col, &zero, sizeof(int32_t), hipMemcpyHostToDevice, cl.c.stream));
+        TD_HIP(hipStreamSynchronize(cl.c.stream));
+    } else
+        cl.row_to_col[0] = 0;
+    deliver_totals(cl, tot, tot);
+    return TD_OK;
 }
 
-namespace {
-int assign_impl(Solver &sv, int n, const int32_t *cost, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
+// the cells of a td_build_assign call exist only as position arrays; the moment the solve leaves the fused path they are
+// written out as the int32 matrix every other pass reads
+int sv_materialise(Solver &sv)
 {
-    // the hint of td_tick is for THIS call only, whatever way the call ends (an early return left it for the
-    // next, unrelated call)
-    const AssignHint hint = g_hint;
-    g_hint.valid = false;
+    if (!sv.gen) return TD_OK;
+    int rc;
+    if ((rc = ensure(sv.genbuf, sizeof(int32_t) * (size_t)sv.n * sv.n))) return rc;
+    if ((rc = td::cost_build_async(sv.gsrc.cab_to, sv.gsrc.n_s, sv.gsrc.dem_from, sv.gsrc.n_d, sv.gsrc.dist, sv.gsrc.S, sv.gsrc.fill, sv.gsrc.thr,
+                                   (int32_t *)sv.genbuf.p)))
+        return rc;
+    sv.d_cost = (const int32_t *)sv.genbuf.p;
+    sv.gen = false;
+    return TD_OK;
+}
+
+// the caller told the shape: the fused pass at once, speculatively (flags with the final read-back)
+int step_hinted_fuse(Solver &sv, Call &cl)
+{
+    const AssignHint &hint = cl.hint;
+    const int n = cl.n;
+    int rc;
+    bool ff = false;
+    int64_t fr = 0;
+    cl.fused_spec = true;
+    if (g_fuse_t >= 2 && n > 2048 && n <= 65536) {
+        if ((rc = sv_compress_fused(sv, &ff, &fr, true, hint.fill, true, hint.fill))) return rc;
+        sv.fused8 = ff;
+    }
+    if (!ff && (rc = sv_compress_fused(sv, &ff, &fr, false, 0, true, hint.fill))) return rc;
+    sv.fused_t = true;
+    cl.transposed = true;
+    cl.hinted_range = hint.fill;
+    cl.max_rounds = std::min(cl.max_rounds, (hint.tick && n < 2048) ? std::min(g_fused_rounds, g_tick_rounds) : g_fused_rounds);
+    sv.tick_sized = hint.tick && n < 2048;
+    return TD_OK;
+}
+
+// the matrix the one k_init_state launch that carries the shape probe samples (null: no probe in this attempt)
+const int32_t *shape_probe_src(const Solver &sv, const Call &cl)
+{
+    return (cl.spec && cl.orient == 0 && g_shape && cl.n >= 64 && cl.n <= g_shape_max_n && !g_solver_eps) ? sv.d_cost : nullptr;
+}
+
+// the narrow copy of this width: the compress pass, or what the fused pass has written
+int step_compress(Solver &sv, Call &cl)
+{
+    if (sv.fused_t) {   // cc already holds the transposed problem (k_compress_tr); the same bytes serve both price widths
+        sv.bid0_done = false;   // (a 1-byte attempt queued before the fused pass may have set it)
+        sv.cc_partial = false;
+        sv.zs_done = false;
+        cl.fits = true;
+        sv.bpc = cl.bpc;
+        if (cl.np_failed) k_fill_i32<<<1, 64, 0, cl.c.stream>>>((int *)sv.misc.p + CTL_FLAG, 2, 0);   // the price-limit flag of the 32-bit attempt
+        return TD_OK;
+    }
+    // 1-byte attempt: state init + the shape probe ride in front of the compress pass, which writes round 0's bids
+    sv.want_bid0 = cl.spec && !g_solver_eps;
+    sv.lazy_cc = true;
+    sv.zs_V = (sv.want_bid0 && cl.orient == 0) ? (g_blocks >= 0 ? g_blocks : (cl.n >= g_blocks_min_n ? 8 : 0)) : 0;
+    sv.probe = shape_probe_src(sv, cl);
+    sv.range_seen = -1;
+    const int rc = sv_compress(sv, cl.bpc, &cl.fits, cl.spec);
+    sv.want_bid0 = false;
+    sv.lazy_cc = false;
+    sv.probe = nullptr;
+    if (rc) return rc;
+    // a width that fits after a mere lower bound of the range (the line probe's "row 0 is too wide for one byte"):
+    // the warm start's schedule and the "is it wide" test need the measured range
+    if (!cl.spec && cl.fits && sv.range_seen > cl.known_range) cl.known_range = sv.range_seen;
+    return TD_OK;
+}
+
+// The probe made the speculative 1-byte pass queued behind it a no-op (its device flag): that attempt was going to be
+// void — row 0 is too wide for one byte, or the model is padded with dummy requests (shape3: see line_probe_wait).
+int step_probe_fused(Solver &sv, Call &cl, const int *shape3, Next &next)
+{
+    const int n = cl.n;
+    int rc;
+    // the rule of the shape probe (k_init_state), on the probe's estimate
+    if (g_fuse_t && g_shape && !g_solver_eps && !cl.no_fuse && shape3[0] >= 16 && shape3[0] - shape3[1] >= fuse_margin(n)) {
+        bool ff = false;
+        int64_t fr = 0;
+        // Speculative (no host round trip) when the fill value looks like one: cells in 0 .. fill, 32-bit prices.
+        // A cell that does not fit raises CTL_FLAG, every later kernel exits, and the final read-back sends the
+        // call back to the general path (Next::restart).
+        cl.fused_spec = g_fuse_spec && shape3[3] >= 255 && (int64_t)shape3[3] <= NP_RANGE;
+        // 1-byte cells + escape first ({small range} u {fill}: every reference model of this kind), else 4-byte cells
+        if (g_fuse_t >= 2 && n > 2048 && n <= 65536) {   // a small model is launch-bound: 64 x 1024 tiles leave most CUs idle (tick: 0.465 vs 0.432 ms)
+            if ((rc = sv_compress_fused(sv, &ff, &fr, true, shape3[3], cl.fused_spec, shape3[3]))) return rc;
+            sv.fused8 = ff;
+        }
+        if (!ff && (rc = sv_compress_fused(sv, &ff, &fr, false, 0, cl.fused_spec, shape3[3]))) return rc;
+        if (cl.fused_spec) fr = shape3[3];
+        if (getenv("TD_DEBUG")) fprintf(stderr, "[td] fused transpose + compress: n=%d fits %d range %lld, %d constant rows\n", n, (int)ff, (long long)fr, sv.nconst);
+        if (ff) {
+            sv.fused_t = true;
+            cl.transposed = true;
+            cl.known_range = fr;
+            // thresholded models are a few huge tie classes: the rounds stop making progress after 5 - 6
+            // (profiles/r3), every further launch is ~10 us of early exits; what is left goes to the finisher
+            cl.max_rounds = std::min(cl.max_rounds, g_fused_rounds);
+            return go(next, Next::next_width);   // on to the 4-byte widths
+        }
+        cl.early_check = true;
+        return go(next, Next::rerun_compress);   // negative cells or a range beyond 32 bits: the general path, from the 1-byte attempt
+    }
+    if (shape3[2]) {   // row 0 does not fit one byte per cell: skip the 1-byte attempt, the next width measures the range
+        cl.known_range = std::max<int64_t>(cl.known_range, 255);
+        return go(next, Next::next_width);
+    }
+    cl.early_check = true;
+    return go(next, Next::rerun_compress);   // only a hint that did not lead anywhere: run the skipped pass
+}
+
+// the line probe's verdict, awaited behind the first compress pass; an accepted answer is handed out here
+int step_line_verdict(Solver &sv, Call &cl, Next &next)
+{
+    const int n = cl.n;
+    int rc;
+    cl.line_pending = false;
+    sv.skip = nullptr;
+    int mode = 0, kd = 0, accepted = 0, susp = 0, shape3[4] = {0, 0, 0, 0};
+    if ((rc = line_probe_wait(&mode, &kd, &susp, shape3))) return rc;
+    if (mode == 0 && susp) return step_probe_fused(sv, cl, shape3, next);
+    if (getenv("TD_DEBUG")) fprintf(stderr, "[td] line probe: n=%d verdict %d, %d constant rows, suspicious %d\n", n, mode, kd, susp);
+    if (!mode) return TD_OK;   // refused: the compress pass has run
+    const int32_t *res = nullptr;
+    bool line_t = false;
+    int64_t tot = 0;
+    if (mode == 2) {
+        // constant trailing COLUMNS (more cabs than requests): the same model on the transpose
+        if ((rc = ensure(sv.tbuf, sizeof(int32_t) * (size_t)n * n))) return rc;
+        k_transpose<<<dim3((n + 63) / 64, (n + 63) / 64), 256, 0, cl.c.stream>>>(n, sv.d_cost, (int32_t *)sv.tbuf.p);
+        TD_HIP(hipGetLastError());
+        const long long *unused = nullptr;
+        if ((rc = line_probe_launch(n, (const int32_t *)sv.tbuf.p, &unused))) return rc;
+        if ((rc = line_probe_wait(&mode, &kd))) return rc;
+        if (getenv("TD_DEBUG")) fprintf(stderr, "[td] line probe on the transpose: verdict %d, %d constant rows\n", mode, kd);
+        line_t = true;
+        cl.c.stats[12] |= LP_TRANSPOSE;
+    }
+    if (mode == 1 || mode == 3) {
+        int fin = 0;
+        if ((rc = line_finish(n, mode == 3 ? kd : 0, line_t ? (const int32_t *)sv.tbuf.p : sv.d_cost, &res, &tot, &accepted, &fin)))
+            return rc;
+        cl.c.stats[12] |= (mode == 1 ? LP_BALANCED : LP_UNBAL) | fin;
+    }
+    if (!accepted) {
+        return go(next, Next::rerun_compress);   // plausible but not proven: the pass above was skipped, run it now
+    }
+    const int64_t line_path = cl.c.stats[12] | LP_ACCEPTED;
+    for (int k = 0; k < 16; k++) cl.c.stats[k] = 0;
+    cl.c.stats[12] = line_path;
+    cl.c.stats[4] = 4;
+    cl.c.stats[7] = line_t ? 1 : 0;
+    cl.c.stats[8] = 1;
+    cl.c.stats[9] = mode == 3 ? kd : 0;
+    if (line_t) {   // res[column] = row of the caller's matrix: invert
+        k_r2c_from_owner<<<(n + 255) / 256, 256, 0, cl.c.stream>>>(n, n, 0, (const int *)res, (int *)sv.r2c.p);
+        TD_HIP(hipGetLastError());
+        res = (const int32_t *)sv.r2c.p;
+    }
+    TD_HIP(hipMemcpyAsync(cl.row_to_col, res, sizeof(int32_t) * (size_t)n,
+                          is_device_ptr(cl.row_to_col) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cl.c.stream));
+    TD_HIP(hipStreamSynchronize(cl.c.stream));
+    deliver_totals(cl, tot, tot);   // the certificate IS the dual bound (sum of row minima + prices)
+    return go(next, Next::delivered);
+}
+
+// state init (unless the compress pass carried it), then the one look at a likely void 1-byte attempt's flags
+int step_begin(Solver &sv, Call &cl, Next &next)
+{
+    // shape probe (inside k_init_state): may ask (CTL_FLAG bit 2) for the transposed formulation;
+    // like a failed width speculation this costs one empty pass through the early-exiting kernels
+    sv.probe = shape_probe_src(sv, cl);
+    int rc = TD_OK;
+    if (!sv.bid0_done) TD_DISPATCH(sv, sv_begin_t, sv);
+    sv.probe = nullptr;
+    if (rc) return rc;
+    if (!(cl.spec && cl.early_check)) return TD_OK;
+    // the line probe saw a row too wide for one byte or a constant last column: this speculative attempt
+    // will most likely be void (width flag, or the shape probe asking for the transpose).  One round trip
+    // now instead of the ~30 launches of rounds and finishers that would exit at once.
+    cl.early_check = false;
+    int ef = 0;
+    if ((rc = sv_readback(sv, nullptr, nullptr, 0, &ef))) return rc;
+    if (ef & 4) {
+        cl.range_hint = cl.c.stats[6] > 254 ? cl.c.stats[6] : -1;
+        next = Next::transpose;
+    } else if (ef) {
+        cl.known_range = cl.c.stats[6];
+        next = Next::next_width;
+    }
+    return TD_OK;
+}
+
+// comparison mode (TD_SOLVER=eps): eps-scaling down to eps < 1 / n, no finisher
+int step_solve_eps(Solver &sv, Call &cl, Next &next)
+{
+    int rc;
+    int64_t er = 0, ep = 0;
+    TD_DISPATCH(sv, sv_solve_eps_t, sv, g_eps0_mult, g_eps_theta, &er, &ep);
+    if (rc) return rc;
+    TD_DISPATCH(sv, sv_totals_t, sv, false);
+    if (rc) return rc;
+    int flag = 0;
+    if ((rc = sv_readback(sv, &cl.tot, &cl.dual, 0, cl.spec ? &flag : nullptr))) return rc;
+    if (cl.spec && flag) {
+        cl.known_range = cl.c.stats[6];
+        return go(next, Next::next_width);
+    }
+    cl.dual = cl.tot;   // exact by the eps < 1/n argument; no certificate pass in this mode
+    cl.c.stats[0] = er;
+    cl.c.stats[1] = ep;
+    return go(next, Next::solved);
+}
+
+int run_rounds(Solver &sv, int round_cap, bool first)
+{
+    for (int r = 0; r < round_cap; r++) {
+        int rc = TD_OK;
+        if (!(r == 0 && first && sv.bid0_done)) TD_DISPATCH(sv, sv_bid_t, sv, r, (unsigned long long *)sv.bid.p);
+        if (rc) return rc;
+        TD_DISPATCH(sv, sv_apply_t, sv, r, (unsigned long long *)sv.bid.p);
+        if (rc) return rc;
+    }
+    return TD_OK;
+}
+
+int run_warm(Solver &sv, Call &cl, int bits)
+{
+    int rc;
+    const int keep = g_warm_bits;
+    g_warm_bits = bits;
+    if (cl.bpc == 2) rc = sv_warm_t<uint16_t>(sv, cl.known_range, &cl.warm_rounds, &cl.random_like);
+    else if (cl.bpc == 5) rc = sv_warm_t<u32n>(sv, cl.known_range, &cl.warm_rounds, &cl.random_like);
+    else rc = sv_warm_t<uint32_t>(sv, cl.known_range, &cl.warm_rounds, &cl.random_like);
+    g_warm_bits = keep;
+    return rc;
+}
+
+// pin[0] = rows still free after the two-hop passes, pin[1] = the width flag
+int read_left(Solver &sv, int *pin)
+{
+    Ctx &c = ctx();
+    TD_HIP(hipMemcpyAsync(pin, (char *)sv.hop.p + offsetof(HopCtl, left), sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    TD_HIP(hipMemcpyAsync(pin + 1, (int *)sv.misc.p + CTL_FLAG, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    TD_HIP(hipStreamSynchronize(c.stream));
+    return TD_OK;
+}
+
+// one-trip sequence: the pass over the whole matrix and the end of the solve are queued at once, gated on
+// the device (k_hop_lists, k_place_const, k_dual, k_final); one synchronisation reads k_final's record
+int block_one_trip(Solver &sv, Call &cl, Next &next)
+{
+    const int n = cl.n;
+    int rc;
+    if (g_hop_global && (rc = sv_hop_t<uint8_t>(sv, n, n, 0, 1, true, nullptr, sv.cc_partial, true))) return rc;
+    const bool dev_out = is_device_ptr(cl.row_to_col);
+    cl.r2c_in_pinned = !dev_out && (size_t)R2C_PIN_OFF + sizeof(int32_t) * (size_t)n <= cl.c.pinned_cap;
+    int *r2c_out = dev_out ? cl.row_to_col : (cl.r2c_in_pinned ? (int *)((char *)cl.c.pinned + R2C_PIN_OFF) : nullptr);
+    if ((rc = sv_end_gated(sv, cl.dual_bound != nullptr, r2c_out))) return rc;
+    TD_HIP(hipStreamSynchronize(cl.c.stream));
+    const char *rec = (const char *)cl.c.pinned + REC_OFF;
+    const int left = ((const int *)rec)[REC_LEFT / sizeof(int)], rflag = ((const int *)rec)[CTL_FLAG];
+    if (left < 0) return fail(TD_EINTERNAL, "the end-of-solve record was not written");
+    if (getenv("TD_DEBUG")) fprintf(stderr, "[td] one trip: %d rows free after the two-hop passes, flag %d\n", left, rflag);
+    if (left == 0 && rflag == 0) {
+        int flag = 0;
+        if ((rc = sv_readback_parse(sv, rec, &cl.tot, &cl.dual, cl.max_rounds, &flag))) return rc;
+        cl.c.stats[1] = 0;
+        cl.c.stats[6] = 0;
+        cl.r2c_on_device = dev_out;
+        return go(next, Next::solved);
+    }
+    // rows left, or the width flag: the rounds and the finishers as before (nothing above has changed the state)
+    cl.r2c_in_pinned = false;
+    cl.round_cap = std::min(cl.max_rounds, g_zs_global_rounds);
+    return TD_OK;
+}
+
+// one small read-back tells whether anything is left for the rounds and the finisher (on tie-heavy instances nothing
+// is: ~30 launches that would all exit at once are not made)
+int block_read_back(Solver &sv, Call &cl)
+{
+    const int n = cl.n;
+    int rc;
+    int *pin = (int *)cl.c.pinned;
+    if ((rc = read_left(sv, pin))) return rc;
+    if (getenv("TD_DEBUG")) fprintf(stderr, "[td] after the block-local start: %d rows free, flag %d\n", pin[0], pin[1]);
+    if (pin[0] > 0 && pin[1] == 0 && g_hop_global && pin[0] <= g_hop_max_rows) {
+        // (nothing has moved a price yet: "tight" is "zero cell" over the whole row too, and the pass needs no row minimum)
+        if ((rc = sv_hop_t<uint8_t>(sv, n, n, 0, 1, true, nullptr, sv.cc_partial))) return rc;
+        if ((rc = read_left(sv, pin))) return rc;
+        if (getenv("TD_DEBUG")) fprintf(stderr, "[td] after the two-hop pass over the whole matrix: %d rows free\n", pin[0]);
+    }
+    cl.all_placed = pin[0] == 0 && pin[1] == 0;
+    cl.round_cap = std::min(cl.max_rounds, g_zs_global_rounds);
+    return TD_OK;
+}
+
+// block-local start (td_blocks.h): zero cells of the diagonal blocks, then one two-hop pass over the whole matrix for what
+// the blocks left (the same TD_HOP_PASSES two-hop passes inside the blocks as the sharded solve makes: the two sequences are the
+// same up to here, and identical altogether when the blocks leave nothing)
+int step_block_start(Solver &sv, Call &cl, Next &next)
+{
+    int rc;
+    const int passes_a = g_hop_passes;
+    if ((rc = sv_phase_a(sv, passes_a))) return rc;
+    if (passes_a <= 0) return TD_OK;
+    if (g_one_trip && !cl.transposed && !sv.gen) return block_one_trip(sv, cl, next);
+    return block_read_back(sv, cl);
+}
+
+// the eps = 0 rounds, then: the finisher at once, a warm start first, or the same instance redone as 4-byte cells
+int step_rounds_warm(Solver &sv, Call &cl, Next &next)
+{
+    const int n = cl.n;
+    int rc;
+    if (!cl.all_placed && (rc = sv_complete_cc(sv))) return rc;   // the rounds and the finishers read whole rows of the narrow copy
+    if (!cl.all_placed && (rc = run_rounds(sv, cl.round_cap, true))) return rc;
+    // Wide, tie-free rows (no constant rows, few rows tied at their minimum) that the eps = 0
+    // rounds leave with many free rows.  One small read-back; only non-speculative attempts
+    // (u16 / u32 rows), which have synchronised for the width flag already.
+    bool wide = false, hard16 = false;
+    if (g_warm && !g_solver_eps && !cl.spec && cl.bpc != 1 && sv.nconst == 0 && cl.known_range >= g_warm_min_range) {
+        k_freelist<<<1, 1024, 0, cl.c.stream>>>(n, (const int *)sv.r2c.p, (int *)sv.list.p, (int *)sv.misc.p);
+        TD_HIP(hipMemcpyAsync(cl.c.pinned, sv.misc.p, CTL_ALL * sizeof(int), hipMemcpyDeviceToHost, cl.c.stream));
+        TD_HIP(hipStreamSynchronize(cl.c.stream));
+        const int nfree_now = ((int *)cl.c.pinned)[CTL_NFREE], tied0 = ((int *)cl.c.pinned)[CTL_TIED];
+        // tied0 counts every 16th row (every row of a model below 1024).  No warm start below TD_WARM_MIN_N rows: a
+        // thresholded 60 x 60 model ran 800 warm rounds = 8 ms for rows the serial workgroup finishes in microseconds
+        // (tools/r4_outliers.py found it: the 4 sampled rows of so small a model missed its ties)
+        wide = n >= g_warm_min_n && !(nfree_now < std::max(g_warm_minfree, n / 64) || (long long)tied0 * (n < 1024 ? 1 : 16) * g_warm_tie_div > n);
+        cl.c.stats[2] = nfree_now;
+        hard16 = cl.bpc == 2 && g_u16_redo_free > 0 && nfree_now >= g_u16_redo_free;
+    }
+    if ((wide || hard16) && cl.bpc == 2 && g_wide_u16_n && n >= g_wide_u16_n && g_narrow_price && !cl.np_failed && cl.known_range >= 0 &&
+        cl.known_range <= NP_RANGE) {
+        // A hard instance (the finisher will dominate) in 2-byte cells: the cooperative finisher k_sapx needs
+        // n / E >= 8 * 256 chunks and the 2-byte kernels carry 64-bit prices.  Redo it as 4-byte cells with
+        // 32-bit prices (the next width of the loop): one more compress pass and 12 rounds, milliseconds
+        // against hundreds (2-D Manhattan grid, n = 8192: 493 -> 224 ms, n = 16 384: 848 -> 640 ms).
+        return go(next, Next::next_width);
+    }
+    if (wide) {
+        // eps > 0 phases down to eps = 1 as a price warm start (sv_warm_t), the rounds once more,
+        // then the dense finisher
+        if ((rc = run_warm(sv, cl, g_warm_bits))) return rc;
+        if (cl.random_like) cl.round_cap = std::max(cl.round_cap, g_rand_rounds);   // (cheap here: a few hundred bidders; halves what is left for the forest)
+        if ((rc = run_rounds(sv, cl.round_cap, false))) return rc;
+    }
+    return TD_OK;
+}
+
+// what the flags of the final read-back say about this width's attempt
+int step_flags(Solver &sv, Call &cl, int flag, Next &next)
+{
+    int rc;
+    if (sv.fused_t && cl.fused_spec && (flag & 1)) {
+        // the speculative fused pass met a cell outside 0 .. fill (or, for 1-byte cells, outside base .. base + 253):
+        // nothing of it can be kept
+        if (getenv("TD_DEBUG")) fprintf(stderr, "[td] speculative fused pass refused (flag %d): general path\n", flag);
+        if (cl.bpc == 6 && !(flag & ~9)) {   // 1-byte cells did not fit: the same pass with 4-byte cells, checked this time
+            bool ff = false;
+            int64_t fr = 0;
+            sv.fused8 = false;
+            cl.fused_spec = false;
+            if ((rc = sv_compress_fused(sv, &ff, &fr))) return rc;
+            if (ff) {
+                cl.known_range = fr;
+                return go(next, Next::next_width);
+            }
+        }
+        cl.no_fuse = true;
+        sv.fused_t = sv.fused8 = false;
+        cl.transposed = false;
+        cl.fused_spec = false;
+        cl.max_rounds = g_max_rounds;
+        cl.early_check = true;
+        next = Next::restart;
+        return sv_materialise(sv);   // (td_build_assign: the general path reads the matrix)
+    }
+    if (cl.bpc == 5 && flag) {   // a price reached the 32-bit limit: the attempt is void, redo with 64-bit prices
+        cl.np_failed = true;
+        return go(next, Next::next_width);
+    }
+    if (cl.bpc == 6 && flag) {   // the same guard for the 1-byte cells with the escape: redo the fused pass as 4-byte cells
+        bool ff = false;
+        int64_t fr = 0;
+        sv.fused8 = false;
+        if ((rc = sv_compress_fused(sv, &ff, &fr))) return rc;
+        if (!ff) return fail(TD_EINTERNAL, "fused transpose pass: 4-byte cells refused after the 1-byte ones fitted");
+        cl.known_range = fr;
+        return go(next, Next::next_width);
+    }
+    if (cl.spec && (flag & 4)) {  // many constant columns: solve the transposed problem instead
+        cl.range_hint = cl.c.stats[6] > 254 ? cl.c.stats[6] : -1;
+        return go(next, Next::transpose);
+    }
+    if (cl.spec && flag) {  // rows did not fit u8: redo with the width the recorded range needs
+        cl.known_range = cl.c.stats[6];
+        return go(next, Next::next_width);
+    }
+    cl.c.stats[6] = (cl.bpc == 5) ? 1 : 0;   // 1: solved in the narrow-price mode
+    return go(next, Next::solved);
+}
+
+// the finisher, the constant rows, the totals and the one read-back of this attempt
+int step_finish(Solver &sv, Call &cl, Next &next)
+{
+    const int n = cl.n;
+    int rc = TD_OK;
+    ShardTab tab{};
+    tab.p[0] = sv.cc.p;
+    tab.rps = n;
+    tab.count = 1;
+    sv.placed = false;
+    if (!cl.all_placed) TD_DISPATCH(sv, sv_finish_t, sv, tab, (int *)sv.r2c.p);
+    if (rc) return rc;
+    if (sv.defer_const && !sv.placed) {
+        ProfScope ps(TD_K_FINAL);
+        k_place_const<<<1, 1024, 0, cl.c.stream>>>(n, (int *)sv.r2c.p, (int *)sv.owner.p, (int *)sv.list.p, (int *)sv.pred.p,
+                                               (int *)sv.misc.p);
+    }
+    if (cl.dual_bound != nullptr && (rc = sv_complete_cc(sv))) return rc;   // (k_dual reads the narrow rows)
+    TD_DISPATCH(sv, sv_totals_t, sv, cl.dual_bound != nullptr);
+    if (rc) return rc;
+    int flag = 0;
+    // a host row_to_col of a small model rides along with the read-back (one round trip, no blocking pageable copy)
+    cl.r2c_in_pinned = !is_device_ptr(cl.row_to_col) && (size_t)R2C_PIN_OFF + sizeof(int32_t) * (size_t)n <= cl.c.pinned_cap;
+    if (cl.r2c_in_pinned)
+        TD_HIP(hipMemcpyAsync((char *)cl.c.pinned + R2C_PIN_OFF, cl.transposed ? sv.owner.p : sv.r2c.p, sizeof(int32_t) * (size_t)n,
+                              hipMemcpyDeviceToHost, cl.c.stream));
+    if ((rc = sv_readback(sv, &cl.tot, &cl.dual, cl.max_rounds, (cl.spec || cl.bpc == 5 || cl.bpc == 6) ? &flag : nullptr))) return rc;
+    cl.c.stats[1] = cl.warm_rounds;
+    return step_flags(sv, cl, flag, next);
+}
+
+// one width of one orientation, from its narrow copy to the verdict on it
+int solve_width(Solver &sv, Call &cl, Next &next)
+{
+    int rc;
+    do {
+        next = Next::go_on;
+        if ((rc = step_compress(sv, cl))) return rc;
+        if (cl.line_pending && (rc = step_line_verdict(sv, cl, next))) return rc;
+    } while (next == Next::rerun_compress);
+    if (next != Next::go_on) return TD_OK;
+    if (!cl.fits) {
+        cl.known_range = cl.c.stats[6];
+        return go(next, Next::next_width);
+    }
+    if ((rc = step_begin(sv, cl, next)) || next != Next::go_on) return rc;
+    if (g_solver_eps) return step_solve_eps(sv, cl, next);
+    cl.round_cap = cl.max_rounds;
+    cl.warm_rounds = 0;
+    cl.random_like = cl.all_placed = false;
+    if (sv.zs_done && ((rc = step_block_start(sv, cl, next)) || next != Next::go_on)) return rc;
+    if ((rc = step_rounds_warm(sv, cl, next)) || next != Next::go_on) return rc;
+    return step_finish(sv, cl, next);
+}
+
+// the explicit transpose the shape probe asked for: the second orientation solves the transposed matrix
+int step_transpose(Solver &sv, Call &cl)
+{
+    const int n = cl.n;
+    int rc;
+    ProfScope ps(TD_K_FINAL);
+    if ((rc = ensure(sv.tbuf, sizeof(int32_t) * (size_t)n * n))) return rc;
+    k_transpose<<<dim3((n + 63) / 64, (n + 63) / 64), 256, 0, cl.c.stream>>>(n, sv.d_cost, (int32_t *)sv.tbuf.p);
+    TD_HIP(hipGetLastError());
+    sv.d_cost = (const int32_t *)sv.tbuf.p;
+    cl.transposed = true;
+    return TD_OK;
+}
+
+// the caller's matrix, then (when the shape probe asks for it) its transpose, each through the widths from narrow to wide
+int solve_orientations(Solver &sv, Call &cl, Next &next)
+{
+    int rc;
+    next = Next::next_width;
+    for (cl.orient = 0; cl.orient < 2; cl.orient++) {
+        cl.known_range = sv.fused_t ? cl.hinted_range : (cl.transposed ? cl.range_hint : -1);
+        for (int bpc : {1, 2, 6, 5, 4}) {   // 5 = 4-byte cells with 32-bit prices (narrow-price mode, see u32n); 6 = 1-byte cells + escape (u8e, fused pass only)
+            if (bpc == 6 && !sv.fused8) continue;
+            if (sv.fused_t && (sv.fused8 ? bpc != 6 : (bpc != 5 && bpc != 4))) continue;   // the widths the fused pass has written
+            if (cl.known_range > 254 && bpc == 1) continue;    // the probe's sampled column range: u8 cannot hold it
+            if (cl.known_range > 65534 && bpc == 2) continue;  // u16 cannot hold it either
+            if (bpc == 5 && (!g_narrow_price || g_solver_eps || cl.np_failed || cl.known_range < 0 || cl.known_range > NP_RANGE)) continue;
+            // the packed bid key keeps (price << 20 | row): prices stay below n * range
+            if (cl.known_range >= 0 && (double)(cl.known_range + 1) * (double)(cl.n + 1) >= 4.0e12)
+                return fail(TD_ERANGE, "row cost range %lld with n=%d overflows the packed bid key (price < 2^43)",
+                            (long long)cl.known_range, cl.n);
+            cl.bpc = bpc;
+            cl.spec = (bpc == 1) && g_speculate;   // u8 is tried speculatively (no host round trip in the common case)
+            cl.fits = false;
+            if ((rc = solve_width(sv, cl, next))) return rc;
+            if (next != Next::next_width) break;
+        }
+        if (next != Next::transpose) break;
+        if ((rc = step_transpose(sv, cl))) return rc;
+    }
+    return TD_OK;
+}
+
+int assign_impl(Solver &sv, const AssignHint &hint, int n, const int32_t *cost, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
+{
     TD_REQUIRE_INIT();
     Ctx &c = ctx();
     c.stats[12] = 0;   // line_path: filled in as the line attempt proceeds, kept when the general solver takes over
     read_tunables();
     if (n < 0) return fail(TD_EINVAL, "n < 0");
-    if (n == 0) {  // solver.py:12  "if n==0: return 0, []"
-        if (total) *total = 0;
-        if (dual_bound) *dual_bound = 0;
-        return TD_OK;
-    }
+    Call cl{c, n, hint, row_to_col, total, dual_bound};
+    if (n == 0) return assign_trivial(sv, cl);
     if (!cost || !row_to_col) return fail(TD_EINVAL, "null array");
     if (n >= (1 << ROW_BITS) - 1) return fail(TD_ERANGE, "n=%d exceeds the packed bid key", n);
     sv.skip = nullptr;
@@ -4159,477 +4689,125 @@ int assign_impl(Solver &sv, int n, const int32_t *cost, int32_t *row_to_col, int
     sv.fused8 = false;
     int rc;
     if ((rc = sv_prepare(sv, n, 0, n, cost))) return rc;
-    int64_t tot = 0, dual = 0;
-    if (n == 1) {
-        TD_HIP(hipMemcpyAsync(c.pinned, sv.d_cost, sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
-        TD_HIP(hipStreamSynchronize(c.stream));
-        tot = dual = ((int32_t *)c.pinned)[0];
-        int32_t zero = 0;
-        if (is_device_ptr(row_to_col)) {
-            TD_HIP(hipMemcpyAsync(row_to_col, &zero, sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
-            TD_HIP(hipStreamSynchronize(c.stream));
-        } else
-            row_to_col[0] = 0;
-        if (total) *total = tot;
-        if (dual_bound) *dual_bound = dual;
-        return TD_OK;
-    }
+    if (n == 1) return assign_trivial(sv, cl);
+    c.stats[8] = c.stats[9] = 0;
+    const bool hinted_fuse = hint.valid && fuse_rule(n, hint.const_cols, hint.const_rows, hint.fill);
+    sv.gen = hint.valid && hint.gen;
+    sv.gsrc = hint.src;
+    if (sv.gen && !hinted_fuse && (rc = sv_materialise(sv))) return rc;
+    sv.ctl_clear = false;
     // The reference's own distance table is a line (greedy_opt.py:122-127): td_line.hip tries the sorted matching
     // and keeps it only if its certificate pass proves it optimal on this matrix.  The probe is queued in
     // front of the first compress pass and its verdict is awaited while that pass runs, so a refusal costs
     // the probe kernel alone; when the probe says "plausible" the compress pass returns at once (sv.skip).
-    bool line_pending = false, early_check = false, r2c_in_pinned = false;
-    constexpr size_t R2C_PIN_OFF = 8192;   // clear of the control words (0..), the totals (1024) and the probe verdict (4096)
-    c.stats[8] = c.stats[9] = 0;
-    const int hint_margin = n / 256 > 32 ? n / 256 : 32;
-    const bool hinted_fuse = hint.valid && g_fuse_t && g_shape && !g_solver_eps && n >= 64 && hint.const_cols >= 16 &&
-                             hint.const_cols - hint.const_rows >= hint_margin && hint.fill >= 255 && (int64_t)hint.fill <= NP_RANGE;
-    sv.gen = hint.valid && hint.gen;
-    sv.gsrc = hint.src;
-    // the cells of a td_build_assign call exist only as position arrays; the moment the solve leaves the fused path they are
-    // written out as the int32 matrix every other pass reads
-    auto materialise = [&]() -> int {
-        if (!sv.gen) return TD_OK;
-        int mrc;
-        if ((mrc = ensure(sv.genbuf, sizeof(int32_t) * (size_t)n * n))) return mrc;
-        if ((mrc = td::cost_build_async(sv.gsrc.cab_to, sv.gsrc.n_s, sv.gsrc.dem_from, sv.gsrc.n_d, sv.gsrc.dist, sv.gsrc.S, sv.gsrc.fill, sv.gsrc.thr,
-                                        (int32_t *)sv.genbuf.p)))
-            return mrc;
-        sv.d_cost = (const int32_t *)sv.genbuf.p;
-        sv.gen = false;
-        return TD_OK;
-    };
-    if (sv.gen && !hinted_fuse && (rc = materialise())) return rc;
-    sv.ctl_clear = false;
     if (!hinted_fuse && g_line && n >= g_line_min_n && !g_solver_eps) {
         // (one-trip sequence: the probe also clears the control words for the compress pass queued behind it)
         if ((rc = line_probe_launch(n, sv.d_cost, &sv.skip, g_one_trip ? (int *)sv.misc.p : nullptr, CTL_ALL))) return rc;
-        line_pending = true;
+        cl.line_pending = true;
         c.stats[12] = LP_PROBE;
         sv.ctl_clear = g_one_trip != 0;
     }
-    c.stats[8] = 0;
-    int max_rounds = g_max_rounds;
-    bool solved = false, transposed = false, np_failed = false, no_fuse = false, fused_spec = false;
-    bool r2c_on_device = false;   // k_final has stored the result into the caller's device row_to_col
-    int64_t range_hint = -1;
+    cl.max_rounds = g_max_rounds;
     sv.defer_const = g_defer_const && !g_solver_eps;
     sv.bid0_done = false;
     sv.tick_sized = false;
-    int64_t hinted_range = -1;
-    if (hinted_fuse) {   // the caller (td_tick) told the shape: the fused pass at once, speculatively (flags with the final read-back)
-        bool ff = false;
-        int64_t fr = 0;
-        fused_spec = true;
-        if (g_fuse_t >= 2 && n > 2048 && n <= 65536) {
-            if ((rc = sv_compress_fused(sv, &ff, &fr, true, hint.fill, true, hint.fill))) return rc;
-            sv.fused8 = ff;
-        }
-        if (!ff && (rc = sv_compress_fused(sv, &ff, &fr, false, 0, true, hint.fill))) return rc;
-        sv.fused_t = true;
-        transposed = true;
-        hinted_range = hint.fill;
-        max_rounds = std::min(max_rounds, (hint.tick && n < 2048) ? std::min(g_fused_rounds, g_tick_rounds) : g_fused_rounds);
-        sv.tick_sized = hint.tick && n < 2048;
+    if (hinted_fuse && (rc = step_hinted_fuse(sv, cl))) return rc;
+    Next next;
+    do {
+        if ((rc = solve_orientations(sv, cl, next))) return rc;
+    } while (next == Next::restart);
+    if (next == Next::delivered) return TD_OK;
+    if (next != Next::solved) return fail(TD_ERANGE, "row cost range exceeds 2^32-2");
+    return deliver(sv, cl);
+}
+
+// Cost build + optimal assignment from DEVICE position arrays without the int32 matrix where the model allows it: a model
+// padded with dummy requests (n_s - n_d beyond the shape rule's margin: every Simulator.java / simulate.py tick) goes
+// through the fused transposing compress pass with its cells made on the fly (CellSrc), k_final sums them the same way;
+// any other shape is built into a buffer of the workspace and solved as it is.  tick: td_tick's remainder.
+int build_assign_dev(Solver &sv, const int32_t *d_cab, int n_s, const int32_t *d_dem, int n_d, const int32_t *d_dist, int S, int32_t fill,
+                     int32_t threshold, bool tick, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
+{
+    read_tunables();
+    const int n = std::max(n_s, n_d);
+    int rc;
+    if ((rc = ensure(sv.misc, 4096))) return rc;
+    AssignHint hint{};
+    hint.const_cols = n - n_d;
+    hint.const_rows = n - n_s;
+    hint.fill = fill;
+    hint.tick = tick;
+    if (!(g_fuse_gen && fuse_rule(n, hint.const_cols, hint.const_rows, fill))) {
+        if ((rc = ensure(sv.genbuf, sizeof(int32_t) * (size_t)n * n))) return rc;
+        if ((rc = td::cost_build_async(d_cab, n_s, d_dem, n_d, d_dist, S, fill, threshold, (int32_t *)sv.genbuf.p))) return rc;
+        hint.valid = tick;   // td_build_assign's matrix is solved like any other
+        return assign_impl(sv, hint, n, (const int32_t *)sv.genbuf.p, row_to_col, total, dual_bound);
     }
-restart:
-    for (int orient = 0; orient < 2 && !solved; orient++) {
-    bool want_transpose = false;
-    int64_t known_range = sv.fused_t ? hinted_range : (transposed ? range_hint : -1);
-    for (int bpc : {1, 2, 6, 5, 4}) {   // 5 = 4-byte cells with 32-bit prices (narrow-price mode, see u32n); 6 = 1-byte cells + escape (u8e, fused pass only)
-        bool fits = false;
-        if (bpc == 6 && !sv.fused8) continue;
-        if (sv.fused_t && (sv.fused8 ? bpc != 6 : (bpc != 5 && bpc != 4))) continue;   // the widths the fused pass has written
-        if (known_range > 254 && bpc == 1) continue;    // the probe's sampled column range: u8 cannot hold it
-        if (known_range > 65534 && bpc == 2) continue;  // u16 cannot hold it either
-        if (bpc == 5 && (!g_narrow_price || g_solver_eps || np_failed || known_range < 0 || known_range > NP_RANGE)) continue;
-        // the packed bid key keeps (price << 20 | row): prices stay below n * range
-        if (known_range >= 0 && (double)(known_range + 1) * (double)(n + 1) >= 4.0e12)
-            return fail(TD_ERANGE, "row cost range %lld with n=%d overflows the packed bid key (price < 2^43)",
-                        (long long)known_range, n);
-        // u8 is tried speculatively (no host round trip in the common case)
-        const bool spec = (bpc == 1) && g_speculate;
-    compress_pass:
-        if (sv.fused_t) {   // cc already holds the transposed problem (k_compress_tr); the same bytes serve both price widths
-            sv.bid0_done = false;   // (a 1-byte attempt queued before the fused pass may have set it)
-            sv.cc_partial = false;
-            sv.zs_done = false;
-            fits = true;
-            sv.bpc = bpc;
-            if (np_failed) k_fill_i32<<<1, 64, 0, c.stream>>>((int *)sv.misc.p + CTL_FLAG, 2, 0);   // the price-limit flag of the 32-bit attempt
-        } else {
-            // 1-byte attempt: state init + the shape probe ride in front of the compress pass, which writes round 0's bids
-            sv.want_bid0 = spec && !g_solver_eps;
-            sv.lazy_cc = true;
-            sv.zs_V = (sv.want_bid0 && orient == 0) ? (g_blocks >= 0 ? g_blocks : (n >= g_blocks_min_n ? 8 : 0)) : 0;
-            sv.probe = (spec && orient == 0 && g_shape && n >= 64 && n <= g_shape_max_n && !g_solver_eps) ? sv.d_cost : nullptr;
-            sv.range_seen = -1;
-            rc = sv_compress(sv, bpc, &fits, spec);
-            sv.want_bid0 = false;
-            sv.lazy_cc = false;
-            sv.probe = nullptr;
-            if (rc) return rc;
-            // a width that fits after a mere lower bound of the range (the line probe's "row 0 is too wide for one byte"):
-            // the warm start's schedule and the "is it wide" test need the measured range
-            if (!spec && fits && sv.range_seen > known_range) known_range = sv.range_seen;
-        }
-        if (line_pending) {
-            line_pending = false;
-            sv.skip = nullptr;
-            int mode = 0, kd = 0, accepted = 0, susp = 0, shape3[4] = {0, 0, 0, 0};
-            if ((rc = line_probe_wait(&mode, &kd, &susp, shape3))) return rc;
-            if (mode == 0 && susp) {
-                // The probe made the speculative 1-byte pass queued behind it a no-op (its device flag): that attempt
-                // was going to be void — row 0 is too wide for one byte, or the model is padded with dummy requests.
-                const int margin = n / 256 > 32 ? n / 256 : 32;   // the rule of the shape probe (k_init_state), on the probe's estimate
-                if (g_fuse_t && g_shape && !g_solver_eps && !no_fuse && shape3[0] >= 16 && shape3[0] - shape3[1] >= margin) {
-                    bool ff = false;
-                    int64_t fr = 0;
-                    // Speculative (no host round trip) when the fill value looks like one: cells in 0 .. fill, 32-bit prices.
-                    // A cell that does not fit raises CTL_FLAG, every later kernel exits, and the final read-back sends the
-                    // call back to the general path (restart).
-                    fused_spec = g_fuse_spec && shape3[3] >= 255 && (int64_t)shape3[3] <= NP_RANGE;
-                    // 1-byte cells + escape first ({small range} u {fill}: every reference model of this kind), else 4-byte cells
-                    if (g_fuse_t >= 2 && n > 2048 && n <= 65536) {   // a small model is launch-bound: 64 x 1024 tiles leave most CUs idle (tick: 0.465 vs 0.432 ms)
-                        if ((rc = sv_compress_fused(sv, &ff, &fr, true, shape3[3], fused_spec, shape3[3]))) return rc;
-                        sv.fused8 = ff;
-                    }
-                    if (!ff && (rc = sv_compress_fused(sv, &ff, &fr, false, 0, fused_spec, shape3[3]))) return rc;
-                    if (fused_spec) fr = shape3[3];
-                    if (getenv("TD_DEBUG")) fprintf(stderr, "[td] fused transpose + compress: n=%d fits %d range %lld, %d constant rows\n", n, (int)ff, (long long)fr, sv.nconst);
-                    if (ff) {
-                        sv.fused_t = true;
-                        transposed = true;
-                        known_range = fr;
-                        // thresholded models are a few huge tie classes: the rounds stop making progress after 5 - 6
-                        // (profiles/r3), every further launch is ~10 us of early exits; what is left goes to the finisher
-                        max_rounds = std::min(max_rounds, g_fused_rounds);
-                        continue;   // on to the 4-byte widths
-                    }
-                    early_check = true;   // the 1-byte attempt is likely void: one look at its flags before the rounds are queued
-                    goto compress_pass;   // negative cells or a range beyond 32 bits: the general path, from the 1-byte attempt
-                }
-                if (shape3[2]) {   // row 0 does not fit one byte per cell: skip the 1-byte attempt, the next width measures the range
-                    known_range = std::max<int64_t>(known_range, 255);
-                    continue;
-                }
-                early_check = true;
-                goto compress_pass;   // only a hint that did not lead anywhere: run the skipped pass
-            }
-            if (getenv("TD_DEBUG")) fprintf(stderr, "[td] line probe: n=%d verdict %d, %d constant rows, suspicious %d\n", n, mode, kd, susp);
-            if (mode) {
-                const int32_t *res = nullptr;
-                bool line_t = false;
-                if (mode == 2) {
-                    // constant trailing COLUMNS (more cabs than requests): the same model on the transpose
-                    if ((rc = ensure(sv.tbuf, sizeof(int32_t) * (size_t)n * n))) return rc;
-                    k_transpose<<<dim3((n + 63) / 64, (n + 63) / 64), 256, 0, c.stream>>>(n, sv.d_cost, (int32_t *)sv.tbuf.p);
-                    TD_HIP(hipGetLastError());
-                    const long long *unused = nullptr;
-                    if ((rc = line_probe_launch(n, (const int32_t *)sv.tbuf.p, &unused))) return rc;
-                    if ((rc = line_probe_wait(&mode, &kd))) return rc;
-                    if (getenv("TD_DEBUG")) fprintf(stderr, "[td] line probe on the transpose: verdict %d, %d constant rows\n", mode, kd);
-                    line_t = true;
-                    c.stats[12] |= LP_TRANSPOSE;
-                }
-                if (mode == 1 || mode == 3) {
-                    int fin = 0;
-                    if ((rc = line_finish(n, mode == 3 ? kd : 0, line_t ? (const int32_t *)sv.tbuf.p : sv.d_cost, &res, &tot, &accepted, &fin)))
-                        return rc;
-                    c.stats[12] |= (mode == 1 ? LP_BALANCED : LP_UNBAL) | fin;
-                }
-                if (accepted) {
-                    const int64_t line_path = c.stats[12] | LP_ACCEPTED;
-                    for (int k = 0; k < 16; k++) c.stats[k] = 0;
-                    c.stats[12] = line_path;
-                    c.stats[4] = 4;
-                    c.stats[7] = line_t ? 1 : 0;
-                    c.stats[8] = 1;
-                    c.stats[9] = mode == 3 ? kd : 0;
-                    if (line_t) {   // res[column] = row of the caller's matrix: invert
-                        k_r2c_from_owner<<<(n + 255) / 256, 256, 0, c.stream>>>(n, n, 0, (const int *)res, (int *)sv.r2c.p);
-                        TD_HIP(hipGetLastError());
-                        res = (const int32_t *)sv.r2c.p;
-                    }
-                    TD_HIP(hipMemcpyAsync(row_to_col, res, sizeof(int32_t) * (size_t)n,
-                                          is_device_ptr(row_to_col) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c.stream));
-                    TD_HIP(hipStreamSynchronize(c.stream));
-                    if (total) *total = tot;
-                    if (dual_bound) *dual_bound = tot;   // the certificate IS the dual bound (sum of row minima + prices)
-                    return TD_OK;
-                }
-                goto compress_pass;   // plausible but not proven: the pass above was skipped, run it now
-            }
-        }
-        if (!fits) {
-            known_range = c.stats[6];
-            continue;
-        }
-        // shape probe (inside k_init_state): may ask (CTL_FLAG bit 2) for the transposed formulation;
-        // like a failed width speculation this costs one empty pass through the early-exiting kernels
-        sv.probe = (spec && orient == 0 && g_shape && n >= 64 && n <= g_shape_max_n && !g_solver_eps) ? sv.d_cost : nullptr;
-        rc = TD_OK;
-        if (!sv.bid0_done) TD_DISPATCH(sv, sv_begin_t, sv);
-        sv.probe = nullptr;
-        if (rc) return rc;
-        if (spec && early_check) {
-            // the line probe saw a row too wide for one byte or a constant last column: this speculative attempt
-            // will most likely be void (width flag, or the shape probe asking for the transpose).  One round trip
-            // now instead of the ~30 launches of rounds and finishers that would exit at once.
-            early_check = false;
-            int ef = 0;
-            if ((rc = sv_readback(sv, nullptr, nullptr, 0, &ef))) return rc;
-            if (ef & 4) {
-                want_transpose = true;
-                range_hint = c.stats[6] > 254 ? c.stats[6] : -1;
-                break;
-            }
-            if (ef) {
-                known_range = c.stats[6];
-                continue;
-            }
-        }
-        int64_t warm_rounds = 0;
-        if (g_solver_eps) {
-            int64_t er = 0, ep = 0;
-            TD_DISPATCH(sv, sv_solve_eps_t, sv, g_eps0_mult, g_eps_theta, &er, &ep);
-            if (rc) return rc;
-            TD_DISPATCH(sv, sv_totals_t, sv, false);
-            if (rc) return rc;
-            int flag = 0;
-            if ((rc = sv_readback(sv, &tot, &dual, 0, spec ? &flag : nullptr))) return rc;
-            if (spec && flag) {
-                known_range = c.stats[6];
-                continue;
-            }
-            dual = tot;   // exact by the eps < 1/n argument; no certificate pass in this mode
-            c.stats[0] = er;
-            c.stats[1] = ep;
-            solved = true;
-            break;
-        }
-        int round_cap = max_rounds;
-        auto rounds = [&](bool first) -> int {
-            for (int r = 0; r < round_cap; r++) {
-                rc = TD_OK;
-                if (!(r == 0 && first && sv.bid0_done)) TD_DISPATCH(sv, sv_bid_t, sv, r, (unsigned long long *)sv.bid.p);
-                if (rc) return rc;
-                TD_DISPATCH(sv, sv_apply_t, sv, r, (unsigned long long *)sv.bid.p);
-                if (rc) return rc;
-            }
-            return TD_OK;
-        };
-        bool random_like = false;
-        auto warm = [&](int bits) -> int {
-            const int keep = g_warm_bits;
-            g_warm_bits = bits;
-            if (bpc == 2) rc = sv_warm_t<uint16_t>(sv, known_range, &warm_rounds, &random_like);
-            else if (bpc == 5) rc = sv_warm_t<u32n>(sv, known_range, &warm_rounds, &random_like);
-            else rc = sv_warm_t<uint32_t>(sv, known_range, &warm_rounds, &random_like);
-            g_warm_bits = keep;
-            return rc;
-        };
-        bool all_placed = false;
-        if (sv.zs_done) {
-            // block-local start (td_blocks.h): zero cells of the diagonal blocks, then one two-hop pass over the whole
-            // matrix for what the blocks left; one small read-back tells whether anything is left for the rounds and the
-            // finisher (on tie-heavy instances nothing is: ~30 launches that would all exit at once are not made)
-            // (the same TD_HOP_PASSES two-hop passes inside the blocks as the sharded solve makes: the two sequences are the
-            // same up to here, and identical altogether when the blocks leave nothing)
-            const int passes_a = g_hop_passes;
-            if ((rc = sv_phase_a(sv, passes_a))) return rc;
-            if (passes_a > 0 && g_one_trip && !transposed && !sv.gen) {
-                // one-trip sequence: the pass over the whole matrix and the end of the solve are queued at once, gated on
-                // the device (k_hop_lists, k_place_const, k_dual, k_final); one synchronisation reads k_final's record
-                if (g_hop_global && (rc = sv_hop_t<uint8_t>(sv, n, n, 0, 1, true, nullptr, sv.cc_partial, true))) return rc;
-                const bool dev_out = is_device_ptr(row_to_col);
-                r2c_in_pinned = !dev_out && (size_t)R2C_PIN_OFF + sizeof(int32_t) * (size_t)n <= c.pinned_cap;
-                int *r2c_out = dev_out ? row_to_col : (r2c_in_pinned ? (int *)((char *)c.pinned + R2C_PIN_OFF) : nullptr);
-                if ((rc = sv_end_gated(sv, dual_bound != nullptr, r2c_out))) return rc;
-                TD_HIP(hipStreamSynchronize(c.stream));
-                const char *rec = (const char *)c.pinned + REC_OFF;
-                const int left = ((const int *)rec)[REC_LEFT / sizeof(int)], rflag = ((const int *)rec)[CTL_FLAG];
-                if (left < 0) return fail(TD_EINTERNAL, "the end-of-solve record was not written");
-                if (getenv("TD_DEBUG")) fprintf(stderr, "[td] one trip: %d rows free after the two-hop passes, flag %d\n", left, rflag);
-                if (left == 0 && rflag == 0) {
-                    int flag = 0;
-                    if ((rc = sv_readback_parse(sv, rec, &tot, &dual, max_rounds, &flag))) return rc;
-                    c.stats[1] = 0;
-                    c.stats[6] = 0;
-                    r2c_on_device = dev_out;
-                    solved = true;
-                    break;
-                }
-                // rows left, or the width flag: the rounds and the finishers as before (nothing above has changed the state)
-                r2c_in_pinned = false;
-                round_cap = std::min(max_rounds, g_zs_global_rounds);
-            } else if (passes_a > 0) {
-                int *pin = (int *)c.pinned;
-                auto read_left = [&]() -> int {
-                    TD_HIP(hipMemcpyAsync(pin, (char *)sv.hop.p + offsetof(HopCtl, left), sizeof(int), hipMemcpyDeviceToHost, c.stream));
-                    TD_HIP(hipMemcpyAsync(pin + 1, (int *)sv.misc.p + CTL_FLAG, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-                    TD_HIP(hipStreamSynchronize(c.stream));
-                    return TD_OK;
-                };
-                if ((rc = read_left())) return rc;
-                if (getenv("TD_DEBUG")) fprintf(stderr, "[td] after the block-local start: %d rows free, flag %d\n", pin[0], pin[1]);
-                if (pin[0] > 0 && pin[1] == 0 && g_hop_global && pin[0] <= g_hop_max_rows) {
-                    // (nothing has moved a price yet: "tight" is "zero cell" over the whole row too, and the pass needs no row minimum)
-                    if ((rc = sv_hop_t<uint8_t>(sv, n, n, 0, 1, true, nullptr, sv.cc_partial))) return rc;
-                    if ((rc = read_left())) return rc;
-                    if (getenv("TD_DEBUG")) fprintf(stderr, "[td] after the two-hop pass over the whole matrix: %d rows free\n", pin[0]);
-                }
-                all_placed = pin[0] == 0 && pin[1] == 0;
-                round_cap = std::min(max_rounds, g_zs_global_rounds);
-            }
-        }
-        if (!all_placed && (rc = sv_complete_cc(sv))) return rc;   // the rounds and the finishers read whole rows of the narrow copy
-        if (!all_placed && (rc = rounds(true))) return rc;
-        // Wide, tie-free rows (no constant rows, few rows tied at their minimum) that the eps = 0
-        // rounds leave with many free rows.  One small read-back; only non-speculative attempts
-        // (u16 / u32 rows), which have synchronised for the width flag already.
-        bool wide = false, hard16 = false;
-        if (g_warm && !g_solver_eps && !spec && bpc != 1 && sv.nconst == 0 && known_range >= g_warm_min_range) {
-            k_freelist<<<1, 1024, 0, c.stream>>>(n, (const int *)sv.r2c.p, (int *)sv.list.p, (int *)sv.misc.p);
-            TD_HIP(hipMemcpyAsync(c.pinned, sv.misc.p, CTL_ALL * sizeof(int), hipMemcpyDeviceToHost, c.stream));
-            TD_HIP(hipStreamSynchronize(c.stream));
-            const int nfree_now = ((int *)c.pinned)[CTL_NFREE], tied0 = ((int *)c.pinned)[CTL_TIED];
-            // tied0 counts every 16th row (every row of a model below 1024).  No warm start below TD_WARM_MIN_N rows: a
-            // thresholded 60 x 60 model ran 800 warm rounds = 8 ms for rows the serial workgroup finishes in microseconds
-            // (tools/r4_outliers.py found it: the 4 sampled rows of so small a model missed its ties)
-            wide = n >= g_warm_min_n && !(nfree_now < std::max(g_warm_minfree, n / 64) || (long long)tied0 * (n < 1024 ? 1 : 16) * g_warm_tie_div > n);
-            c.stats[2] = nfree_now;
-            hard16 = bpc == 2 && g_u16_redo_free > 0 && nfree_now >= g_u16_redo_free;
-        }
-        if ((wide || hard16) && bpc == 2 && g_wide_u16_n && n >= g_wide_u16_n && g_narrow_price && !np_failed && known_range >= 0 &&
-            known_range <= NP_RANGE) {
-            // A hard instance (the finisher will dominate) in 2-byte cells: the cooperative finisher k_sapx needs
-            // n / E >= 8 * 256 chunks and the 2-byte kernels carry 64-bit prices.  Redo it as 4-byte cells with
-            // 32-bit prices (the next width of the loop): one more compress pass and 12 rounds, milliseconds
-            // against hundreds (2-D Manhattan grid, n = 8192: 493 -> 224 ms, n = 16 384: 848 -> 640 ms).
-            continue;
-        }
-        if (wide) {
-            // eps > 0 phases down to eps = 1 as a price warm start (sv_warm_t), the rounds once more,
-            // then the dense finisher
-            if ((rc = warm(g_warm_bits))) return rc;
-            if (random_like) round_cap = std::max(round_cap, g_rand_rounds);   // (cheap here: a few hundred bidders; halves what is left for the forest)
-            if ((rc = rounds(false))) return rc;
-        }
-        ShardTab tab{};
-        tab.p[0] = sv.cc.p;
-        tab.rps = n;
-        tab.count = 1;
-        sv.placed = false;
-        if (!all_placed) TD_DISPATCH(sv, sv_finish_t, sv, tab, (int *)sv.r2c.p);
-        if (rc) return rc;
-        if (sv.defer_const && !sv.placed) {
-            ProfScope ps(TD_K_FINAL);
-            k_place_const<<<1, 1024, 0, c.stream>>>(n, (int *)sv.r2c.p, (int *)sv.owner.p, (int *)sv.list.p, (int *)sv.pred.p,
-                                                   (int *)sv.misc.p);
-        }
-        if (dual_bound != nullptr && (rc = sv_complete_cc(sv))) return rc;   // (k_dual reads the narrow rows)
-        TD_DISPATCH(sv, sv_totals_t, sv, dual_bound != nullptr);
-        if (rc) return rc;
-        int flag = 0;
-        // a host row_to_col of a small model rides along with the read-back (one round trip, no blocking pageable copy)
-        r2c_in_pinned = !is_device_ptr(row_to_col) && (size_t)R2C_PIN_OFF + sizeof(int32_t) * (size_t)n <= c.pinned_cap;
-        if (r2c_in_pinned)
-            TD_HIP(hipMemcpyAsync((char *)c.pinned + R2C_PIN_OFF, transposed ? sv.owner.p : sv.r2c.p, sizeof(int32_t) * (size_t)n,
-                                  hipMemcpyDeviceToHost, c.stream));
-        if ((rc = sv_readback(sv, &tot, &dual, max_rounds, (spec || bpc == 5 || bpc == 6) ? &flag : nullptr))) return rc;
-        c.stats[1] = warm_rounds;
-        if (sv.fused_t && fused_spec && (flag & 1)) {
-            // the speculative fused pass met a cell outside 0 .. fill (or, for 1-byte cells, outside base .. base + 253):
-            // nothing of it can be kept
-            if (getenv("TD_DEBUG")) fprintf(stderr, "[td] speculative fused pass refused (flag %d): general path\n", flag);
-            if (bpc == 6 && !(flag & ~9)) {   // 1-byte cells did not fit: the same pass with 4-byte cells, checked this time
-                bool ff = false;
-                int64_t fr = 0;
-                sv.fused8 = false;
-                fused_spec = false;
-                if ((rc = sv_compress_fused(sv, &ff, &fr))) return rc;
-                if (ff) {
-                    known_range = fr;
-                    continue;
-                }
-            }
-            no_fuse = true;
-            sv.fused_t = sv.fused8 = false;
-            transposed = false;
-            fused_spec = false;
-            max_rounds = g_max_rounds;
-            early_check = true;
-            if ((rc = materialise())) return rc;   // (td_build_assign: the general path reads the matrix)
-            goto restart;
-        }
-        if (bpc == 5 && flag) {   // a price reached the 32-bit limit: the attempt is void, redo with 64-bit prices
-            np_failed = true;
-            continue;
-        }
-        if (bpc == 6 && flag) {   // the same guard for the 1-byte cells with the escape: redo the fused pass as 4-byte cells
-            bool ff = false;
-            int64_t fr = 0;
-            sv.fused8 = false;
-            if ((rc = sv_compress_fused(sv, &ff, &fr))) return rc;
-            if (!ff) return fail(TD_EINTERNAL, "fused transpose pass: 4-byte cells refused after the 1-byte ones fitted");
-            known_range = fr;
-            continue;
-        }
-        if (spec && (flag & 4)) {  // many constant columns: solve the transposed problem instead
-            want_transpose = true;
-            range_hint = c.stats[6] > 254 ? c.stats[6] : -1;
-            break;
-        }
-        if (spec && flag) {  // rows did not fit u8: redo with the width the recorded range needs
-            known_range = c.stats[6];
-            continue;
-        }
-        c.stats[6] = (bpc == 5) ? 1 : 0;   // 1: solved in the narrow-price mode
-        solved = true;
-        break;
-    }
-    if (!want_transpose) break;
-    {
-        ProfScope ps(TD_K_FINAL);
-        if ((rc = ensure(sv.tbuf, sizeof(int32_t) * (size_t)n * n))) return rc;
-        k_transpose<<<dim3((n + 63) / 64, (n + 63) / 64), 256, 0, c.stream>>>(n, sv.d_cost, (int32_t *)sv.tbuf.p);
-        TD_HIP(hipGetLastError());
-        sv.d_cost = (const int32_t *)sv.tbuf.p;
-        transposed = true;
-    }
-    }
-    if (!solved) return fail(TD_ERANGE, "row cost range exceeds 2^32-2");
-    // transposed solve: its columns are the caller's rows, owner[] is the caller's row_to_col
-    const void *res = transposed ? sv.owner.p : sv.r2c.p;
-    c.stats[7] = transposed ? 1 : 0;
-    if (r2c_in_pinned) {
-        memcpy(row_to_col, (const char *)c.pinned + R2C_PIN_OFF, sizeof(int32_t) * (size_t)n);
-        if (total) *total = tot;
-        if (dual_bound) *dual_bound = dual;
+    hint.valid = true;
+    hint.gen = true;
+    hint.src = CellSrc{d_cab, d_dem, d_dist, n_s, n_d, S, fill, threshold};
+    return assign_impl(sv, hint, n, (const int32_t *)sv.misc.p /* placeholder: no matrix exists */, row_to_col, total, dual_bound);
+}
+
+// td_build_assign / td_solver_build_assign: the (small) position arrays and a host distance table once on the device, in a
+// buffer of the solver's workspace
+int build_assign_host(Solver &sv, const int32_t *cab_to, int n_s, const int32_t *dem_from, int n_d, const int32_t *dist, int S, int32_t fill,
+                      int32_t threshold, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
+{
+    TD_REQUIRE_INIT();
+    Ctx &c = ctx();
+    if (n_s < 0 || n_d < 0) return fail(TD_EINVAL, "negative sizes n_s=%d n_d=%d", n_s, n_d);
+    const int n = std::max(n_s, n_d);
+    if (n == 0) {   // simulate.py:38  n == 0 -> (0, [], 0)
+        if (total) *total = 0;
+        if (dual_bound) *dual_bound = 0;
         return TD_OK;
     }
-    if (r2c_on_device) {   // (k_final stored it, and the stream has been synchronised)
-        if (total) *total = tot;
-        if (dual_bound) *dual_bound = dual;
-        return TD_OK;
+    if ((n_s && !cab_to) || (n_d && !dem_from) || !row_to_col) return fail(TD_EINVAL, "null array");
+    if (dist && S <= 0) return fail(TD_EINVAL, "dist given but S=%d", S);
+    int rc;
+    const size_t words = (size_t)n_s + n_d + ((dist && !is_device_ptr(dist)) ? (size_t)S * S : 0) + 16;
+    if ((rc = ensure(sv.gpos, sizeof(int32_t) * words))) return rc;
+    int32_t *buf = (int32_t *)sv.gpos.p;
+    const int32_t *d_cab = cab_to, *d_dem = dem_from, *d_dist = dist;
+    if (n_s && !is_device_ptr(cab_to)) {
+        TD_HIP(hipMemcpyAsync(buf, cab_to, sizeof(int32_t) * (size_t)n_s, hipMemcpyHostToDevice, c.stream));
+        d_cab = buf;
     }
-    if (is_device_ptr(row_to_col)) {
-        TD_HIP(hipMemcpyAsync(row_to_col, res, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, c.stream));
-    } else {
-        TD_HIP(hipMemcpyAsync(row_to_col, res, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c.stream));
+    if (n_d && !is_device_ptr(dem_from)) {
+        TD_HIP(hipMemcpyAsync(buf + n_s, dem_from, sizeof(int32_t) * (size_t)n_d, hipMemcpyHostToDevice, c.stream));
+        d_dem = buf + n_s;
     }
-    TD_HIP(hipStreamSynchronize(c.stream));
-    if (total) *total = tot;
-    if (dual_bound) *dual_bound = dual;
-    return TD_OK;
+    if (dist && !is_device_ptr(dist)) {
+        TD_HIP(hipMemcpyAsync(buf + n_s + n_d, dist, sizeof(int32_t) * (size_t)S * S, hipMemcpyHostToDevice, c.stream));
+        d_dist = buf + n_s + n_d;
+    }
+    return build_assign_dev(sv, d_cab, n_s, d_dem, n_d, d_dist, S, fill, threshold, false, row_to_col, total, dual_bound);
 }
 
 }  // namespace
 
-// ---- handle-scoped solvers ("re-entrant per handle"): a td_solver owns its grow-only workspace, so a process can
-// keep, say, one sized for N = 65 536 and one for ticks side by side; calls stay synchronous and one at a time, like the
-// reference (td_assign itself is the solver of the library's own default handle)
+int td::build_assign_device(const int32_t *d_cab, int n_s, const int32_t *d_dem, int n_d, const int32_t *d_dist, int S, int32_t fill,
+                            int32_t threshold, bool tick, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
+{
+    return build_assign_dev(g_default, d_cab, n_s, d_dem, n_d, d_dist, S, fill, threshold, tick, row_to_col, total, dual_bound);
+}
+
+extern "C" int td_assign(int n, const int32_t *cost, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
+{
+    return assign_impl(g_default, AssignHint(), n, cost, row_to_col, total, dual_bound);
+}
+
+extern "C" int td_build_assign(const int32_t *cab_to, int n_s, const int32_t *dem_from, int n_d, const int32_t *dist, int S, int32_t fill,
+                               int32_t threshold, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
+{
+    return build_assign_host(g_default, cab_to, n_s, dem_from, n_d, dist, S, fill, threshold, row_to_col, total, dual_bound);
+}
+
+// ---- handle-scoped solvers: a td_solver owns its grow-only workspace, so a process can keep, say, one sized
+// for N = 65 536 and one for ticks side by side.  Calls stay synchronous and one at a time per process, whichever handle
+// they go to: the stream, the pinned read-back block and td_last_stats belong to the library context (td_assign itself is
+// the solver of the library's own default handle)
 struct td_solver {
     td_shard ws;
 };
@@ -4654,54 +4832,14 @@ extern "C" int td_solver_destroy(td_solver *h)
 extern "C" int td_solver_assign(td_solver *h, int n, const int32_t *cost, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
 {
     if (!h) return fail(TD_EINVAL, "null solver");
-    return assign_impl(h->ws, n, cost, row_to_col, total, dual_bound);
+    return assign_impl(h->ws, AssignHint(), n, cost, row_to_col, total, dual_bound);
 }
 
 extern "C" int td_solver_build_assign(td_solver *h, const int32_t *cab_to, int n_s, const int32_t *dem_from, int n_d, const int32_t *dist, int S,
                                       int32_t fill, int32_t threshold, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
 {
     if (!h) return fail(TD_EINVAL, "null solver");
-    Solver *was = g_active;
-    g_active = &h->ws;
-    const int rc = td_build_assign(cab_to, n_s, dem_from, n_d, dist, S, fill, threshold, row_to_col, total, dual_bound);
-    g_active = was;
-    return rc;
-}
-
-extern "C" int td_build_assign(const int32_t *cab_to, int n_s, const int32_t *dem_from, int n_d, const int32_t *dist, int S, int32_t fill,
-                               int32_t threshold, int32_t *row_to_col, int64_t *total, int64_t *dual_bound)
-{
-    TD_REQUIRE_INIT();
-    Ctx &c = ctx();
-    if (n_s < 0 || n_d < 0) return fail(TD_EINVAL, "negative sizes n_s=%d n_d=%d", n_s, n_d);
-    const int n = std::max(n_s, n_d);
-    if (n == 0) {   // simulate.py:38  n == 0 -> (0, [], 0)
-        if (total) *total = 0;
-        if (dual_bound) *dual_bound = 0;
-        return TD_OK;
-    }
-    if ((n_s && !cab_to) || (n_d && !dem_from) || !row_to_col) return fail(TD_EINVAL, "null array");
-    if (dist && S <= 0) return fail(TD_EINVAL, "dist given but S=%d", S);
-    // the (small) position arrays and a host distance table: once on the device, in a buffer of the solver's workspace
-    Solver &sv = *g_active;
-    int rc;
-    const size_t words = (size_t)n_s + n_d + ((dist && !is_device_ptr(dist)) ? (size_t)S * S : 0) + 16;
-    if ((rc = ensure(sv.gpos, sizeof(int32_t) * words))) return rc;
-    int32_t *buf = (int32_t *)sv.gpos.p;
-    const int32_t *d_cab = cab_to, *d_dem = dem_from, *d_dist = dist;
-    if (n_s && !is_device_ptr(cab_to)) {
-        TD_HIP(hipMemcpyAsync(buf, cab_to, sizeof(int32_t) * (size_t)n_s, hipMemcpyHostToDevice, c.stream));
-        d_cab = buf;
-    }
-    if (n_d && !is_device_ptr(dem_from)) {
-        TD_HIP(hipMemcpyAsync(buf + n_s, dem_from, sizeof(int32_t) * (size_t)n_d, hipMemcpyHostToDevice, c.stream));
-        d_dem = buf + n_s;
-    }
-    if (dist && !is_device_ptr(dist)) {
-        TD_HIP(hipMemcpyAsync(buf + n_s + n_d, dist, sizeof(int32_t) * (size_t)S * S, hipMemcpyHostToDevice, c.stream));
-        d_dist = buf + n_s + n_d;
-    }
-    return td::build_assign_device(d_cab, n_s, d_dem, n_d, d_dist, S, fill, threshold, false, row_to_col, total, dual_bound);
+    return build_assign_host(h->ws, cab_to, n_s, dem_from, n_d, dist, S, fill, threshold, row_to_col, total, dual_bound);
 }
 
 extern "C" int td_set_line_metric(int on)
@@ -4847,8 +4985,8 @@ int td_shard_phase_a(td_shard *s)
 //   global row ids, -1 free) and the constant-row flags of its rows (rows_per_shard words).
 // The caller all-gathers the segments (rank order) and hands the concatenation to td_shard_state_import, which fills in
 // the other ranks' owner slices, the owned bits of the packed prices and the replicated constant-row mask
-// (td_shard_const_rows' job), and returns summary[0..4] = {all fit, all ran phase A, free rows left in total,
-// constant rows in total, largest row range}.
+// (td_shard_const_rows' job), and returns summary[0..5] = {all fit, all ran phase A, free rows left in total,
+// constant rows in total, largest row range, rank 0's segment word 6}.
 int td_shard_state_words(td_shard *s, int rows_per_shard) { return s ? 16 + 2 * rows_per_shard : 0; }
 }   // extern "C"
 
@@ -4927,11 +5065,11 @@ int td_shard_state_export(td_shard *s, int rows_per_shard, int fits, int32_t *se
     return TD_OK;
 }
 
-int td_shard_state_import(td_shard *s, int world, int rank, int rows_per_shard, const int32_t *all, int64_t *summary5)
+int td_shard_state_import(td_shard *s, int world, int rank, int rows_per_shard, const int32_t *all, int64_t *summary6)
 {
     TD_REQUIRE_INIT();
     Ctx &c = ctx();
-    if (!s || !all || !summary5 || world < 1 || rank < 0 || rank >= world) return fail(TD_EINVAL, "td_shard_state_import: bad arguments");
+    if (!s || !all || !summary6 || world < 1 || rank < 0 || rank >= world) return fail(TD_EINVAL, "td_shard_state_import: bad arguments");
     if (!is_device_ptr(all)) return fail(TD_EINVAL, "td_shard_state_import: the segments must be device memory");
     if ((long long)rows_per_shard * world < s->n) return fail(TD_EINVAL, "td_shard_state_import: rows_per_shard * world < n");
     int rc;
@@ -4946,7 +5084,7 @@ int td_shard_state_import(td_shard *s, int world, int rank, int rows_per_shard, 
     TD_HIP(hipGetLastError());
     TD_HIP(hipMemcpyAsync(c.pinned, sum_dev, 6 * sizeof(long long), hipMemcpyDeviceToHost, c.stream));
     TD_HIP(hipStreamSynchronize(c.stream));
-    for (int k = 0; k < 6; k++) summary5[k] = ((const long long *)c.pinned)[k];
+    for (int k = 0; k < 6; k++) summary6[k] = ((const long long *)c.pinned)[k];
     s->have_cmask = true;
     s->defer_const = g_defer_const && !g_solver_eps;
     return TD_OK;

@@ -471,9 +471,3 @@ __global__ __launch_bounds__(HOP_MATCH_T) void k_hop_match(int nrows, int row0, 
     }
 }
 
-// ---- after the exchange of the owner slices: the owned bit of the columns other ranks own (prices are all 0)
-__global__ void k_zs_owned_bits(int n, const int *__restrict__ owner, int32_t *__restrict__ pk)
-{
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) pk[j] = (pk[j] & ~1) | (owner[j] >= 0 ? 1 : 0);
-}

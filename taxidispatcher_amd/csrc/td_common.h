@@ -57,6 +57,12 @@ void buf_free(Buf &b);
 bool is_device_ptr(const void *p);
 // returns a device pointer holding `bytes` of src (src itself when already on the device)
 int to_device(const void *src, size_t bytes, Buf &stage, const void **out);
+// a slot of the pinned input ring for `bytes` of host input (the ring wraps after a stream synchronisation); *slot = nullptr
+// when there is no ring or the input is empty or larger than PIN_IN_MAX: the caller copies from its own array
+constexpr size_t PIN_IN_MAX = 32768;
+int pin_in_slot(size_t bytes, void **slot);
+// queues the copy of a HOST array to the device, through the ring when it fits
+int copy_in(void *dst, const void *src, size_t bytes);
 // td_line.hip: sorted matching + certificate pass for line-metric matrices (tried first by td_assign)
 //   line_probe_launch  queues the O(n) probe; *skip_dev = device word that is non-zero unless the probe refuses;
 //                      clear_words non-null: the probe also zeroes clear_words[0 .. nclear) (td_assign's control words)
@@ -73,10 +79,7 @@ int line_probe_wait(int *mode, int *k, int *suspicious = nullptr /* the 1-byte a
                     int *shape3 = nullptr /* int[4]: estimated constant columns / rows, row 0 too wide for one byte, value of the last column */);
 int line_finish(int n, int k, const int32_t *d_cost, const int32_t **r2c_dev, int64_t *total, int *accepted, int *path);
 void line_release_workspace();
-// td_assign.hip: a hint for the NEXT td_assign call of this process (consumed by it): the matrix is a model padded with
-// `const_cols` dummy requests and `const_rows` dummy cabs of value `fill` (td_tick knows this from its position arrays)
-void assign_hint_padded(int const_cols, int const_rows, int32_t fill);
-// td_assign.hip: cost build + optimal assignment from DEVICE position arrays (td_build_assign after staging, td_tick's remainder);
+// td_assign.hip: cost build + optimal assignment from DEVICE position arrays in the default workspace (td_tick's remainder);
 // a model padded with dummy requests never exists as an int32 matrix (its cells are made inside the fused compress pass)
 int build_assign_device(const int32_t *d_cab, int n_s, const int32_t *d_dem, int n_d, const int32_t *d_dist, int S, int32_t fill,
                         int32_t threshold, bool tick, int32_t *row_to_col, int64_t *total, int64_t *dual_bound);

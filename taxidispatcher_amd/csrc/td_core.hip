@@ -76,22 +76,37 @@ int to_device(const void *src, size_t bytes, Buf &stage, const void **out)
     }
     int rc = ensure(stage, bytes);
     if (rc) return rc;
-    Ctx &c = g_ctx;
-    if (c.pin_in && bytes > 0 && bytes <= 32768) {
-        // small input: through the pinned ring (the slot is reused only after a stream synchronisation at wrap-around)
-        const size_t need = (bytes + 255) & ~(size_t)255;
-        if (c.pin_in_off + need > c.pin_in_cap) {
-            TD_HIP(hipStreamSynchronize(c.stream));
-            c.pin_in_off = 0;
-        }
-        void *slot = (char *)c.pin_in + c.pin_in_off;
-        c.pin_in_off += need;
-        memcpy(slot, src, bytes);
-        TD_HIP(hipMemcpyAsync(stage.p, slot, bytes, hipMemcpyHostToDevice, c.stream));
-    } else {
-        TD_HIP(hipMemcpyAsync(stage.p, src, bytes, hipMemcpyHostToDevice, c.stream));
-    }
+    if ((rc = copy_in(stage.p, src, bytes))) return rc;
     *out = stage.p;
+    return TD_OK;
+}
+
+int pin_in_slot(size_t bytes, void **slot)
+{
+    Ctx &c = g_ctx;
+    *slot = nullptr;
+    if (!c.pin_in || bytes == 0 || bytes > PIN_IN_MAX) return TD_OK;
+    // the slot is reused only after a stream synchronisation at wrap-around
+    const size_t need = (bytes + 255) & ~(size_t)255;
+    if (c.pin_in_off + need > c.pin_in_cap) {
+        TD_HIP(hipStreamSynchronize(c.stream));
+        c.pin_in_off = 0;
+    }
+    *slot = (char *)c.pin_in + c.pin_in_off;
+    c.pin_in_off += need;
+    return TD_OK;
+}
+
+int copy_in(void *dst, const void *src, size_t bytes)
+{
+    void *slot = nullptr;
+    int rc = pin_in_slot(bytes, &slot);
+    if (rc) return rc;
+    if (slot) {
+        memcpy(slot, src, bytes);
+        src = slot;
+    }
+    TD_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, g_ctx.stream));
     return TD_OK;
 }
 

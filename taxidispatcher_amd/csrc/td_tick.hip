@@ -112,53 +112,31 @@ extern "C" int td_tick(const int32_t *cab_to, int n_s, const int32_t *dem_from, 
     // position arrays (and a host distance table) once on the device: both cost builds and the shrink read them there
     int32_t *d_pos = (int32_t *)t.pos.p;
     int32_t *d_cab = d_pos, *d_dem = d_pos + n, *d_cab2 = d_pos + 2 * (size_t)n, *d_dem2 = d_pos + 3 * (size_t)n;
-    auto put = [&](const int32_t *src, int cnt, int32_t *dst) -> int {
+    // small host arrays go through the library's pinned ring when they fit (a pageable async copy blocks the host)
+    auto put = [&c](const int32_t *src, int cnt, int32_t *dst) -> int {
         if (cnt == 0) return TD_OK;
-        const void *d = nullptr;
-        Buf tmp;   // to_device() stages small host arrays through the pinned ring into `tmp`... keep it simple: direct copies
-        (void)tmp;
-        (void)d;
-        TD_HIP(hipMemcpyAsync(dst, src, sizeof(int32_t) * (size_t)cnt, is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                              c.stream));
+        const size_t bytes = sizeof(int32_t) * (size_t)cnt;
+        if (!is_device_ptr(src)) return copy_in(dst, src, bytes);
+        TD_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c.stream));
         return TD_OK;
     };
-    // small host arrays go through the library's pinned ring when they fit (a pageable async copy blocks the host)
-    auto put_small = [&](const int32_t *src, int cnt, int32_t *dst) -> int {
-        const size_t bytes = sizeof(int32_t) * (size_t)cnt;
-        if (cnt > 0 && !is_device_ptr(src) && c.pin_in && bytes <= 32768) {
-            const size_t need = (bytes + 255) & ~(size_t)255;
-            if (c.pin_in_off + need > c.pin_in_cap) {
-                TD_HIP(hipStreamSynchronize(c.stream));
-                c.pin_in_off = 0;
-            }
-            void *slot = (char *)c.pin_in + c.pin_in_off;
-            c.pin_in_off += need;
-            memcpy(slot, src, bytes);
-            TD_HIP(hipMemcpyAsync(dst, slot, bytes, hipMemcpyHostToDevice, c.stream));
-            return TD_OK;
-        }
-        return put(src, cnt, dst);
-    };
-    if (n_s > 0 && n_d > 0 && !is_device_ptr(cab_to) && !is_device_ptr(dem_from) && c.pin_in && sizeof(int32_t) * 2 * (size_t)n <= 32768) {
+    void *slot = nullptr;
+    if (n_s > 0 && n_d > 0 && !is_device_ptr(cab_to) && !is_device_ptr(dem_from) && sizeof(int32_t) * 2 * (size_t)n <= PIN_IN_MAX) {
         // both position arrays in ONE staged copy (d_cab and d_dem are n apart)
-        const size_t bytes = sizeof(int32_t) * ((size_t)n + n_d), need = (bytes + 255) & ~(size_t)255;
-        if (c.pin_in_off + need > c.pin_in_cap) {
-            TD_HIP(hipStreamSynchronize(c.stream));
-            c.pin_in_off = 0;
-        }
-        int32_t *slot = (int32_t *)((char *)c.pin_in + c.pin_in_off);
-        c.pin_in_off += need;
+        if ((rc = pin_in_slot(sizeof(int32_t) * ((size_t)n + n_d), &slot))) return rc;
+    }
+    if (slot) {
         memcpy(slot, cab_to, sizeof(int32_t) * (size_t)n_s);
-        memcpy(slot + n, dem_from, sizeof(int32_t) * (size_t)n_d);
-        TD_HIP(hipMemcpyAsync(d_cab, slot, bytes, hipMemcpyHostToDevice, c.stream));
+        memcpy((int32_t *)slot + n, dem_from, sizeof(int32_t) * (size_t)n_d);
+        TD_HIP(hipMemcpyAsync(d_cab, slot, sizeof(int32_t) * ((size_t)n + n_d), hipMemcpyHostToDevice, c.stream));
     } else {
-        if ((rc = put_small(cab_to, n_s, d_cab))) return rc;
-        if ((rc = put_small(dem_from, n_d, d_dem))) return rc;
+        if ((rc = put(cab_to, n_s, d_cab))) return rc;
+        if ((rc = put(dem_from, n_d, d_dem))) return rc;
     }
     const int32_t *d_dist = dist;
     if (dist && !is_device_ptr(dist)) {
         int32_t *dd = d_pos + 4 * (size_t)n;
-        if ((rc = put_small(dist, S * S, dd))) return rc;
+        if ((rc = put(dist, S * S, dd))) return rc;
         d_dist = dd;
     }
     int k = 0;

@@ -154,7 +154,9 @@ def build_assign(cab_to, dem_from, distances=None, fill=BIG_COST, threshold=-1, 
 
 class Solver:
     """A handle-scoped solver (td_solver_*): its own grow-only workspace on the GPU, same calls and answers as assign() /
-    build_assign().  Several can live in one process (re-entrant per handle); calls stay synchronous."""
+    build_assign().  Several can live in one process, each keeping the workspace of its own models; calls stay synchronous and
+    one at a time per process, whichever handle they go to (the stream, the pinned read-back block and last_stats() belong to
+    the library context, not to the handle)."""
 
     def __init__(self):
         self.lib = _ffi.lib()
