@@ -1020,17 +1020,21 @@ __global__ __launch_bounds__(256) void k_assign(int n, int nrows, int row0, unsi
 // Ordered list of the entries equal to `want` (free rows: r2c == -1), built by ONE workgroup: every thread counts the free
 // rows of its own contiguous slice, one block-wide exclusive scan (wave DPP-free shuffle scan +
 // 16-entry LDS exchange), then every thread writes its rows at its offset.  Returns the count.
-__device__ __forceinline__ int build_free_list(int n, const int *__restrict__ r2c, int *__restrict__ list, int want = -1)
+// The two halves of the list are functions of their own: free_list_count only loads (a kernel may run it in front of its
+// flag and gate tests), free_list_fill writes the thread's entries at its offset.
+__device__ __forceinline__ bool free_list_vec(int n, const int *r2c)
 {
-    __shared__ int s_fl_w[16];
-    __shared__ int s_fl_tot;
-    const int T = blockDim.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = T >> 6;
+    // 16-byte loads where a thread's slice allows it (n = 16 384 with 1024 threads: 4 independent loads instead of 16)
+    return (((n + (int)blockDim.x - 1) / (int)blockDim.x) & 3) == 0 && (reinterpret_cast<uintptr_t>(r2c) & 15) == 0;
+}
+
+__device__ __forceinline__ int free_list_count(int n, const int *__restrict__ r2c, int want)
+{
+    const int T = blockDim.x, tid = threadIdx.x;
     const int per = (n + T - 1) / T;
     const int lo = tid * per, hi = min(n, lo + per);
     int cnt = 0;
-    // 16-byte loads where a thread's slice allows it (n = 16 384 with 1024 threads: 4 independent loads instead of 16)
-    const bool vec = (per & 3) == 0 && (reinterpret_cast<uintptr_t>(r2c) & 15) == 0;
-    if (vec) {
+    if (free_list_vec(n, r2c)) {
         int r = lo;
 #pragma unroll 4
         for (; r + 4 <= hi; r += 4) {
@@ -1040,6 +1044,73 @@ __device__ __forceinline__ int build_free_list(int n, const int *__restrict__ r2
         for (; r < hi; r++) cnt += (r2c[r] == want) ? 1 : 0;
     } else
         for (int r = lo; r < hi; r++) cnt += (r2c[r] == want) ? 1 : 0;
+    return cnt;
+}
+
+// the counts of two arrays of the same length in one loop: the loads of both arrays, four entries (or four 16-byte
+// pieces) each, are in flight together
+__device__ __forceinline__ void free_list_count2(int n, const int *__restrict__ a, int wanta, const int *__restrict__ b, int wantb,
+                                                 int &cnta, int &cntb)
+{
+    const int T = blockDim.x, tid = threadIdx.x;
+    const int per = (n + T - 1) / T;
+    const int lo = tid * per, hi = min(n, lo + per);
+    int ca = 0, cb = 0;
+    if ((n & 3) == 0 && free_list_vec(n, a) && free_list_vec(n, b)) {   // (every slice that is not empty is whole 16-byte pieces)
+        for (int r = lo; r < hi; r += 16) {
+            int4 xa[4], xb[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int rr = min(r + 4 * q, hi - 4);
+                xa[q] = *reinterpret_cast<const int4 *>(a + rr), xb[q] = *reinterpret_cast<const int4 *>(b + rr);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                if (r + 4 * q < hi) {
+                    ca += (xa[q].x == wanta) + (xa[q].y == wanta) + (xa[q].z == wanta) + (xa[q].w == wanta);
+                    cb += (xb[q].x == wantb) + (xb[q].y == wantb) + (xb[q].z == wantb) + (xb[q].w == wantb);
+                }
+        }
+    } else
+        for (int r = lo; r < hi; r += 4) {
+            int va[4], vb[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) va[q] = a[min(r + q, hi - 1)], vb[q] = b[min(r + q, hi - 1)];
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                if (r + q < hi) ca += va[q] == wanta, cb += vb[q] == wantb;
+        }
+    cnta = ca, cntb = cb;
+}
+
+__device__ __forceinline__ void free_list_fill(int n, const int *__restrict__ r2c, int *__restrict__ list, int want, int cnt, int pos)
+{
+    if (!cnt) return;   // (most slices hold nothing to list)
+    const int T = blockDim.x, tid = threadIdx.x;
+    const int per = (n + T - 1) / T;
+    const int lo = tid * per, hi = min(n, lo + per);
+    if (free_list_vec(n, r2c)) {
+        int r = lo;
+        for (; r + 4 <= hi; r += 4) {
+            const int4 x = *reinterpret_cast<const int4 *>(r2c + r);
+            if (x.x == want) list[pos++] = r;
+            if (x.y == want) list[pos++] = r + 1;
+            if (x.z == want) list[pos++] = r + 2;
+            if (x.w == want) list[pos++] = r + 3;
+        }
+        for (; r < hi; r++)
+            if (r2c[r] == want) list[pos++] = r;
+    } else
+        for (int r = lo; r < hi; r++)
+            if (r2c[r] == want) list[pos++] = r;
+}
+
+__device__ __forceinline__ int build_free_list(int n, const int *__restrict__ r2c, int *__restrict__ list, int want = -1)
+{
+    __shared__ int s_fl_w[16];
+    __shared__ int s_fl_tot;
+    const int T = blockDim.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int cnt = free_list_count(n, r2c, want);
     int incl = cnt;  // inclusive scan within the wave
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -1051,27 +1122,38 @@ __device__ __forceinline__ int build_free_list(int n, const int *__restrict__ r2
     int base = 0;
     for (int k = 0; k < w; k++) base += s_fl_w[k];
     if (tid == T - 1) s_fl_tot = base + incl;
-    int pos = base + incl - cnt;
-    if (cnt) {   // (most slices hold nothing to list)
-        if (vec) {
-            int r = lo;
-            for (; r + 4 <= hi; r += 4) {
-                const int4 x = *reinterpret_cast<const int4 *>(r2c + r);
-                if (x.x == want) list[pos++] = r;
-                if (x.y == want) list[pos++] = r + 1;
-                if (x.z == want) list[pos++] = r + 2;
-                if (x.w == want) list[pos++] = r + 3;
-            }
-            for (; r < hi; r++)
-                if (r2c[r] == want) list[pos++] = r;
-        } else
-            for (int r = lo; r < hi; r++)
-                if (r2c[r] == want) list[pos++] = r;
-    }
+    free_list_fill(n, r2c, list, want, cnt, base + incl - cnt);
     __syncthreads();
     const int tot = s_fl_tot;
     __syncthreads();   // the scratch is reused by a second call
     return tot;
+}
+
+// Two lists in one pass: the counts of both arrays come from the caller (free_list_count, whose loads of both arrays are
+// then in flight together), one scan and one pair of barriers serve both.  The lists are the bytes two calls of
+// build_free_list write.
+__device__ __forceinline__ void build_free_list2(int na, const int *__restrict__ a, int *__restrict__ lista, int wanta, int cnta,
+                                                 int nb, const int *__restrict__ b, int *__restrict__ listb, int wantb, int cntb,
+                                                 int &tota, int &totb)
+{
+    __shared__ int s_fl2_w[2][16];
+    __shared__ int s_fl2_tot[2];
+    const int T = blockDim.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int ia = cnta, ib = cntb;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int va = __shfl_up(ia, o), vb = __shfl_up(ib, o);
+        if (lane >= o) ia += va, ib += vb;
+    }
+    if (lane == 63) s_fl2_w[0][w] = ia, s_fl2_w[1][w] = ib;
+    __syncthreads();
+    int basea = 0, baseb = 0;
+    for (int k = 0; k < w; k++) basea += s_fl2_w[0][k], baseb += s_fl2_w[1][k];
+    if (tid == T - 1) s_fl2_tot[0] = basea + ia, s_fl2_tot[1] = baseb + ib;
+    free_list_fill(na, a, lista, wanta, cnta, basea + ia - cnta);
+    free_list_fill(nb, b, listb, wantb, cntb, baseb + ib - cntb);
+    __syncthreads();
+    tota = s_fl2_tot[0], totb = s_fl2_tot[1];
 }
 
 __global__ __launch_bounds__(1024) void k_freelist(int n, const int *__restrict__ r2c, int *__restrict__ list,
@@ -1114,8 +1196,12 @@ __global__ __launch_bounds__(1024) void k_place_const(int n, int *__restrict__ r
                                                       int *__restrict__ lista, int *__restrict__ listb,
                                                       int *__restrict__ ctl, const int *__restrict__ gate_left = nullptr)
 {
-    if (ctl[CTL_FLAG]) return;
-    if (gate_left && *gate_left != 0) return;
+    // flag, gate and the count of constant rows are one round trip (on a solve without constant rows this is all it does)
+    const int flag = __hip_atomic_load(&ctl[CTL_FLAG], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int nconst = __hip_atomic_load(&ctl[CTL_NCONST], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int left = gate_left ? *gate_left : 0;
+    asm volatile("" :: "v"(flag), "v"(nconst), "s"(left));   // (td_blocks.h: the loads of a group in front of its tests)
+    if (flag || left != 0 || nconst == 0) return;
     place_const_tail(n, r2c, owner, lista, listb, ctl);
 }
 
@@ -2932,18 +3018,30 @@ __global__ __launch_bounds__(256) void k_final(int n, int nrows, int row0, const
                                                int *__restrict__ r2c_out = nullptr, unsigned int *__restrict__ ticket = nullptr,
                                                int *__restrict__ rec = nullptr)
 {
-    const bool go = !ctl[CTL_FLAG] && !(gate_left && *gate_left != 0);
+    // flag, gate and the first row's column are one round trip (the row index clamped: a thread past the end uses nothing);
+    // the owner and the cell of a row are one more: both addresses come from j alone (clamped into the matrix, a bad j is
+    // caught by the test as before)
+    const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
+    const int flag = __hip_atomic_load(&ctl[CTL_FLAG], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int left = gate_left ? *gate_left : 0;
+    const int j0 = r2c[min(i0, nrows - 1)];
+    asm volatile("" :: "v"(flag), "s"(left), "v"(j0));   // (td_blocks.h: the loads of a group in front of its tests)
+    const bool go = !flag && left == 0;
     if (go) {
     long long s = 0;
     int bad = 0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += gridDim.x * blockDim.x) {
-        const int j = r2c[i];
+    for (int i = i0; i < nrows; i += gridDim.x * blockDim.x) {
+        const int j = i == i0 ? j0 : r2c[i];
         if (r2c_out) r2c_out[i] = j;
-        if (j < 0 || j >= n || owner[j] != row0 + i)
+        const int jc = min(max(j, 0), n - 1);
+        const int own = owner[jc];
+        long long cell = 0;
+        // the fused transposed solve never materialises the transposed int32 matrix: its cell (i, j) is the caller's (j, i)
+        if constexpr (!GEN) cell = (long long)(cost_is_transposed ? cost[(int64_t)jc * n + i] : cost[(int64_t)i * n + jc]);
+        if (j < 0 || j >= n || own != row0 + i)
             bad = 1;
-        else   // the fused transposed solve never materialises the transposed int32 matrix: its cell (i, j) is the caller's (j, i)
-            s += GEN ? (long long)(cost_is_transposed ? src.cell(j, i) : src.cell(i, j))
-                     : (long long)(cost_is_transposed ? cost[(int64_t)j * n + i] : cost[(int64_t)i * n + j]);
+        else
+            s += GEN ? (long long)(cost_is_transposed ? src.cell(j, i) : src.cell(i, j)) : cell;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -3031,7 +3129,11 @@ __global__ __launch_bounds__(256) void k_dual(int n, int nrows, int row0, int nc
 {
     using PT = typename Tr<CT>::PT;
     constexpr int E = Tr<CT>::E;
-    if (gate_left && (*gate_left != 0 || ctl[CTL_FLAG] != 0)) return;   // (see k_final)
+    if (gate_left) {   // (see k_final; gate and flag in one round trip)
+        const int left = *gate_left, flag = ctl[CTL_FLAG];
+        asm volatile("" :: "s"(left), "s"(flag));   // (td_blocks.h: the loads of a group in front of its tests)
+        if (left != 0 || flag != 0) return;
+    }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const size_t pitch = (size_t)nchunks * E;
     long long acc = 0;
@@ -3402,6 +3504,9 @@ int sv_hop_t(Solver &sv, int rpb, int ncols_blk, int col_lo, int nb, bool window
 // Phase A of a 1-byte attempt whose compress pass wrote the zero-slice bids (sv.zs_done): everything local to this
 // shard's diagonal blocks, no price moves.  Leaves the ordinary state (owner / r2c / packed prices with the owned bit)
 // for the global rounds; the free rows it left are counted in HopCtl::left.
+// The launches: k_zs_assign, g_zs_rounds x (k_zs_bid with one wave per row, k_zs_assign), hop_passes x (k_hop_lists,
+// k_hop_table, k_hop_match): 9 + 3 * hop_passes dependent launches, none shorter than about 4.4 us on an idle MI355X
+// whatever it loads (td_blocks.h, "The kernels of the chain"; DESIGN 7.1 has the figures).
 int sv_phase_a(Solver &sv, int hop_passes)
 {
     Ctx &c = ctx();
@@ -3422,7 +3527,7 @@ int sv_phase_a(Solver &sv, int hop_passes)
     };
     assign();   // round 0: its bids were written by the compress pass
     for (int r = 1; r <= g_zs_rounds; r++) {
-        k_zs_bid<<<std::min(nrows, c.n_cu * 16), 256, 0, c.stream>>>(nrows, sv.row0, sv.nchunks, rpb, (const uint8_t *)sv.cc.p,
+        k_zs_bid<<<(nrows + 3) / 4, 256, 0, c.stream>>>(nrows, sv.row0, sv.nchunks, rpb, (const uint8_t *)sv.cc.p,
                                                                      (const uint8_t *)sv.ob.p, (const int *)sv.r2c.p, bid, ctl, r, g_tie_evict);
         assign();
     }

@@ -14,7 +14,7 @@
 // (complementary slackness exact, all prices 0), found without a word exchanged:
 //   round 0      the 1-byte compress pass writes every row's first zero cell of its own column slice in the row's
 //                rotated order (k_compress_reg<.., BID0> with zs_rpb > 0), k_zs_assign resolves the columns;
-//   rounds 1..R  k_zs_bid (one workgroup per free row, 1/V of the row is read) + k_zs_assign: a free column is
+//   rounds 1..R  k_zs_bid (one wave per free row, 1/V of the row is read) + k_zs_assign: a free column is
 //                preferred, else the row takes an owned zero column and the evicted row bids again (the tie eviction
 //                of k_bid, restricted to the block);
 //   two hops     k_hop_*: what the rounds leave free (a few dozen rows per block) is matched through paths
@@ -49,74 +49,98 @@ __device__ __forceinline__ uint32_t zs_zero_bytes(uint32_t w)   // 0x80 in every
     return ~(((w & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | w | 0x7F7F7F7Fu);
 }
 
-// ---- phase A, rounds >= 1: one workgroup per free row, zero cells of the row's own column slice only
+// The kernels of the chain behind the compress pass start on cold lines (the kernel before them ran on other XCDs), so
+// what they cost is the number of DEPENDENT global round trips, not the bytes.  Each of them therefore issues the width
+// flag, its gate and its counts TOGETHER with the first data loads whose addresses depend on kernel arguments and ids
+// only, and tests them afterwards.  Such a load is in bounds whatever flag, gate and counts say (indices are clamped),
+// no store and no atomic stands in front of the tests, and a load whose address comes from a loaded value stays behind
+// that value's test.  Left to itself the compiler moves a load whose value is used on one side of a branch only back
+// behind the branch (and waits for the flag first): an empty `asm volatile` that names ALL the values of the group as
+// operands ("s" scalar, "v" vector register) stands between the loads and the tests, so every load is issued in front
+// of it and the one wait is there.  Where a loop stands between a flag load and its test the flag is read with a relaxed
+// atomic load, which stays where it is written and waits only at its use.
+
+// ---- phase A, rounds >= 1: one WAVE per free row, zero cells of the row's own column slice only
 // ob[j] = 1 once column j has an owner (phase A never changes a price: all are 0)
+// A wave takes one row (nrows / 4 workgroups, one trip); its r2c word is loaded with the width flag, in front.  The lanes
+// stride over the cpb = rpb / 16 chunks of the slice, two chunks a lane and trip with all four loads issued together (an
+// index past the end is clamped to the last chunk: the same candidate twice).  No LDS, no barrier: the minimum is the
+// shuffle ladder's, lane 0 issues the atomicMax.  The key a row writes is a pure function of the row, the round, cc and ob
+// (the smallest `owned << 24 | rotated position` over the slice), so any partition of the rows over waves and of the
+// chunks over lanes gives the keys of one workgroup per row.  (Two consecutive rows per wave in half as many workgroups,
+// their r2c words loaded together: 8.1 / 6.2 / 5.4 / 4.7 us for the four rounds of a g1 step against 7.0 / 4.4 / 4.4 / 4.5.)
 __global__ __launch_bounds__(256) void k_zs_bid(int nrows, int row0, int nchunks, int rpb, const uint8_t *__restrict__ cc,
                                                 const uint8_t *__restrict__ ob, const int *__restrict__ r2c,
                                                 unsigned long long *__restrict__ bid, const int *__restrict__ ctl, int round,
                                                 int tie_evict)
 {
-    __shared__ int s_best[4];
-    if (ctl[CTL_FLAG]) return;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int lane = threadIdx.x & 63;
+    const int lrow = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int flag = ctl[CTL_FLAG], col = r2c[min(lrow, nrows - 1)];
+    asm volatile("" :: "s"(flag), "s"(col));
+    if (flag || lrow >= nrows || col != -1) return;   // uniform
     const int cpb = rpb >> 4;
     const size_t pitch = (size_t)nchunks * 16;
-    for (int lrow = blockIdx.x; lrow < nrows; lrow += gridDim.x) {
-        if (r2c[lrow] != -1) continue;   // uniform
-        const int row = row0 + lrow;
-        const int c0 = (row / rpb) * cpb;   // first chunk of the row's column slice
-        const uint32_t hsh = ((uint32_t)row + 1u) * 0x9E3779B1u + (uint32_t)round * 0x85EBCA6Bu;
-        const int rot = (int)(((uint64_t)(hsh ^ (hsh >> 15)) * (uint64_t)cpb) >> 32);
-        const uint8_t *rp = cc + (size_t)lrow * pitch;
-        int best = INT_MAX;   // owned << 24 | rotated cell position
-        for (int t = tid; t < cpb; t += 256) {
-            int ch = t + rot;
+    const int row = row0 + lrow;
+    const int c0 = (row / rpb) * cpb;   // first chunk of the row's column slice
+    const uint32_t hsh = ((uint32_t)row + 1u) * 0x9E3779B1u + (uint32_t)round * 0x85EBCA6Bu;
+    const int rot = (int)(((uint64_t)(hsh ^ (hsh >> 15)) * (uint64_t)cpb) >> 32);
+    const uint8_t *rp = cc + (size_t)lrow * pitch;
+    int best = INT_MAX;   // owned << 24 | rotated cell position
+    for (int t0 = lane; t0 < cpb; t0 += 128) {
+        int t[2] = {t0, min(t0 + 64, cpb - 1)};
+        uint4 cv[2], ov[2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            int ch = t[u] + rot;
             if (ch >= cpb) ch -= cpb;
             ch += c0;
-            const uint4 cv = *reinterpret_cast<const uint4 *>(rp + (size_t)ch * 16);
-            const uint4 ov = *reinterpret_cast<const uint4 *>(ob + (size_t)ch * 16);
-            const uint32_t cw[4] = {cv.x, cv.y, cv.z, cv.w}, ow[4] = {ov.x, ov.y, ov.z, ov.w};
+            cv[u] = *reinterpret_cast<const uint4 *>(rp + (size_t)ch * 16);
+            ov[u] = *reinterpret_cast<const uint4 *>(ob + (size_t)ch * 16);
+        }
+        // (else a word of ob is loaded again behind the test of its cells: a second round trip)
+        asm volatile("" :: "v"(cv[0].x), "v"(cv[0].y), "v"(cv[0].z), "v"(cv[0].w), "v"(ov[0].x), "v"(ov[0].y), "v"(ov[0].z), "v"(ov[0].w),
+                     "v"(cv[1].x), "v"(cv[1].y), "v"(cv[1].z), "v"(cv[1].w), "v"(ov[1].x), "v"(ov[1].y), "v"(ov[1].z), "v"(ov[1].w));
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint32_t z = zs_zero_bytes(cw[k]);
+        for (int u = 0; u < 2; u++) {
+            const uint32_t cw[4] = {cv[u].x, cv[u].y, cv[u].z, cv[u].w}, ow[4] = {ov[u].x, ov[u].y, ov[u].z, ov[u].w};
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const uint32_t z = zs_zero_bytes(cw[q]);
                 if (!z) continue;
-                const uint32_t zf = z & zs_zero_bytes(ow[k]);   // zero cell in a free column
+                const uint32_t zf = z & zs_zero_bytes(ow[q]);   // zero cell in a free column
                 const uint32_t pick = zf ? zf : z;
-                const int cand = (zf ? 0 : (1 << 24)) | (t * 16 + k * 4 + (__builtin_ctz(pick) >> 3));
+                const int cand = (zf ? 0 : (1 << 24)) | (t[u] * 16 + q * 4 + (__builtin_ctz(pick) >> 3));
                 best = min(best, cand);
             }
         }
+    }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
-        if (lane == 0) s_best[w] = best;
-        __syncthreads();
-        if (tid == 0) {
-            best = min(min(s_best[0], s_best[1]), min(s_best[2], s_best[3]));
-            if (best != INT_MAX) {
-                const bool owned = (best >> 24) != 0;
-                const int pos = best & 0xFFFFFF;
-                int ch = (pos >> 4) + rot;
-                if (ch >= cpb) ch -= cpb;
-                const int j = (c0 + ch) * 16 + (pos & 15);
-                if (!owned || tie_evict) atomicMax(&bid[j], (unsigned long long)(row + 1));   // price 0: the key is the row
-            }
-        }
-        __syncthreads();
+    for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
+    if (lane == 0 && best != INT_MAX) {
+        const bool owned = (best >> 24) != 0;
+        const int pos = best & 0xFFFFFF;
+        int ch = (pos >> 4) + rot;
+        if (ch >= cpb) ch -= cpb;
+        const int j = (c0 + ch) * 16 + (pos & 15);
+        if (!owned || tie_evict) atomicMax(&bid[j], (unsigned long long)(row + 1));   // price 0: the key is the row
     }
 }
 
 // ---- phase A: resolve the bids on the columns [col_lo, col_hi) of this shard's blocks (prices stay 0)
+// the flag, the bid and the column's owner are one round trip
 __global__ __launch_bounds__(256) void k_zs_assign(int col_lo, int col_hi, int nrows, int row0, unsigned long long *__restrict__ bid,
                                                    int32_t *__restrict__ pk, int *__restrict__ owner, int *__restrict__ r2c,
                                                    uint8_t *__restrict__ ob, const int *__restrict__ ctl)
 {
-    if (ctl[CTL_FLAG]) return;
     const int j = col_lo + blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= col_hi) return;
-    const unsigned long long k = bid[j];
-    if (!k) return;
+    const int jc = min(j, col_hi - 1);
+    int flag = ctl[CTL_FLAG];
+    unsigned long long k = bid[jc];
+    int old = owner[jc];
+    asm volatile("" :: "s"(flag), "v"(k), "v"(old));
+    if (flag || j >= col_hi || !k) return;
     const int row = (int)(k & ((1ull << ROW_BITS) - 1)) - 1;
-    const int old = owner[j];
     if (old >= row0 && old < row0 + nrows) r2c[old - row0] = -1;
     owner[j] = row;
     if (row >= row0 && row < row0 + nrows) r2c[row - row0] = j;
@@ -137,22 +161,30 @@ __global__ __launch_bounds__(1024) void k_hop_lists(int rpb, int ncols_blk, int 
                                                     HopCtl *__restrict__ hc, const int *__restrict__ ctl, int gate_max = 0,
                                                     int *__restrict__ tab_preset = nullptr)
 {
-    if (ctl[CTL_FLAG]) return;
+    // in-block call: one round trip for the flag and both arrays' slices (the counting half of both lists only loads).
+    // Gated call: the flag and the gate are one round trip and the slices come behind the open gate: it is shut on the
+    // instances that leave many rows, and one workgroup counting the whole r2c and owner for nothing cost 16 us at
+    // n = 65 536 (k_hop_lists 4.8 -> 21.0 us).  Every thread reads the gate itself: its value is used in front of the first
+    // barrier, thread 0 stores `left` behind it
     const int lb = blockIdx.x;
+    const int flag = __hip_atomic_load(&ctl[CTL_FLAG], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (gate_max > 0) {
-        __shared__ int s_go;
-        if (threadIdx.x == 0) {
-            const int left = hc->left;
-            s_go = left > 0 && left <= gate_max;
-        }
-        __syncthreads();
-        if (!s_go) {
+        const int left = __hip_atomic_load(&hc->left, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("" :: "v"(flag), "v"(left));
+        if (flag) return;
+        if (!(left > 0 && left <= gate_max)) {
             if (threadIdx.x == 0) hc->nfr[lb] = 0, hc->nfc[lb] = 0;
             return;
         }
     }
-    const int nfr = build_free_list(rpb, r2c + (size_t)lb * rpb, frl + (size_t)lb * rpb, -1);
-    const int nfc = build_free_list(ncols_blk, owner + col_lo + (size_t)lb * ncols_blk, fcl + (size_t)lb * ncols_blk, -1);
+    const int *rs = r2c + (size_t)lb * rpb, *os = owner + col_lo + (size_t)lb * ncols_blk;
+    int cntr, cntc;
+    if (rpb == ncols_blk) free_list_count2(rpb, rs, -1, os, -1, cntr, cntc);
+    else cntr = free_list_count(rpb, rs, -1), cntc = free_list_count(ncols_blk, os, -1);
+    asm volatile("" :: "v"(cntr), "v"(cntc));
+    if (flag) return;
+    int nfr, nfc;
+    build_free_list2(rpb, rs, frl + (size_t)lb * rpb, -1, cntr, ncols_blk, os, fcl + (size_t)lb * ncols_blk, -1, cntc, nfr, nfc);
     if (threadIdx.x == 0) {
         hc->nfr[lb] = nfr;
         hc->nfc[lb] = nfc;
@@ -198,13 +230,19 @@ __global__ __launch_bounds__(256) void k_hop_table(int n, int nrows, int row0, i
     __shared__ int s_ncand, s_nhit;
     __shared__ long long s_v[4];
     constexpr int HU = 4;
-    if (ctl[CTL_FLAG]) return;
     const int seg = SPLIT ? (int)blockIdx.x % nseg : 0, ba = SPLIT ? (int)blockIdx.x / nseg : (int)blockIdx.x;
     const int lb = ba / HOP_FMAX, a = ba % HOP_FMAX;
-    const int nfr = hc->nfr[lb];
-    if (nfr > max_rows || a >= min(nfr, HOP_FMAX)) return;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int lrow = lb * rpb + frl[(size_t)lb * rpb + a];
+    // one round trip: flag, counts, the free row's list entry and the free columns (list indices clamped into the block's
+    // lists: entries at or past the counts are stale words nobody uses)
+    int flag = ctl[CTL_FLAG];
+    int nfr = hc->nfr[lb], nfc_all = hc->nfc[lb];
+    int fr_a = frl[(size_t)lb * rpb + min(a, rpb - 1)];
+    int fc_t = fcl[(size_t)lb * ncols_blk + min(tid & (HOP_FMAX - 1), ncols_blk - 1)];
+    asm volatile("" :: "s"(flag), "s"(nfr), "s"(nfc_all), "s"(fr_a), "v"(fc_t));
+    if (flag) return;
+    if (nfr > max_rows || a >= min(nfr, HOP_FMAX)) return;
+    const int lrow = lb * rpb + fr_a;
     const size_t pitch = (size_t)nchunks * E;
     const unsigned char *rp = reinterpret_cast<const unsigned char *>(cc) + (size_t)lrow * pitch * (RAW ? 4 : sizeof(CT));
     const int32_t mn = RAW ? rowmin[lrow] : 0;
@@ -220,9 +258,9 @@ __global__ __launch_bounds__(256) void k_hop_table(int n, int nrows, int row0, i
         if constexpr (RAW) return (long long)(uint32_t)(reinterpret_cast<const int32_t *>(cc)[(size_t)rl * pitch + col] - rowmin[rl]);
         else return (long long)(uint32_t)cc[(size_t)rl * pitch + col];
     };
-    const int nfc = min(hc->nfc[lb], HOP_FMAX);
+    const int nfc = min(nfc_all, HOP_FMAX);
     const int cb = col_lo + lb * ncols_blk;
-    if (tid < nfc) s_fc[tid] = fcl[(size_t)lb * ncols_blk + tid];
+    if (tid < nfc) s_fc[tid] = fc_t;
     int *tab_row = tab + ((size_t)lb * HOP_FMAX + a) * HOP_FMAX;
     if (!SPLIT && tid < HOP_FMAX) s_tab[tid] = INT_MAX;
     if (tid == 0) s_ncand = 0, s_nhit = 0;
@@ -358,6 +396,10 @@ __global__ __launch_bounds__(256) void k_hop_table(int n, int nrows, int row0, i
 //   - after one more barrier thread a rewires match a.  The pairs of different matches share no row and no column (a
 //     free row, an r' and a free column are each used once, col(r') is r''s alone), so these loads and stores need no
 //     order among themselves; inside the walk the load of col(r') was a global round trip per matched row.
+// The flag, the counts, the thread's free row and the table rows of the first 32 free rows are loaded in one group in front
+// of the tests ("The kernels of the chain" above); further table rows are staged four 16-byte loads a thread at a time.
+// Every in-block pass is still a launch triple of its own: running the passes after the first inside this kernel (one
+// workgroup per block rebuilding its lists and its table rows) was specified and not built, see DESIGN 7.1.
 // dynamic LDS: HOP_FMAX * HOP_FMAX table entries, then one bit per row of the block.
 constexpr int HOP_MATCH_T = 256;
 template <typename PT>
@@ -370,29 +412,52 @@ __global__ __launch_bounds__(HOP_MATCH_T) void k_hop_match(int nrows, int row0, 
     extern __shared__ uint32_t s_hop_dyn[];
     __shared__ int s_st[HOP_FMAX];        // rotated start of free row a
     __shared__ int s_win[HOP_FMAX][2];    // match of free row a: r' (-1: none), free column index
-    if (ctl[CTL_FLAG]) return;
+    // one round trip: flag, counts, this thread's free row and the first HOP_TAB_U quads a thread stages (the table rows of
+    // 32 free rows; a block's table is HOP_FMAX * HOP_FMAX words whatever its counts say, the list index is clamped)
+    constexpr int HOP_TAB_U = 4;
     const int lb = blockIdx.x;
-    const int nfr = hc->nfr[lb];
     const int tid = threadIdx.x;
+    const int *fr = frl + (size_t)lb * rpb, *fc = fcl + (size_t)lb * ncols_blk;
+    const int4 *src = reinterpret_cast<const int4 *>(tab + (size_t)lb * HOP_FMAX * HOP_FMAX);
+    int flag = ctl[CTL_FLAG];
+    int nfr = hc->nfr[lb], nfc_all = hc->nfc[lb];
+    int fr_t = fr[min(tid & (HOP_FMAX - 1), rpb - 1)];
+    int4 x0[HOP_TAB_U];
+#pragma unroll
+    for (int q = 0; q < HOP_TAB_U; q++) x0[q] = src[tid + q * HOP_MATCH_T];
+    asm volatile("" :: "s"(flag), "s"(nfr), "s"(nfc_all), "v"(fr_t), "v"(x0[0].x), "v"(x0[0].y), "v"(x0[0].z), "v"(x0[0].w),
+                 "v"(x0[1].x), "v"(x0[1].y), "v"(x0[1].z), "v"(x0[1].w), "v"(x0[2].x), "v"(x0[2].y), "v"(x0[2].z), "v"(x0[2].w),
+                 "v"(x0[3].x), "v"(x0[3].y), "v"(x0[3].z), "v"(x0[3].w));
+    static_assert(HOP_TAB_U == 4, "the operand list above");
+    if (flag) return;
     if (nfr == 0) return;
     if (nfr > max_rows) {
         if (tid == 0) atomicAdd(&hc->left, nfr);
         return;
     }
-    const int na = min(nfr, HOP_FMAX), nc = min(hc->nfc[lb], HOP_FMAX);
+    const int na = min(nfr, HOP_FMAX), nc = min(nfc_all, HOP_FMAX);
     int *s_tab = reinterpret_cast<int *>(s_hop_dyn);
     uint32_t *s_usedr = s_hop_dyn + HOP_FMAX * HOP_FMAX;
-    const int *fr = frl + (size_t)lb * rpb, *fc = fcl + (size_t)lb * ncols_blk;
     const int blk_row0 = row0 + lb * rpb;
-    const int my_i = tid < na ? blk_row0 + fr[tid] : 0;   // free row `tid` of the block
+    const int my_i = tid < na ? blk_row0 + fr_t : 0;   // free row `tid` of the block
     {
-        const int4 *src = reinterpret_cast<const int4 *>(tab + (size_t)lb * HOP_FMAX * HOP_FMAX);
         int4 *dst = reinterpret_cast<int4 *>(s_tab);
         auto norm = [&](int r, int col) { return (r == HOP_NONE || col >= nc) ? -1 : r; };   // -1: no candidate
-        for (int k = tid; k < na * (HOP_FMAX / 4); k += HOP_MATCH_T) {
-            const int4 x = src[k];
+        auto stage = [&](int k, const int4 &x) {
             const int col = (k * 4) & (HOP_FMAX - 1);
             dst[k] = make_int4(norm(x.x, col), norm(x.y, col + 1), norm(x.z, col + 2), norm(x.w, col + 3));
+        };
+        const int nq = na * (HOP_FMAX / 4);
+#pragma unroll
+        for (int q = 0; q < HOP_TAB_U; q++)
+            if (tid + q * HOP_MATCH_T < nq) stage(tid + q * HOP_MATCH_T, x0[q]);
+        for (int k0 = tid + HOP_TAB_U * HOP_MATCH_T; k0 < nq; k0 += HOP_TAB_U * HOP_MATCH_T) {   // (na > 32: four loads in flight)
+            int4 x[HOP_TAB_U];
+#pragma unroll
+            for (int q = 0; q < HOP_TAB_U; q++) x[q] = src[min(k0 + q * HOP_MATCH_T, nq - 1)];
+#pragma unroll
+            for (int q = 0; q < HOP_TAB_U; q++)
+                if (k0 + q * HOP_MATCH_T < nq) stage(k0 + q * HOP_MATCH_T, x[q]);
         }
         for (int k = tid; k < (rpb + 31) / 32; k += HOP_MATCH_T) s_usedr[k] = 0u;
         if (tid < na) {
