@@ -480,6 +480,40 @@ TD_API int td_simb_state(td_simb *s, int world, int32_t *c_from, int32_t *c_to, 
                          int32_t *c_start, int32_t *d_cab, int32_t *d_pick, int32_t *d_pool_id, int32_t *d_pool_plan,
                          int32_t *d_pool_cost);
 TD_API int td_simb_metrics(td_simb *s, int64_t *out);
+/* ---- the pooling policy of a world -----------------------------------------------------------------------
+ * Until *_pooling is called a world pools as Simulator.java:691 does: the greedy over every ordered pair (TD_POOL_GREEDY,
+ * max_loss <= 0), through the calls and kernels it always used.  td_sim_pooling sets one world's policy, td_simb_pooling
+ * every world's (mode [B], NULL = greedy everywhere; max_loss [B] doubles, NULL = every ordered pair everywhere; host or
+ * device memory).  It takes effect from the next begin, allocates nothing (the batch's per-world flag is part of the handle
+ * since create) and nothing per tick.  TD_EINVAL: a mode outside 0 .. 2, a NaN max_loss, a call while a tick with demand
+ * waits for its apply; the policy is then unchanged.
+ *   TD_POOL_NONE     findPool and analyzePool do not run: the demand after pooling is the demand (copied in list order), no
+ *                    TD_EV_POOL / TD_EV_POOL_PAIR record, max_POOL_MEM_size and max_POOL_size untouched.  In a batch the world
+ *                    is left out of the pool lists the way a world without supply is.
+ *   TD_POOL_GREEDY   td_sim: td_pool2_loss (td_pool2 when max_loss <= 0).  td_simb: td_pool2_batched_v on the device lists,
+ *                    ONE call for all policies of the batch; in a tick where some world has more than 2048 requests, world by
+ *                    world through td_pool2_loss with that world's max_loss.
+ *   TD_POOL_OPTIMAL  the lexicographic optimum of td_pool2_batched(optimal = 1) under max_loss: the most pools, then the least
+ *                    cost, each pool in its cheaper candidate direction, listed in ascending (cost, custA, custB), which is the
+ *                    plan order of the event log.  td_sim runs the same device code on its one model.  More than 2048 requests
+ *                    before pooling in a tick of such a world (with supply): TD_EINVAL from begin, the message names the world
+ *                    and the count; the handle is left as a failing td_pool2 inside begin leaves it: the tick counts as begun
+ *                    (last tick = t, waiting for its apply), nothing of it was pooled, and it cannot be completed.
+ * max_POOL_MEM_size stays n (n - 1) under a rule as well: it counts the pairs examined, not the pairs admitted.
+ * max_POOL_size, total_second_passengers and the event records follow from the plans as they always did; analyzePool, the
+ * apply kernels, td_tick and td_tick_batched do not know the policy.
+ * td_sim_pools / td_simb_pools: the plans of the tick last begun (of world `world`), in plan order: cust_a[i] picks up
+ * cust_b[i], indices into that tick's demand list before pooling, plan and cost as td_pool2 states them; host or device
+ * destinations.  *n = 0 when no pooling ran (no demand, no supply, fewer than two requests, TD_POOL_NONE).  More plans than
+ * max_pools: TD_EINVAL with *n set, nothing copied.  The plans are read where the pool call left them for the event log. */
+#define TD_POOL_NONE 0
+#define TD_POOL_GREEDY 1
+#define TD_POOL_OPTIMAL 2
+TD_API int td_sim_pooling(td_sim *s, int mode, double max_loss);
+TD_API int td_simb_pooling(td_simb *s, const int32_t *mode /* [B], NULL = greedy */, const double *max_loss /* [B], NULL = every pair */);
+TD_API int td_sim_pools(td_sim *s, int max_pools, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n);
+TD_API int td_simb_pools(td_simb *s, int world, int max_pools, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n);
+
 /* the batch's event log: td_sim_log / td_sim_events above with a world word; ONE log for the handle, within a tick world 0's
  * records first; the number of launches the log adds to a tick (three kernels, two fills) does not depend on B */
 TD_API int td_simb_log(td_simb *s, uint32_t kinds, int64_t capacity);
@@ -495,6 +529,16 @@ TD_API int td_simb_events(td_simb *s, int64_t max_records, int32_t *records, int
  */
 TD_API int td_pool2(int n, const int32_t *from, const int32_t *to, const int32_t *dist, int S,
                     int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n_pairs);
+/* td_pool2_loss: td_pool2 under the reference's own candidate rule (pool_opt_min.py:56-64, Simulator.java's unread
+ * max_loss = 1.01).  max_loss <= 0 (or NaN) is td_pool2, call for call.  max_loss > 0: the ordered pair (A, B) is a
+ * candidate iff plan 1 or plan 2 passes its loss test, compared in double (the one definition, csrc/td_pool_rule.h, is
+ * td_pool2_batched's); a refused pair carries the diagonal's INT_MAX marker in the pair-cost matrix and the greedy ends
+ * where the candidates do, so fewer than n / 2 plans, or none, may come back.  plan and cost are those of the pair whether
+ * or not its cheaper plan passed.  The model is spread over the device exactly as td_pool2's (same kernels, same paths,
+ * same lcm_path stats word, no n beyond td_pool2's); for n <= 2048 the result equals td_pool2_batched(batch = 1,
+ * optimal = 0, max_loss).  Errors are td_pool2's. */
+TD_API int td_pool2_loss(int n, const int32_t *from, const int32_t *to, const int32_t *dist, int S, double max_loss,
+                         int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n_pairs);
 
 /* ---- maximum-weight matching of MANY general graphs, and optimal pools of two (pool_opt_min.py, pool_optimum.py) -------
  * One workgroup (one wave) per model runs the primal-dual weighted blossom method (Edmonds; Galil's O(n^3) form) in exact
@@ -524,12 +568,22 @@ TD_API int td_pool2(int n, const int32_t *from, const int32_t *to, const int32_t
  *       candidate direction (the smaller cust_a on a tie), listed in ascending (cost, cust_a, cust_b).
  *   TD_EINVAL: n > 2048, batch < 0, bad offsets, a model larger than n, a stand outside the table, null outputs; TD_ERANGE:
  *   a pair cost outside int32, or (optimal = 1 only) pool weights K - cost, K = floor(m/2) * cost span + 1, of 2^33 or more;
- *   TD_EINTERNAL as above. */
+ *   TD_EINTERNAL as above.
+ *
+ * td_pool2_batched_v: td_pool2_batched with a policy per model.  max_loss [batch] doubles (NULL = every ordered pair
+ *   everywhere), optimal [batch] int32, each 0 or 1 (NULL = greedy everywhere; any other entry is TD_EINVAL before anything
+ *   is written); host or device memory.  Model b is exactly td_pool2_batched with the scalars max_loss[b], optimal[b] on that
+ *   model alone; the TD_ERANGE weight check applies to the optimal models only.  The launches of a call do not depend on the
+ *   batch or on the mix: with an optimal array both the greedy and the matching kernel run and each sees the models of the
+ *   other kind as empty.  td_pool2_batched is the uniform case of the same code. */
 TD_API int td_match_batched(int batch, int n, const int32_t *ns, const int32_t *weight, int32_t *mate, int64_t *total,
                             int64_t *dual_bound, int64_t *dual_vertex, int32_t *blossom_parent, int64_t *dual_blossom);
 TD_API int td_pool2_batched(int batch, int n, const int32_t *off, const int32_t *from, const int32_t *to, const int32_t *dist,
                             int S, double max_loss, int optimal, int32_t *cust_a, int32_t *cust_b, int32_t *plan,
                             int32_t *cost, int32_t *n_pools, int64_t *total);
+TD_API int td_pool2_batched_v(int batch, int n, const int32_t *off, const int32_t *from, const int32_t *to, const int32_t *dist,
+                              int S, const double *max_loss, const int32_t *optimal, int32_t *cust_a, int32_t *cust_b,
+                              int32_t *plan, int32_t *cost, int32_t *n_pools, int64_t *total);
 
 /* ---- f-4 pools of up to 4 passengers ---------------------------------------------------
  * Replaces pool_n.c:101-207 (findPool / drop_customers / removeDuplicates; Pool.java:32-113 is the

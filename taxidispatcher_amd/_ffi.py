@@ -96,8 +96,17 @@ SIGNATURES = {
     "td_simb_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "td_simb_log": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int64]),
     "td_simb_events": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_i32p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "td_sim_pooling": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]),
+    "td_simb_pooling": (ctypes.c_int, [ctypes.c_void_p, c_i32p, ctypes.c_void_p]),
+    "td_sim_pools": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_int32)]),
+    "td_simb_pools": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p,
+                                     ctypes.POINTER(ctypes.c_int32)]),
     "td_pool2": (ctypes.c_int, [ctypes.c_int, c_i32p, c_i32p, c_i32p, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p,
                                 ctypes.POINTER(ctypes.c_int32)]),
+    "td_pool2_loss": (ctypes.c_int, [ctypes.c_int, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_double, c_i32p, c_i32p, c_i32p, c_i32p,
+                                     ctypes.POINTER(ctypes.c_int32)]),
+    "td_pool2_batched_v": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_void_p,
+                                          c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
     "td_match_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
     "td_pool2_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_double,
                                         ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),

@@ -13,6 +13,7 @@
 #include <limits.h>
 
 #include "td_common.h"
+#include "td_pool_rule.h"
 
 using namespace td;
 
@@ -901,20 +902,42 @@ __global__ void k_pool2_check(int n, const int32_t *__restrict__ from, const int
     if (i < n && ((uint32_t)from[i] >= (uint32_t)S || (uint32_t)to[i] >= (uint32_t)S)) atomicOr(flag, 1);
 }
 
-// pair cost matrix: pc[A][B] = min(cost1, cost2), diagonal = INT_MAX (never a candidate)
+// pair cost matrix: pc[A][B] = min(cost1, cost2), diagonal = INT_MAX (never a candidate).  RULE (td_pool2_loss with
+// max_loss > 0): a pair that pool_pair (td_pool_rule.h, the one definition of the candidate test) refuses gets the same
+// INT_MAX marker, so everything downstream sees it as it sees the diagonal; the stands are clamped into the table first,
+// as pool_d clamps them (k_pool2_check reports them).  The every-pair instantiation is the code it always was.
+template <bool RULE>
 __global__ __launch_bounds__(256) void k_pool2_cost(int n, const int32_t *__restrict__ from,
                                                     const int32_t *__restrict__ to, const int32_t *__restrict__ dist,
-                                                    int S, int32_t *__restrict__ pc)
+                                                    int S, double max_loss, int32_t *__restrict__ pc)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n) return;
-    const int bf = from[b], bt = to[b];
-    for (int a = blockIdx.y; a < n; a += gridDim.y) {
-        const int af = from[a], at = to[a];
-        const int head = pool_d(dist, S, af, bf);
-        const int cost1 = head + pool_d(dist, S, bf, at) + pool_d(dist, S, at, bt);   // Simulator.java:693-695
-        const int cost2 = head + pool_d(dist, S, bf, bt) + pool_d(dist, S, bt, at);   // :697-699
-        pc[(int64_t)a * n + b] = (a == b) ? INT_MAX : (cost1 < cost2 ? cost1 : cost2);
+    if constexpr (RULE) {
+        int bf = from[b], bt = to[b];
+        if (dist) {
+            bf = min(max(bf, 0), S - 1);
+            bt = min(max(bt, 0), S - 1);
+        }
+        for (int a = blockIdx.y; a < n; a += gridDim.y) {
+            int af = from[a], at = to[a];
+            if (dist) {
+                af = min(max(af, 0), S - 1);
+                at = min(max(at, 0), S - 1);
+            }
+            int64_t c1, c2;
+            const bool cand = pool_pair(af, at, bf, bt, dist, S, max_loss, &c1, &c2);
+            pc[(int64_t)a * n + b] = (a == b || !cand) ? INT_MAX : (int32_t)(c1 < c2 ? c1 : c2);
+        }
+    } else {
+        const int bf = from[b], bt = to[b];
+        for (int a = blockIdx.y; a < n; a += gridDim.y) {
+            const int af = from[a], at = to[a];
+            const int head = pool_d(dist, S, af, bf);
+            const int cost1 = head + pool_d(dist, S, bf, at) + pool_d(dist, S, at, bt);   // Simulator.java:693-695
+            const int cost2 = head + pool_d(dist, S, bf, bt) + pool_d(dist, S, bt, at);   // :697-699
+            pc[(int64_t)a * n + b] = (a == b) ? INT_MAX : (cost1 < cost2 ? cost1 : cost2);
+        }
     }
 }
 
@@ -1253,10 +1276,13 @@ extern "C" int td_lcm_shard_round_commit(td_lcm_shard *s, const int64_t *taken)
     return TD_OK;
 }
 
-extern "C" int td_pool2(int n, const int32_t *from, const int32_t *to, const int32_t *dist, int S, int32_t *cust_a,
-                        int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n_pairs)
+// td_pool2 (max_loss <= 0) and td_pool2_loss.  Under a rule the greedy ends where the candidates do: a model without a
+// candidate counts 0 cells in k_lcms_minmax, takes the row-scan path with the base word left at INT_MAX (every narrow code
+// 255, every row key LCM_INF) and k_lcm_loop leaves at its first argmin; a model with fewer than n / 2 plans ends with
+// k_lcms_greedy<true>'s lists exhausted, or with k_lcm_loop's LCM_INF, and n_pairs is what was taken.
+static int pool2_impl(int n, const int32_t *from, const int32_t *to, const int32_t *dist, int S, double max_loss, int32_t *cust_a,
+                      int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n_pairs)
 {
-    TD_REQUIRE_INIT();
     Ctx &c = ctx();
     c.stats[11] = 0;
     int64_t path = LP_POOL2;
@@ -1298,7 +1324,10 @@ extern "C" int td_pool2(int n, const int32_t *from, const int32_t *to, const int
         if (d_dist)
             k_pool2_check<<<(n + 255) / 256, 256, 0, c.stream>>>(n, (const int32_t *)d_from, (const int32_t *)d_to, S, (int *)((char *)c.lcm_d.p + 192));
         dim3 g((n + 255) / 256, std::min(n, 1024));
-        k_pool2_cost<<<g, 256, 0, c.stream>>>(n, (const int32_t *)d_from, (const int32_t *)d_to, (const int32_t *)d_dist, S, pc);
+        if (max_loss > 0)
+            k_pool2_cost<true><<<g, 256, 0, c.stream>>>(n, (const int32_t *)d_from, (const int32_t *)d_to, (const int32_t *)d_dist, S, max_loss, pc);
+        else
+            k_pool2_cost<false><<<g, 256, 0, c.stream>>>(n, (const int32_t *)d_from, (const int32_t *)d_to, (const int32_t *)d_dist, S, 0.0, pc);
     }
     // The greedy pass over the n (n - 1) ordered pairs: level lists as in td_lcm (pair costs are sums of three
     // distances: a few dozen to ~150 distinct values), walked by k_lcms_greedy<SYM>; the row-scan loop otherwise.
@@ -1388,6 +1417,20 @@ extern "C" int td_pool2(int n, const int32_t *from, const int32_t *to, const int
     if (n_pairs) *n_pairs = k;
     c.stats[11] = path;
     return TD_OK;
+}
+
+extern "C" int td_pool2(int n, const int32_t *from, const int32_t *to, const int32_t *dist, int S, int32_t *cust_a,
+                        int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n_pairs)
+{
+    TD_REQUIRE_INIT();
+    return pool2_impl(n, from, to, dist, S, 0.0, cust_a, cust_b, plan, cost, n_pairs);
+}
+
+extern "C" int td_pool2_loss(int n, const int32_t *from, const int32_t *to, const int32_t *dist, int S, double max_loss,
+                             int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n_pairs)
+{
+    TD_REQUIRE_INIT();
+    return pool2_impl(n, from, to, dist, S, max_loss, cust_a, cust_b, plan, cost, n_pairs);
 }
 
 // =====================================================================================

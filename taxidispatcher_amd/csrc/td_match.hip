@@ -18,6 +18,7 @@
 
 #include "td_common.h"
 #include "td_match_core.h"
+#include "td_pool_rule.h"
 
 using namespace td;
 
@@ -104,47 +105,32 @@ __global__ __launch_bounds__(64) void k_match_batched(int batch, int n, const in
 // ---------------------------------------------------------------------------------------------------------------------
 // pools: distances, the candidate rule, the pair-cost block
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t pd(const int32_t *dist, int S, int a, int b)
-{
-    return dist ? (int64_t)dist[(int64_t)a * S + b] : (int64_t)(a > b ? a - b : b - a);
-}
+// (pd / pool_pair, the candidate rule: td_pool_rule.h, shared with td_lcm.hip)
 
-// pool_opt_min.py:56-64 for the ordered pair (A, B): cost1 / cost2, and whether the pair is a candidate (every pair is one
-// when max_loss <= 0: Simulator.java:691).  The comparisons are made in double, as Python makes them.
-__device__ __forceinline__ bool pool_pair(int af, int at, int bf, int bt, const int32_t *dist, int S, double max_loss, int64_t *c1,
-                                          int64_t *c2)
-{
-    const int64_t ab = pd(dist, S, af, bf), bfat = pd(dist, S, bf, at), atbt = pd(dist, S, at, bt), bfbt = pd(dist, S, bf, bt),
-                  btat = pd(dist, S, bt, at);
-    *c1 = ab + bfat + atbt;
-    *c2 = ab + bfbt + btat;
-    if (max_loss <= 0) return true;
-    const double aa = (double)pd(dist, S, af, at);
-    const bool p1 = (double)(bfat + atbt) < (double)bfbt * max_loss && (double)(ab + bfat) < aa * max_loss;
-    const bool p2 = (double)*c2 < aa * max_loss;
-    return p1 || p2;
-}
-
-// model b0 + q of the chunk: pc[q][A][B] = min(cost1, cost2) of a candidate, INT_MAX otherwise (stride n); ns[q] = its size;
+// model b0 + q of the chunk: pc[q][A][B] = min(cost1, cost2) of a candidate, INT_MAX otherwise (stride n);
 // K[q] = floor(m/2) * (max(c_max, 0) + max(-c_min, 0)) + 1, range-checked only for the optimum (the greedy never reads it).
-// 256 threads per model.
-__global__ __launch_bounds__(256) void k_pool_costs(int nq, int b0, int n, int optimal, const int32_t *__restrict__ off,
-                                                    const int32_t *__restrict__ from,
+// The policy is per model: opt_v / ml_v [batch] when given (td_pool2_batched_v), the scalars otherwise.  The model's size
+// goes to the list of its own kind, ns_g (greedy) or ns_m (optimum), and 0 to the other: the greedy launch and k_pool_match
+// each see the other kind as an empty model.  256 threads per model.
+__global__ __launch_bounds__(256) void k_pool_costs(int nq, int b0, int n, int optimal, const int32_t *__restrict__ opt_v,
+                                                    const int32_t *__restrict__ off, const int32_t *__restrict__ from,
                                                     const int32_t *__restrict__ to, const int32_t *__restrict__ dist, int S, double max_loss,
-                                                    int32_t *__restrict__ pc, int32_t *__restrict__ ns, int64_t *__restrict__ K,
-                                                    int *__restrict__ err)
+                                                    const double *__restrict__ ml_v, int32_t *__restrict__ pc, int32_t *__restrict__ ns_g,
+                                                    int32_t *__restrict__ ns_m, int64_t *__restrict__ K, int *__restrict__ err)
 {
     __shared__ int64_t s_mx[4], s_mn[4];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     for (int q = blockIdx.x; q < nq; q += gridDim.x) {
         const int o = off[b0 + q], m = off[b0 + q + 1] - o;
+        const int opt = opt_v ? opt_v[b0 + q] : optimal;
+        const double ml = ml_v ? ml_v[b0 + q] : max_loss;
         int32_t *blk = pc + (int64_t)q * n * n;
         int64_t mx = INT64_MIN, mn = INT64_MAX;
         for (int a = 0; a < m; a++)
             for (int bb = tid; bb < m; bb += 256) {
                 int32_t v = INT_MAX;
                 int64_t c1, c2;
-                if (a != bb && pool_pair(from[o + a], to[o + a], from[o + bb], to[o + bb], dist, S, max_loss, &c1, &c2)) {
+                if (a != bb && pool_pair(from[o + a], to[o + a], from[o + bb], to[o + bb], dist, S, ml, &c1, &c2)) {
                     const int64_t cc = c1 < c2 ? c1 : c2;
                     if (cc >= INT_MAX || cc <= INT_MIN) atomicOr(err, ERR_POOL_RANGE);
                     v = (int32_t)cc;
@@ -169,12 +155,13 @@ __global__ __launch_bounds__(256) void k_pool_costs(int nq, int b0, int n, int o
                 mx = s_mx[k] > mx ? s_mx[k] : mx;
                 mn = s_mn[k] < mn ? s_mn[k] : mn;
             }
-            ns[q] = m;
+            ns_g[q] = opt ? 0 : m;
+            ns_m[q] = opt ? m : 0;
             int64_t kk = 1;
             if (mx != INT64_MIN) {
                 const int64_t span = (mx > 0 ? mx : 0) + (mn < 0 ? -mn : 0);
                 kk = (int64_t)(m / 2) * span + 1;
-                if (optimal && kk + span >= POOL_KMAX) atomicOr(err, ERR_POOL_RANGE);
+                if (opt && kk + span >= POOL_KMAX) atomicOr(err, ERR_POOL_RANGE);
             }
             K[q] = kk;
         }
@@ -199,8 +186,9 @@ __global__ __launch_bounds__(64) void k_pool_match(int nq, int n, const int32_t 
 
 // the pools of model b0 + q: greedy (pairs in pick order from rows / cols) or optimal (from the mates: each pair in its
 // cheaper candidate direction, the smaller custA on a tie, listed in ascending (cost, custA, custB)); plan = cost1 < cost2.
-// One wave per model; dynamic LDS: custA, custB, cost int32[n / 2 + 1] each.
-__global__ __launch_bounds__(64) void k_pool_finish(int nq, int b0, int n, int optimal, const int32_t *__restrict__ off,
+// The kind is per model (opt_v [batch] when given).  One wave per model; dynamic LDS: custA, custB, cost int32[n / 2 + 1] each.
+__global__ __launch_bounds__(64) void k_pool_finish(int nq, int b0, int n, int optimal_s, const int32_t *__restrict__ opt_v,
+                                                    const int32_t *__restrict__ off,
                                                     const int32_t *__restrict__ from, const int32_t *__restrict__ to,
                                                     const int32_t *__restrict__ dist, int S, const int32_t *__restrict__ pc,
                                                     const int32_t *__restrict__ mate, const int32_t *__restrict__ rows,
@@ -214,6 +202,7 @@ __global__ __launch_bounds__(64) void k_pool_finish(int nq, int b0, int n, int o
     const int lane = threadIdx.x;
     for (int q = blockIdx.x; q < nq; q += gridDim.x) {
         const int b = b0 + q, o = off[b], m = off[b + 1] - o;
+        const int optimal = opt_v ? opt_v[b] : optimal_s;   // uniform over the wave
         const int32_t *blk = pc + (int64_t)q * n * n;
         __syncthreads();
         int k = 0;
@@ -279,7 +268,7 @@ __global__ __launch_bounds__(64) void k_pool_finish(int nq, int b0, int n, int o
 Buf g_ws;                   // per-workgroup solver state (models too large for LDS)
 Buf g_res;                  // device results for host destinations + the error word
 Buf g_pool;                 // pool chunk: pair-cost slab, sizes, K, mates, totals, greedy pairs
-Buf g_in[4];                // device copies of host inputs
+Buf g_in[6];                // device copies of host inputs
 std::vector<int32_t> g_h;   // host copies (validation)
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -434,13 +423,18 @@ int td_match_batched(int batch, int n, const int32_t *ns, const int32_t *weight,
     return outputs_finish(fn, o, 6, err_off);
 }
 
-int td_pool2_batched(int batch, int n, const int32_t *off, const int32_t *from, const int32_t *to, const int32_t *dist, int S,
-                     double max_loss, int optimal, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n_pools,
-                     int64_t *total)
+}  // extern "C"
+
+namespace {
+
+// td_pool2_batched and td_pool2_batched_v: the policy of model b is (ml_v[b], opt_v[b]) where the arrays are given, the
+// scalars otherwise.  The launches of a chunk: k_pool_costs, the greedy and / or k_pool_match, k_pool_finish; which of the
+// two middle ones run depends on whether opt_v is given (both) or on the scalar, never on the batch or the arrays' contents.
+int pool2_batched_impl(const char *fn, int batch, int n, const int32_t *off, const int32_t *from, const int32_t *to, const int32_t *dist,
+                       int S, double max_loss, int optimal, const double *ml_v, const int32_t *opt_v, int32_t *cust_a, int32_t *cust_b,
+                       int32_t *plan, int32_t *cost, int32_t *n_pools, int64_t *total)
 {
-    TD_REQUIRE_INIT();
     Ctx &c = ctx();
-    const char *fn = "td_pool2_batched";
     if (batch < 0) return fail(TD_EINVAL, "%s: batch = %d < 0", fn, batch);
     if (n < 0 || n > MATCH_NMAX) return fail(TD_EINVAL, "%s: n = %d outside [0, %d]", fn, n, MATCH_NMAX);
     if (dist && (S <= 0 || S > 46340)) return fail(TD_EINVAL, "%s: S = %d outside [1, 46340] with a distance table", fn, S);
@@ -460,6 +454,16 @@ int td_pool2_batched(int batch, int n, const int32_t *off, const int32_t *from, 
     }
     const size_t tot_c = (size_t)h_off[batch];
     if (tot_c && (!from || !to)) return fail(TD_EINVAL, "%s: null from / to", fn);
+    const void *d_optv = nullptr, *d_mlv = nullptr;
+    if (opt_v) {
+        std::vector<int32_t> ho;
+        if ((rc = host_copy(opt_v, (size_t)batch, ho))) return rc;
+        for (int b = 0; b < batch; b++)
+            if (ho[b] != 0 && ho[b] != 1) return fail(TD_EINVAL, "%s: optimal[%d] = %d, neither 0 nor 1", fn, b, ho[b]);
+        if ((rc = to_device(opt_v, sizeof(int32_t) * (size_t)batch, g_in[4], &d_optv))) return rc;
+    }
+    if (ml_v && (rc = to_device(ml_v, sizeof(double) * (size_t)batch, g_in[5], &d_mlv))) return rc;
+    const bool run_match = opt_v || optimal, run_greedy = opt_v || !optimal;
     if (dist && tot_c) {   // never index outside the table
         std::vector<int32_t> hf, ht;
         if ((rc = host_copy(from, tot_c, hf)) || (rc = host_copy(to, tot_c, ht))) return rc;
@@ -490,10 +494,11 @@ int td_pool2_batched(int batch, int n, const int32_t *off, const int32_t *from, 
     const size_t b_pc = align256(sizeof(int32_t) * Q * NN), b_ns = align256(sizeof(int32_t) * Q), b_k = align256(sizeof(int64_t) * Q),
                  b_mate = align256(sizeof(int32_t) * Q * (size_t)std::max(n, 1)), b_tot = align256(sizeof(int64_t) * Q),
                  b_pair = align256(sizeof(int32_t) * Q * Hs);
-    if ((rc = ensure(g_pool, b_pc + b_ns + b_k + b_mate + b_tot + 2 * b_pair + b_ns))) return rc;
+    if ((rc = ensure(g_pool, b_pc + 2 * b_ns + b_k + b_mate + b_tot + 2 * b_pair + b_ns))) return rc;
     char *p = (char *)g_pool.p;
     int32_t *pc = (int32_t *)p;
-    int32_t *d_ns = (int32_t *)(p += b_pc);
+    int32_t *d_ns = (int32_t *)(p += b_pc);     // sizes as the greedy sees them
+    int32_t *d_nsm = (int32_t *)(p += b_ns);    // sizes as k_pool_match sees them
     int64_t *d_K = (int64_t *)(p += b_ns);
     int32_t *d_mate = (int32_t *)(p += b_k);
     int64_t *d_tot = (int64_t *)(p += b_mate);
@@ -504,25 +509,25 @@ int td_pool2_batched(int batch, int n, const int32_t *off, const int32_t *from, 
     unsigned char *ws = nullptr;
     size_t per = 0;
     int mgrid = 0;
-    if (optimal && (rc = state_plan(chunk, nmax, &lds, &ws, &per, &mgrid))) return rc;
+    if (run_match && (rc = state_plan(chunk, nmax, &lds, &ws, &per, &mgrid))) return rc;
     const size_t shm_fin = sizeof(int32_t) * 3 * (H + 1);
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nq = std::min(chunk, batch - b0);
         const int grid = std::min(nq, 1 << 20);
-        k_pool_costs<<<grid, 256, 0, c.stream>>>(nq, b0, n, optimal, (const int32_t *)d_off, (const int32_t *)d_from, (const int32_t *)d_to,
-                                                 (const int32_t *)d_dist, S, max_loss, pc, d_ns, d_K, d_err);
-        if (optimal) {
+        k_pool_costs<<<grid, 256, 0, c.stream>>>(nq, b0, n, optimal, (const int32_t *)d_optv, (const int32_t *)d_off, (const int32_t *)d_from,
+                                                 (const int32_t *)d_to, (const int32_t *)d_dist, S, max_loss, (const double *)d_mlv, pc, d_ns,
+                                                 d_nsm, d_K, d_err);
+        if (run_match) {
             const int g = std::min(nq, mgrid);
             if (lds) {
                 lds_allow(k_pool_match<true>, per);
-                k_pool_match<true><<<g, 64, per, c.stream>>>(nq, n, d_ns, pc, d_K, ws, per, d_mate, d_tot, d_err);
+                k_pool_match<true><<<g, 64, per, c.stream>>>(nq, n, d_nsm, pc, d_K, ws, per, d_mate, d_tot, d_err);
             } else {
-                k_pool_match<false><<<g, 64, 0, c.stream>>>(nq, n, d_ns, pc, d_K, ws, per, d_mate, d_tot, d_err);
+                k_pool_match<false><<<g, 64, 0, c.stream>>>(nq, n, d_nsm, pc, d_K, ws, per, d_mate, d_tot, d_err);
             }
-        } else {
-            pool2_greedy_launch(nq, n, d_ns, pc, d_rows, d_cols, d_np);
         }
-        k_pool_finish<<<grid, 64, shm_fin, c.stream>>>(nq, b0, n, optimal, (const int32_t *)d_off, (const int32_t *)d_from,
+        if (run_greedy) pool2_greedy_launch(nq, n, d_ns, pc, d_rows, d_cols, d_np);
+        k_pool_finish<<<grid, 64, shm_fin, c.stream>>>(nq, b0, n, optimal, (const int32_t *)d_optv, (const int32_t *)d_off, (const int32_t *)d_from,
                                                         (const int32_t *)d_to, (const int32_t *)d_dist, S, pc, d_mate, d_rows, d_cols, d_np,
                                                         (int32_t *)o[0].dptr(), (int32_t *)o[1].dptr(), (int32_t *)o[2].dptr(),
                                                         (int32_t *)o[3].dptr(), (int32_t *)o[4].dptr(), (int64_t *)o[5].dptr());
@@ -530,10 +535,32 @@ int td_pool2_batched(int batch, int n, const int32_t *off, const int32_t *from, 
     return outputs_finish(fn, o, 6, err_off);
 }
 
+}  // namespace
+
+extern "C" {
+
+int td_pool2_batched(int batch, int n, const int32_t *off, const int32_t *from, const int32_t *to, const int32_t *dist, int S,
+                     double max_loss, int optimal, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n_pools,
+                     int64_t *total)
+{
+    TD_REQUIRE_INIT();
+    return pool2_batched_impl("td_pool2_batched", batch, n, off, from, to, dist, S, max_loss, optimal, nullptr, nullptr, cust_a, cust_b, plan,
+                              cost, n_pools, total);
+}
+
+int td_pool2_batched_v(int batch, int n, const int32_t *off, const int32_t *from, const int32_t *to, const int32_t *dist, int S,
+                       const double *max_loss, const int32_t *optimal, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost,
+                       int32_t *n_pools, int64_t *total)
+{
+    TD_REQUIRE_INIT();
+    return pool2_batched_impl("td_pool2_batched_v", batch, n, off, from, to, dist, S, 0.0, 0, max_loss, optimal, cust_a, cust_b, plan, cost,
+                              n_pools, total);
+}
+
 }  // extern "C"
 
 void td::match_release_workspace()
 {
-    Buf *bs[] = {&g_ws, &g_res, &g_pool, &g_in[0], &g_in[1], &g_in[2], &g_in[3]};
+    Buf *bs[] = {&g_ws, &g_res, &g_pool, &g_in[0], &g_in[1], &g_in[2], &g_in[3], &g_in[4], &g_in[5]};
     for (Buf *b : bs) buf_free(*b);
 }

@@ -14,7 +14,8 @@
 //           k_dem_count / k_scatter      createTempDemand: the drop and the per-workgroup count in one pass, then the ordered scatter
 //           k_flags<req>                 "some unassigned request starts here" (after the drop)
 //           k_count / k_scatter          createTempSupply
-//           td_pool2 (device lists)      findPool
+//           td_pool2 (device lists)      findPool; under td_sim_pooling: td_pool2_loss (the candidate rule), td_pool2_batched on
+//                                        the one model (the optimum), or nothing (TD_POOL_NONE: the demand is copied as it is)
 //           k_pool_mark, k_count / k_scatter   analyzePool: B customers out, A customers annotated, order kept
 //   apply   k_pair_map                   first pair per cab / per request (setdefault), indices checked
 //           k_apply_pairs                analyzePairs' two loops, one thread per cab / request of the model
@@ -91,6 +92,9 @@ struct td_sim {
     bool begun = false;          // a tick with demand waits for td_sim_apply
     int n_dem = 0, n_sup = 0, n_dem2 = 0;
     int n_pool = 0;              // this tick's plans (the event log reads them where td_pool2 left them)
+    int n_pooled = 0;            // the customers findPool looked at in this tick: the demand, or 0 where it did not run
+    int pool_mode = TD_POOL_GREEDY;   // td_sim_pooling: the policy from the next begin on
+    double max_loss = 0.0;            // <= 0: every ordered pair is a candidate
     EvLog ev;                    // td_sim_log
     // the host side of Simulator.m
     int64_t lcm_used = 0, max_model = 0, max_solver = 0, max_pool_mem = 0, max_pool = 0;
@@ -99,6 +103,7 @@ struct td_sim {
 namespace {
 
 constexpr int HEAD_INTS = 64;   // ints reserved for the head block
+constexpr int SIM_POOL_OPT_NMAX = 2048;   // largest model of td_pool2_batched: the optimum of a tick is one such model
 static_assert(sizeof(Head) <= sizeof(int32_t) * HEAD_INTS && sizeof(Head) <= 256, "the head fits its device block and the pinned block's front");
 
 // world 0's segment of a list: it begins at 0; its size is the host's (n), or still on the device (dev non-null: a kept list)
@@ -201,7 +206,7 @@ int sim_ev_flush(td_sim *s, int phase)
     const World &w = s->w;
     const EvLog &e = s->ev;
     const Seg1 cabs{w.n_cabs, nullptr}, reqs{w.n_req, nullptr}, dem{s->n_dem, nullptr}, sup{s->n_sup, nullptr}, d2{s->n_dem2, nullptr};
-    const EvSrc<Seg1, Plans1> src{w, cabs, reqs, dem, sup, d2, Plans1{s->n_pool, s->n_dem}, s->max_non_lcm, s->last_t, phase, e.kinds,
+    const EvSrc<Seg1, Plans1> src{w, cabs, reqs, dem, sup, d2, Plans1{s->n_pool, s->n_pooled}, s->max_non_lcm, s->last_t, phase, e.kinds,
                                   e.st_arr, e.st_drop, e.st_pairs, e.st_sol, s->dem_idx, s->pl_a, s->pl_b};
     const size_t vmax = (size_t)w.n_cabs + w.n_req + 2 + s->n_dem + s->n_pool + 2 * ((size_t)s->n_sup + s->n_dem2) + 2 * (size_t)s->n_sup;
     return ev_flush(s->ev, src, 1, vmax);
@@ -229,7 +234,7 @@ int sim_begin(td_sim *s, int t, int32_t info[4])
     const size_t shm = sizeof(uint32_t) * (size_t)words;
     const Seg1 cabs{w.n_cabs, nullptr}, reqs{w.n_req, nullptr};
     const bool log = s->ev.kinds != 0;
-    s->n_pool = 0;
+    s->n_pool = s->n_pooled = 0;
     if (log)
         k_arrive<<<nblocks(w.n_cabs), CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOn{s->ev.st_arr});
     else
@@ -268,9 +273,24 @@ int sim_begin(td_sim *s, int t, int32_t info[4])
     // findPool on the device lists, the plans stay on the device
     int32_t k = 0;
     const int n = h.n_dem;
-    if (n >= 2) {
-        s->max_pool_mem = std::max(s->max_pool_mem, (int64_t)n * (n - 1));
-        if ((rc = td_pool2(n, s->dem_from, s->dem_to, s->dist, s->dist ? w.n_stands : 0, s->pl_a, s->pl_b, s->pl_plan, s->pl_cost, &k))) return rc;
+    const bool find = s->pool_mode != TD_POOL_NONE;   // NONE: no findPool; the demand list is copied below as it is, no mark set
+    if (find) s->n_pooled = n;
+    if (find && n >= 2) {
+        const int S = s->dist ? w.n_stands : 0;
+        if (s->pool_mode == TD_POOL_OPTIMAL && n > SIM_POOL_OPT_NMAX)
+            return fail(TD_EINVAL, "td_sim_begin: world 0 has %d requests before pooling in tick %d, more than the %d an optimal pool model holds", n,
+                        t, SIM_POOL_OPT_NMAX);
+        s->max_pool_mem = std::max(s->max_pool_mem, (int64_t)n * (n - 1));   // the pairs examined, whatever the rule admits
+        if (s->pool_mode == TD_POOL_OPTIMAL) {   // the batched call's device code on one model: its plans lie at 0 .. k
+            const int32_t off[2] = {0, n};
+            int64_t tot = 0;
+            rc = td_pool2_batched(1, n, off, s->dem_from, s->dem_to, s->dist, S, s->max_loss, 1, s->pl_a, s->pl_b, s->pl_plan, s->pl_cost, &k, &tot);
+        } else if (s->max_loss > 0) {
+            rc = td_pool2_loss(n, s->dem_from, s->dem_to, s->dist, S, s->max_loss, s->pl_a, s->pl_b, s->pl_plan, s->pl_cost, &k);
+        } else {
+            rc = td_pool2(n, s->dem_from, s->dem_to, s->dist, S, s->pl_a, s->pl_b, s->pl_plan, s->pl_cost, &k);
+        }
+        if (rc) return rc;
         s->max_pool = std::max(s->max_pool, (int64_t)k);
         s->n_pool = k;
     }
@@ -538,6 +558,36 @@ extern "C" int td_sim_begin(td_sim *s, int t, int32_t info[4])
     if (s->begun) return fail(TD_EINVAL, "td_sim_begin: tick %d still waits for td_sim_apply", s->last_t);
     if (t <= s->last_t) return fail(TD_EINVAL, "td_sim_begin: tick %d after tick %d (a tick begins once, time runs forward)", t, s->last_t);
     return sim_begin(s, t, info);
+}
+
+extern "C" int td_sim_pooling(td_sim *s, int mode, double max_loss)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (mode < TD_POOL_NONE || mode > TD_POOL_OPTIMAL) return fail(TD_EINVAL, "td_sim_pooling: mode = %d outside 0 .. 2", mode);
+    if (max_loss != max_loss) return fail(TD_EINVAL, "td_sim_pooling: max_loss is not a number");
+    if (s->begun) return fail(TD_EINVAL, "td_sim_pooling: tick %d still waits for td_sim_apply", s->last_t);
+    s->pool_mode = mode;
+    s->max_loss = max_loss;
+    return TD_OK;
+}
+
+extern "C" int td_sim_pools(td_sim *s, int max_pools, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !n) return fail(TD_EINVAL, "null argument");
+    if (max_pools < 0) return fail(TD_EINVAL, "td_sim_pools: negative max_pools");
+    const int k = s->n_pool;
+    *n = k;
+    if (k > max_pools) return fail(TD_EINVAL, "td_sim_pools: %d plans, more than max_pools = %d", k, max_pools);
+    if (k == 0) return TD_OK;
+    if (!cust_a || !cust_b || !plan || !cost) return fail(TD_EINVAL, "null destination");
+    int rc;
+    if ((rc = get(cust_a, s->pl_a, (size_t)k)) || (rc = get(cust_b, s->pl_b, (size_t)k)) || (rc = get(plan, s->pl_plan, (size_t)k)) ||
+        (rc = get(cost, s->pl_cost, (size_t)k)))
+        return rc;
+    TD_HIP(hipStreamSynchronize(ctx().stream));
+    return TD_OK;
 }
 
 extern "C" int td_sim_model(td_sim *s, int32_t *cab_to, int32_t *dem_from)

@@ -539,9 +539,10 @@ struct EvSrc {
         sup(b, &s0, &ns);
         d2(b, &d0, &nd);
         const bool p1 = phase & 1, p2 = phase & 2, pooled = ne > 0 && ns > 0;
+        const bool found = pooled && pl.n_act(b) > 0;   // findPool ran: not in a world whose policy is TD_POOL_NONE
         int np = 0;   // plans: never more than the pooled customers allow, whatever the count word says
-        if (pooled) np = min(max(pl.count(b), 0), pl.n_act(b) / 2);
-        const int nA = p1 ? nc : 0, nB = p1 ? nr : 0, nC = p1 ? 1 : 0, nD = p1 ? ne : 0, nE = p1 && pooled ? 1 : 0, nF = p1 ? np : 0;
+        if (found) np = min(max(pl.count(b), 0), pl.n_act(b) / 2);
+        const int nA = p1 ? nc : 0, nB = p1 ? nr : 0, nC = p1 ? 1 : 0, nD = p1 ? ne : 0, nE = p1 && found ? 1 : 0, nF = p1 ? np : 0;
         const int nG = p2 && ne > 0 && world_lcm(ns, nd, max_non_lcm) ? 2 * (ns + nd) : 0, nH = p2 && pooled ? 2 * ns : 0;
         int4 r = make_int4(0, -1, -1, -1);
         int u = v;

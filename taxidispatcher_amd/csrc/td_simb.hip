@@ -27,6 +27,8 @@
 // A world without demand in a tick has empty lists (its supply is not listed either); a world with demand and no supply keeps
 // its demand list as its model and is left out of the pool and tick calls (their lists pl_* / tk_* hold the worlds WITH
 // supply only).  The error word is one for the handle: a pair outside its world's model applies nothing in any world.
+// Under td_simb_pooling every world has its own policy: ONE td_pool2_batched_v call serves them all (a policy per model), and
+// a world whose policy is TD_POOL_NONE is left out of pl_* as a world without supply is (k_offsets' gate), but not out of tk_*.
 //
 // A batch on a distance table (td_simb_create_dist): the worlds share ONE city, so the handle owns one copy of the table and
 // one pair of neighbour bit matrices (k_nb_build of td_sim_core.h, which also validates the table); the near bitsets are
@@ -135,13 +137,20 @@ struct td_simb {
     std::vector<int32_t> n_dem, n_sup, n_d2;
     EvLog ev;                    // td_simb_log
     std::vector<int64_t> lcm_used, max_model, max_solver, max_pool_mem, max_pool;
+    // td_simb_pooling: the policy of every world from the next begin on.  pool_set == false: the handle pools as it always did
+    bool pool_set = false, has_none = false;
+    std::vector<int32_t> pool_mode, pool_opt;   // TD_POOL_*; 1 where the mode is TD_POOL_OPTIMAL
+    std::vector<double> pool_ml;
+    int32_t *d_none = nullptr;                  // device [B]: 1 = the world is left out of the pool lists (read only when has_none)
+    std::vector<int32_t> h_npool, h_pbase;      // this tick's plans per world and where they begin in pa / pb / pp / pc
 };
 
 namespace {
 
 // ONE workgroup: per-workgroup counts -> per-world totals -> offset arrays (exclusive scans over the worlds, B in slices of CB).
 //   off_a = the list counted in cnt_a; off_b (cnt_b non-null) = the list counted in cnt_b.
-//   begin_mode: a = demand, b = supply: a world without demand lists no supply, off_c = the demand of the worlds WITH supply.
+//   begin_mode: a = demand, b = supply: a world without demand lists no supply, off_c = the demand of the worlds WITH supply
+//   that pool (gate non-null: gate[b] != 0 leaves world b out, its policy is TD_POOL_NONE).
 //   else: off_c (non-null) = list a restricted to the worlds with gate[b + 1] > gate[b].
 __global__ __launch_bounds__(CB) void k_offsets(int B, const int32_t *__restrict__ cnt_a, int nc_a, const int32_t *__restrict__ cnt_b, int nc_b,
                                                 int begin_mode, const int32_t *__restrict__ gate, int32_t *__restrict__ off_a,
@@ -158,7 +167,7 @@ __global__ __launch_bounds__(CB) void k_offsets(int B, const int32_t *__restrict
                 for (int j = 0; j < nc_b; j++) nb += cnt_b[b * nc_b + j];
             if (begin_mode) {
                 if (na == 0) nb = 0;
-                nc = nb > 0 ? na : 0;
+                nc = nb > 0 && !(gate && gate[b]) ? na : 0;
             } else if (off_c) {
                 nc = gate[b + 1] > gate[b] ? na : 0;
             }
@@ -293,7 +302,7 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     if (s->dist) k_near_b<<<grid_n, CB, shm_n, c.stream>>>(B, w.n_stands, s->words, s->nb_sup, s->bits, s->near, 1);
     const SupPred sp{w, s->words, s->bits, s->near};
     k_count<SegOff, SupPred><<<grid_c, CB, 0, c.stream>>>(cabs, sp, s->cnt_b);
-    k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, gr, s->cnt_b, gc, 1, nullptr, s->dem_off, s->sup_off, s->pl_off);
+    k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, gr, s->cnt_b, gc, 1, s->has_none ? s->d_none : nullptr, s->dem_off, s->sup_off, s->pl_off);
     k_scatter<DemPred, DemEmit><<<grid_r, CB, 0, c.stream>>>(s->d_req_off, dp, DemEmit{w, s->dem_idx, s->dem_from, s->dem_to, s->pl_from, s->pl_to},
                                                            s->cnt_a, s->dem_off, s->pl_off);
     k_scatter<SupPred, SupEmit><<<grid_c, CB, 0, c.stream>>>(s->d_cab_off, sp, SupEmit{w, s->sup_cab, s->sup_to}, s->cnt_b, s->sup_off, nullptr);
@@ -302,6 +311,7 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     if (*h_of(s, s->gerr)) return fail(TD_EINTERNAL, "td_simb: device error word %d", *h_of(s, s->gerr));
     s->last_t = t;
     s->pool_ragged = 0;
+    s->h_npool.assign((size_t)B, 0);
     const int32_t *hd = h_of(s, s->dem_off), *hs = h_of(s, s->sup_off), *hp = h_of(s, s->pl_off);
     int max_dem = 0, max_act = 0;
     for (int b = 0; b < B; b++) {
@@ -314,12 +324,41 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     s->begun = true;
     // findPool for the worlds with supply, the plans stay on the device
     if (max_act >= 2) {
-        for (int b = 0; b < B; b++)
-            if (s->n_sup[b] > 0 && s->n_dem[b] >= 2) s->max_pool_mem[b] = std::max(s->max_pool_mem[b], (int64_t)s->n_dem[b] * (s->n_dem[b] - 1));
+        if (s->pool_set)   // the optimum of a world is ONE model of the batched call: refused before anything is pooled
+            for (int b = 0; b < B; b++)
+                if (s->pool_opt[b] && hp[b + 1] - hp[b] > SIMB_NMAX)
+                    return fail(TD_EINVAL, "td_simb_begin: world %d has %d requests before pooling in tick %d, more than the %d an optimal pool model holds", b,
+                                hp[b + 1] - hp[b], t, SIMB_NMAX);
+        for (int b = 0; b < B; b++)   // the pairs examined, whatever the world's rule admits; a world that does not pool has hp's segment empty
+            if (hp[b + 1] - hp[b] >= 2) s->max_pool_mem[b] = std::max(s->max_pool_mem[b], (int64_t)s->n_dem[b] * (s->n_dem[b] - 1));
+        const int S = s->dist ? w.n_stands : 0;
         if (max_act <= SIMB_NMAX) {
             s->pool_h = std::max(1, max_act / 2);
-            if ((rc = td_pool2_batched(B, max_act, hp, s->pl_from, s->pl_to, s->dist, s->dist ? w.n_stands : 0, 0.0, 0, s->pa, s->pb, s->pp, s->pc, s->n_pools, s->p_total)))
-                return rc;
+            if (!s->pool_set)
+                rc = td_pool2_batched(B, max_act, hp, s->pl_from, s->pl_to, s->dist, S, 0.0, 0, s->pa, s->pb, s->pp, s->pc, s->n_pools, s->p_total);
+            else   // one call for every policy of the batch: its launches do not depend on B or on the mix
+                rc = td_pool2_batched_v(B, max_act, hp, s->pl_from, s->pl_to, s->dist, S, s->pool_ml.data(), s->pool_opt.data(), s->pa, s->pb, s->pp, s->pc,
+                                        s->n_pools, s->p_total);
+            if (rc) return rc;
+        } else if (s->pool_set) {
+            // world by world as below, each under its own policy (an optimal world: the batched call on its one model)
+            s->pool_ragged = 1;
+            int32_t *np = s->h_stage;
+            for (int b = 0; b < B; b++) {
+                const int m = hp[b + 1] - hp[b], q = hp[b] >> 1;
+                np[b] = 0;
+                if (m < 2) continue;
+                if (s->pool_opt[b]) {
+                    const int32_t off[2] = {0, m};
+                    int64_t tot = 0;
+                    rc = td_pool2_batched(1, m, off, s->pl_from + hp[b], s->pl_to + hp[b], s->dist, S, s->pool_ml[b], 1, s->pa + q, s->pb + q, s->pp + q, s->pc + q,
+                                          &np[b], &tot);
+                } else {
+                    rc = td_pool2_loss(m, s->pl_from + hp[b], s->pl_to + hp[b], s->dist, S, s->pool_ml[b], s->pa + q, s->pb + q, s->pp + q, s->pc + q, &np[b]);
+                }
+                if (rc) return rc;
+            }
+            TD_HIP(hipMemcpyAsync(s->n_pools, np, sizeof(int32_t) * B, hipMemcpyHostToDevice, c.stream));
         } else {
             // a world beyond the batched call's model size: td_pool2 world by world, plans packed at pl_off[b] / 2 (a world
             // of m customers has at most m / 2 plans).  Only td_simb_begin / _model / _apply serve such a tick.
@@ -357,7 +396,11 @@ int simb_begin(td_simb *s, int t, int32_t *info)
         return fail(TD_EINTERNAL, "td_simb: a pool plan names a customer outside the demand list");
     }
     const int32_t *h2 = h_of(s, s->d2_off), *hn = h_of(s, s->n_pools);
+    hp = h_of(s, s->pl_off);
     for (int b = 0; b < B; b++) {
+        const int m = hp[b + 1] - hp[b];
+        s->h_npool[b] = m >= 2 ? std::min(std::max(hn[b], 0), m / 2) : 0;
+        s->h_pbase[b] = s->pool_ragged ? hp[b] >> 1 : b * s->pool_h;
         s->n_d2[b] = h2[b + 1] - h2[b];
         if (s->n_dem[b] == 0) continue;
         info[4 * b] = 1;
@@ -365,7 +408,7 @@ int simb_begin(td_simb *s, int t, int32_t *info)
         info[4 * b + 2] = s->n_sup[b];
         info[4 * b + 3] = s->n_d2[b];
         if (s->n_sup[b] > 0) {
-            if (s->n_dem[b] >= 2) s->max_pool[b] = std::max(s->max_pool[b], (int64_t)hn[b]);
+            if (m >= 2) s->max_pool[b] = std::max(s->max_pool[b], (int64_t)hn[b]);
             s->max_model[b] = std::max(s->max_model[b], (int64_t)std::max(s->n_sup[b], s->n_d2[b]));
         }
     }
@@ -532,7 +575,9 @@ static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_
     s->ncap = std::max(1, std::min(SIMB_NMAX, std::max(max_cabs, max_req)));
     s->hcap = std::max(1, std::min(SIMB_NMAX, max_req) / 2);
     s->in_cap = in_cap;
-    for (std::vector<int32_t> *v : {&s->n_dem, &s->n_sup, &s->n_d2}) v->assign((size_t)B, 0);
+    for (std::vector<int32_t> *v : {&s->n_dem, &s->n_sup, &s->n_d2, &s->pool_opt, &s->h_npool, &s->h_pbase}) v->assign((size_t)B, 0);
+    s->pool_mode.assign((size_t)B, TD_POOL_GREEDY);
+    s->pool_ml.assign((size_t)B, 0.0);
     for (std::vector<int64_t> *v : {&s->lcm_used, &s->max_model, &s->max_solver, &s->max_pool_mem, &s->max_pool}) v->assign((size_t)B, 0);
     const size_t nb = (size_t)B, nr = (size_t)std::max(n_req, 1), nc = (size_t)nc_tot, words = (size_t)s->words;
     const size_t n_cnt = nb * (size_t)nchunks(std::max(max_cabs, max_req));
@@ -543,7 +588,7 @@ static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_
     const size_t ints = table_ints + s->head_ints + 2 * (nb + 1) + 2 * words * nb + 2 * n_cnt + 9 * nr + 5 * nc   // head, offsets, bits, counts, tables
                         + 5 * nr + 2 * nc + 6 * nr + 2 * nc + 5 * nr + 2 * nr                        // dem / pl, sup, d2 / tk, ks, kd, isb / ainfo
                         + 4 * s->pool_cap + 4 * nb + nc + nr                                         // plans, two int64 [B], pair maps
-                        + 3 * in_cap + 2 * (nb + 1) + nb + 3 * tk_cap + std::max<size_t>(max_cabs, 1) + 64;
+                        + 3 * in_cap + 2 * (nb + 1) + nb + 3 * tk_cap + std::max<size_t>(max_cabs, 1) + nb + 64;   // .., tmp, d_none
     rc = ensure(s->mem, sizeof(int32_t) * ints);
     if (rc) {
         delete s;
@@ -642,6 +687,7 @@ static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_
     s->tk_cols = take(tk_cap);
     s->tk_r2c = take(tk_cap);
     s->tmp = take(std::max<size_t>(max_cabs, 1));
+    s->d_none = take(nb);
     auto bail = [&](int code) {
         td_simb_destroy(s);
         return code;
@@ -727,6 +773,55 @@ extern "C" int td_simb_begin(td_simb *s, int t, int32_t *info)
     if (s->begun) return fail(TD_EINVAL, "td_simb_begin: tick %d still waits for td_simb_apply", s->last_t);
     if (t <= s->last_t) return fail(TD_EINVAL, "td_simb_begin: tick %d after tick %d (a tick begins once, time runs forward)", t, s->last_t);
     return simb_begin(s, t, info);
+}
+
+extern "C" int td_simb_pooling(td_simb *s, const int32_t *mode, const double *max_loss)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (s->begun) return fail(TD_EINVAL, "td_simb_pooling: tick %d still waits for td_simb_apply", s->last_t);
+    const size_t B = (size_t)s->B;
+    int rc;
+    std::vector<int32_t> hm(B, TD_POOL_GREEDY);
+    std::vector<double> hl(B, 0.0);
+    if (mode && (rc = host_copy(mode, B, hm))) return rc;
+    if (max_loss) TD_HIP(hipMemcpy(hl.data(), max_loss, sizeof(double) * B, hipMemcpyDefault));
+    bool none = false;
+    for (size_t b = 0; b < B; b++) {
+        if (hm[b] < TD_POOL_NONE || hm[b] > TD_POOL_OPTIMAL) return fail(TD_EINVAL, "td_simb_pooling: mode[%zu] = %d outside 0 .. 2", b, hm[b]);
+        if (hl[b] != hl[b]) return fail(TD_EINVAL, "td_simb_pooling: max_loss[%zu] is not a number", b);
+        none = none || hm[b] == TD_POOL_NONE;
+    }
+    int32_t *st = s->h_stage;   // pinned, at least 3 (B + 1) ints
+    for (size_t b = 0; b < B; b++) st[b] = hm[b] == TD_POOL_NONE;
+    TD_HIP(hipMemcpyAsync(s->d_none, st, sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx().stream));
+    TD_HIP(hipStreamSynchronize(ctx().stream));
+    s->pool_mode = hm;
+    s->pool_ml = hl;
+    for (size_t b = 0; b < B; b++) s->pool_opt[b] = hm[b] == TD_POOL_OPTIMAL;
+    s->has_none = none;
+    s->pool_set = true;
+    return TD_OK;
+}
+
+extern "C" int td_simb_pools(td_simb *s, int world, int max_pools, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !n) return fail(TD_EINVAL, "null argument");
+    if (world < 0 || world >= s->B) return fail(TD_EINVAL, "td_simb_pools: world %d outside 0 .. %d", world, s->B - 1);
+    if (max_pools < 0) return fail(TD_EINVAL, "td_simb_pools: negative max_pools");
+    const int k = s->h_npool[world];
+    *n = k;
+    if (k > max_pools) return fail(TD_EINVAL, "td_simb_pools: world %d has %d plans, more than max_pools = %d", world, k, max_pools);
+    if (k == 0) return TD_OK;
+    if (!cust_a || !cust_b || !plan || !cost) return fail(TD_EINVAL, "null destination");
+    const size_t q = (size_t)s->h_pbase[world];
+    int rc;
+    if ((rc = get(cust_a, s->pa + q, (size_t)k)) || (rc = get(cust_b, s->pb + q, (size_t)k)) || (rc = get(plan, s->pp + q, (size_t)k)) ||
+        (rc = get(cost, s->pc + q, (size_t)k)))
+        return rc;
+    TD_HIP(hipStreamSynchronize(ctx().stream));
+    return TD_OK;
 }
 
 extern "C" int td_simb_model(td_simb *s, int32_t *cab_off, int32_t *cab_to, int32_t *dem_off, int32_t *dem_from)

@@ -360,9 +360,11 @@ def tick(cab_to, dem_from, distances=None, big_cost=BIG_COST, drop_time=10, max_
             "solved": solved}
 
 
-def find_pool(frm, to, distances=None):
+def find_pool(frm, to, distances=None, max_loss=None):
     """Simulator.java:681-758 findPool on the GPU: requests given by their from/to stands ->
-    list of (custA, custB, plan, cost) in the order the reference keeps them."""
+    list of (custA, custB, plan, cost) in the order the reference keeps them.  max_loss=None: every ordered pair is a
+    candidate (td_pool2); else pool_opt_min.py:56-64's loss tests decide (td_pool2_loss), and fewer than n // 2 plans, or
+    none, may come back."""
     lib = _ffi.lib()
     frm, to = _ffi.as_i32(frm), _ffi.as_i32(to)
     n = int(frm.size)
@@ -374,8 +376,12 @@ def find_pool(frm, to, distances=None):
     plan = np.empty(n // 2 + 1, np.int32)
     cost = np.empty(n // 2 + 1, np.int32)
     k = ctypes.c_int32(0)
-    _ffi.check(lib.td_pool2(n, _ffi.addr(frm), _ffi.addr(to), dptr, S, _ffi.addr(a), _ffi.addr(b), _ffi.addr(plan),
-                            _ffi.addr(cost), ctypes.byref(k)))
+    if max_loss is None:
+        _ffi.check(lib.td_pool2(n, _ffi.addr(frm), _ffi.addr(to), dptr, S, _ffi.addr(a), _ffi.addr(b), _ffi.addr(plan),
+                                _ffi.addr(cost), ctypes.byref(k)))
+    else:
+        _ffi.check(lib.td_pool2_loss(n, _ffi.addr(frm), _ffi.addr(to), dptr, S, float(max_loss), _ffi.addr(a), _ffi.addr(b),
+                                     _ffi.addr(plan), _ffi.addr(cost), ctypes.byref(k)))
     del keep
     return [(int(a[i]), int(b[i]), int(plan[i]), int(cost[i])) for i in range(k.value)]
 
@@ -840,6 +846,8 @@ def pool2_batched(froms, tos, distances=None, max_loss=None, optimal=True):
     froms / tos: ragged lists as in pack_ragged (the same model sizes on both sides).  max_loss=None: every ordered pair is a
     candidate (Simulator.java:691); else pool_opt_min.py:58-64's loss tests.  optimal=False: the reference's greedy in its
     keep order; optimal=True: the most pools, then the least total cost, in ascending (cost, custA, custB).
+    max_loss and optimal may also be lists with one entry per model (None in a max_loss list: every ordered pair for that
+    model): td_pool2_batched_v, the same launches whatever the mix; model b comes out exactly as a uniform call on it alone.
     Returns (cust_a, cust_b, plan, cost: int32[B, n // 2], n_pools int32[B], total int64[B]); model b's pools are the first
     n_pools[b] entries of its rows; customer indices are positions within the model."""
     lib = _ffi.lib()
@@ -853,9 +861,23 @@ def pool2_batched(froms, tos, distances=None, max_loss=None, optimal=True):
     half = n // 2
     a, b, plan, cost = (_out((batch, half), np.int32) for _ in range(4))
     k, total = _out((batch,), np.int32), _out((batch,), np.int64)
-    ml = 0.0 if max_loss is None else float(max_loss)
-    _ffi.check(lib.td_pool2_batched(batch, n, _ffi.addr(fo), _ffi.addr(fv), _ffi.addr(tv), dptr, S, ml, 1 if optimal else 0,
-                                    _ffi.addr(a), _ffi.addr(b), _ffi.addr(plan), _ffi.addr(cost), _ffi.addr(k), _ffi.addr(total)))
+    ml_list = isinstance(max_loss, (list, tuple, np.ndarray))
+    opt_list = isinstance(optimal, (list, tuple, np.ndarray))
+    if ml_list or opt_list:
+        mlv = optv = None
+        if max_loss is not None:
+            mlv = np.array([0.0 if x is None else float(x) for x in (max_loss if ml_list else [max_loss] * batch)], np.float64)
+        if opt_list or optimal:
+            optv = np.array([int(x) for x in (optimal if opt_list else [1] * batch)], np.int32)
+        for v, what in ((mlv, "max_loss"), (optv, "optimal")):
+            if v is not None and v.size != batch:
+                raise _ffi.TdError("%s has %d entries for %d models" % (what, v.size, batch))
+        _ffi.check(lib.td_pool2_batched_v(batch, n, _ffi.addr(fo), _ffi.addr(fv), _ffi.addr(tv), dptr, S, _ffi.addr(mlv), _ffi.addr(optv),
+                                          _ffi.addr(a), _ffi.addr(b), _ffi.addr(plan), _ffi.addr(cost), _ffi.addr(k), _ffi.addr(total)))
+    else:
+        ml = 0.0 if max_loss is None else float(max_loss)
+        _ffi.check(lib.td_pool2_batched(batch, n, _ffi.addr(fo), _ffi.addr(fv), _ffi.addr(tv), dptr, S, ml, 1 if optimal else 0,
+                                        _ffi.addr(a), _ffi.addr(b), _ffi.addr(plan), _ffi.addr(cost), _ffi.addr(k), _ffi.addr(total)))
     del keep
     return a, b, plan, cost, k, total
 

@@ -63,13 +63,27 @@ def check_dist(dist, n_stands=None):
     return np.ascontiguousarray(d.astype(np.int32))
 
 
-class HipBackend:
-    """cost build / LCM / optimal assignment on the GPU through the C ABI; dist: a stand-to-stand table (None = |a - b|)."""
+POOL_MODES = {"none": 0, "greedy": 1, "optimal": 2}      # TD_POOL_NONE / TD_POOL_GREEDY / TD_POOL_OPTIMAL
 
-    def __init__(self, dist=None):
+
+def pool_mode(pool):
+    """a pooling policy by name -> its TD_POOL_* value (ValueError for anything else)"""
+    if pool not in POOL_MODES:
+        raise ValueError("pool=%r: one of %s" % (pool, ", ".join(sorted(POOL_MODES))))
+    return POOL_MODES[pool]
+
+
+class HipBackend:
+    """cost build / LCM / optimal assignment on the GPU through the C ABI; dist: a stand-to-stand table (None = |a - b|).
+    pool / max_loss: the policy find_pool follows when the caller names none ("greedy": dispatch.find_pool, "optimal":
+    dispatch.find_pool_optimal; max_loss=None: every ordered pair is a candidate)."""
+
+    def __init__(self, dist=None, pool="greedy", max_loss=None):
         from . import dispatch
         self.d = dispatch
         self.dist = None if dist is None else check_dist(dist)
+        pool_mode(pool)
+        self.pool, self.max_loss = pool, max_loss
 
     def calculate_cost(self, cab_to, dem_from):
         return self.d.cost_build(cab_to, dem_from, self.dist, fill=BIG_COST, threshold=DROP_TIME)[1]
@@ -80,8 +94,12 @@ class HipBackend:
     def solve(self, cost):
         return self.d.assign(cost)[0]
 
-    def find_pool(self, frm, to):
-        return self.d.find_pool(frm, to, self.dist)
+    def find_pool(self, frm, to, max_loss=None, optimal=None):
+        optimal = self.pool == "optimal" if optimal is None else optimal
+        max_loss = self.max_loss if max_loss is None else max_loss
+        if optimal:
+            return self.d.find_pool_optimal(frm, to, self.dist, max_loss)
+        return self.d.find_pool(frm, to, self.dist, max_loss)
 
 
 class HipTickBackend(HipBackend):
@@ -139,9 +157,17 @@ class Simulator:
     """dist: a stand-to-stand distance table (N_STANDS x N_STANDS, see check_dist; None = the line, |a - b|).  The row is
     always the stand the cab is at or heads to: dist[cab][request].  The backend has to work on the same table
     (HipBackend(dist=...)).  cheat_a_bit stays the reference's stand arithmetic (from +- cost against N_STANDS), which
-    means something on a line only; it is kept as it is, bug-compatible, in a table world too."""
+    means something on a line only; it is kept as it is, bug-compatible, in a table world too.
+    pool / max_loss: the pooling policy, the specification of td_sim_pooling.  "greedy" with max_loss=None is
+    Simulator.java:691 (every ordered pair, stable cost order) and calls backend.find_pool(frm, to) as it always did; any
+    other policy calls backend.find_pool(frm, to, max_loss=..., optimal=...): max_loss > 0 admits the pairs that pass
+    pool_opt_min.py:56-64's loss tests, "optimal" takes the most pools, then the least cost, in ascending (cost, custA,
+    custB).  "none": findPool and analyzePool do not run, no pool event is written, max_POOL_* stay as they are."""
 
-    def __init__(self, demand_rows, backend=None, n_cabs=N_CABS, on_solver_instance=None, dist=None, events=False):
+    def __init__(self, demand_rows, backend=None, n_cabs=N_CABS, on_solver_instance=None, dist=None, events=False, pool="greedy",
+                 max_loss=None):
+        pool_mode(pool)
+        self.pool, self.max_loss = pool, (None if max_loss is None or not max_loss > 0 else float(max_loss))
         self._events_on = bool(events)
         self.events = []         # events=True: the records of simulog.txt (format_events), in the order the Java writes them
         self.dist = None if dist is None else check_dist(dist, N_STANDS).astype(np.int64)
@@ -260,12 +286,21 @@ class Simulator:
         to = np.array([r[2] for r in temp_demand], np.int64)
         self.m["max_POOL_MEM_size"] = max(self.m["max_POOL_MEM_size"], n * (n - 1))
         # pool of two on the backend (td_pool2 on the GPU; the tests' comparator restates it on the host)
-        out = self.be.find_pool(frm, to)
+        if self.pool == "greedy" and self.max_loss is None:
+            out = self.be.find_pool(frm, to)
+        else:
+            out = self.be.find_pool(frm, to, max_loss=self.max_loss, optimal=self.pool == "optimal")
         self.m["max_POOL_size"] = max(self.m["max_POOL_size"], len(out))
         self._ev(t, EV_POOL, aux=len(out))                                                    # :742 / :756
         for p in out:
             self._ev(t, EV_POOL_PAIR, customer=temp_demand[p[0]][0], aux=temp_demand[p[1]][0])   # :746
         return out
+
+    # findPool + analyzePool under the world's policy; "none": the demand as it is, in the model's six-field form
+    def _pooled(self, temp_demand, t):
+        if self.pool == "none":
+            return [[r[0], r[1], r[2], -1, -1, 0] for r in temp_demand]
+        return self.analyze_pool(self.find_pool(temp_demand, t), temp_demand)
 
     # ---- Simulator.java:760-784
     @staticmethod
@@ -383,7 +418,7 @@ class Simulator:
         if temp_supply and hasattr(self.be, "tick"):
             return self._tick_one_call(t, line, temp_demand, temp_supply)
         if temp_supply:
-            temp_demand = self.analyze_pool(self.find_pool(temp_demand, t), temp_demand)
+            temp_demand = self._pooled(temp_demand, t)
             cost = self.calculate_cost(temp_demand, temp_supply)
             self.m["max_model_size"] = max(self.m["max_model_size"], cost.shape[0])
             if cost.shape[0] > MAX_NON_LCM:
@@ -404,7 +439,7 @@ class Simulator:
 
     # ---- the same tick (Simulator.java:163-208) with the whole path behind ONE backend call (td_tick)
     def _tick_one_call(self, t, line, temp_demand, temp_supply):
-        temp_demand = self.analyze_pool(self.find_pool(temp_demand, t), temp_demand)
+        temp_demand = self._pooled(temp_demand, t)
         n = max(len(temp_demand), len(temp_supply))
         self.m["max_model_size"] = max(self.m["max_model_size"], n)
         res = self.be.tick([s[2] for s in temp_supply], [d[1] for d in temp_demand])
@@ -508,6 +543,15 @@ def format_events(records, world=None):
     return lines
 
 
+def _read_pools(sim, call, n_req):
+    cap = max(n_req // 2, 1)
+    a, b, plan, cost = (np.empty(cap, np.int32) for _ in range(4))
+    k = sim._ct.c_int32(0)
+    ad = sim._ffi.addr
+    sim._ffi.check(call(cap, ad(a), ad(b), ad(plan), ad(cost), sim._ct.byref(k)))
+    return [(int(a[i]), int(b[i]), int(plan[i]), int(cost[i])) for i in range(k.value)]
+
+
 class _DeviceEvents:
     """the event log of a device handle (td_sim_log / td_sim_events or their td_simb twins), shared by both classes"""
 
@@ -552,7 +596,9 @@ class DeviceSimulator(_DeviceEvents):
     events: True or an iterable of event kinds (EV_*) switches the event log on (td_sim_log); `events()` drains it,
     `format_events` makes simulog.txt's lines of it.  event_capacity: the records the log holds; the default,
     4 * (n_cabs + n_req) + 64, holds any one tick of the world (a tick writes at most 3 n_cabs + 3.5 n_req + 2 records), so
-    a caller that drains after every tick loses nothing."""
+    a caller that drains after every tick loses nothing.
+    pool / max_loss: the pooling policy as `Simulator` takes it (td_sim_pooling); `pools()` reads the plans of the tick last
+    begun (td_sim_pools)."""
 
     M_KEYS = ("total_dropped", "total_pickup_time", "total_pickup_numb", "total_LCM_used", "max_model_size", "max_solver_size",
               "max_POOL_MEM_size", "max_POOL_size", "total_second_passengers")
@@ -560,8 +606,9 @@ class DeviceSimulator(_DeviceEvents):
     REQ_KEYS = ("d_cab", "d_pick", "d_pool_id", "d_pool_plan", "d_pool_cost")
 
     def __init__(self, demand_rows, n_cabs=None, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None, events=None,
-                 event_capacity=None):
+                 event_capacity=None, pool="greedy", max_loss=None):
         import ctypes
+        mode = pool_mode(pool)
         from . import _ffi
         self._ffi, self._ct = _ffi, ctypes
         self._lib = _ffi.lib()
@@ -591,6 +638,14 @@ class DeviceSimulator(_DeviceEvents):
         self._info = None
         self.log = []
         self._events_init(self._lib.td_sim_log, self._lib.td_sim_events, events, event_capacity, 4 * (self.n_cabs + self.n_req) + 64)
+        self.pool, self.max_loss = pool, max_loss
+        if pool != "greedy" or max_loss is not None:      # a default world never calls td_sim_pooling
+            _ffi.check(self._lib.td_sim_pooling(self._h, mode, 0.0 if max_loss is None else float(max_loss)))
+
+    def pools(self):
+        """the plans of the tick last begun: a list of (custA, custB, plan, cost), indices into that tick's demand list
+        before pooling, in plan order; [] when no pooling ran"""
+        return _read_pools(self, lambda *a: self._lib.td_sim_pools(self._h, *a), self.n_req)
 
     def close(self):
         if self._h is not None:
@@ -730,14 +785,23 @@ class DeviceSimulatorBatch(_DeviceEvents):
     diagonal and entries by td_simb_create_dist on the device, which raises TdError.
     events / event_capacity: as `DeviceSimulator` takes them; ONE log for the handle (td_simb_log), a record's second word is
     its world, and within a tick world 0's records come first.  The default capacity, 4 * (all cabs + all requests) + 64 * B,
-    holds any one tick of the batch."""
+    holds any one tick of the batch.
+    pool / max_loss: the pooling policy, one for the batch or a list with one entry per world (td_simb_pooling; None in a
+    max_loss list: every ordered pair in that world); `pools(b)` reads world b's plans of the tick last begun."""
 
     M_KEYS, CAB_KEYS, REQ_KEYS = DeviceSimulator.M_KEYS, DeviceSimulator.CAB_KEYS, DeviceSimulator.REQ_KEYS
     format_line = staticmethod(DeviceSimulator.format_line)
 
     def __init__(self, demand_rows_list, n_cabs_list, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None,
-                 events=None, event_capacity=None):
+                 events=None, event_capacity=None, pool="greedy", max_loss=None):
         import ctypes
+        n_cabs_list = list(n_cabs_list)
+        nb = len(n_cabs_list)
+        pools = list(pool) if isinstance(pool, (list, tuple)) else [pool] * nb
+        losses = list(max_loss) if isinstance(max_loss, (list, tuple, np.ndarray)) else [max_loss] * nb
+        if len(pools) != nb or len(losses) != nb:
+            raise ValueError("pool / max_loss: %d / %d entries for %d worlds" % (len(pools), len(losses), nb))
+        modes = np.array([pool_mode(p) for p in pools], np.int32)
         from . import _ffi
         self._ffi, self._ct = _ffi, ctypes
         self._h = None
@@ -779,6 +843,14 @@ class DeviceSimulatorBatch(_DeviceEvents):
         self.logs = [[] for _ in range(self.batch)]
         self._events_init(self._lib.td_simb_log, self._lib.td_simb_events, events, event_capacity,
                           4 * (sum(self.n_cabs) + sum(self.n_req)) + 64 * self.batch)
+        self.pool, self.max_loss = pools, losses
+        if any(p != "greedy" for p in pools) or any(x is not None for x in losses):      # a default batch never calls td_simb_pooling
+            ml = np.array([0.0 if x is None else float(x) for x in losses], np.float64)
+            _ffi.check(self._lib.td_simb_pooling(self._h, _ffi.addr(modes), _ffi.addr(ml)))
+
+    def pools(self, b):
+        """world b's plans of the tick last begun, as DeviceSimulator.pools lists them"""
+        return _read_pools(self, lambda *a: self._lib.td_simb_pools(self._h, int(b), *a), self.n_req[b])
 
     def close(self):
         if self._h is not None:

@@ -8,7 +8,11 @@
 (td_simb_create_dist); the stands of the demand file must lie inside it.
 --events FILE: the run's event log, Simulator.java's simulog.txt, written to FILE (every world: the host world records it
 itself, a device world through td_sim_log / td_sim_events, drained after every tick); with --cabs a,b,c one file per world,
-FILE with the world's number put before its extension (simulog.0.txt, simulog.1.txt, ...)."""
+FILE with the world's number put before its extension (simulog.0.txt, simulog.1.txt, ...).
+--pool none|greedy|optimal and --max-loss X: the pooling policy (default: greedy over every ordered pair, Simulator.java:691;
+X > 0 admits the pairs that pass pool_opt_min.py's loss tests, 0 = every pair); with --cabs a,b,c either may be a list a,b,c
+with one entry per world, and a single value holds for every world.  An optimal world refuses a tick with more than 2048
+requests before pooling (the committed demand file has such ticks at 1300 cabs and fewer)."""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,9 +23,21 @@ ap.add_argument("--world", choices=("host", "device"), default="host")
 ap.add_argument("--cabs", default=None, help="comma-separated fleet sizes: one world per size, run as one batch (needs --world device)")
 ap.add_argument("--dist", default=None, metavar="FILE.npy", help="a stand-to-stand distance table (numpy.save of a square integer array)")
 ap.add_argument("--events", default=None, metavar="FILE", help="write the event log (simulog.txt) of the run to FILE")
+ap.add_argument("--pool", default="greedy", metavar="none|greedy|optimal[,...]", help="the pooling policy; a list goes with a --cabs list")
+ap.add_argument("--max-loss", default=None, metavar="X[,...]", help="the candidate rule's max_loss (0: every pair); a list goes with a --cabs list")
 args = ap.parse_args()
 if args.cabs and args.world != "device":
     ap.error("--cabs needs --world device")
+n_worlds = len(args.cabs.split(",")) if args.cabs else 1
+pools = args.pool.split(",")
+losses = [float(v) if float(v) > 0 else None for v in args.max_loss.split(",")] if args.max_loss else [None]
+for what, vals in (("--pool", pools), ("--max-loss", losses)):
+    if len(vals) not in (1, n_worlds):
+        ap.error("%s has %d entries for %d world(s)" % (what, len(vals), n_worlds))
+for v in pools:
+    if v not in simulator.POOL_MODES:
+        ap.error("--pool %s: one of none, greedy, optimal" % v)
+pools, losses = pools * (n_worlds // len(pools)), losses * (n_worlds // len(losses))
 dist = None
 if args.dist:
     try:
@@ -60,7 +76,7 @@ def run_logged(sim, ticks):
 
 if args.world == "device" and args.cabs:
     fleets = [int(v) for v in args.cabs.split(",")]
-    sim = simulator.DeviceSimulatorBatch([rows] * len(fleets), fleets, dist=dist, events=True if args.events else None)
+    sim = simulator.DeviceSimulatorBatch([rows] * len(fleets), fleets, dist=dist, events=True if args.events else None, pool=pools, max_loss=losses)
     t0 = time.time()
     if args.events:
         records, logs = run_logged(sim, 120), sim.logs
@@ -73,12 +89,12 @@ if args.world == "device" and args.cabs:
             write_events("%s.%d%s" % (stem, b, ext), records, world=b)
     print("120 ticks of %d worlds in %.2f s; worlds and path on the GPU, one td_simb_step call per tick for all worlds" % (len(fleets), dt))
     for b, n in enumerate(fleets):
-        print("\n=== world %d: %d cabs ===" % (b, n))
+        print("\n=== world %d: %d cabs, pool %s, max_loss %s ===" % (b, n, pools[b], losses[b]))
         print("\n".join(logs[b][-2:]))
         print(sim.metrics_text(b, total_simul_time=int(dt)))
     sys.exit(0)
 if args.world == "device":
-    sim = simulator.DeviceSimulator(rows, dist=dist, events=True if args.events else None)
+    sim = simulator.DeviceSimulator(rows, dist=dist, events=True if args.events else None, pool=pools[0], max_loss=losses[0])
     t0 = time.time()
     if args.events:
         records, log = run_logged(sim, 120), sim.log
@@ -91,7 +107,7 @@ if args.world == "device":
     print("\n".join(log[-3:]))
     print(sim.metrics_text(total_simul_time=int(dt)))
     sys.exit(0)
-sim = simulator.Simulator(rows, dist=dist, events=bool(args.events))
+sim = simulator.Simulator(rows, dist=dist, events=bool(args.events), pool=pools[0], max_loss=losses[0])
 t0 = time.time()
 per = {"pool": 0.0, "cost": 0.0, "lcm": 0.0, "solve": 0.0}
 be = sim.be
