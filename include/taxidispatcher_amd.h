@@ -258,6 +258,45 @@ TD_API int td_split_batched(int batch, int n, const int32_t *cab_off, const int3
                             int size, int parts, int32_t fill, int32_t *cab_req, int32_t *cab_stage,
                             int64_t *total, int64_t *rest_total, int32_t *n_rest, int64_t *dual_gap);
 
+/* ---- MANY dispatch models in one call, a dispatch method per model ---------------------------------------------------------
+ * td_tick_batched's inputs and output layout (ragged lists behind offsets, host or device memory, synchronous, batch == 0 is
+ * a no-op, n = the output stride <= 2048), plus a policy per model: mode[b], stop_size[b], parts[b], each int32[B], host or
+ * device memory, each may be NULL (mode 0 everywhere; the LCM never runs; 4 parts).  size = the number of stands the split's
+ * ranges are cut over (read for split models only).
+ *   TD_DISPATCH_LCM_OPT  model b is what td_tick_batched makes of it with stop_size[b], every output.
+ *   TD_DISPATCH_OPT      the LCM never runs: td_tick_batched with stop_size < 0.
+ *   TD_DISPATCH_LCM      the LCM of Simulator.java:523-549 with stop size 0, run to its end (no candidate below fill left, or
+ *                        every row taken); the model is never solved, whatever the last minimum was.  Pairs, n_pairs and
+ *                        lcm_last_min as td_tick_batched; kept lists = who is in no pair; n_rest = the larger kept count;
+ *                        row_to_col -1, total and dual_bound 0.
+ *   TD_DISPATCH_SPLIT    split.py:61-119 (td_split_batched's ranges of parts[b] over size, region optima, collection of the
+ *                        left-overs, the fifth solve) on the model's thresholded cells: a cell is dist below threshold, else
+ *                        fill (threshold < 0: dist).  A cab is served only on a real cell below fill: a pair on a thresholded
+ *                        cell leaves its cab and its request to the rest (after the fifth solve: unserved), and only cells
+ *                        below fill are summed.  n_pairs 0, lcm_last_min fill, n_rest = max(n_s, n_d), kept lists = the whole
+ *                        model in order, row_to_col[b*n + i] = the request cab i serves within the model's request list or -1
+ *                        (td_split_batched's cab_req; -1 for i >= n_s), total = the split total, dual_bound = total minus the
+ *                        case's dual gap: dual_bound == total certifies every model solved for the case.  With threshold < 0
+ *                        row_to_col and total equal td_split_batched's cab_req and total bit for bit.
+ * Launches (csrc/td_batch.hip): the tick's two take every model that is not split, the split's five take the split models
+ * and run only when there is one: 2 without a split model, 7 with one, whatever B and the mix.
+ * TD_EINVAL, with every output left unwritten: td_tick_batched's rules; with a split model td_split_batched's (S < size with a
+ * table, fill < 1, on the line size - 1 >= fill, a position of a split model outside [0, size), a table entry used as its
+ * cell outside [0, fill)); a mode outside 0 .. 3; a split model with more than 1024 cabs or requests; parts[b] outside
+ * [1, 32] or size < parts[b] for a split model; a TD_DISPATCH_OPT / _LCM_OPT model whose remainder (by its own stop_size)
+ * has more than 1024 rows.  TD_EINTERNAL if a model hit a defensive loop cap. */
+#define TD_DISPATCH_LCM_OPT 0
+#define TD_DISPATCH_OPT 1
+#define TD_DISPATCH_LCM 2
+#define TD_DISPATCH_SPLIT 3
+TD_API int td_dispatch_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab_to,
+                               const int32_t *dem_off, const int32_t *dem_from, const int32_t *dist, int S,
+                               int32_t fill, int32_t threshold, int size, const int32_t *mode,
+                               const int32_t *stop_size, const int32_t *parts,
+                               int32_t *lcm_rows, int32_t *lcm_cols, int32_t *n_pairs, int32_t *lcm_last_min,
+                               int32_t *kept_cabs, int32_t *kept_dems, int32_t *n_rest, int32_t *row_to_col,
+                               int64_t *total, int64_t *dual_bound);
+
 /* Row-sharded LCM: rank r owns cost rows [row0, row0 + nrows).  Per pick every shard
  * reports its smallest live cell {value, global row, column} (value = INT64_MAX: none), the caller
  * takes the minimum in the reference's order (value, row, column) over all shards — one all-gather of
@@ -513,6 +552,37 @@ TD_API int td_sim_pooling(td_sim *s, int mode, double max_loss);
 TD_API int td_simb_pooling(td_simb *s, const int32_t *mode /* [B], NULL = greedy */, const double *max_loss /* [B], NULL = every pair */);
 TD_API int td_sim_pools(td_sim *s, int max_pools, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n);
 TD_API int td_simb_pools(td_simb *s, int world, int max_pools, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n);
+
+/* ---- the dispatch policy of a world ------------------------------------------------------------------------------
+ * Until *_dispatch is called a world dispatches as Simulator.java:163-208 does, "the LCM down to max_non_lcm, then the
+ * optimum", with the max_non_lcm it was created with, through the calls and kernels it always used.  td_sim_dispatch sets one
+ * world's method (TD_DISPATCH_*, above), its max_non_lcm and, for the split, the number of parts over the n_stands stands;
+ * td_simb_dispatch every world's (mode, max_non_lcm, parts: int32[B] each, host or device memory; NULL = lcm+opt everywhere /
+ * the max_non_lcm the handle was created with / 4).  It takes effect from the next begin and allocates nothing, then or per
+ * tick (the batch's per-world rule is part of the handle since create).  TD_EINVAL, the policy unchanged: a mode outside
+ * 0 .. 3, a negative max_non_lcm, a max_non_lcm above 1024 in a batch, parts outside 1 .. min(32, n_stands) for a split world,
+ * a call while a tick with demand waits for its apply.
+ * "The LCM ran" is then the world's rule, wherever it is evaluated (the apply kernels, the kept lists, the event log, the
+ * line, total_LCM_used): TD_DISPATCH_LCM_OPT: the model is larger than the world's max_non_lcm; TD_DISPATCH_LCM: always,
+ * with supply; TD_DISPATCH_OPT and TD_DISPATCH_SPLIT: never.
+ *   td_sim_step    LCM_OPT: td_tick with the world's max_non_lcm.  OPT: td_tick with stop_size -1.  LCM: td_tick with stop_size
+ *                  0, applied without a solution: line = {1, d, s, 1, k, 0, d - k, s - k, -1}.  SPLIT: td_dispatch_batched's
+ *                  device code on the one model (cells below drop_time, parts ranges over n_stands), applied as a solution
+ *                  over the whole model: decisions are logged with the method word of the optimum, max_solver_size takes the
+ *                  whole model size, line = {1, d, s, 0, 0, 0, d, s, OPT count} as for OPT.  A split model with more than
+ *                  1024 cabs or requests: TD_EINVAL, the message names the tick and the counts; the tick stays begun and is
+ *                  finished through td_sim_model / td_sim_apply.  td_dispatch_batched's refusals apply (a table entry used as
+ *                  a cell must lie below big_cost).
+ *   td_simb_step   when some world's policy is not the handle's own (lcm+opt with the created max_non_lcm): ONE
+ *                  td_dispatch_batched on the device lists with the policy arrays (2 launches, 7 when a world splits) instead of
+ *                  td_tick_batched; else td_tick_batched exactly as before.  A split world's or an optimum-alone world's model
+ *                  with more than 1024 cabs or requests: TD_EINVAL, the message names the world and the counts; the tick stays
+ *                  begun and is finished through td_simb_model / td_simb_apply.  The lines are td_sim_step's per world.
+ *   td_sim_apply   with decisions from elsewhere follows the same rule: pairs are read only where the LCM ran under the world's
+ *                  policy, `solved` is ignored in a TD_DISPATCH_LCM world (nothing is solved there), row_to_col is over the
+ *                  whole model in OPT and SPLIT worlds (the request of each cab). */
+TD_API int td_sim_dispatch(td_sim *s, int mode, int max_non_lcm, int parts);
+TD_API int td_simb_dispatch(td_simb *s, const int32_t *mode, const int32_t *max_non_lcm, const int32_t *parts); /* [B] each, NULL = as created / 4 */
 
 /* the batch's event log: td_sim_log / td_sim_events above with a world word; ONE log for the handle, within a tick world 0's
  * records first; the number of launches the log adds to a tick (three kernels, two fills) does not depend on B */

@@ -56,6 +56,9 @@ SIGNATURES = {
                                        c_i32p, c_i32p]),
     "td_split_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
+    "td_dispatch_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int32,
+                                           ctypes.c_int32, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p,
+                                           c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
     "td_lcm_shard_create":(ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p, ctypes.c_int, ctypes.c_int32,
                                            ctypes.POINTER(ctypes.c_void_p)]),
     "td_lcm_shard_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -78,6 +81,7 @@ SIGNATURES = {
     "td_sim_model": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p]),
     "td_sim_apply": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int, c_i32p,
                                     ctypes.POINTER(ctypes.c_int32)]),
+    "td_sim_dispatch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "td_sim_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p]),
     "td_sim_state": (ctypes.c_int, [ctypes.c_void_p] + [c_i32p] * 10),
     "td_sim_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -97,6 +101,7 @@ SIGNATURES = {
     "td_simb_log": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int64]),
     "td_simb_events": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_i32p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "td_sim_pooling": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]),
+    "td_simb_dispatch": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p]),
     "td_simb_pooling": (ctypes.c_int, [ctypes.c_void_p, c_i32p, ctypes.c_void_p]),
     "td_sim_pools": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_int32)]),
     "td_simb_pools": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p,

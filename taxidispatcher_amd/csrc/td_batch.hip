@@ -2,7 +2,8 @@
 // (td_lcm_batched) of B square models of size <= 1024, one workgroup per model; and the same solve and LCM for B ragged
 // dispatch models made from cab / request positions (td_build_assign_batched, td_tick_batched: cells through PosCells, no
 // cost matrix); and split.py's whole heuristic for B ragged cases (td_split_batched: partition into stand ranges, the region
-// models, the left-overs' fifth model, the sums).  gfx950 only.
+// models, the left-overs' fifth model, the sums); and a dispatch call with a policy per model (td_dispatch_batched: the tick,
+// the optimum alone, the LCM alone or the split heuristic on thresholded cells, chosen per model).  gfx950 only.
 //
 // Nothing here waits on another workgroup: a model's whole solve lives in one workgroup's LDS and registers (no
 // cross-workgroup atomics, no spins), and a grid-stride loop over the models covers batches larger than the grid.
@@ -378,7 +379,8 @@ __global__ __launch_bounds__(T) void k_assign_batched(int batch, int n, const in
 // ---------------------------------------------------------------------------------------------------------------------
 // optimal assignment of position models (td_build_assign_batched, td_tick_batched's remainder): model b's cabs are
 // cab[cab_off[b] ...], its requests dem[dem_off[b] ...]; the counts are cab_off[b + 1] - cab_off[b] (cnt == null) or
-// cnt[2b] / cnt[2b + 1] (the tick's kept lists, 0 / 0 = no solve).  nl >= every max(count) bounds the LDS arrays.
+// cnt[2b] / cnt[2b + 1] (the tick's kept lists, 0 / 0 = no solve; -1 / -1: model b is not this launch's, nothing of it is
+// written).  nl >= every max(count) bounds the LDS arrays.
 // dynamic LDS: v int64[nl] | pred, y, x int32[nl] | cab, dem int32[nl] | table int32[S*S] (LDS_DIST)
 // ---------------------------------------------------------------------------------------------------------------------
 template <int T, int CPT, bool LDS_DIST>
@@ -408,6 +410,7 @@ __global__ __launch_bounds__(T) void k_assign_pos_batched(int batch, int n_out, 
         const int c0 = cab_off[b], d0 = dem_off[b];
         const int ns = cnt ? cnt[2 * b] : cab_off[b + 1] - c0;
         const int nd = cnt ? cnt[2 * b + 1] : dem_off[b + 1] - d0;
+        if (ns < 0 || nd < 0) continue;   // uniform: both counts are -1 for td_dispatch_batched's split models and in a refused call
         const int nb = ns > nd ? ns : nd;
         if (nb > nl) {   // validated on the host; never index LDS past nl
             if (tid == 0) *err = ERR_SIZE;
@@ -597,15 +600,22 @@ __global__ __launch_bounds__(T) void k_pool2_lcm_batched(int batch, int n, const
 // then the shrink: the cabs / requests in no pair, in order (k_tick_shrink's ordered compaction, per model).  Their
 // indices go to kept_c / kept_d (may be null), their positions to cab2 / dem2 at the model's own offsets, their counts to
 // cnt[2b] / cnt[2b + 1] for the solve (0 / 0 when the LCM ended on fill: no solve, Simulator.java:188-189).
+// td_dispatch_batched hands in a policy per model (mode non-null; stop_arr non-null: model b's own stop size): TD_DISPATCH_OPT
+// is stop size -1, TD_DISPATCH_LCM is stop size 0 and never a solve (0 / 0), a TD_DISPATCH_SPLIT model is not this launch's
+// (counts -1 / -1, nothing else written); and gate (non-null): a non-zero word = the split launches before this one refused
+// the input, every model gets -1 / -1 and no output is written.  All of that is the POLICY instantiation; td_tick_batched's
+// (POLICY = false) reads none of the three and is the kernel it was.
 // dynamic LDS (nl = the largest n(b)): row cache uint64[nl] | rescan list, cab, dem int32[nl] | column mask, row mask
 // uint32[(nl + 31) / 32] each | table int32[S*S] (LDS_DIST)
 // ---------------------------------------------------------------------------------------------------------------------
-template <int T, bool LDS_DIST>
+template <int T, bool LDS_DIST, bool POLICY>
 __global__ __launch_bounds__(T) void k_tick_lcm_batched(int batch, int n_out, int nl, const int32_t *__restrict__ cab_off,
                                                         const int32_t *__restrict__ cab, const int32_t *__restrict__ dem_off,
                                                         const int32_t *__restrict__ dem, const int32_t *__restrict__ dist, int S,
-                                                        int32_t fill, int32_t thr, int stop_size, int32_t *__restrict__ rows,
-                                                        int32_t *__restrict__ cols, int32_t *__restrict__ n_pairs,
+                                                        int32_t fill, int32_t thr, int stop_size, const int32_t *__restrict__ mode,
+                                                        const int32_t *__restrict__ stop_arr, const int *__restrict__ gate,
+                                                        int32_t *__restrict__ rows, int32_t *__restrict__ cols,
+                                                        int32_t *__restrict__ n_pairs,
                                                         int32_t *__restrict__ last_min, int32_t *__restrict__ kept_c,
                                                         int32_t *__restrict__ kept_d, int32_t *__restrict__ n_rest,
                                                         int32_t *__restrict__ cab2, int32_t *__restrict__ dem2, int32_t *__restrict__ cnt)
@@ -625,21 +635,38 @@ __global__ __launch_bounds__(T) void k_tick_lcm_batched(int batch, int n_out, in
     __shared__ int s_w[NW];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     int par = 0;
+    if (POLICY && gate) {   // nothing in this launch writes the word: one read per workgroup
+        if (tid == 0) s_cnt = *gate;
+        __syncthreads();
+        const int refused = s_cnt;
+        __syncthreads();
+        if (refused) {
+            if (tid == 0)
+                for (int q = blockIdx.x; q < batch; q += gridDim.x) cnt[2 * q] = cnt[2 * q + 1] = -1;
+            return;
+        }
+    }
     if constexpr (LDS_DIST)
         for (int q = tid; q < S * S; q += T) s_dist[q] = dist[q];   // read after the first model's barrier
     for (int b = blockIdx.x; b < batch; b += gridDim.x) {
+        const int md = POLICY && mode ? mode[b] : TD_DISPATCH_LCM_OPT;
+        if (POLICY && md == TD_DISPATCH_SPLIT) {   // uniform
+            if (tid == 0) cnt[2 * b] = cnt[2 * b + 1] = -1;
+            continue;
+        }
+        const int stop_b = !POLICY ? stop_size : md == TD_DISPATCH_OPT ? -1 : md == TD_DISPATCH_LCM ? 0 : stop_arr ? stop_arr[b] : stop_size;
         const int c0 = cab_off[b], d0 = dem_off[b];
         const int ns = cab_off[b + 1] - c0, nd = dem_off[b + 1] - d0, nb = ns > nd ? ns : nd;
         __syncthreads();   // the previous model's LDS is no longer read
         for (int i = tid; i < ns; i += T) s_cab[i] = cab[c0 + i];
         for (int j = tid; j < nd; j += T) s_dem[j] = dem[d0 + j];
-        const bool lcm_runs = stop_size >= 0 && stop_size < nb;
+        const bool lcm_runs = stop_b >= 0 && stop_b < nb;
         int np = 0;
         int32_t lm = fill;
         if (lcm_runs) {
             const PosCells<LDS_DIST> C{s_cab, s_dem, LDS_DIST ? s_dist : dist, ns, nd, S, fill, thr};
             int64_t tot;
-            lcm_model<T>(C, ns, nd, nb, (int64_t)fill, fill, -1, 1, fill, stop_size, (int64_t)fill, s_rb, s_list, s_cm, s_rm, s_red,
+            lcm_model<T>(C, ns, nd, nb, (int64_t)fill, fill, -1, 1, fill, stop_b, (int64_t)fill, s_rb, s_list, s_cm, s_rm, s_red,
                          &s_cnt, par, rows + (int64_t)b * n_out, cols + (int64_t)b * n_out, np, lm, tot);
         } else {
             for (int q = tid; q < WL; q += T) {
@@ -680,7 +707,7 @@ __global__ __launch_bounds__(T) void k_tick_lcm_batched(int batch, int n_out, in
         }
         if (tid == 0) {
             const int kc = s_kept[0], kd = s_kept[1];
-            const bool solve = !(lcm_runs && lm == fill);   // Simulator.java:188-189
+            const bool solve = md != TD_DISPATCH_LCM && !(lcm_runs && lm == fill);   // Simulator.java:188-189
             n_pairs[b] = np;
             last_min[b] = lm;
             n_rest[b] = kc > kd ? kc : kd;
@@ -903,22 +930,24 @@ void launch_pos_assign(int batch, int n_out, int nl, const PosIn &in, const int3
         launch_pos_assign_t<256, 4>(batch, n_out, nl, in, cab, dem, cnt, S, fill, thr, r2c, tot, dual, err);
 }
 
-template <int T>
-void launch_tick_lcm_t(int batch, int n_out, int nl, const PosIn &in, int S, int32_t fill, int32_t thr, int stop_size, void *const *o,
-                       int32_t *cab2, int32_t *dem2, int32_t *cnt)
+template <int T, bool POLICY>
+void launch_tick_lcm_t(int batch, int n_out, int nl, const PosIn &in, int S, int32_t fill, int32_t thr, int stop_size,
+                       const int32_t *mode, const int32_t *stop_arr, const int *gate, void *const *o, int32_t *cab2, int32_t *dem2,
+                       int32_t *cnt)
 {
     const size_t shm = (size_t)nl * (sizeof(uint64_t) + 3 * sizeof(int32_t)) + 2 * sizeof(uint32_t) * (((size_t)nl + 31) / 32);
     const size_t tab = in.dist ? sizeof(int32_t) * (size_t)S * S : 0;
     const int grid = std::min(batch, 1 << 20);
     hipStream_t st = ctx().stream;
 #define TD_TICK_LCM_ARGS                                                                                                          \
-    batch, n_out, nl, in.cab_off, in.cab, in.dem_off, in.dem, in.dist, S, fill, thr, stop_size, (int32_t *)o[0], (int32_t *)o[1],  \
-        (int32_t *)o[2], (int32_t *)o[3], (int32_t *)o[4], (int32_t *)o[5], (int32_t *)o[6], cab2, dem2, cnt
+    batch, n_out, nl, in.cab_off, in.cab, in.dem_off, in.dem, in.dist, S, fill, thr, stop_size, mode, stop_arr, gate,              \
+        (int32_t *)o[0], (int32_t *)o[1], (int32_t *)o[2], (int32_t *)o[3], (int32_t *)o[4], (int32_t *)o[5], (int32_t *)o[6], cab2, \
+        dem2, cnt
     if (in.dist && shm + tab <= lds_budget()) {
-        lds_allow(k_tick_lcm_batched<T, true>, shm + tab);
-        k_tick_lcm_batched<T, true><<<grid, T, shm + tab, st>>>(TD_TICK_LCM_ARGS);
+        lds_allow(k_tick_lcm_batched<T, true, POLICY>, shm + tab);
+        k_tick_lcm_batched<T, true, POLICY><<<grid, T, shm + tab, st>>>(TD_TICK_LCM_ARGS);
     } else {
-        k_tick_lcm_batched<T, false><<<grid, T, shm, st>>>(TD_TICK_LCM_ARGS);
+        k_tick_lcm_batched<T, false, POLICY><<<grid, T, shm, st>>>(TD_TICK_LCM_ARGS);
     }
 #undef TD_TICK_LCM_ARGS
 }
@@ -985,7 +1014,11 @@ __device__ __forceinline__ bool split_cells_bad(const int32_t *pa, int na, const
 // stably: scab / sdem get the positions, scab_idx / sdem_idx the index within the case.  Region model m = c * R + r starts
 // at roff_c[m] / roff_d[m] (absolute, inside the case's segment) and has rcnt[2m] / rcnt[2m + 1] rows / columns: 0 / 0 for
 // a region with one side empty, which the solver reads as "no solve".  With a table, every cell of a region model is checked.
-__global__ __launch_bounds__(256) void k_split_part(int batch, int R, int ss, int size, const int32_t *__restrict__ cab_off,
+// td_dispatch_batched: mode (non-null) leaves every case that is not TD_DISPATCH_SPLIT out as an empty case, and parts
+// (non-null) gives case c its own range width size / parts[c]; R is then the largest range count of the batch, and the
+// regions beyond a case's own count are empty.
+__global__ __launch_bounds__(256) void k_split_part(int batch, int R, int ss, int size, const int32_t *__restrict__ mode,
+                                                    const int32_t *__restrict__ parts, const int32_t *__restrict__ cab_off,
                                                     const int32_t *__restrict__ cab, const int32_t *__restrict__ dem_off,
                                                     const int32_t *__restrict__ dem, const int32_t *__restrict__ dist, int S,
                                                     int32_t fill, int32_t *__restrict__ roff_c, int32_t *__restrict__ roff_d,
@@ -1000,9 +1033,12 @@ __global__ __launch_bounds__(256) void k_split_part(int batch, int R, int ss, in
     __shared__ int s_bad;
     const int tid = threadIdx.x, T = blockDim.x;
     for (int c = blockIdx.x; c < batch; c += gridDim.x) {
+        const bool act = !mode || mode[c] == TD_DISPATCH_SPLIT;
         const int c0 = cab_off[c], d0 = dem_off[c];
-        const int ns = cab_off[c + 1] - c0, nd = dem_off[c + 1] - d0;
-        if (ns > BATCH_NMAX || nd > BATCH_NMAX) {   // validated on the host; never index LDS past its arrays
+        const int ns = act ? cab_off[c + 1] - c0 : 0, nd = act ? dem_off[c + 1] - d0 : 0;
+        const int pc = parts && act ? parts[c] : 0;
+        const int ssc = pc >= 1 && pc <= size ? size / pc : ss;   // validated on the host; never divide by zero
+        if (ns > BATCH_NMAX || nd > BATCH_NMAX || (size + ssc - 1) / ssc > R) {   // validated on the host; never index LDS past its arrays
             if (tid == 0) {
                 atomicOr(err, ERR_SIZE);
                 cnt2[2 * c] = cnt2[2 * c + 1] = 0;
@@ -1020,7 +1056,7 @@ __global__ __launch_bounds__(256) void k_split_part(int batch, int R, int ss, in
             for (int i = tid; i < m; i += T) {
                 const int p = src[i];
                 const bool ok = (uint32_t)p < (uint32_t)size;
-                const int r = ok ? p / ss : 0;
+                const int r = ok ? p / ssc : 0;
                 if (!ok) s_bad = 1;
                 s_rng[side][i] = r;
                 atomicAdd(&s_hist[side][r], 1);
@@ -1083,7 +1119,10 @@ __global__ __launch_bounds__(256) void k_split_part(int batch, int R, int ss, in
 // request of the case goes to the rest lists in case order (ballot + popcount ranks): positions to rcab / rdem, case
 // indices to rcab_idx / rdem_idx, at the case's own offsets; nrest = their sizes, cnt2 = the same when both are non-empty
 // (else 0 / 0: no fifth solve).  A case with no cabs or no requests has no solve and no lists (split.py:62-64).
-__global__ __launch_bounds__(256) void k_split_rest(int batch, int R, int n_out, const int32_t *__restrict__ cab_off,
+// thr >= 0 (td_dispatch_batched): the models were solved on thresholded cells, and a pair on a cell at or above thr is no
+// service: both its cab and its request go to the rest.  mode (non-null): a case that is not TD_DISPATCH_SPLIT is empty.
+__global__ __launch_bounds__(256) void k_split_rest(int batch, int R, int n_out, int32_t thr, const int32_t *__restrict__ mode,
+                                                    const int32_t *__restrict__ cab_off,
                                                     const int32_t *__restrict__ cab, const int32_t *__restrict__ dem_off,
                                                     const int32_t *__restrict__ dem, const int32_t *__restrict__ dist, int S,
                                                     int32_t fill, const int32_t *__restrict__ roff_c,
@@ -1107,8 +1146,9 @@ __global__ __launch_bounds__(256) void k_split_rest(int batch, int R, int n_out,
     __syncthreads();
     if (s_err) return;   // an earlier launch refused the input: nothing below is needed
     for (int c = blockIdx.x; c < batch; c += gridDim.x) {
+        const bool act = !mode || mode[c] == TD_DISPATCH_SPLIT;
         const int c0 = cab_off[c], d0 = dem_off[c];
-        const int ns = cab_off[c + 1] - c0, nd = dem_off[c + 1] - d0;
+        const int ns = act ? cab_off[c + 1] - c0 : 0, nd = act ? dem_off[c + 1] - d0 : 0;
         if (ns > BATCH_NMAX || nd > BATCH_NMAX) continue;   // k_split_part has set the error word
         __syncthreads();   // the previous case's LDS is no longer read
         for (int i = tid; i < ns; i += T) s_req[i] = -1;
@@ -1132,10 +1172,13 @@ __global__ __launch_bounds__(256) void k_split_rest(int batch, int R, int n_out,
             for (int i = tid; i < nsr; i += T) {
                 const int j = r2c1[(int64_t)m * n_out + i];
                 if ((uint32_t)j < (uint32_t)ndr) {   // a real cell; a dummy column leaves the cab to the rest
-                    const int ci = scab_idx[rc + i], dj = sdem_idx[rd + j];
-                    s_req[ci] = dj;
-                    s_dsv[dj] = 1;
-                    sum += pos_dist(dist, S, scab[rc + i], sdem[rd + j]);
+                    const int32_t x = pos_dist(dist, S, scab[rc + i], sdem[rd + j]);
+                    if (thr < 0 || x < thr) {   // a thresholded cell is fill: no service
+                        const int ci = scab_idx[rc + i], dj = sdem_idx[rd + j];
+                        s_req[ci] = dj;
+                        s_dsv[dj] = 1;
+                        sum += x;
+                    }
                 }
             }
             if (tid == 0) gap += tot1[m] - dual1[m];
@@ -1185,7 +1228,19 @@ __global__ __launch_bounds__(256) void k_split_rest(int batch, int R, int n_out,
 
 // launch 5: the fifth models' row_to_col back to case indices (stage 1), their real-cell sums, and the caller's outputs.
 // Nothing is written when the error word is set: a refused call leaves every output as it was.
-__global__ __launch_bounds__(256) void k_split_final(int batch, int n_out, const int32_t *__restrict__ cab_off,
+// thr >= 0: as in k_split_rest.  td_dispatch_batched (dp.mode non-null) has only its TD_DISPATCH_SPLIT cases finished here, and
+// their results written in td_tick_batched's layout (stride dp.n): no pairs, last minimum fill, the kept lists = the whole
+// model in order, row_to_col = the request of each cab, dual_bound = total - the case's dual gap.
+struct SplitDisp {
+    const int32_t *mode;
+    int n;
+    int32_t fill;
+    int32_t *n_pairs, *last_min, *kept_c, *kept_d, *n_rest, *r2c;
+    int64_t *total, *dual;
+};
+
+__global__ __launch_bounds__(256) void k_split_final(int batch, int n_out, int32_t thr, SplitDisp dp,
+                                                     const int32_t *__restrict__ cab_off,
                                                      const int32_t *__restrict__ dem_off, const int32_t *__restrict__ dist, int S,
                                                      const int32_t *__restrict__ ws_req, const int32_t *__restrict__ rcab,
                                                      const int32_t *__restrict__ rcab_idx, const int32_t *__restrict__ rdem,
@@ -1203,6 +1258,7 @@ __global__ __launch_bounds__(256) void k_split_final(int batch, int n_out, const
     const int tid = threadIdx.x, T = blockDim.x;
     if (*err) return;   // uniform: nothing in this launch writes the word
     for (int c = blockIdx.x; c < batch; c += gridDim.x) {
+        if (dp.mode && dp.mode[c] != TD_DISPATCH_SPLIT) continue;   // uniform: the tick's launches have written this model
         const int c0 = cab_off[c], d0 = dem_off[c];
         const int ns = cab_off[c + 1] - c0;
         __syncthreads();   // the previous case's LDS is no longer read
@@ -1217,13 +1273,34 @@ __global__ __launch_bounds__(256) void k_split_final(int batch, int n_out, const
         for (int i = tid; i < kc; i += T) {
             const int j = r2c2[(int64_t)c * n_out + i];
             if ((uint32_t)j < (uint32_t)kd) {
-                const int ci = rcab_idx[c0 + i];
-                s_req[ci] = rdem_idx[d0 + j];
-                s_stage[ci] = 1;
-                sum += pos_dist(dist, S, rcab[c0 + i], rdem[d0 + j]);
+                const int32_t x = pos_dist(dist, S, rcab[c0 + i], rdem[d0 + j]);
+                if (thr < 0 || x < thr) {
+                    const int ci = rcab_idx[c0 + i];
+                    s_req[ci] = rdem_idx[d0 + j];
+                    s_stage[ci] = 1;
+                    sum += x;
+                }
             }
         }
         sum = block_sum_i64(sum, s_sum);
+        if (dp.mode) {
+            const int nd = dem_off[c + 1] - d0;
+            const int64_t at = (int64_t)c * dp.n;
+            for (int i = tid; i < dp.n; i += T) {
+                dp.r2c[at + i] = i < ns ? s_req[i] : -1;
+                if (dp.kept_c && i < ns) dp.kept_c[at + i] = i;
+                if (dp.kept_d && i < nd) dp.kept_d[at + i] = i;
+            }
+            if (tid == 0) {
+                const int64_t tot = sum0[c] + sum;
+                dp.n_pairs[c] = 0;
+                dp.last_min[c] = dp.fill;
+                dp.n_rest[c] = ns > nd ? ns : nd;
+                dp.total[c] = tot;
+                if (dp.dual) dp.dual[c] = tot - (gap0[c] + tot2[c] - dual2[c]);
+            }
+            continue;
+        }
         for (int i = tid; i < ns; i += T) {
             cab_req[c0 + i] = s_req[i];
             if (cab_stage) cab_stage[c0 + i] = s_stage[i];
@@ -1242,6 +1319,73 @@ __global__ __launch_bounds__(256) void k_split_final(int batch, int n_out, const
 
 Buf g_sp;                       // td_split_batched's device workspace (grow-only)
 std::vector<char> g_sp_host;    // its host destinations land here first: a refused call leaves the caller's arrays unwritten
+
+// the split launches' workspace inside g_sp: B cases, M = B * R region models, nl = the largest model, nc / nd positions
+struct SplitWs {
+    int64_t *tot1, *dual1, *tot2, *dual2, *sum0, *gap0;
+    int32_t *roff_c, *roff_d, *rcnt, *scab, *scab_idx, *sdem, *sdem_idx, *r2c1, *ws_req, *rcab, *rcab_idx, *rdem, *rdem_idx, *cnt2, *nrest,
+        *r2c2;
+};
+
+int split_ws(size_t B, size_t M, size_t nl, size_t nc, size_t nd, SplitWs *s)
+{
+    // the int64 arrays first, every array 256-byte aligned
+    size_t at = 0;
+    auto take = [&at](size_t bytes) {
+        const size_t o = at;
+        at += align256(bytes);
+        return o;
+    };
+    const size_t o_tot1 = take(8 * M), o_dual1 = take(8 * M), o_tot2 = take(8 * B), o_dual2 = take(8 * B), o_sum0 = take(8 * B),
+                 o_gap0 = take(8 * B), o_roffc = take(4 * (M + 1)), o_roffd = take(4 * (M + 1)), o_rcnt = take(8 * M),
+                 o_scab = take(4 * nc), o_scabi = take(4 * nc), o_sdem = take(4 * nd), o_sdemi = take(4 * nd),
+                 o_r2c1 = take(4 * M * nl), o_wsreq = take(4 * nc), o_rcab = take(4 * nc), o_rcabi = take(4 * nc),
+                 o_rdem = take(4 * nd), o_rdemi = take(4 * nd), o_cnt2 = take(8 * B), o_nrest = take(8 * B),
+                 o_r2c2 = take(4 * B * nl);
+    int rc = ensure(g_sp, at + 256);
+    if (rc) return rc;
+    char *w = (char *)g_sp.p;
+    *s = SplitWs{(int64_t *)(w + o_tot1),  (int64_t *)(w + o_dual1),  (int64_t *)(w + o_tot2), (int64_t *)(w + o_dual2),
+                 (int64_t *)(w + o_sum0),  (int64_t *)(w + o_gap0),   (int32_t *)(w + o_roffc), (int32_t *)(w + o_roffd),
+                 (int32_t *)(w + o_rcnt),  (int32_t *)(w + o_scab),   (int32_t *)(w + o_scabi), (int32_t *)(w + o_sdem),
+                 (int32_t *)(w + o_sdemi), (int32_t *)(w + o_r2c1),   (int32_t *)(w + o_wsreq), (int32_t *)(w + o_rcab),
+                 (int32_t *)(w + o_rcabi), (int32_t *)(w + o_rdem),   (int32_t *)(w + o_rdemi), (int32_t *)(w + o_cnt2),
+                 (int32_t *)(w + o_nrest), (int32_t *)(w + o_r2c2)};
+    return TD_OK;
+}
+
+// launches 1 to 4 of the split: partition, the region models, collection, the fifth models (thr, mode, parts: see the kernels)
+void split_launches(int batch, int R, int ss, int size, int nl, const PosIn &in, int S, int32_t fill, int32_t thr, const int32_t *mode,
+                    const int32_t *parts, const SplitWs &w, int *d_err)
+{
+    Ctx &c = ctx();
+    const int T = nl <= 64 ? 64 : 256, grid = std::min(batch, SPLIT_GRID);
+    const int M = batch * R;
+    k_split_part<<<grid, T, 0, c.stream>>>(batch, R, ss, size, mode, parts, in.cab_off, in.cab, in.dem_off, in.dem, in.dist, S, fill,
+                                           w.roff_c, w.roff_d, w.rcnt, w.scab, w.scab_idx, w.sdem, w.sdem_idx, w.cnt2, d_err);
+    PosIn rin = in;
+    rin.cab_off = w.roff_c;
+    rin.dem_off = w.roff_d;
+    launch_pos_assign(M, nl, nl, rin, w.scab, w.sdem, w.rcnt, S, fill, thr, w.r2c1, w.tot1, w.dual1, d_err);
+    k_split_rest<<<grid, T, 0, c.stream>>>(batch, R, nl, thr, mode, in.cab_off, in.cab, in.dem_off, in.dem, in.dist, S, fill, w.roff_c,
+                                           w.roff_d, w.rcnt, w.scab, w.scab_idx, w.sdem, w.sdem_idx, w.r2c1, w.tot1, w.dual1, w.ws_req,
+                                           w.rcab, w.rcab_idx, w.rdem, w.rdem_idx, w.cnt2, w.nrest, w.sum0, w.gap0, d_err);
+    launch_pos_assign(batch, nl, nl, in, w.rcab, w.rdem, w.cnt2, S, fill, thr, w.r2c2, w.tot2, w.dual2, d_err);
+}
+
+// the split's refusals that are found on the device, from the error word
+int split_error(const char *fn, int e, int size, int32_t fill)
+{
+    if (e & ERR_POS) return fail(TD_EINVAL, "%s: a cab_to / dem_from position outside [0, %d)", fn, size);
+    if (e & ERR_CELL) return fail(TD_EINVAL, "%s: a table entry used as a cell is outside [0, fill = %d)", fn, (int)fill);
+    if (e)
+        return fail(TD_EINTERNAL, "%s: a model hit a defensive loop cap (error word 0x%x: 1 search steps, 2 augmenting path, "
+                    "4 label range, 8 model size)", fn, e);
+    return TD_OK;
+}
+
+Buf g_pol[3];                    // td_dispatch_batched: device copies of host mode / stop_size / parts
+std::vector<int32_t> g_polh[3];  // their host copies (validated there)
 
 }  // namespace
 
@@ -1380,9 +1524,9 @@ int td_tick_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab
     void *od[7];
     for (int k = 0; k < 7; k++) od[k] = o[k].dptr();
     if (in.nmax <= 128)
-        launch_tick_lcm_t<64>(batch, n, in.nmax, in, S, fill, threshold, stop_size, od, cab2, dem2, cnt);
+        launch_tick_lcm_t<64, false>(batch, n, in.nmax, in, S, fill, threshold, stop_size, nullptr, nullptr, nullptr, od, cab2, dem2, cnt);
     else
-        launch_tick_lcm_t<256>(batch, n, in.nmax, in, S, fill, threshold, stop_size, od, cab2, dem2, cnt);
+        launch_tick_lcm_t<256, false>(batch, n, in.nmax, in, S, fill, threshold, stop_size, nullptr, nullptr, nullptr, od, cab2, dem2, cnt);
     launch_pos_assign(batch, n, nsol, in, cab2, dem2, cnt, S, fill, threshold, (int32_t *)o[7].dptr(), (int64_t *)o[8].dptr(),
                       (int64_t *)o[9].dptr(), (int *)((char *)g_out.p + err_off));
     return outputs_finish("td_tick_batched", o, 10, err_off);
@@ -1409,50 +1553,19 @@ int td_split_batched(int batch, int n, const int32_t *cab_off, const int32_t *ca
     if (R >= SPLIT_RMAX) return fail(TD_EINTERNAL, "%s: %d ranges", fn, R);   // parts <= 32 gives at most 63
     if ((int64_t)batch * R > INT_MAX / 2) return fail(TD_EINVAL, "%s: %d cases of %d ranges are more than 2^30 region models", fn, batch, R);
     const size_t B = (size_t)batch, M = B * (size_t)R, nc = (size_t)g_off[0][batch], nd = (size_t)g_off[1][batch];
-    // workspace: the int64 arrays first, every array 256-byte aligned
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-        const size_t o = at;
-        at += align256(bytes);
-        return o;
-    };
-    const size_t o_tot1 = take(8 * M), o_dual1 = take(8 * M), o_tot2 = take(8 * B), o_dual2 = take(8 * B), o_sum0 = take(8 * B),
-                 o_gap0 = take(8 * B), o_roffc = take(4 * (M + 1)), o_roffd = take(4 * (M + 1)), o_rcnt = take(8 * M),
-                 o_scab = take(4 * nc), o_scabi = take(4 * nc), o_sdem = take(4 * nd), o_sdemi = take(4 * nd),
-                 o_r2c1 = take(4 * M * (size_t)nl), o_wsreq = take(4 * nc), o_rcab = take(4 * nc), o_rcabi = take(4 * nc),
-                 o_rdem = take(4 * nd), o_rdemi = take(4 * nd), o_cnt2 = take(8 * B), o_nrest = take(8 * B),
-                 o_r2c2 = take(4 * B * (size_t)nl);
-    if ((rc = ensure(g_sp, at + 256))) return rc;
-    char *w = (char *)g_sp.p;
-    int64_t *tot1 = (int64_t *)(w + o_tot1), *dual1 = (int64_t *)(w + o_dual1), *tot2 = (int64_t *)(w + o_tot2),
-            *dual2 = (int64_t *)(w + o_dual2), *sum0 = (int64_t *)(w + o_sum0), *gap0 = (int64_t *)(w + o_gap0);
-    int32_t *roff_c = (int32_t *)(w + o_roffc), *roff_d = (int32_t *)(w + o_roffd), *rcnt = (int32_t *)(w + o_rcnt),
-            *scab = (int32_t *)(w + o_scab), *scab_idx = (int32_t *)(w + o_scabi), *sdem = (int32_t *)(w + o_sdem),
-            *sdem_idx = (int32_t *)(w + o_sdemi), *r2c1 = (int32_t *)(w + o_r2c1), *ws_req = (int32_t *)(w + o_wsreq),
-            *rcab = (int32_t *)(w + o_rcab), *rcab_idx = (int32_t *)(w + o_rcabi), *rdem = (int32_t *)(w + o_rdem),
-            *rdem_idx = (int32_t *)(w + o_rdemi), *cnt2 = (int32_t *)(w + o_cnt2), *nrest = (int32_t *)(w + o_nrest),
-            *r2c2 = (int32_t *)(w + o_r2c2);
+    SplitWs w;
+    if ((rc = split_ws(B, M, (size_t)nl, nc, nd, &w))) return rc;
     Out o[6] = {{cab_req, sizeof(int32_t) * nc},   {cab_stage, sizeof(int32_t) * nc}, {total, sizeof(int64_t) * B},
                 {rest_total, sizeof(int64_t) * B}, {n_rest, sizeof(int32_t) * 2 * B}, {dual_gap, sizeof(int64_t) * B}};
     size_t err_off;
     if ((rc = outputs_prepare(o, 6, &err_off))) return rc;
     int *d_err = (int *)((char *)g_out.p + err_off);
     Ctx &c = ctx();
-    const int T = nl <= 64 ? 64 : 256, grid = std::min(batch, SPLIT_GRID);
-    k_split_part<<<grid, T, 0, c.stream>>>(batch, R, ss, size, in.cab_off, in.cab, in.dem_off, in.dem, in.dist, S, fill, roff_c, roff_d,
-                                           rcnt, scab, scab_idx, sdem, sdem_idx, cnt2, d_err);
-    PosIn rin = in;
-    rin.cab_off = roff_c;
-    rin.dem_off = roff_d;
-    launch_pos_assign((int)M, nl, nl, rin, scab, sdem, rcnt, S, fill, -1, r2c1, tot1, dual1, d_err);
-    k_split_rest<<<grid, T, 0, c.stream>>>(batch, R, nl, in.cab_off, in.cab, in.dem_off, in.dem, in.dist, S, fill, roff_c, roff_d, rcnt,
-                                           scab, scab_idx, sdem, sdem_idx, r2c1, tot1, dual1, ws_req, rcab, rcab_idx, rdem, rdem_idx,
-                                           cnt2, nrest, sum0, gap0, d_err);
-    launch_pos_assign(batch, nl, nl, in, rcab, rdem, cnt2, S, fill, -1, r2c2, tot2, dual2, d_err);
-    k_split_final<<<grid, T, 0, c.stream>>>(batch, nl, in.cab_off, in.dem_off, in.dist, S, ws_req, rcab, rcab_idx, rdem, rdem_idx, cnt2,
-                                            nrest, sum0, gap0, r2c2, tot2, dual2, (int32_t *)o[0].dptr(), (int32_t *)o[1].dptr(),
-                                            (int64_t *)o[2].dptr(), (int64_t *)o[3].dptr(), (int32_t *)o[4].dptr(),
-                                            (int64_t *)o[5].dptr(), d_err);
+    split_launches(batch, R, ss, size, nl, in, S, fill, -1, nullptr, nullptr, w, d_err);
+    k_split_final<<<std::min(batch, SPLIT_GRID), nl <= 64 ? 64 : 256, 0, c.stream>>>(
+        batch, nl, -1, SplitDisp{}, in.cab_off, in.dem_off, in.dist, S, w.ws_req, w.rcab, w.rcab_idx, w.rdem, w.rdem_idx, w.cnt2, w.nrest,
+        w.sum0, w.gap0, w.r2c2, w.tot2, w.dual2, (int32_t *)o[0].dptr(), (int32_t *)o[1].dptr(), (int64_t *)o[2].dptr(),
+        (int64_t *)o[3].dptr(), (int32_t *)o[4].dptr(), (int64_t *)o[5].dptr(), d_err);
     TD_HIP(hipGetLastError());
     // host destinations: through g_sp_host (same layout as g_out), handed over only when the call succeeded
     g_sp_host.resize(err_off);
@@ -1462,12 +1575,132 @@ int td_split_batched(int batch, int n, const int32_t *cab_off, const int32_t *ca
     TD_HIP(hipMemcpyAsync(c.pinned, d_err, sizeof(int), hipMemcpyDeviceToHost, c.stream));
     TD_HIP(hipStreamSynchronize(c.stream));
     const int e = *(int *)c.pinned;
-    if (e & ERR_POS) return fail(TD_EINVAL, "%s: a cab_to / dem_from position outside [0, %d)", fn, size);
-    if (e & ERR_CELL) return fail(TD_EINVAL, "%s: a table entry used as a cell is outside [0, fill = %d)", fn, (int)fill);
-    if (e)
-        return fail(TD_EINTERNAL, "%s: a model hit a defensive loop cap (error word 0x%x: 1 search steps, 2 augmenting path, "
-                    "4 label range, 8 model size)", fn, e);
+    if ((rc = split_error(fn, e, size, fill))) return rc;
     for (int i = 0; i < 6; i++)
+        if (o[i].user && !o[i].dev && o[i].bytes) memcpy(o[i].user, g_sp_host.data() + o[i].off, o[i].bytes);
+    return TD_OK;
+}
+
+// A policy per model, structured as td_pool2_batched_v is: the tick's two launches take every model that is not a split model
+// (a split model is not theirs), the split's launches take the split models (every other case is empty for them) and run
+// only when there is one: 2 launches without a split model, 7 with one, whatever the batch and the mix.  The split launches
+// come first, so that an input they refuse on the device (a position, a table entry) stops the tick's launches before they
+// write an output.
+int td_dispatch_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab_to, const int32_t *dem_off, const int32_t *dem_from,
+                        const int32_t *dist, int S, int32_t fill, int32_t threshold, int size, const int32_t *mode,
+                        const int32_t *stop_size, const int32_t *parts, int32_t *lcm_rows, int32_t *lcm_cols, int32_t *n_pairs,
+                        int32_t *lcm_last_min, int32_t *kept_cabs, int32_t *kept_dems, int32_t *n_rest, int32_t *row_to_col,
+                        int64_t *total, int64_t *dual_bound)
+{
+    TD_REQUIRE_INIT();
+    const char *fn = "td_dispatch_batched";
+    PosIn in;
+    int rc = pos_args(fn, batch, n, TICK_NMAX, cab_off, cab_to, dem_off, dem_from, dist, S, &in);
+    if (rc) return rc;
+    if (batch == 0) return TD_OK;
+    if (!lcm_rows || !lcm_cols || !n_pairs || !lcm_last_min || !n_rest || !row_to_col || !total)
+        return fail(TD_EINVAL, "%s: null output array", fn);
+    Ctx &c = ctx();
+    const size_t B = (size_t)batch;
+    // the policy arrays on the host (validated there) and on the device
+    const int32_t *pol[3] = {mode, stop_size, parts}, *d_pol[3] = {nullptr, nullptr, nullptr};
+    bool from_device = false;   // the device arrays come home in one synchronisation
+    for (int k = 0; k < 3; k++) {
+        if (!pol[k]) continue;
+        std::vector<int32_t> &h = g_polh[k];
+        h.resize(B);
+        if (is_device_ptr(pol[k])) {
+            TD_HIP(hipMemcpyAsync(h.data(), pol[k], sizeof(int32_t) * B, hipMemcpyDeviceToHost, c.stream));
+            from_device = true;
+        } else {
+            memcpy(h.data(), pol[k], sizeof(int32_t) * B);
+        }
+    }
+    if (from_device) TD_HIP(hipStreamSynchronize(c.stream));
+    int nsol = 0, nsplit = 0, nl_split = 0, R = 1;
+    for (int b = 0; b < batch; b++) {
+        const int md = mode ? g_polh[0][b] : TD_DISPATCH_LCM_OPT;
+        const int ns = g_off[0][b + 1] - g_off[0][b], nd = g_off[1][b + 1] - g_off[1][b], nb = std::max(ns, nd);
+        if (md < TD_DISPATCH_LCM_OPT || md > TD_DISPATCH_SPLIT) return fail(TD_EINVAL, "%s: mode[%d] = %d outside 0 .. 3", fn, b, md);
+        if (md == TD_DISPATCH_SPLIT) {
+            const int p = parts ? g_polh[2][b] : 4;
+            if (nb > BATCH_NMAX)
+                return fail(TD_EINVAL, "%s: split model %d has %d cabs and %d requests, more than %d", fn, b, ns, nd, BATCH_NMAX);
+            if (p < 1 || p > 32) return fail(TD_EINVAL, "%s: parts[%d] = %d outside [1, 32]", fn, b, p);
+            if (size < p) return fail(TD_EINVAL, "%s: size = %d < parts[%d] = %d", fn, size, b, p);
+            const int ss = size / p;
+            R = std::max(R, (size + ss - 1) / ss);
+            nl_split = std::max(nl_split, nb);
+            nsplit++;
+        } else if (md != TD_DISPATCH_LCM) {
+            // the remainder that goes to the solver: stop_size rows where the LCM runs, the whole model where it does not
+            const int st = md == TD_DISPATCH_OPT || !stop_size ? -1 : g_polh[1][b];
+            const int rest = st >= 0 && st < nb ? st : nb;
+            if (rest > BATCH_NMAX)
+                return fail(TD_EINVAL, "%s: model %d leaves %d rows to the solver, more than %d (stop_size = %d)", fn, b, rest, BATCH_NMAX, st);
+            nsol = std::max(nsol, rest);
+        }
+    }
+    if (nsplit) {
+        if (dist && S < size) return fail(TD_EINVAL, "%s: the table has S = %d stands, fewer than size = %d", fn, S, size);
+        if (dist && fill < 1) return fail(TD_EINVAL, "%s: fill = %d < 1", fn, (int)fill);
+        if (!dist && (int64_t)size - 1 >= (int64_t)fill)
+            return fail(TD_EINVAL, "%s: the distance %d of the line's ends is not below fill = %d", fn, size - 1, (int)fill);
+        if (R >= SPLIT_RMAX) return fail(TD_EINTERNAL, "%s: %d ranges", fn, R);   // parts <= 32 gives at most 63
+        if ((int64_t)batch * R > INT_MAX / 2)
+            return fail(TD_EINVAL, "%s: %d cases of %d ranges are more than 2^30 region models", fn, batch, R);
+    }
+    const void *p;
+    for (int k = 0; k < 3; k++) {
+        if (!pol[k]) continue;
+        if ((rc = to_device(is_device_ptr(pol[k]) ? (const void *)pol[k] : (const void *)g_polh[k].data(), sizeof(int32_t) * B, g_pol[k], &p)))
+            return rc;
+        d_pol[k] = (const int32_t *)p;
+    }
+    const size_t N = (size_t)n, nc = (size_t)g_off[0][batch], nd = (size_t)g_off[1][batch];
+    if ((rc = ensure(g_ws, sizeof(int32_t) * (nc + nd + 2 * B)))) return rc;
+    int32_t *cab2 = (int32_t *)g_ws.p, *dem2 = cab2 + nc, *cnt = dem2 + nd;
+    SplitWs w{};
+    if (nsplit && (rc = split_ws(B, B * (size_t)R, (size_t)nl_split, nc, nd, &w))) return rc;
+    Out o[10] = {{lcm_rows, sizeof(int32_t) * B * N}, {lcm_cols, sizeof(int32_t) * B * N}, {n_pairs, sizeof(int32_t) * B},
+                 {lcm_last_min, sizeof(int32_t) * B},  {kept_cabs, sizeof(int32_t) * B * N}, {kept_dems, sizeof(int32_t) * B * N},
+                 {n_rest, sizeof(int32_t) * B},       {row_to_col, sizeof(int32_t) * B * N}, {total, sizeof(int64_t) * B},
+                 {dual_bound, sizeof(int64_t) * B}};
+    size_t err_off;
+    if ((rc = outputs_prepare(o, 10, &err_off))) return rc;
+    int *d_err = (int *)((char *)g_out.p + err_off);
+    void *od[7];
+    for (int k = 0; k < 7; k++) od[k] = o[k].dptr();
+    // the range width of a case without a parts entry: 4 parts (parts == NULL), or any width for a case that is not split
+    if (nsplit) split_launches(batch, R, parts ? size : size / 4, size, nl_split, in, S, fill, threshold, d_pol[0], d_pol[2], w, d_err);
+    const int *gate = nsplit ? d_err : nullptr;
+    if (in.nmax <= 128)
+        launch_tick_lcm_t<64, true>(batch, n, in.nmax, in, S, fill, threshold, -1, d_pol[0], d_pol[1], gate, od, cab2, dem2, cnt);
+    else
+        launch_tick_lcm_t<256, true>(batch, n, in.nmax, in, S, fill, threshold, -1, d_pol[0], d_pol[1], gate, od, cab2, dem2, cnt);
+    launch_pos_assign(batch, n, nsol, in, cab2, dem2, cnt, S, fill, threshold, (int32_t *)o[7].dptr(), (int64_t *)o[8].dptr(),
+                      (int64_t *)o[9].dptr(), d_err);
+    if (nsplit) {
+        const SplitDisp dp{d_pol[0],          n,
+                           fill,              (int32_t *)od[2],
+                           (int32_t *)od[3],  (int32_t *)od[4],
+                           (int32_t *)od[5],  (int32_t *)od[6],
+                           (int32_t *)o[7].dptr(), (int64_t *)o[8].dptr(),
+                           (int64_t *)o[9].dptr()};
+        k_split_final<<<std::min(batch, SPLIT_GRID), nl_split <= 64 ? 64 : 256, 0, c.stream>>>(
+            batch, nl_split, threshold, dp, in.cab_off, in.dem_off, in.dist, S, w.ws_req, w.rcab, w.rcab_idx, w.rdem, w.rdem_idx, w.cnt2,
+            w.nrest, w.sum0, w.gap0, w.r2c2, w.tot2, w.dual2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_err);
+    }
+    TD_HIP(hipGetLastError());
+    // host destinations: through g_sp_host (same layout as g_out), handed over only when the call succeeded
+    g_sp_host.resize(err_off);
+    for (int i = 0; i < 10; i++)
+        if (o[i].user && !o[i].dev && o[i].bytes)
+            TD_HIP(hipMemcpyAsync(g_sp_host.data() + o[i].off, (char *)g_out.p + o[i].off, o[i].bytes, hipMemcpyDeviceToHost, c.stream));
+    TD_HIP(hipMemcpyAsync(c.pinned, d_err, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    TD_HIP(hipStreamSynchronize(c.stream));
+    if ((rc = split_error(fn, *(int *)c.pinned, size, fill))) return rc;
+    for (int i = 0; i < 10; i++)
         if (o[i].user && !o[i].dev && o[i].bytes) memcpy(o[i].user, g_sp_host.data() + o[i].off, o[i].bytes);
     return TD_OK;
 }
@@ -1476,6 +1709,6 @@ int td_split_batched(int batch, int n, const int32_t *cab_off, const int32_t *ca
 
 void td::batch_release_workspace()
 {
-    Buf *bs[] = {&g_out, &g_ws, &g_sp, &g_in[0], &g_in[1], &g_in[2], &g_in[3], &g_in[4]};
+    Buf *bs[] = {&g_out, &g_ws, &g_sp, &g_in[0], &g_in[1], &g_in[2], &g_in[3], &g_in[4], &g_pol[0], &g_pol[1], &g_pol[2]};
     for (Buf *b : bs) buf_free(*b);
 }

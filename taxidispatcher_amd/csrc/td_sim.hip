@@ -95,6 +95,12 @@ struct td_sim {
     int n_pooled = 0;            // the customers findPool looked at in this tick: the demand, or 0 where it did not run
     int pool_mode = TD_POOL_GREEDY;   // td_sim_pooling: the policy from the next begin on
     double max_loss = 0.0;            // <= 0: every ordered pair is a candidate
+    // td_sim_dispatch: the dispatch method from the next begin on.  The world kernels take the LCM rule as one number
+    // ("the LCM ran when the model is larger than it"), so a policy is that number: lcm_rule() below.
+    int disp_mode = TD_DISPATCH_LCM_OPT, disp_parts = 4;
+    // the model size above which the LCM ran in this world: its max_non_lcm; -1 where it always runs (with supply a model has
+    // at least one row); INT_MAX where it never does
+    int lcm_rule() const { return disp_mode == TD_DISPATCH_LCM_OPT ? max_non_lcm : disp_mode == TD_DISPATCH_LCM ? -1 : INT_MAX; }
     EvLog ev;                    // td_sim_log
     // the host side of Simulator.m
     int64_t lcm_used = 0, max_model = 0, max_solver = 0, max_pool_mem = 0, max_pool = 0;
@@ -206,7 +212,7 @@ int sim_ev_flush(td_sim *s, int phase)
     const World &w = s->w;
     const EvLog &e = s->ev;
     const Seg1 cabs{w.n_cabs, nullptr}, reqs{w.n_req, nullptr}, dem{s->n_dem, nullptr}, sup{s->n_sup, nullptr}, d2{s->n_dem2, nullptr};
-    const EvSrc<Seg1, Plans1> src{w, cabs, reqs, dem, sup, d2, Plans1{s->n_pool, s->n_pooled}, s->max_non_lcm, s->last_t, phase, e.kinds,
+    const EvSrc<Seg1, Plans1> src{w, cabs, reqs, dem, sup, d2, Plans1{s->n_pool, s->n_pooled}, LcmRule1{s->lcm_rule()}, s->last_t, phase, e.kinds,
                                   e.st_arr, e.st_drop, e.st_pairs, e.st_sol, s->dem_idx, s->pl_a, s->pl_b};
     const size_t vmax = (size_t)w.n_cabs + w.n_req + 2 + s->n_dem + s->n_pool + 2 * ((size_t)s->n_sup + s->n_dem2) + 2 * (size_t)s->n_sup;
     return ev_flush(s->ev, src, 1, vmax);
@@ -316,16 +322,18 @@ int sim_apply(td_sim *s, int n_pairs, const int32_t *rows, const int32_t *cols, 
 {
     Ctx &c = ctx();
     const World &w = s->w;
-    const int t = s->last_t, n_s = s->n_sup, n_d = s->n_dem2, n = std::max(n_s, n_d), mnl = s->max_non_lcm;
+    const int t = s->last_t, n_s = s->n_sup, n_d = s->n_dem2, n = std::max(n_s, n_d);
+    const LcmRule1 mnl{s->lcm_rule()};
     int rc;
     *opt_count = 0;
+    if (s->disp_mode == TD_DISPATCH_LCM) solved = 0;   // the LCM alone: never a solution, whatever the caller says
     if (n_s == 0) {   // no supply: analyzeSolution walks an empty list, the line ends in "; OPT count=0"
         s->begun = false;
         return sim_ev_tick_done(s);
     }
     const bool log = s->ev.kinds != 0;
     if (log && (rc = ev_clear_apply(s->ev, (size_t)n_s, (size_t)n_d))) return rc;
-    const bool lcm = n > mnl;
+    const bool lcm = n > mnl.v;
     if (lcm && !solved) *opt_count = -1;
     const int nr = solved ? n_r2c : 0;
     const Dec1 dec{s->in_rows, s->in_cols, s->in_r2c, n_pairs, nr, solved};
@@ -572,6 +580,21 @@ extern "C" int td_sim_pooling(td_sim *s, int mode, double max_loss)
     return TD_OK;
 }
 
+extern "C" int td_sim_dispatch(td_sim *s, int mode, int max_non_lcm, int parts)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (mode < TD_DISPATCH_LCM_OPT || mode > TD_DISPATCH_SPLIT) return fail(TD_EINVAL, "td_sim_dispatch: mode = %d outside 0 .. 3", mode);
+    if (max_non_lcm < 0) return fail(TD_EINVAL, "td_sim_dispatch: max_non_lcm = %d is negative", max_non_lcm);
+    if (mode == TD_DISPATCH_SPLIT && (parts < 1 || parts > 32 || parts > s->w.n_stands))
+        return fail(TD_EINVAL, "td_sim_dispatch: parts = %d outside 1 .. min(32, n_stands = %d)", parts, s->w.n_stands);
+    if (s->begun) return fail(TD_EINVAL, "td_sim_dispatch: tick %d still waits for td_sim_apply", s->last_t);
+    s->disp_mode = mode;
+    s->max_non_lcm = max_non_lcm;
+    if (mode == TD_DISPATCH_SPLIT) s->disp_parts = parts;
+    return TD_OK;
+}
+
 extern "C" int td_sim_pools(td_sim *s, int max_pools, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n)
 {
     TD_REQUIRE_INIT();
@@ -630,13 +653,29 @@ extern "C" int td_sim_step(td_sim *s, int t, int32_t line[9])
     int32_t k = 0, lm = 0, n_rest = 0, opt = 0;
     int64_t total = 0;
     int solved = 0;
-    if (n_s > 0) {
-        // the arguments HipTickBackend.tick hands td_tick, with the position lists (and the table) where they already are
-        if ((rc = td_tick(s->sup_to, n_s, s->d2_from, n_d, s->dist, s->dist ? s->w.n_stands : 0, s->w.big_cost, s->w.drop_time, s->max_non_lcm, s->h_rows, s->h_cols, &k, &lm,
+    if (n_s > 0 && s->disp_mode == TD_DISPATCH_SPLIT) {
+        // the batched call's device code on this one model: the lists stay where they are, the offsets are two host words
+        if (n > 1024)
+            return fail(TD_EINVAL,
+                        "td_sim_step: the split model of tick %d has %d cabs and %d requests, more than 1024 per side; finish the tick through "
+                        "td_sim_model / td_sim_apply", t, n_s, n_d);
+        const int32_t c_off[2] = {0, n_s}, d_off[2] = {0, n_d}, mode = TD_DISPATCH_SPLIT, parts = s->disp_parts;
+        if ((rc = td_dispatch_batched(1, n, c_off, s->sup_to, d_off, s->d2_from, s->dist, s->dist ? s->w.n_stands : 0, s->w.big_cost, s->w.drop_time,
+                                      s->w.n_stands, &mode, nullptr, &parts, s->h_rows, s->h_cols, &k, &lm, s->h_kc, s->h_kd, &n_rest, s->h_r2c,
+                                      &total, nullptr)))
+            return rc;
+        solved = 1;   // row_to_col is over the whole model: the request of each cab
+        line[6] = n_d;
+        line[7] = n_s;
+    } else if (n_s > 0) {
+        // the arguments HipTickBackend.tick hands td_tick, with the position lists (and the table) where they already are; the stop
+        // size is the policy's: the world's max_non_lcm, -1 (the optimum alone: the LCM never runs) or 0 (the LCM alone, to its end)
+        const int stop = s->disp_mode == TD_DISPATCH_OPT ? -1 : s->disp_mode == TD_DISPATCH_LCM ? 0 : s->max_non_lcm;
+        if ((rc = td_tick(s->sup_to, n_s, s->d2_from, n_d, s->dist, s->dist ? s->w.n_stands : 0, s->w.big_cost, s->w.drop_time, stop, s->h_rows, s->h_cols, &k, &lm,
                           s->h_kc, s->h_kd, &n_rest, s->h_r2c, &total)))
             return rc;
-        const bool lcm = s->max_non_lcm < n;
-        solved = n_rest > 0 && !(lcm && lm == s->w.big_cost);
+        const bool lcm = s->lcm_rule() < n;
+        solved = s->disp_mode != TD_DISPATCH_LCM && n_rest > 0 && !(lcm && lm == s->w.big_cost);
         line[3] = lcm;
         line[4] = lcm ? k : 0;
         line[5] = lcm && solved;

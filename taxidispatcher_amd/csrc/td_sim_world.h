@@ -103,6 +103,17 @@ __device__ __forceinline__ int block_err(const int32_t *gerr)
 
 // does world b's model go through the LCM (analyzePairs)?  Without supply there is no model at all.
 __device__ __forceinline__ bool world_lcm(int n_s, int n_d, int max_non_lcm) { return n_s > 0 && (n_s > n_d ? n_s : n_d) > max_non_lcm; }
+// the model size above which the LCM ran in world b, as the kernels below take it (`max_non_lcm(b)`): one number for every
+// world of the launch (a td_sim world, a td_simb handle without td_simb_dispatch), or a number per world (td_simb_dispatch:
+// the world's own max_non_lcm; -1 where the LCM always runs, a model with supply has a row; INT_MAX where it never does)
+struct LcmRule1 {
+    int v;
+    __device__ __forceinline__ int operator()(int) const { return v; }
+};
+struct LcmRuleB {
+    const int32_t *v;
+    __device__ __forceinline__ int operator()(int b) const { return v[b]; }
+};
 
 // the segments of a list behind an offset array [B + 1]
 struct SegOff {
@@ -272,17 +283,17 @@ struct PoolEmit {
     }
 };
 // the cabs / requests of an LCM world that are in no pair (analyzePairs' supply2 / demand2)
-template <class S>
+template <class S, class L = LcmRule1>
 struct KeptPred {
     const int32_t *pair_of;
     S sup, d2;
-    int max_non_lcm;
+    L max_non_lcm;
     __device__ bool operator()(int i, int b) const
     {
         int s0, n_s, d0, n_d;
         sup(b, &s0, &n_s);
         d2(b, &d0, &n_d);
-        return world_lcm(n_s, n_d, max_non_lcm) && pair_of[i] == NONE;
+        return world_lcm(n_s, n_d, max_non_lcm(b)) && pair_of[i] == NONE;
     }
 };
 struct KeptSupEmit {
@@ -367,15 +378,15 @@ __global__ __launch_bounds__(256) void k_pool_mark(PL pl, S dem, const int32_t *
 }
 
 // by_cab / by_clnt of analyzePairs (Simulator.java:613-674) in every LCM world: the FIRST pair of a cab / of a request
-template <class D, class S>
-__global__ __launch_bounds__(256) void k_pair_map(D dec, int max_non_lcm, S sup, S d2, int32_t *__restrict__ pair_cab,
+template <class D, class S, class L>
+__global__ __launch_bounds__(256) void k_pair_map(D dec, L max_non_lcm, S sup, S d2, int32_t *__restrict__ pair_cab,
                                                   int32_t *__restrict__ pair_dem, int32_t *gerr)
 {
     const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
     int s0, n_s, d0, n_d;
     sup(b, &s0, &n_s);
     d2(b, &d0, &n_d);
-    if (!world_lcm(n_s, n_d, max_non_lcm)) return;
+    if (!world_lcm(n_s, n_d, max_non_lcm(b))) return;
     int base, cnt;
     dec.pairs(b, &base, &cnt);
     if (p >= cnt) return;
@@ -393,8 +404,8 @@ __global__ __launch_bounds__(256) void k_pair_map(D dec, int max_non_lcm, S sup,
 // request stores is world-local: cab minus where the world's fleet begins.
 // ev: EvOff, or EvOn on the pairs stage (cleared by the host before the launch): thread l of world b owns slots
 // 2 (s0 + d0 + l) and + 1, so the cab loop's records precede the request loop's and :654 precedes the same request's :432.
-template <class D, class S, class EV>
-__global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, int max_non_lcm, S cabs, S sup, S d2,
+template <class D, class S, class EV, class L>
+__global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, L max_non_lcm, S cabs, S sup, S d2,
                                                     const int32_t *__restrict__ pair_cab, const int32_t *__restrict__ pair_dem,
                                                     const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
                                                     const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_partner,
@@ -407,7 +418,7 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, int m
     cabs(b, &c0, &n_c);
     sup(b, &s0, &n_s);
     d2(b, &d0, &n_d);
-    if (!world_lcm(n_s, n_d, max_non_lcm) || (int)blockIdx.x * CB >= n_s + n_d) return;
+    if (!world_lcm(n_s, n_d, max_non_lcm(b)) || (int)blockIdx.x * CB >= n_s + n_d) return;
     int base, cnt;
     dec.pairs(b, &base, &cnt);
     const int l = blockIdx.x * CB + threadIdx.x;
@@ -447,8 +458,8 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, int m
 // cabs and the lists are copies), so that test is not repeated.
 // ev: EvOff, or EvOn on the solution stage (cleared by the host before the launch): cab l of world b's model owns slots
 // 2 (s0 + l) and + 1 with s0 = where the world's SUPPLY list begins (a kept list is no longer): :432 first, then :448 / :486.
-template <class D, class S, class EV>
-__global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, int max_non_lcm, S cabs, S sup, S d2, S ks, S kd,
+template <class D, class S, class EV, class L>
+__global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, L max_non_lcm, S cabs, S sup, S d2, S ks, S kd,
                                                        const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
                                                        const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_from,
                                                        const int32_t *__restrict__ d_partner, const int32_t *__restrict__ d_plan,
@@ -466,7 +477,7 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, in
     sup(b, &s0, &n_s);
     d2(b, &d0, &n_d);
     if (n_s == 0 || (int)blockIdx.x * CB >= n_s) return;
-    const bool lcm = world_lcm(n_s, n_d, max_non_lcm);
+    const bool lcm = world_lcm(n_s, n_d, max_non_lcm(b));
     int rb, nr;
     bool solved;
     dec.r2c_of(b, lcm, w.big_cost, &rb, &nr, &solved);
@@ -520,12 +531,13 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, in
 //   C  1        the tempDemand header                 G  2 (ns+nd)  the pairs stage (k_apply_pairs), LCM worlds
 //   D  n_dem    the demand list before pooling        H  2 ns       the solution stage (k_apply_solution)
 // C .. F are not staged: they are read from the lists where they lie.  phase bit 0 = A .. F (td_*_begin's), bit 1 = G, H.
-template <class S, class PL>
+template <class S, class PL, class L = LcmRule1>
 struct EvSrc {
     World w;
     S cabs, reqs, dem, sup, d2;
     PL pl;
-    int max_non_lcm, t, phase;
+    L max_non_lcm;
+    int t, phase;
     uint32_t kinds;
     const int4 *st_arr, *st_drop, *st_pairs, *st_sol;
     const int32_t *dem_idx, *pl_a, *pl_b;
@@ -543,7 +555,7 @@ struct EvSrc {
         int np = 0;   // plans: never more than the pooled customers allow, whatever the count word says
         if (found) np = min(max(pl.count(b), 0), pl.n_act(b) / 2);
         const int nA = p1 ? nc : 0, nB = p1 ? nr : 0, nC = p1 ? 1 : 0, nD = p1 ? ne : 0, nE = p1 && found ? 1 : 0, nF = p1 ? np : 0;
-        const int nG = p2 && ne > 0 && world_lcm(ns, nd, max_non_lcm) ? 2 * (ns + nd) : 0, nH = p2 && pooled ? 2 * ns : 0;
+        const int nG = p2 && ne > 0 && world_lcm(ns, nd, max_non_lcm(b)) ? 2 * (ns + nd) : 0, nH = p2 && pooled ? 2 * ns : 0;
         int4 r = make_int4(0, -1, -1, -1);
         int u = v;
         if (u < nA) {

@@ -58,6 +58,7 @@ struct SimbDec {
     const int32_t *pair_off, *r2c_off, *solved;
     const int32_t *n_pairs, *n_rest, *last_min;
     int stride;
+    const int32_t *rule;   // td_simb_dispatch's per-world LCM rule (null without one): -1 = the LCM alone, a world that is never solved
     __device__ __forceinline__ void pairs(int b, int *base, int *cnt) const
     {
         if (stride) {
@@ -73,11 +74,11 @@ struct SimbDec {
     {
         if (stride) {
             *base = b * stride;
-            *sol = n_rest[b] > 0 && !(lcm && last_min[b] == big_cost);
+            *sol = n_rest[b] > 0 && !(lcm && last_min[b] == big_cost) && !(rule && rule[b] < 0);
             *nr = *sol ? n_rest[b] : 0;
         } else {
             *base = r2c_off[b];
-            *sol = solved[b] != 0;
+            *sol = solved[b] != 0 && !(rule && rule[b] < 0);
             *nr = *sol ? r2c_off[b + 1] - *base : 0;
         }
     }
@@ -143,7 +144,26 @@ struct td_simb {
     std::vector<double> pool_ml;
     int32_t *d_none = nullptr;                  // device [B]: 1 = the world is left out of the pool lists (read only when has_none)
     std::vector<int32_t> h_npool, h_pbase;      // this tick's plans per world and where they begin in pa / pb / pp / pc
+    // td_simb_dispatch: the dispatch policy of every world from the next begin on.  disp_set == false: the handle dispatches as it
+    // always did, through td_tick_batched and the one-number instantiations of the world kernels
+    bool disp_set = false;
+    std::vector<int32_t> disp_mode, disp_mnl, disp_parts;   // host mirrors: what td_dispatch_batched is handed
+    int32_t *d_rule = nullptr;                              // device [B]: rule(b), read by the world kernels when disp_set
+    // the model size above which the LCM ran in world b (LcmRuleB of td_sim_world.h)
+    int rule(int b) const
+    {
+        if (!disp_set) return max_non_lcm;
+        return disp_mode[b] == TD_DISPATCH_LCM_OPT ? disp_mnl[b] : disp_mode[b] == TD_DISPATCH_LCM ? -1 : INT_MAX;
+    }
+    bool lcm_alone(int b) const { return disp_set && disp_mode[b] == TD_DISPATCH_LCM; }
 };
+
+// f(the LCM rule as the world kernels take it): one number for a handle without td_simb_dispatch, else a number per world
+template <class F>
+static auto with_rule(const td_simb *s, F f)
+{
+    return s->disp_set ? f(LcmRuleB{s->d_rule}) : f(LcmRule1{s->max_non_lcm});
+}
 
 namespace {
 
@@ -250,15 +270,18 @@ int clear_err(td_simb *s)
 int simb_ev_flush(td_simb *s, int phase)
 {
     const EvLog &e = s->ev;
-    const EvSrc<SegOff, SimbPlans> src{s->w, SegOff{s->d_cab_off}, SegOff{s->d_req_off}, SegOff{s->dem_off}, SegOff{s->sup_off}, SegOff{s->d2_off},
-                                       SimbPlans{s->pool_h, s->pool_ragged, s->pl_off, s->n_pools}, s->max_non_lcm, s->last_t, phase, e.kinds,
-                                       e.st_arr, e.st_drop, e.st_pairs, e.st_sol, s->dem_idx, s->pa, s->pb};
     size_t vmax = 0;
     for (int b = 0; b < s->B; b++) {
         const size_t nc = (size_t)(s->cab_off[b + 1] - s->cab_off[b]), nr = (size_t)(s->req_off[b + 1] - s->req_off[b]), ns = (size_t)s->n_sup[b];
         vmax = std::max(vmax, nc + nr + 2 + s->n_dem[b] + s->n_dem[b] / 2 + 2 * (ns + s->n_d2[b]) + 2 * ns);
     }
-    return ev_flush(s->ev, src, s->B, vmax);
+    return with_rule(s, [&](auto rule) {
+        const EvSrc<SegOff, SimbPlans, decltype(rule)> src{s->w, SegOff{s->d_cab_off}, SegOff{s->d_req_off}, SegOff{s->dem_off}, SegOff{s->sup_off},
+                                                           SegOff{s->d2_off}, SimbPlans{s->pool_h, s->pool_ragged, s->pl_off, s->n_pools}, rule,
+                                                           s->last_t, phase, e.kinds, e.st_arr, e.st_drop, e.st_pairs, e.st_sol, s->dem_idx, s->pa,
+                                                           s->pb};
+        return ev_flush(s->ev, src, s->B, vmax);
+    });
 }
 
 // a tick is over (no world has anything to apply, or applied): what the log has not seen of it goes there
@@ -420,7 +443,7 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
 {
     Ctx &c = ctx();
     const World &w = s->w;
-    const int B = s->B, t = s->last_t, mnl = s->max_non_lcm;
+    const int B = s->B, t = s->last_t;
     int rc;
     int max_s = 0, max_d = 0, max_sd = 0;
     bool any_lcm = false, any_sup = false;
@@ -429,7 +452,7 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
         if (n_s == 0) continue;
         any_sup = true;
         max_s = std::max(max_s, n_s);
-        if (std::max(n_s, n_d) > mnl) {
+        if (std::max(n_s, n_d) > s->rule(b)) {
             any_lcm = true;
             max_d = std::max(max_d, n_d);
             max_sd = std::max(max_sd, n_s + n_d);
@@ -439,6 +462,8 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
     const SegOff cabs{s->d_cab_off}, sup{s->sup_off}, d2{s->d2_off};
     const bool log = s->ev.kinds != 0;
     if (log && (rc = ev_clear_apply(s->ev, (size_t)hs[B], (size_t)h2[B]))) return rc;
+    rc = with_rule(s, [&](auto mnl) -> int {
+    using L = decltype(mnl);
     if (any_lcm) {
         TD_HIP(hipMemsetAsync(s->pair_cab, 0x7f, sizeof(int32_t) * (size_t)hs[B], c.stream));
         TD_HIP(hipMemsetAsync(s->pair_dem, 0x7f, sizeof(int32_t) * (size_t)h2[B], c.stream));
@@ -453,13 +478,13 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
         else
             pairs(EvOff{});
         const dim3 grid_s(nchunks(max_s), B), grid_d(nchunks(max_d), B);
-        const KeptPred<SegOff> ps{s->pair_cab, sup, d2, mnl}, pd{s->pair_dem, sup, d2, mnl};
-        k_count<SegOff, KeptPred<SegOff>><<<grid_s, CB, 0, c.stream>>>(sup, ps, s->cnt_a);
-        k_count<SegOff, KeptPred<SegOff>><<<grid_d, CB, 0, c.stream>>>(d2, pd, s->cnt_b);
+        const KeptPred<SegOff, L> ps{s->pair_cab, sup, d2, mnl}, pd{s->pair_dem, sup, d2, mnl};
+        k_count<SegOff, KeptPred<SegOff, L>><<<grid_s, CB, 0, c.stream>>>(sup, ps, s->cnt_a);
+        k_count<SegOff, KeptPred<SegOff, L>><<<grid_d, CB, 0, c.stream>>>(d2, pd, s->cnt_b);
         k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, (int)grid_s.x, s->cnt_b, (int)grid_d.x, 0, nullptr, s->ks_off, s->kd_off, nullptr);
-        k_scatter<KeptPred<SegOff>, KeptSupEmit><<<grid_s, CB, 0, c.stream>>>(s->sup_off, ps, KeptSupEmit{s->sup_cab, s->sup_to, s->ks_cab, s->ks_to},
+        k_scatter<KeptPred<SegOff, L>, KeptSupEmit><<<grid_s, CB, 0, c.stream>>>(s->sup_off, ps, KeptSupEmit{s->sup_cab, s->sup_to, s->ks_cab, s->ks_to},
                                                                             s->cnt_a, s->ks_off, nullptr);
-        k_scatter<KeptPred<SegOff>, KeptDemEmit><<<grid_d, CB, 0, c.stream>>>(
+        k_scatter<KeptPred<SegOff, L>, KeptDemEmit><<<grid_d, CB, 0, c.stream>>>(
             s->d2_off, pd, KeptDemEmit{s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost},
             s->cnt_b, s->kd_off, nullptr);
     }
@@ -473,6 +498,9 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
         solution(EvOn{s->ev.st_sol});
     else if (any_sup)
         solution(EvOff{});
+    return TD_OK;
+    });
+    if (rc) return rc;
     TD_HIP(hipGetLastError());
     if ((rc = read_head(s))) return rc;
     const int err = *h_of(s, s->gerr);
@@ -488,8 +516,8 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
         opt_count[b] = 0;
         const int n_s = s->n_sup[b], n = std::max(n_s, s->n_d2[b]);
         if (s->n_dem[b] == 0 || n_s == 0) continue;
-        const bool lcm = n > mnl;
-        const bool solved = h_solved ? h_solved[b] != 0 : (hrest[b] > 0 && !(lcm && hlm[b] == w.big_cost));
+        const bool lcm = n > s->rule(b);
+        const bool solved = !s->lcm_alone(b) && (h_solved ? h_solved[b] != 0 : (hrest[b] > 0 && !(lcm && hlm[b] == w.big_cost)));
         if (lcm) s->lcm_used[b]++;
         if (lcm && !solved) {
             opt_count[b] = -1;
@@ -588,7 +616,7 @@ static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_
     const size_t ints = table_ints + s->head_ints + 2 * (nb + 1) + 2 * words * nb + 2 * n_cnt + 9 * nr + 5 * nc   // head, offsets, bits, counts, tables
                         + 5 * nr + 2 * nc + 6 * nr + 2 * nc + 5 * nr + 2 * nr                        // dem / pl, sup, d2 / tk, ks, kd, isb / ainfo
                         + 4 * s->pool_cap + 4 * nb + nc + nr                                         // plans, two int64 [B], pair maps
-                        + 3 * in_cap + 2 * (nb + 1) + nb + 3 * tk_cap + std::max<size_t>(max_cabs, 1) + nb + 64;   // .., tmp, d_none
+                        + 3 * in_cap + 2 * (nb + 1) + nb + 3 * tk_cap + std::max<size_t>(max_cabs, 1) + 2 * nb + 64;   // .., tmp, d_none, d_rule
     rc = ensure(s->mem, sizeof(int32_t) * ints);
     if (rc) {
         delete s;
@@ -688,6 +716,7 @@ static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_
     s->tk_r2c = take(tk_cap);
     s->tmp = take(std::max<size_t>(max_cabs, 1));
     s->d_none = take(nb);
+    s->d_rule = take(nb);
     auto bail = [&](int code) {
         td_simb_destroy(s);
         return code;
@@ -804,6 +833,39 @@ extern "C" int td_simb_pooling(td_simb *s, const int32_t *mode, const double *ma
     return TD_OK;
 }
 
+extern "C" int td_simb_dispatch(td_simb *s, const int32_t *mode, const int32_t *max_non_lcm, const int32_t *parts)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (s->begun) return fail(TD_EINVAL, "td_simb_dispatch: tick %d still waits for td_simb_apply", s->last_t);
+    const size_t B = (size_t)s->B;
+    int rc;
+    std::vector<int32_t> hm(B, TD_DISPATCH_LCM_OPT), hl(B, s->max_non_lcm), hp(B, 4);
+    if (mode && (rc = host_copy(mode, B, hm))) return rc;
+    if (max_non_lcm && (rc = host_copy(max_non_lcm, B, hl))) return rc;
+    if (parts && (rc = host_copy(parts, B, hp))) return rc;
+    for (size_t b = 0; b < B; b++) {
+        if (hm[b] < TD_DISPATCH_LCM_OPT || hm[b] > TD_DISPATCH_SPLIT) return fail(TD_EINVAL, "td_simb_dispatch: mode[%zu] = %d outside 0 .. 3", b, hm[b]);
+        if (hl[b] < 0) return fail(TD_EINVAL, "td_simb_dispatch: max_non_lcm[%zu] = %d is negative", b, hl[b]);
+        if (hl[b] > 1024)
+            return fail(TD_EINVAL, "td_simb_dispatch: max_non_lcm[%zu] = %d > 1024 (the remainder td_dispatch_batched hands its solver)", b, hl[b]);
+        if (hm[b] == TD_DISPATCH_SPLIT && (hp[b] < 1 || hp[b] > 32 || hp[b] > s->w.n_stands))
+            return fail(TD_EINVAL, "td_simb_dispatch: parts[%zu] = %d outside 1 .. min(32, n_stands = %d)", b, hp[b], s->w.n_stands);
+    }
+    int32_t *st = s->h_stage;   // pinned, at least 3 (B + 1) ints
+    for (size_t b = 0; b < B; b++)
+        st[b] = hm[b] == TD_DISPATCH_LCM_OPT ? hl[b] : hm[b] == TD_DISPATCH_LCM ? -1 : INT_MAX;
+    TD_HIP(hipMemcpyAsync(s->d_rule, st, sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx().stream));
+    TD_HIP(hipStreamSynchronize(ctx().stream));
+    for (size_t b = 0; b < B; b++)
+        if (hm[b] != TD_DISPATCH_SPLIT) hp[b] = 4;   // read for the split only
+    s->disp_mode = hm;
+    s->disp_mnl = hl;
+    s->disp_parts = hp;
+    s->disp_set = true;
+    return TD_OK;
+}
+
 extern "C" int td_simb_pools(td_simb *s, int world, int max_pools, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n)
 {
     TD_REQUIRE_INIT();
@@ -863,7 +925,7 @@ extern "C" int td_simb_apply(td_simb *s, const int32_t *pair_off, const int32_t 
     if ((rc = put(s->in_rows, lcm_rows, (size_t)hp[B])) || (rc = put(s->in_cols, lcm_cols, (size_t)hp[B])) ||
         (rc = put(s->in_r2c, row_to_col, (size_t)hr[B])))
         return rc;
-    const SimbDec dec{s->in_rows, s->in_cols, s->in_r2c, s->in_pair_off, s->in_r2c_off, s->in_solved, nullptr, nullptr, nullptr, 0};
+    const SimbDec dec{s->in_rows, s->in_cols, s->in_r2c, s->in_pair_off, s->in_r2c_off, s->in_solved, nullptr, nullptr, nullptr, 0, s->disp_set ? s->d_rule : nullptr};
     return simb_apply(s, dec, max_pairs, hsol.data(), opt_count);
 }
 
@@ -887,7 +949,26 @@ extern "C" int td_simb_step(td_simb *s, int t, int32_t *line)
                         b, s->n_dem[b], t, SIMB_NMAX);
         n = std::max(n, std::max(s->n_sup[b], s->n_d2[b]));
     }
-    if (n > 0) {
+    // some world has a policy that is not the handle's own: every world's model goes through td_dispatch_batched
+    bool policy = false;
+    for (int b = 0; b < B && s->disp_set; b++)
+        policy = policy || s->disp_mode[b] != TD_DISPATCH_LCM_OPT || s->disp_mnl[b] != s->max_non_lcm;
+    if (n > 0 && policy) {
+        for (int b = 0; b < B; b++) {
+            const int n_s = s->n_sup[b], n_d = s->n_d2[b], md = s->disp_mode[b];
+            if (n_s == 0 || std::max(n_s, n_d) <= 1024) continue;
+            if (md == TD_DISPATCH_SPLIT || md == TD_DISPATCH_OPT)
+                return fail(TD_EINVAL,
+                            "td_simb_step: world %d's %s model has %d cabs and %d requests in tick %d, more than 1024 per side; finish the tick "
+                            "through td_simb_model / td_simb_apply",
+                            b, md == TD_DISPATCH_SPLIT ? "split" : "optimum-alone", n_s, n_d, t);
+        }
+        // the host mirrors of the policy go with the device lists: no read-back of a policy array per tick
+        if ((rc = td_dispatch_batched(B, n, h_of(s, s->sup_off), s->sup_to, h_of(s, s->tk_off), s->tk_from, s->dist, s->dist ? s->w.n_stands : 0,
+                                      s->w.big_cost, s->w.drop_time, s->w.n_stands, s->disp_mode.data(), s->disp_mnl.data(), s->disp_parts.data(),
+                                      s->tk_rows, s->tk_cols, s->tk_np, s->tk_lm, nullptr, nullptr, s->tk_rest, s->tk_r2c, s->tk_total, nullptr)))
+            return rc;
+    } else if (n > 0) {
         // the arguments HipTickBackend.tick hands td_tick, for every world with supply at once; the lists stay where they are
         if ((rc = td_tick_batched(B, n, h_of(s, s->sup_off), s->sup_to, h_of(s, s->tk_off), s->tk_from, s->dist, s->dist ? s->w.n_stands : 0, s->w.big_cost, s->w.drop_time,
                                   s->max_non_lcm, s->tk_rows, s->tk_cols, s->tk_np, s->tk_lm, nullptr, nullptr, s->tk_rest, s->tk_r2c, s->tk_total,
@@ -895,7 +976,8 @@ extern "C" int td_simb_step(td_simb *s, int t, int32_t *line)
             return rc;
     }
     const int stride = std::max(n, 1);
-    const SimbDec dec{s->tk_rows, s->tk_cols, s->tk_r2c, nullptr, nullptr, nullptr, s->tk_np, s->tk_rest, s->tk_lm, stride};
+    const SimbDec dec{s->tk_rows, s->tk_cols, s->tk_r2c, nullptr, nullptr, nullptr, s->tk_np, s->tk_rest, s->tk_lm, stride,
+                      s->disp_set ? s->d_rule : nullptr};
     if ((rc = simb_apply(s, dec, stride, nullptr, opt.data()))) return rc;
     const int32_t *hk = h_of(s, s->tk_np), *hrest = h_of(s, s->tk_rest), *hlm = h_of(s, s->tk_lm);
     for (int b = 0; b < B; b++) {
@@ -906,8 +988,8 @@ extern "C" int td_simb_step(td_simb *s, int t, int32_t *line)
         ln[2] = s->n_sup[b];
         const int n_s = s->n_sup[b], n_d = s->n_d2[b];
         if (n_s > 0) {
-            const bool lcm = s->max_non_lcm < std::max(n_s, n_d);
-            const bool solved = hrest[b] > 0 && !(lcm && hlm[b] == s->w.big_cost);
+            const bool lcm = s->rule(b) < std::max(n_s, n_d);
+            const bool solved = !s->lcm_alone(b) && hrest[b] > 0 && !(lcm && hlm[b] == s->w.big_cost);
             const int k = lcm ? hk[b] : 0;
             ln[3] = lcm;
             ln[4] = k;

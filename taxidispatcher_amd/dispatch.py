@@ -25,6 +25,7 @@ Reference map (file:line in boguszjelinski/taxidispatcher):
     tick_batched          tick() of many ragged position models per call (Simulator.java:163-208 per zone / per seed)
     match_batched         maximum-weight matching of many general graphs per call (the optimum behind pool_opt_min.py)
     split_batched         split.py:61-119 as a whole, for many cases per call (td_split_batched)
+    dispatch_batched      many models per call, a dispatch method per model: LCM + optimum, optimum, LCM, split (td_dispatch_batched)
     solve_split           split.py:61-119 for one case, the reference's call shape  -> total
     split_gap             split.py's main (optimum, split total, LCM) as library calls
     pool2_batched         greedy (pool_opt_min.py:81-102) or optimal (:114-122) pools of two of many ragged models per call
@@ -761,6 +762,69 @@ def split_batched(cab_tos, dem_froms, size, parts=4, distances=None, fill=BIG_CO
                                     _ffi.addr(gap)))
     del keep
     return {"cab_req": req, "cab_stage": stage, "total": total, "rest_total": rest, "n_rest": n_rest, "dual_gap": gap, "cab_off": ch}
+
+
+# ----------------------------------------------------------------------------------------
+# many dispatch models per call, a dispatch method per model (td_dispatch_batched)
+# ----------------------------------------------------------------------------------------
+DISPATCH_MODES = {"lcm+opt": 0, "opt": 1, "lcm": 2, "split": 3}   # TD_DISPATCH_LCM_OPT / _OPT / _LCM / _SPLIT: the one table
+
+
+def dispatch_mode(m):
+    """a dispatch method as the C ABI's number: a name of DISPATCH_MODES, or the number itself"""
+    if isinstance(m, str):
+        if m not in DISPATCH_MODES:
+            raise _ffi.TdError("dispatch method %r is none of %s" % (m, sorted(DISPATCH_MODES)))
+        return DISPATCH_MODES[m]
+    return int(m)
+
+
+def _policy(v, batch, what, conv=int):
+    """one policy argument of dispatch_batched -> None, a torch CUDA int32 tensor handed on as it is, or int32[batch]"""
+    if v is None:
+        return None
+    if hasattr(v, "data_ptr") and not isinstance(v, np.ndarray):
+        _require_i32(v, what)
+        if int(v.numel()) != batch:
+            raise _ffi.TdError("%s has %d entries for %d models" % (what, int(v.numel()), batch))
+        return v
+    if isinstance(v, (str, int, np.integer)):
+        return np.full(max(batch, 1), conv(v), np.int32)[:batch]
+    a = np.ascontiguousarray([conv(x) for x in v], np.int32).reshape(-1)
+    if a.size != batch:
+        raise _ffi.TdError("%s has %d entries for %d models" % (what, a.size, batch))
+    return a
+
+
+def dispatch_batched(cab_tos, dem_froms, distances=None, big_cost=BIG_COST, drop_time=10, size=None, mode=None, max_non_lcm=None,
+                     parts=None, n=None):
+    """td_dispatch_batched: B ragged dispatch models in one call, a dispatch method per model.  cab_tos / dem_froms: see
+    pack_ragged; one shared distance table (None: |a - b|).  mode: "lcm+opt" (tick_batched with the model's own max_non_lcm),
+    "opt", "lcm" (the LCM to its end, never a solve) or "split" (split.py:61-119 on the cells below drop_time, parts ranges over
+    `size` stands; size defaults to the table's), or their numbers; mode / max_non_lcm / parts are a scalar for all models, a
+    list per model, a torch CUDA int32 tensor, or None (lcm+opt / the LCM never runs / 4).  n: the output stride (default: the
+    largest model).  Returns a dict of td_tick_batched's arrays: lcm_rows, lcm_cols, kept_cabs, kept_dems, row_to_col
+    int32[B, n]; n_pairs, lcm_min_val, n_rest int32[B]; total, dual_bound int64[B]; for a split model row_to_col[b, i] is the
+    request cab i serves (or -1) and dual_bound == total certifies every model solved for it."""
+    lib = _ffi.lib()
+    cv, co, dv, do, batch, nmax = pack_ragged(cab_tos, dem_froms)
+    n = nmax if n is None else int(n)
+    dptr, S, keep = _dist_arg(distances)
+    if size is None:
+        size = S
+    md = _policy(mode, batch, "mode", dispatch_mode)
+    st = _policy(max_non_lcm, batch, "max_non_lcm")
+    pt = _policy(parts, batch, "parts")
+    rows, cols, kc, kd, r2c = (_out((batch, n), np.int32) for _ in range(5))
+    k, lm, n2 = (_out((batch,), np.int32) for _ in range(3))
+    total, dual = _out((batch,), np.int64), _out((batch,), np.int64)
+    _ffi.check(lib.td_dispatch_batched(batch, n, _ffi.addr(co), _ffi.addr(cv), _ffi.addr(do), _ffi.addr(dv), dptr, S, int(big_cost),
+                                       -1 if drop_time is None else int(drop_time), int(size), _ffi.addr(md), _ffi.addr(st),
+                                       _ffi.addr(pt), _ffi.addr(rows), _ffi.addr(cols), _ffi.addr(k), _ffi.addr(lm), _ffi.addr(kc),
+                                       _ffi.addr(kd), _ffi.addr(n2), _ffi.addr(r2c), _ffi.addr(total), _ffi.addr(dual)))
+    del keep
+    return {"lcm_rows": rows, "lcm_cols": cols, "n_pairs": k, "lcm_min_val": lm, "kept_cabs": kc, "kept_dems": kd, "n_rest": n2,
+            "row_to_col": r2c, "total": total, "dual_bound": dual}
 
 
 def solve_split(distances, demand, cabs, size, parts=4):

@@ -73,6 +73,16 @@ def pool_mode(pool):
     return POOL_MODES[pool]
 
 
+from .dispatch import DISPATCH_MODES   # the one table: TD_DISPATCH_LCM_OPT / _OPT / _LCM / _SPLIT by name
+
+
+def dispatch_mode(dispatch):
+    """a dispatch method by name -> its TD_DISPATCH_* value (ValueError for anything else, as pool_mode)"""
+    if dispatch not in DISPATCH_MODES:
+        raise ValueError("dispatch=%r: one of %s" % (dispatch, ", ".join(sorted(DISPATCH_MODES))))
+    return DISPATCH_MODES[dispatch]
+
+
 class HipBackend:
     """cost build / LCM / optimal assignment on the GPU through the C ABI; dist: a stand-to-stand table (None = |a - b|).
     pool / max_loss: the policy find_pool follows when the caller names none ("greedy": dispatch.find_pool, "optimal":
@@ -88,11 +98,19 @@ class HipBackend:
     def calculate_cost(self, cab_to, dem_from):
         return self.d.cost_build(cab_to, dem_from, self.dist, fill=BIG_COST, threshold=DROP_TIME)[1]
 
-    def lcm(self, cost):
-        return self.d.LCM_simulator(cost, max_non_lcm=MAX_NON_LCM, big_cost=BIG_COST)
+    def lcm(self, cost, max_non_lcm=None):
+        return self.d.LCM_simulator(cost, max_non_lcm=MAX_NON_LCM if max_non_lcm is None else max_non_lcm, big_cost=BIG_COST)
 
     def solve(self, cost):
         return self.d.assign(cost)[0]
+
+    def split(self, cab_to, dem_from, parts=4):
+        """the split heuristic on the tick's thresholded model (td_dispatch_batched, TD_DISPATCH_SPLIT, a batch of one):
+        the request each cab serves within dem_from, or -1"""
+        cab_to, dem_from = np.asarray(cab_to, np.int32), np.asarray(dem_from, np.int32)
+        res = self.d.dispatch_batched([cab_to], [dem_from], self.dist, big_cost=BIG_COST, drop_time=DROP_TIME, size=N_STANDS, mode="split",
+                                      parts=parts)
+        return res["row_to_col"][0, :cab_to.size]
 
     def find_pool(self, frm, to, max_loss=None, optimal=None):
         optimal = self.pool == "optimal" if optimal is None else optimal
@@ -162,11 +180,24 @@ class Simulator:
     Simulator.java:691 (every ordered pair, stable cost order) and calls backend.find_pool(frm, to) as it always did; any
     other policy calls backend.find_pool(frm, to, max_loss=..., optimal=...): max_loss > 0 admits the pairs that pass
     pool_opt_min.py:56-64's loss tests, "optimal" takes the most pools, then the least cost, in ascending (cost, custA,
-    custB).  "none": findPool and analyzePool do not run, no pool event is written, max_POOL_* stay as they are."""
+    custB).  "none": findPool and analyzePool do not run, no pool event is written, max_POOL_* stay as they are.
+    dispatch / max_non_lcm / parts: the dispatch policy, the specification of td_dispatch_batched's modes inside a world.
+    "lcm+opt" with max_non_lcm=None is Simulator.java:163-208 with the module's MAX_NON_LCM, through the calls it always made.
+    Any other policy goes step by step through backend.calculate_cost / lcm(cost, max_non_lcm=...) / solve / split:
+    "lcm+opt" with its own max_non_lcm; "opt": the LCM never runs; "lcm": the LCM with stop size 0, run to its end, with
+    supply always, and the solver never (the line ends after the pairs, total_LCM_used counts the tick); "split":
+    backend.split(cab_to, dem_from, parts) on the whole model, applied by analyze_solution (method OPT), max_solver_size takes
+    the whole model size."""
 
     def __init__(self, demand_rows, backend=None, n_cabs=N_CABS, on_solver_instance=None, dist=None, events=False, pool="greedy",
-                 max_loss=None):
+                 max_loss=None, dispatch="lcm+opt", max_non_lcm=None, parts=4):
         pool_mode(pool)
+        dispatch_mode(dispatch)
+        if max_non_lcm is not None and int(max_non_lcm) < 0:
+            raise ValueError("max_non_lcm=%r is negative" % (max_non_lcm,))
+        if dispatch == "split" and not 1 <= int(parts) <= min(32, N_STANDS):
+            raise ValueError("parts=%r outside 1 .. min(32, the number of stands)" % (parts,))
+        self.dispatch, self.max_non_lcm, self.parts = dispatch, (None if max_non_lcm is None else int(max_non_lcm)), int(parts)
         self.pool, self.max_loss = pool, (None if max_loss is None or not max_loss > 0 else float(max_loss))
         self._events_on = bool(events)
         self.events = []         # events=True: the records of simulog.txt (format_events), in the order the Java writes them
@@ -415,6 +446,8 @@ class Simulator:
         line = "t:%d. Initial Count of demand=%d, supply=%d. " % (t, len(temp_demand), len(temp_supply))
         cost = np.zeros((0, 0), np.int32)
         r2c = []
+        if temp_supply and (self.dispatch != "lcm+opt" or self.max_non_lcm is not None):
+            return self._tick_policy(t, line, temp_demand, temp_supply)
         if temp_supply and hasattr(self.be, "tick"):
             return self._tick_one_call(t, line, temp_demand, temp_supply)
         if temp_supply:
@@ -459,6 +492,33 @@ class Simulator:
         r2c = res["row_to_col"]
         # analyzeSolution reads cost[s][c] < big_cost (:378-383): a real cell of the thresholded model
         count = self.analyze_solution(t, r2c, _RealCells(temp_supply, temp_demand, self.dist), temp_demand, temp_supply)
+        return line + "; OPT count=%d" % count
+
+    # ---- the same tick under a dispatch policy of its own (td_dispatch_batched's modes)
+    def _tick_policy(self, t, line, temp_demand, temp_supply):
+        temp_demand = self._pooled(temp_demand, t)
+        n = max(len(temp_demand), len(temp_supply))
+        self.m["max_model_size"] = max(self.m["max_model_size"], n)
+        mnl = MAX_NON_LCM if self.max_non_lcm is None else self.max_non_lcm
+        if self.dispatch == "split":
+            self.m["max_solver_size"] = max(self.m["max_solver_size"], n)
+            r2c = self.be.split([s[2] for s in temp_supply], [d[1] for d in temp_demand], self.parts)
+            count = self.analyze_solution(t, r2c, _RealCells(temp_supply, temp_demand, self.dist), temp_demand, temp_supply)
+            return line + "; OPT count=%d" % count
+        if self.dispatch == "lcm" or (self.dispatch == "lcm+opt" and n > mnl):
+            pairs, lcm_min_val = self.be.lcm(self.calculate_cost(temp_demand, temp_supply), max_non_lcm=0 if self.dispatch == "lcm" else mnl)
+            self.m["total_LCM_used"] += 1
+            line += "LCM n_pairs=%d" % len(pairs)
+            temp_supply, temp_demand = self.analyze_pairs(t, pairs, temp_demand, temp_supply)
+            # the LCM alone never solves; :188 no input for the solver; and nobody left over is no model (td_tick's rule)
+            if self.dispatch == "lcm" or lcm_min_val == BIG_COST or not (temp_supply or temp_demand):
+                return line
+            line += ". Sent to solver: demand=%d, supply=%d. " % (len(temp_demand), len(temp_supply))
+        cost = self.calculate_cost(temp_demand, temp_supply)
+        self.m["max_solver_size"] = max(self.m["max_solver_size"], cost.shape[0])
+        if self.on_solver_instance is not None:
+            self.on_solver_instance(t, temp_supply, temp_demand, cost)
+        count = self.analyze_solution(t, self.be.solve(cost), cost, temp_demand, temp_supply)
         return line + "; OPT count=%d" % count
 
     # ---- Simulator.java:256-277 printMetrics (wall-clock lines are the caller's: pass them in)
@@ -598,7 +658,9 @@ class DeviceSimulator(_DeviceEvents):
     4 * (n_cabs + n_req) + 64, holds any one tick of the world (a tick writes at most 3 n_cabs + 3.5 n_req + 2 records), so
     a caller that drains after every tick loses nothing.
     pool / max_loss: the pooling policy as `Simulator` takes it (td_sim_pooling); `pools()` reads the plans of the tick last
-    begun (td_sim_pools)."""
+    begun (td_sim_pools).
+    dispatch / parts: the dispatch policy as `Simulator` takes it (td_sim_dispatch, with the world's max_non_lcm); None: the
+    world never calls td_sim_dispatch and dispatches as it always did."""
 
     M_KEYS = ("total_dropped", "total_pickup_time", "total_pickup_numb", "total_LCM_used", "max_model_size", "max_solver_size",
               "max_POOL_MEM_size", "max_POOL_size", "total_second_passengers")
@@ -606,9 +668,11 @@ class DeviceSimulator(_DeviceEvents):
     REQ_KEYS = ("d_cab", "d_pick", "d_pool_id", "d_pool_plan", "d_pool_cost")
 
     def __init__(self, demand_rows, n_cabs=None, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None, events=None,
-                 event_capacity=None, pool="greedy", max_loss=None):
+                 event_capacity=None, pool="greedy", max_loss=None, dispatch=None, parts=4):
         import ctypes
         mode = pool_mode(pool)
+        if dispatch is not None:
+            dispatch_mode(dispatch)
         from . import _ffi
         self._ffi, self._ct = _ffi, ctypes
         self._lib = _ffi.lib()
@@ -641,6 +705,16 @@ class DeviceSimulator(_DeviceEvents):
         self.pool, self.max_loss = pool, max_loss
         if pool != "greedy" or max_loss is not None:      # a default world never calls td_sim_pooling
             _ffi.check(self._lib.td_sim_pooling(self._h, mode, 0.0 if max_loss is None else float(max_loss)))
+        self.dispatch, self.parts = "lcm+opt", int(parts)
+        if dispatch is not None:                          # a default world never calls td_sim_dispatch
+            self.set_dispatch(dispatch, self.max_non_lcm, parts)
+
+    def set_dispatch(self, dispatch, max_non_lcm=None, parts=4):
+        """td_sim_dispatch: the dispatch method ("lcm+opt", "opt", "lcm", "split"), its max_non_lcm (None: as it is) and the
+        split's parts, from the next begin on"""
+        mnl = self.max_non_lcm if max_non_lcm is None else int(max_non_lcm)
+        self._ffi.check(self._lib.td_sim_dispatch(self._h, dispatch_mode(dispatch), mnl, int(parts)))
+        self.dispatch, self.max_non_lcm, self.parts = dispatch, mnl, int(parts)
 
     def pools(self):
         """the plans of the tick last begun: a list of (custA, custB, plan, cost), indices into that tick's demand list
@@ -792,11 +866,20 @@ class DeviceSimulatorBatch(_DeviceEvents):
     M_KEYS, CAB_KEYS, REQ_KEYS = DeviceSimulator.M_KEYS, DeviceSimulator.CAB_KEYS, DeviceSimulator.REQ_KEYS
     format_line = staticmethod(DeviceSimulator.format_line)
 
+    # dispatch / max_non_lcm / parts: the dispatch policy per world (td_simb_dispatch), each a list with one entry per world or one
+    # value for all; dispatch=None with a scalar max_non_lcm: the batch never calls td_simb_dispatch and dispatches as it always did
     def __init__(self, demand_rows_list, n_cabs_list, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None,
-                 events=None, event_capacity=None, pool="greedy", max_loss=None):
+                 events=None, event_capacity=None, pool="greedy", max_loss=None, dispatch=None, parts=4):
         import ctypes
         n_cabs_list = list(n_cabs_list)
         nb = len(n_cabs_list)
+        mnl_list = None
+        if isinstance(max_non_lcm, (list, tuple, np.ndarray)):      # a max_non_lcm per world is part of the dispatch policy
+            mnl_list = [int(v) for v in max_non_lcm]
+            if len(mnl_list) != nb:
+                raise ValueError("max_non_lcm: %d entries for %d worlds" % (len(mnl_list), nb))
+            max_non_lcm = max(mnl_list) if mnl_list else None
+            dispatch = "lcm+opt" if dispatch is None else dispatch
         pools = list(pool) if isinstance(pool, (list, tuple)) else [pool] * nb
         losses = list(max_loss) if isinstance(max_loss, (list, tuple, np.ndarray)) else [max_loss] * nb
         if len(pools) != nb or len(losses) != nb:
@@ -847,6 +930,20 @@ class DeviceSimulatorBatch(_DeviceEvents):
         if any(p != "greedy" for p in pools) or any(x is not None for x in losses):      # a default batch never calls td_simb_pooling
             ml = np.array([0.0 if x is None else float(x) for x in losses], np.float64)
             _ffi.check(self._lib.td_simb_pooling(self._h, _ffi.addr(modes), _ffi.addr(ml)))
+        self.dispatch, self.max_non_lcms, self.parts = ["lcm+opt"] * nb, [self.max_non_lcm] * nb, [4] * nb
+        if dispatch is not None:                          # a default batch never calls td_simb_dispatch
+            self.set_dispatch(dispatch, mnl_list, parts)
+
+    def set_dispatch(self, dispatch, max_non_lcm=None, parts=4):
+        """td_simb_dispatch: the dispatch method ("lcm+opt", "opt", "lcm", "split"), max_non_lcm (None: as created) and the
+        split's parts of every world, from the next begin on; each a list per world, or one value for all worlds"""
+        per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * self.batch
+        ds, ms, ps = per(dispatch), per(self.max_non_lcm if max_non_lcm is None else max_non_lcm), per(parts)
+        if not len(ds) == len(ms) == len(ps) == self.batch:
+            raise ValueError("dispatch / max_non_lcm / parts: %d / %d / %d entries for %d worlds" % (len(ds), len(ms), len(ps), self.batch))
+        arrs = [np.array([dispatch_mode(d) for d in ds], np.int32), np.array(ms, np.int32), np.array(ps, np.int32)]
+        self._ffi.check(self._lib.td_simb_dispatch(self._h, *[self._ffi.addr(a) for a in arrs]))
+        self.dispatch, self.max_non_lcms, self.parts = ds, [int(v) for v in ms], [int(v) for v in ps]
 
     def pools(self, b):
         """world b's plans of the tick last begun, as DeviceSimulator.pools lists them"""

@@ -12,7 +12,12 @@ FILE with the world's number put before its extension (simulog.0.txt, simulog.1.
 --pool none|greedy|optimal and --max-loss X: the pooling policy (default: greedy over every ordered pair, Simulator.java:691;
 X > 0 admits the pairs that pass pool_opt_min.py's loss tests, 0 = every pair); with --cabs a,b,c either may be a list a,b,c
 with one entry per world, and a single value holds for every world.  An optimal world refuses a tick with more than 2048
-requests before pooling (the committed demand file has such ticks at 1300 cabs and fewer)."""
+requests before pooling (the committed demand file has such ticks at 1300 cabs and fewer).
+--dispatch lcm+opt|opt|lcm|split, --max-non-lcm N, --parts P: the dispatch policy (td_sim_dispatch / td_simb_dispatch, or
+Simulator(dispatch=...) with --world host); with --cabs a,b,c each may be a list a,b,c with one entry per world, and a single
+value holds for every world, e.g. --cabs 400,400,400 --dispatch lcm,opt,split --max-non-lcm 0,16,600 --parts 4.  A split world,
+and in a batch an optimum-alone world, refuses a tick whose model has more than 1024 cabs or requests, which the committed
+demand reaches at 1300 cabs."""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,9 +30,29 @@ ap.add_argument("--dist", default=None, metavar="FILE.npy", help="a stand-to-sta
 ap.add_argument("--events", default=None, metavar="FILE", help="write the event log (simulog.txt) of the run to FILE")
 ap.add_argument("--pool", default="greedy", metavar="none|greedy|optimal[,...]", help="the pooling policy; a list goes with a --cabs list")
 ap.add_argument("--max-loss", default=None, metavar="X[,...]", help="the candidate rule's max_loss (0: every pair); a list goes with a --cabs list")
+ap.add_argument("--dispatch", default=None, metavar="lcm+opt|opt|lcm|split[,...]", help="the dispatch method; a list goes with a --cabs list")
+ap.add_argument("--max-non-lcm", default=None, metavar="N[,...]", help="max_non_lcm under lcm+opt; a list goes with a --cabs list")
+ap.add_argument("--parts", default="4", metavar="P[,...]", help="the split's number of stand ranges; a list goes with a --cabs list")
 args = ap.parse_args()
 if args.cabs and args.world != "device":
     ap.error("--cabs needs --world device")
+policy = {}
+if args.dispatch or args.max_non_lcm is not None:
+    n_w = len(args.cabs.split(",")) if args.cabs else 1
+    lists = {"dispatch": (args.dispatch or "lcm+opt").split(","), "parts": [int(v) for v in args.parts.split(",")],
+             "max_non_lcm": [int(v) for v in args.max_non_lcm.split(",")] if args.max_non_lcm is not None else [None]}
+    for what, vals in lists.items():
+        if len(vals) not in (1, n_w):
+            ap.error("--%s has %d entries for %d world(s)" % (what.replace("_", "-"), len(vals), n_w))
+    for v in lists["dispatch"]:
+        if v not in simulator.DISPATCH_MODES:
+            ap.error("--dispatch %s: one of %s" % (v, ", ".join(sorted(simulator.DISPATCH_MODES))))
+    if args.cabs:
+        policy = {k: v * (n_w // len(v)) for k, v in lists.items()}
+        if policy["max_non_lcm"][0] is None:
+            policy["max_non_lcm"] = None
+    else:
+        policy = {k: v[0] for k, v in lists.items()}
 n_worlds = len(args.cabs.split(",")) if args.cabs else 1
 pools = args.pool.split(",")
 losses = [float(v) if float(v) > 0 else None for v in args.max_loss.split(",")] if args.max_loss else [None]
@@ -76,7 +101,8 @@ def run_logged(sim, ticks):
 
 if args.world == "device" and args.cabs:
     fleets = [int(v) for v in args.cabs.split(",")]
-    sim = simulator.DeviceSimulatorBatch([rows] * len(fleets), fleets, dist=dist, events=True if args.events else None, pool=pools, max_loss=losses)
+    sim = simulator.DeviceSimulatorBatch([rows] * len(fleets), fleets, dist=dist, events=True if args.events else None, pool=pools, max_loss=losses,
+                                         **policy)
     t0 = time.time()
     if args.events:
         records, logs = run_logged(sim, 120), sim.logs
@@ -89,12 +115,13 @@ if args.world == "device" and args.cabs:
             write_events("%s.%d%s" % (stem, b, ext), records, world=b)
     print("120 ticks of %d worlds in %.2f s; worlds and path on the GPU, one td_simb_step call per tick for all worlds" % (len(fleets), dt))
     for b, n in enumerate(fleets):
-        print("\n=== world %d: %d cabs, pool %s, max_loss %s ===" % (b, n, pools[b], losses[b]))
+        print("\n=== world %d: %d cabs, pool %s, max_loss %s, dispatch %s, max_non_lcm %d, parts %d ===" % (b, n, pools[b], losses[b], sim.dispatch[b],
+                                                                                                         sim.max_non_lcms[b], sim.parts[b]))
         print("\n".join(logs[b][-2:]))
         print(sim.metrics_text(b, total_simul_time=int(dt)))
     sys.exit(0)
 if args.world == "device":
-    sim = simulator.DeviceSimulator(rows, dist=dist, events=True if args.events else None, pool=pools[0], max_loss=losses[0])
+    sim = simulator.DeviceSimulator(rows, dist=dist, events=True if args.events else None, pool=pools[0], max_loss=losses[0], **policy)
     t0 = time.time()
     if args.events:
         records, log = run_logged(sim, 120), sim.log
@@ -107,7 +134,7 @@ if args.world == "device":
     print("\n".join(log[-3:]))
     print(sim.metrics_text(total_simul_time=int(dt)))
     sys.exit(0)
-sim = simulator.Simulator(rows, dist=dist, events=bool(args.events), pool=pools[0], max_loss=losses[0])
+sim = simulator.Simulator(rows, dist=dist, events=bool(args.events), pool=pools[0], max_loss=losses[0], **policy)
 t0 = time.time()
 per = {"pool": 0.0, "cost": 0.0, "lcm": 0.0, "solve": 0.0}
 be = sim.be
