@@ -28,7 +28,7 @@
 
 #include <vector>
 
-#include "td_common.h"
+#include "td_stage.h"
 
 using namespace td;
 
@@ -723,8 +723,6 @@ __global__ __launch_bounds__(T) void k_tick_lcm_batched(int batch, int n_out, in
 Buf g_out;                    // device results for host destinations + the error word (grow-only)
 std::vector<int32_t> g_ns;    // host copy of ns (validated here; stays alive while its upload may still be in flight)
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // validates the arguments shared by both entry points; *d_ns = device copy of ns (nullptr: every model is n x n)
 int batch_args(const char *fn, int batch, int n, const int32_t *ns, const int32_t *cost, const int32_t **d_ns,
                const int32_t **d_cost)
@@ -739,18 +737,12 @@ int batch_args(const char *fn, int batch, int n, const int32_t *ns, const int32_
     *d_cost = nullptr;
     if (ns && batch > 0) {
         std::vector<int32_t> &h = g_ns;
-        h.resize((size_t)batch);
-        if (is_device_ptr(ns)) {
-            TD_HIP(hipMemcpyAsync(h.data(), ns, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, c.stream));
-            TD_HIP(hipStreamSynchronize(c.stream));
-        } else {
-            memcpy(h.data(), ns, sizeof(int32_t) * h.size());
-        }
+        int rc = host_copy(ns, (size_t)batch, h);
+        if (rc) return rc;
         for (int b = 0; b < batch; b++)
             if (h[b] < 0 || h[b] > n) return fail(TD_EINVAL, "%s: ns[%d] = %d outside [0, %d]", fn, b, h[b], n);
         const void *p;
-        int rc = to_device(is_device_ptr(ns) ? (const void *)ns : (const void *)h.data(), sizeof(int32_t) * h.size(), c.stage_a, &p);
-        if (rc) return rc;
+        if ((rc = to_device(is_device_ptr(ns) ? (const void *)ns : (const void *)h.data(), sizeof(int32_t) * h.size(), c.stage_a, &p))) return rc;
         *d_ns = (const int32_t *)p;
     }
     if (batch > 0 && n > 0) {
@@ -763,43 +755,18 @@ int batch_args(const char *fn, int batch, int n, const int32_t *ns, const int32_
     return TD_OK;
 }
 
-// one output array: the caller's device pointer, or a slice of g_out that is copied back to the caller's host array
-struct Out {
-    void *user;
-    size_t bytes, off;
-    bool dev;
-    void *dptr() const { return dev ? user : (user ? (char *)g_out.p + off : nullptr); }
-};
-
-int outputs_prepare(Out *o, int k, size_t *err_off)
+// what the solver kernels leave in the error word
+int cap_error(const char *fn, int e)
 {
-    size_t off = 0;
-    for (int i = 0; i < k; i++) {
-        o[i].dev = o[i].user && is_device_ptr(o[i].user);
-        o[i].off = off;
-        if (o[i].user && !o[i].dev) off += align256(o[i].bytes);
-    }
-    *err_off = off;
-    int rc = ensure(g_out, off + 256);
-    if (rc) return rc;
-    TD_HIP(hipMemsetAsync((char *)g_out.p + off, 0, sizeof(int), ctx().stream));
-    return TD_OK;
-}
-
-int outputs_finish(const char *fn, const Out *o, int k, size_t err_off)
-{
-    Ctx &c = ctx();
-    TD_HIP(hipGetLastError());
-    for (int i = 0; i < k; i++)
-        if (o[i].user && !o[i].dev && o[i].bytes)
-            TD_HIP(hipMemcpyAsync(o[i].user, (char *)g_out.p + o[i].off, o[i].bytes, hipMemcpyDeviceToHost, c.stream));
-    TD_HIP(hipMemcpyAsync(c.pinned, (char *)g_out.p + err_off, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    TD_HIP(hipStreamSynchronize(c.stream));
-    const int e = *(int *)c.pinned;
     if (e)
         return fail(TD_EINTERNAL, "%s: a model hit a defensive loop cap (error word 0x%x: 1 search steps, 2 augmenting path, "
                     "4 label range, 8 model size)", fn, e);
     return TD_OK;
+}
+
+int batch_finish(const char *fn, const Out *o, int k, const int *d_err)
+{
+    return outputs_finish(o, k, d_err, [fn](int e) { return cap_error(fn, e); });
 }
 
 template <int T, int CPT, bool STAGE>
@@ -818,21 +785,6 @@ Buf g_in[5];                                    // device copies of host inputs:
 Buf g_ws;                                       // td_tick_batched: kept positions (ragged, at the models' offsets) + counts
 std::vector<int32_t> g_off[2];                  // host copies of the offsets (validated here)
 
-// dynamic LDS one workgroup may take (gfx950: 160 KiB per CU, all of it for one workgroup), less the static arrays
-size_t lds_budget()
-{
-    static size_t cap = 0;
-    if (!cap) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx().device) != hipSuccess || v <= 0) {
-            (void)hipGetLastError();
-            v = 64 * 1024;
-        }
-        cap = std::min<size_t>((size_t)v, 160 * 1024) - 1024;
-    }
-    return cap;
-}
-
 struct PosIn {
     const int32_t *cab_off, *dem_off, *cab, *dem, *dist;   // device pointers
     int nmax;                                              // the largest max(n_s, n_d)
@@ -842,7 +794,6 @@ struct PosIn {
 int pos_args(const char *fn, int batch, int n, int nlim, const int32_t *cab_off, const int32_t *cab_to, const int32_t *dem_off,
              const int32_t *dem_from, const int32_t *dist, int S, PosIn *in)
 {
-    Ctx &c = ctx();
     *in = PosIn{};
     if (batch < 0) return fail(TD_EINVAL, "%s: batch = %d < 0", fn, batch);
     if (n < 0) return fail(TD_EINVAL, "%s: n = %d < 0", fn, n);
@@ -851,21 +802,12 @@ int pos_args(const char *fn, int batch, int n, int nlim, const int32_t *cab_off,
     if (dist && (S <= 0 || S > 46340)) return fail(TD_EINVAL, "%s: S = %d outside [1, 46340] with a distance table", fn, S);
     if (batch == 0) return TD_OK;
     if (!cab_off || !dem_off) return fail(TD_EINVAL, "%s: null offsets", fn);
-    const int32_t *offs[2] = {cab_off, dem_off};
-    for (int s = 0; s < 2; s++) {
-        std::vector<int32_t> &h = g_off[s];
-        h.resize((size_t)batch + 1);
-        if (is_device_ptr(offs[s])) {
-            TD_HIP(hipMemcpyAsync(h.data(), offs[s], sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, c.stream));
-            TD_HIP(hipStreamSynchronize(c.stream));
-        } else {
-            memcpy(h.data(), offs[s], sizeof(int32_t) * h.size());
-        }
-        const char *what = s ? "dem_off" : "cab_off";
-        if (h[0] != 0) return fail(TD_EINVAL, "%s: %s[0] = %d, not 0", fn, what, h[0]);
-        for (int b = 0; b < batch; b++)
-            if (h[b + 1] < h[b]) return fail(TD_EINVAL, "%s: %s decreases at model %d (%d -> %d)", fn, what, b, h[b], h[b + 1]);
-    }
+    int rc = host_copy({{cab_off, (size_t)batch + 1, &g_off[0]}, {dem_off, (size_t)batch + 1, &g_off[1]}});
+    if (rc) return rc;
+    Ragged rg;
+    if ((rc = ragged_check(fail, fn, "cab_off", "model", g_off[0].data(), batch, &rg)) ||
+        (rc = ragged_check(fail, fn, "dem_off", "model", g_off[1].data(), batch, &rg)))
+        return rc;
     int nmax = 0;
     for (int b = 0; b < batch; b++) {
         const int ns = g_off[0][b + 1] - g_off[0][b], nd = g_off[1][b + 1] - g_off[1][b], nb = std::max(ns, nd);
@@ -875,7 +817,6 @@ int pos_args(const char *fn, int batch, int n, int nlim, const int32_t *cab_off,
     const size_t nc = (size_t)g_off[0][batch], nd = (size_t)g_off[1][batch];
     if ((nc && !cab_to) || (nd && !dem_from)) return fail(TD_EINVAL, "%s: null position array", fn);
     const void *p;
-    int rc;
     const int32_t *srcs[5] = {is_device_ptr(cab_off) ? cab_off : g_off[0].data(), is_device_ptr(dem_off) ? dem_off : g_off[1].data(),
                               cab_to, dem_from, dist};
     const size_t bytes[5] = {sizeof(int32_t) * ((size_t)batch + 1), sizeof(int32_t) * ((size_t)batch + 1), sizeof(int32_t) * nc,
@@ -888,12 +829,6 @@ int pos_args(const char *fn, int batch, int n, int nlim, const int32_t *cab_off,
     }
     in->nmax = nmax;
     return TD_OK;
-}
-
-template <class K>
-void lds_allow(K kernel, size_t shm)
-{
-    if (shm > 64 * 1024) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
 }
 
 // the optimum of every position model: nl >= every model's max(count); cnt: see k_assign_pos_batched
@@ -1329,29 +1264,23 @@ struct SplitWs {
 
 int split_ws(size_t B, size_t M, size_t nl, size_t nc, size_t nd, SplitWs *s)
 {
-    // the int64 arrays first, every array 256-byte aligned
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-        const size_t o = at;
-        at += align256(bytes);
-        return o;
-    };
-    const size_t o_tot1 = take(8 * M), o_dual1 = take(8 * M), o_tot2 = take(8 * B), o_dual2 = take(8 * B), o_sum0 = take(8 * B),
-                 o_gap0 = take(8 * B), o_roffc = take(4 * (M + 1)), o_roffd = take(4 * (M + 1)), o_rcnt = take(8 * M),
-                 o_scab = take(4 * nc), o_scabi = take(4 * nc), o_sdem = take(4 * nd), o_sdemi = take(4 * nd),
-                 o_r2c1 = take(4 * M * nl), o_wsreq = take(4 * nc), o_rcab = take(4 * nc), o_rcabi = take(4 * nc),
-                 o_rdem = take(4 * nd), o_rdemi = take(4 * nd), o_cnt2 = take(8 * B), o_nrest = take(8 * B),
-                 o_r2c2 = take(4 * B * nl);
-    int rc = ensure(g_sp, at + 256);
-    if (rc) return rc;
-    char *w = (char *)g_sp.p;
-    *s = SplitWs{(int64_t *)(w + o_tot1),  (int64_t *)(w + o_dual1),  (int64_t *)(w + o_tot2), (int64_t *)(w + o_dual2),
-                 (int64_t *)(w + o_sum0),  (int64_t *)(w + o_gap0),   (int32_t *)(w + o_roffc), (int32_t *)(w + o_roffd),
-                 (int32_t *)(w + o_rcnt),  (int32_t *)(w + o_scab),   (int32_t *)(w + o_scabi), (int32_t *)(w + o_sdem),
-                 (int32_t *)(w + o_sdemi), (int32_t *)(w + o_r2c1),   (int32_t *)(w + o_wsreq), (int32_t *)(w + o_rcab),
-                 (int32_t *)(w + o_rcabi), (int32_t *)(w + o_rdem),   (int32_t *)(w + o_rdemi), (int32_t *)(w + o_cnt2),
-                 (int32_t *)(w + o_nrest), (int32_t *)(w + o_r2c2)};
-    return TD_OK;
+    return carve_buf(g_sp, [&](Carve &c) {
+        for (int64_t **a : {&s->tot1, &s->dual1}) *a = c.take<int64_t>(M);
+        for (int64_t **a : {&s->tot2, &s->dual2, &s->sum0, &s->gap0}) *a = c.take<int64_t>(B);
+        s->roff_c = c.take<int32_t>(M + 1);
+        s->roff_d = c.take<int32_t>(M + 1);
+        s->rcnt = c.take<int32_t>(2 * M);
+        s->scab = c.take<int32_t>(nc);
+        s->scab_idx = c.take<int32_t>(nc);
+        s->sdem = c.take<int32_t>(nd);
+        s->sdem_idx = c.take<int32_t>(nd);
+        s->r2c1 = c.take<int32_t>(M * nl);
+        for (int32_t **a : {&s->ws_req, &s->rcab, &s->rcab_idx}) *a = c.take<int32_t>(nc);
+        for (int32_t **a : {&s->rdem, &s->rdem_idx}) *a = c.take<int32_t>(nd);
+        s->cnt2 = c.take<int32_t>(2 * B);
+        s->nrest = c.take<int32_t>(2 * B);
+        s->r2c2 = c.take<int32_t>(B * nl);
+    });
 }
 
 // launches 1 to 4 of the split: partition, the region models, collection, the fifth models (thr, mode, parts: see the kernels)
@@ -1378,9 +1307,31 @@ int split_error(const char *fn, int e, int size, int32_t fill)
 {
     if (e & ERR_POS) return fail(TD_EINVAL, "%s: a cab_to / dem_from position outside [0, %d)", fn, size);
     if (e & ERR_CELL) return fail(TD_EINVAL, "%s: a table entry used as a cell is outside [0, fill = %d)", fn, (int)fill);
-    if (e)
-        return fail(TD_EINTERNAL, "%s: a model hit a defensive loop cap (error word 0x%x: 1 search steps, 2 augmenting path, "
-                    "4 label range, 8 model size)", fn, e);
+    return cap_error(fn, e);
+}
+
+// the split's argument refusals, in the order they are tested; `which` selects the groups a call tests at this point.
+// model >= 0: p is parts[model] of td_dispatch_batched, named so in the message
+enum { SPLIT_PARTS = 1, SPLIT_CITY = 2, SPLIT_RANGES = 4 };
+int split_refusal(const char *fn, int which, int model, int p, int size, const int32_t *dist, int S, int32_t fill, int batch, int R)
+{
+    if ((which & SPLIT_PARTS) && (p < 1 || p > 32 || size < p)) {
+        char idx[24] = "";
+        if (model >= 0) snprintf(idx, sizeof(idx), "[%d]", model);
+        if (p < 1 || p > 32) return fail(TD_EINVAL, "%s: parts%s = %d outside [1, 32]", fn, idx, p);
+        return fail(TD_EINVAL, "%s: size = %d < parts%s = %d", fn, size, idx, p);
+    }
+    if (which & SPLIT_CITY) {
+        if (dist && S < size) return fail(TD_EINVAL, "%s: the table has S = %d stands, fewer than size = %d", fn, S, size);
+        if (dist && fill < 1) return fail(TD_EINVAL, "%s: fill = %d < 1", fn, (int)fill);
+        if (!dist && (int64_t)size - 1 >= (int64_t)fill)
+            return fail(TD_EINVAL, "%s: the distance %d of the line's ends is not below fill = %d", fn, size - 1, (int)fill);
+    }
+    if (which & SPLIT_RANGES) {
+        if (R >= SPLIT_RMAX) return fail(TD_EINTERNAL, "%s: %d ranges", fn, R);   // parts <= 32 gives at most 63
+        if ((int64_t)batch * R > INT_MAX / 2)
+            return fail(TD_EINVAL, "%s: %d cases of %d ranges are more than 2^30 region models", fn, batch, R);
+    }
     return TD_OK;
 }
 
@@ -1416,9 +1367,8 @@ int td_assign_batched(int batch, int n, const int32_t *ns, const int32_t *cost, 
     const size_t B = (size_t)batch, N = (size_t)n;
     Out o[4] = {{row_to_col, sizeof(int32_t) * B * N}, {total, sizeof(int64_t) * B}, {dual_bound, sizeof(int64_t) * B},
                 {col_price, sizeof(int64_t) * B * N}};
-    size_t err_off;
-    if ((rc = outputs_prepare(o, 4, &err_off))) return rc;
-    int *d_err = (int *)((char *)g_out.p + err_off);
+    int *d_err;
+    if ((rc = outputs_prepare(g_out, o, 4, &d_err))) return rc;
     int32_t *r2c = (int32_t *)o[0].dptr();
     int64_t *tot = (int64_t *)o[1].dptr(), *dual = (int64_t *)o[2].dptr(), *price = (int64_t *)o[3].dptr();
     const size_t shm = N * (sizeof(int64_t) + 3 * sizeof(int32_t));
@@ -1435,7 +1385,7 @@ int td_assign_batched(int batch, int n, const int32_t *ns, const int32_t *cost, 
         launch_assign<256, 2, false>(batch, n, d_ns, d_cost, r2c, tot, dual, price, d_err, shm);
     else
         launch_assign<256, 4, false>(batch, n, d_ns, d_cost, r2c, tot, dual, price, d_err, shm);
-    return outputs_finish("td_assign_batched", o, 4, err_off);
+    return batch_finish("td_assign_batched", o, 4, d_err);
 }
 
 int td_lcm_batched(int batch, int n, const int32_t *ns, const int32_t *cost, int32_t mask, int32_t threshold, int stop_value_on,
@@ -1451,8 +1401,8 @@ int td_lcm_batched(int batch, int n, const int32_t *ns, const int32_t *cost, int
     const size_t B = (size_t)batch, N = (size_t)n;
     Out o[5] = {{rows, sizeof(int32_t) * B * N}, {cols, sizeof(int32_t) * B * N}, {n_pairs, sizeof(int32_t) * B},
                 {total, sizeof(int64_t) * B}, {last_min, sizeof(int32_t) * B}};
-    size_t err_off;
-    if ((rc = outputs_prepare(o, 5, &err_off))) return rc;
+    int *d_err;
+    if ((rc = outputs_prepare(g_out, o, 5, &d_err))) return rc;
     // Java's scan only ever sees cells strictly below big_cost (Simulator.java:529-537)
     const int64_t cand_limit = stop_value_on ? (int64_t)stop_value : (int64_t)INT64_MAX;
     const size_t shm = N * (sizeof(uint64_t) + sizeof(int32_t)) + sizeof(uint32_t) * ((N + 31) / 32);
@@ -1467,7 +1417,7 @@ int td_lcm_batched(int batch, int n, const int32_t *ns, const int32_t *cost, int
                                                          stop_value, stop_size, sum_below, (int32_t *)o[0].dptr(),
                                                          (int32_t *)o[1].dptr(), (int32_t *)o[2].dptr(), (int64_t *)o[3].dptr(),
                                                          (int32_t *)o[4].dptr());
-    return outputs_finish("td_lcm_batched", o, 5, err_off);
+    return batch_finish("td_lcm_batched", o, 5, d_err);
 }
 
 int td_build_assign_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab_to, const int32_t *dem_off,
@@ -1482,11 +1432,11 @@ int td_build_assign_batched(int batch, int n, const int32_t *cab_off, const int3
     if (!row_to_col || !total) return fail(TD_EINVAL, "td_build_assign_batched: null row_to_col / total");
     const size_t B = (size_t)batch, N = (size_t)n;
     Out o[3] = {{row_to_col, sizeof(int32_t) * B * N}, {total, sizeof(int64_t) * B}, {dual_bound, sizeof(int64_t) * B}};
-    size_t err_off;
-    if ((rc = outputs_prepare(o, 3, &err_off))) return rc;
+    int *d_err;
+    if ((rc = outputs_prepare(g_out, o, 3, &d_err))) return rc;
     launch_pos_assign(batch, n, in.nmax, in, in.cab, in.dem, nullptr, S, fill, threshold, (int32_t *)o[0].dptr(), (int64_t *)o[1].dptr(),
-                      (int64_t *)o[2].dptr(), (int *)((char *)g_out.p + err_off));
-    return outputs_finish("td_build_assign_batched", o, 3, err_off);
+                      (int64_t *)o[2].dptr(), d_err);
+    return batch_finish("td_build_assign_batched", o, 3, d_err);
 }
 
 int td_tick_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab_to, const int32_t *dem_off, const int32_t *dem_from,
@@ -1519,8 +1469,8 @@ int td_tick_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab
                  {lcm_last_min, sizeof(int32_t) * B},  {kept_cabs, sizeof(int32_t) * B * N}, {kept_dems, sizeof(int32_t) * B * N},
                  {n_rest, sizeof(int32_t) * B},       {row_to_col, sizeof(int32_t) * B * N}, {total, sizeof(int64_t) * B},
                  {dual_bound, sizeof(int64_t) * B}};
-    size_t err_off;
-    if ((rc = outputs_prepare(o, 10, &err_off))) return rc;
+    int *d_err;
+    if ((rc = outputs_prepare(g_out, o, 10, &d_err))) return rc;
     void *od[7];
     for (int k = 0; k < 7; k++) od[k] = o[k].dptr();
     if (in.nmax <= 128)
@@ -1528,8 +1478,8 @@ int td_tick_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab
     else
         launch_tick_lcm_t<256, false>(batch, n, in.nmax, in, S, fill, threshold, stop_size, nullptr, nullptr, nullptr, od, cab2, dem2, cnt);
     launch_pos_assign(batch, n, nsol, in, cab2, dem2, cnt, S, fill, threshold, (int32_t *)o[7].dptr(), (int64_t *)o[8].dptr(),
-                      (int64_t *)o[9].dptr(), (int *)((char *)g_out.p + err_off));
-    return outputs_finish("td_tick_batched", o, 10, err_off);
+                      (int64_t *)o[9].dptr(), d_err);
+    return batch_finish("td_tick_batched", o, 10, d_err);
 }
 
 int td_split_batched(int batch, int n, const int32_t *cab_off, const int32_t *cab_to, const int32_t *dem_off, const int32_t *dem_from,
@@ -1538,47 +1488,29 @@ int td_split_batched(int batch, int n, const int32_t *cab_off, const int32_t *ca
 {
     TD_REQUIRE_INIT();
     const char *fn = "td_split_batched";
-    if (parts < 1 || parts > 32) return fail(TD_EINVAL, "%s: parts = %d outside [1, 32]", fn, parts);
-    if (size < parts) return fail(TD_EINVAL, "%s: size = %d < parts = %d", fn, size, parts);
-    if (dist && S < size) return fail(TD_EINVAL, "%s: the table has S = %d stands, fewer than size = %d", fn, S, size);
-    if (dist && fill < 1) return fail(TD_EINVAL, "%s: fill = %d < 1", fn, (int)fill);
-    if (!dist && (int64_t)size - 1 >= (int64_t)fill)
-        return fail(TD_EINVAL, "%s: the distance %d of the line's ends is not below fill = %d", fn, size - 1, (int)fill);
-    PosIn in;
-    int rc = pos_args(fn, batch, n, BATCH_NMAX, cab_off, cab_to, dem_off, dem_from, dist, S, &in);
+    int rc = split_refusal(fn, SPLIT_PARTS | SPLIT_CITY, -1, parts, size, dist, S, fill, 0, 0);
     if (rc) return rc;
+    PosIn in;
+    if ((rc = pos_args(fn, batch, n, BATCH_NMAX, cab_off, cab_to, dem_off, dem_from, dist, S, &in))) return rc;
     if (batch == 0) return TD_OK;
     if (!cab_req || !total) return fail(TD_EINVAL, "%s: null cab_req / total", fn);
     const int ss = size / parts, R = (size + ss - 1) / ss, nl = in.nmax;
-    if (R >= SPLIT_RMAX) return fail(TD_EINTERNAL, "%s: %d ranges", fn, R);   // parts <= 32 gives at most 63
-    if ((int64_t)batch * R > INT_MAX / 2) return fail(TD_EINVAL, "%s: %d cases of %d ranges are more than 2^30 region models", fn, batch, R);
+    if ((rc = split_refusal(fn, SPLIT_RANGES, -1, parts, size, dist, S, fill, batch, R))) return rc;
     const size_t B = (size_t)batch, M = B * (size_t)R, nc = (size_t)g_off[0][batch], nd = (size_t)g_off[1][batch];
     SplitWs w;
     if ((rc = split_ws(B, M, (size_t)nl, nc, nd, &w))) return rc;
     Out o[6] = {{cab_req, sizeof(int32_t) * nc},   {cab_stage, sizeof(int32_t) * nc}, {total, sizeof(int64_t) * B},
                 {rest_total, sizeof(int64_t) * B}, {n_rest, sizeof(int32_t) * 2 * B}, {dual_gap, sizeof(int64_t) * B}};
-    size_t err_off;
-    if ((rc = outputs_prepare(o, 6, &err_off))) return rc;
-    int *d_err = (int *)((char *)g_out.p + err_off);
+    int *d_err;
+    if ((rc = outputs_prepare(g_out, o, 6, &d_err))) return rc;
     Ctx &c = ctx();
     split_launches(batch, R, ss, size, nl, in, S, fill, -1, nullptr, nullptr, w, d_err);
     k_split_final<<<std::min(batch, SPLIT_GRID), nl <= 64 ? 64 : 256, 0, c.stream>>>(
         batch, nl, -1, SplitDisp{}, in.cab_off, in.dem_off, in.dist, S, w.ws_req, w.rcab, w.rcab_idx, w.rdem, w.rdem_idx, w.cnt2, w.nrest,
         w.sum0, w.gap0, w.r2c2, w.tot2, w.dual2, (int32_t *)o[0].dptr(), (int32_t *)o[1].dptr(), (int64_t *)o[2].dptr(),
         (int64_t *)o[3].dptr(), (int32_t *)o[4].dptr(), (int64_t *)o[5].dptr(), d_err);
-    TD_HIP(hipGetLastError());
-    // host destinations: through g_sp_host (same layout as g_out), handed over only when the call succeeded
-    g_sp_host.resize(err_off);
-    for (int i = 0; i < 6; i++)
-        if (o[i].user && !o[i].dev && o[i].bytes)
-            TD_HIP(hipMemcpyAsync(g_sp_host.data() + o[i].off, (char *)g_out.p + o[i].off, o[i].bytes, hipMemcpyDeviceToHost, c.stream));
-    TD_HIP(hipMemcpyAsync(c.pinned, d_err, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    TD_HIP(hipStreamSynchronize(c.stream));
-    const int e = *(int *)c.pinned;
-    if ((rc = split_error(fn, e, size, fill))) return rc;
-    for (int i = 0; i < 6; i++)
-        if (o[i].user && !o[i].dev && o[i].bytes) memcpy(o[i].user, g_sp_host.data() + o[i].off, o[i].bytes);
-    return TD_OK;
+    // host destinations: through g_sp_host, handed over only when the call succeeded
+    return outputs_finish_on_success(o, 6, d_err, g_sp_host, [&](int e) { return split_error(fn, e, size, fill); });
 }
 
 // A policy per model, structured as td_pool2_batched_v is: the tick's two launches take every model that is not a split model
@@ -1604,19 +1536,8 @@ int td_dispatch_batched(int batch, int n, const int32_t *cab_off, const int32_t 
     const size_t B = (size_t)batch;
     // the policy arrays on the host (validated there) and on the device
     const int32_t *pol[3] = {mode, stop_size, parts}, *d_pol[3] = {nullptr, nullptr, nullptr};
-    bool from_device = false;   // the device arrays come home in one synchronisation
-    for (int k = 0; k < 3; k++) {
-        if (!pol[k]) continue;
-        std::vector<int32_t> &h = g_polh[k];
-        h.resize(B);
-        if (is_device_ptr(pol[k])) {
-            TD_HIP(hipMemcpyAsync(h.data(), pol[k], sizeof(int32_t) * B, hipMemcpyDeviceToHost, c.stream));
-            from_device = true;
-        } else {
-            memcpy(h.data(), pol[k], sizeof(int32_t) * B);
-        }
-    }
-    if (from_device) TD_HIP(hipStreamSynchronize(c.stream));
+    // the device arrays come home in one synchronisation
+    if ((rc = host_copy({{mode, B, &g_polh[0]}, {stop_size, B, &g_polh[1]}, {parts, B, &g_polh[2]}}))) return rc;
     int nsol = 0, nsplit = 0, nl_split = 0, R = 1;
     for (int b = 0; b < batch; b++) {
         const int md = mode ? g_polh[0][b] : TD_DISPATCH_LCM_OPT;
@@ -1626,8 +1547,7 @@ int td_dispatch_batched(int batch, int n, const int32_t *cab_off, const int32_t 
             const int p = parts ? g_polh[2][b] : 4;
             if (nb > BATCH_NMAX)
                 return fail(TD_EINVAL, "%s: split model %d has %d cabs and %d requests, more than %d", fn, b, ns, nd, BATCH_NMAX);
-            if (p < 1 || p > 32) return fail(TD_EINVAL, "%s: parts[%d] = %d outside [1, 32]", fn, b, p);
-            if (size < p) return fail(TD_EINVAL, "%s: size = %d < parts[%d] = %d", fn, size, b, p);
+            if ((rc = split_refusal(fn, SPLIT_PARTS, b, p, size, dist, S, fill, batch, R))) return rc;
             const int ss = size / p;
             R = std::max(R, (size + ss - 1) / ss);
             nl_split = std::max(nl_split, nb);
@@ -1641,15 +1561,7 @@ int td_dispatch_batched(int batch, int n, const int32_t *cab_off, const int32_t 
             nsol = std::max(nsol, rest);
         }
     }
-    if (nsplit) {
-        if (dist && S < size) return fail(TD_EINVAL, "%s: the table has S = %d stands, fewer than size = %d", fn, S, size);
-        if (dist && fill < 1) return fail(TD_EINVAL, "%s: fill = %d < 1", fn, (int)fill);
-        if (!dist && (int64_t)size - 1 >= (int64_t)fill)
-            return fail(TD_EINVAL, "%s: the distance %d of the line's ends is not below fill = %d", fn, size - 1, (int)fill);
-        if (R >= SPLIT_RMAX) return fail(TD_EINTERNAL, "%s: %d ranges", fn, R);   // parts <= 32 gives at most 63
-        if ((int64_t)batch * R > INT_MAX / 2)
-            return fail(TD_EINVAL, "%s: %d cases of %d ranges are more than 2^30 region models", fn, batch, R);
-    }
+    if (nsplit && (rc = split_refusal(fn, SPLIT_CITY | SPLIT_RANGES, -1, 0, size, dist, S, fill, batch, R))) return rc;
     const void *p;
     for (int k = 0; k < 3; k++) {
         if (!pol[k]) continue;
@@ -1666,9 +1578,8 @@ int td_dispatch_batched(int batch, int n, const int32_t *cab_off, const int32_t 
                  {lcm_last_min, sizeof(int32_t) * B},  {kept_cabs, sizeof(int32_t) * B * N}, {kept_dems, sizeof(int32_t) * B * N},
                  {n_rest, sizeof(int32_t) * B},       {row_to_col, sizeof(int32_t) * B * N}, {total, sizeof(int64_t) * B},
                  {dual_bound, sizeof(int64_t) * B}};
-    size_t err_off;
-    if ((rc = outputs_prepare(o, 10, &err_off))) return rc;
-    int *d_err = (int *)((char *)g_out.p + err_off);
+    int *d_err;
+    if ((rc = outputs_prepare(g_out, o, 10, &d_err))) return rc;
     void *od[7];
     for (int k = 0; k < 7; k++) od[k] = o[k].dptr();
     // the range width of a case without a parts entry: 4 parts (parts == NULL), or any width for a case that is not split
@@ -1691,18 +1602,8 @@ int td_dispatch_batched(int batch, int n, const int32_t *cab_off, const int32_t 
             batch, nl_split, threshold, dp, in.cab_off, in.dem_off, in.dist, S, w.ws_req, w.rcab, w.rcab_idx, w.rdem, w.rdem_idx, w.cnt2,
             w.nrest, w.sum0, w.gap0, w.r2c2, w.tot2, w.dual2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_err);
     }
-    TD_HIP(hipGetLastError());
-    // host destinations: through g_sp_host (same layout as g_out), handed over only when the call succeeded
-    g_sp_host.resize(err_off);
-    for (int i = 0; i < 10; i++)
-        if (o[i].user && !o[i].dev && o[i].bytes)
-            TD_HIP(hipMemcpyAsync(g_sp_host.data() + o[i].off, (char *)g_out.p + o[i].off, o[i].bytes, hipMemcpyDeviceToHost, c.stream));
-    TD_HIP(hipMemcpyAsync(c.pinned, d_err, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    TD_HIP(hipStreamSynchronize(c.stream));
-    if ((rc = split_error(fn, *(int *)c.pinned, size, fill))) return rc;
-    for (int i = 0; i < 10; i++)
-        if (o[i].user && !o[i].dev && o[i].bytes) memcpy(o[i].user, g_sp_host.data() + o[i].off, o[i].bytes);
-    return TD_OK;
+    // host destinations: through g_sp_host, handed over only when the call succeeded
+    return outputs_finish_on_success(o, 10, d_err, g_sp_host, [&](int e) { return split_error(fn, e, size, fill); });
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // generator (a-10), x expansion and objective evaluation (a-7).  gfx950 only.
 #include <stdarg.h>
 
-#include "td_common.h"
+#include "td_stage.h"
 
 namespace td {
 
@@ -107,6 +107,53 @@ int copy_in(void *dst, const void *src, size_t bytes)
         src = slot;
     }
     TD_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, g_ctx.stream));
+    return TD_OK;
+}
+
+int host_copy(std::initializer_list<HostCopy> list)
+{
+    bool from_device = false;
+    for (const HostCopy &q : list) {
+        if (!q.src) continue;
+        q.h->resize(q.n);
+        if (!q.n) continue;
+        if (is_device_ptr(q.src)) {
+            TD_HIP(hipMemcpyAsync(q.h->data(), q.src, sizeof(int32_t) * q.n, hipMemcpyDeviceToHost, g_ctx.stream));
+            from_device = true;
+        } else {
+            memcpy(q.h->data(), q.src, sizeof(int32_t) * q.n);
+        }
+    }
+    if (from_device) TD_HIP(hipStreamSynchronize(g_ctx.stream));
+    return TD_OK;
+}
+
+int outputs_prepare(Buf &buf, Out *o, int k, int **d_err)
+{
+    size_t off = 0;
+    for (int i = 0; i < k; i++) {
+        o[i].dev = o[i].user && is_device_ptr(o[i].user);
+        o[i].off = off;
+        if (o[i].user && !o[i].dev) off += align256(o[i].bytes);
+    }
+    int rc = ensure(buf, off + 256);
+    if (rc) return rc;
+    for (int i = 0; i < k; i++) o[i].dev_ptr = o[i].dev ? o[i].user : (o[i].user ? (char *)buf.p + o[i].off : nullptr);
+    *d_err = (int *)((char *)buf.p + off);
+    TD_HIP(hipMemsetAsync(*d_err, 0, sizeof(int), g_ctx.stream));
+    return TD_OK;
+}
+
+int outputs_fetch(const Out *o, int k, const int *d_err, char *bounce, int *e)
+{
+    Ctx &c = g_ctx;
+    TD_HIP(hipGetLastError());
+    for (int i = 0; i < k; i++)
+        if (o[i].user && !o[i].dev && o[i].bytes)
+            TD_HIP(hipMemcpyAsync(bounce ? (void *)(bounce + o[i].off) : o[i].user, o[i].dev_ptr, o[i].bytes, hipMemcpyDeviceToHost, c.stream));
+    TD_HIP(hipMemcpyAsync(c.pinned, d_err, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    TD_HIP(hipStreamSynchronize(c.stream));
+    *e = *(int *)c.pinned;
     return TD_OK;
 }
 

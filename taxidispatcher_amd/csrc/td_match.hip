@@ -16,7 +16,7 @@
 
 #include <vector>
 
-#include "td_common.h"
+#include "td_stage.h"
 #include "td_match_core.h"
 #include "td_pool_rule.h"
 
@@ -271,28 +271,6 @@ Buf g_pool;                 // pool chunk: pair-cost slab, sizes, K, mates, tota
 Buf g_in[6];                // device copies of host inputs
 std::vector<int32_t> g_h;   // host copies (validation)
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-size_t lds_budget()
-{
-    static size_t cap = 0;
-    if (!cap) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx().device) != hipSuccess || v <= 0) {
-            (void)hipGetLastError();
-            v = 64 * 1024;
-        }
-        cap = std::min<size_t>((size_t)v, 160 * 1024) - 1024;
-    }
-    return cap;
-}
-
-template <class K>
-void lds_allow(K kernel, size_t shm)
-{
-    if (shm > 64 * 1024) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-}
-
 // solver state for `batch` models of up to nmax vertices: *lds = in LDS, else *ws = slices of *per bytes, one per workgroup;
 // *grid = the workgroups to launch
 int state_plan(int batch, int nmax, bool *lds, unsigned char **ws, size_t *per, int *grid)
@@ -310,63 +288,37 @@ int state_plan(int batch, int nmax, bool *lds, unsigned char **ws, size_t *per, 
     return TD_OK;
 }
 
-// one output array: the caller's device pointer, or a slice of g_res copied back to the caller's host array
-struct Out {
-    void *user;
-    size_t bytes, off;
-    bool dev;
-    void *dptr() const { return dev ? user : (user ? (char *)g_res.p + off : nullptr); }
-};
-
-int outputs_prepare(Out *o, int k, size_t *err_off)
+// what the matching kernels leave in the error word
+int match_finish(const char *fn, const Out *o, int k, const int *d_err)
 {
-    size_t off = 0;
-    for (int i = 0; i < k; i++) {
-        o[i].dev = o[i].user && is_device_ptr(o[i].user);
-        o[i].off = off;
-        if (o[i].user && !o[i].dev) off += align256(o[i].bytes);
-    }
-    *err_off = off;
-    int rc = ensure(g_res, off + 256);
-    if (rc) return rc;
-    TD_HIP(hipMemsetAsync((char *)g_res.p + off, 0, sizeof(int), ctx().stream));
-    return TD_OK;
-}
-
-int outputs_finish(const char *fn, const Out *o, int k, size_t err_off)
-{
-    Ctx &c = ctx();
-    TD_HIP(hipGetLastError());
-    for (int i = 0; i < k; i++)
-        if (o[i].user && !o[i].dev && o[i].bytes)
-            TD_HIP(hipMemcpyAsync(o[i].user, (char *)g_res.p + o[i].off, o[i].bytes, hipMemcpyDeviceToHost, c.stream));
-    TD_HIP(hipMemcpyAsync(c.pinned, (char *)g_res.p + err_off, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    TD_HIP(hipStreamSynchronize(c.stream));
-    const int e = *(int *)c.pinned;
-    if (e & ERR_POOL_RANGE)
-        return fail(TD_ERANGE, "%s: a pool cost, or a pool weight K - cost (K = floor(m/2) * cost span + 1), leaves the solver's "
-                    "integer range", fn);
-    if (e)
-        return fail(TD_EINTERNAL, "%s: a model failed (error word 0x%x: 1 defensive loop cap, 2 inconsistent state, 4 certificate "
-                    "violated, 8 weight range)", fn, e);
-    return TD_OK;
-}
-
-// host copy of n int32 values (host or device source)
-int host_copy(const int32_t *src, size_t n, std::vector<int32_t> &h)
-{
-    h.resize(n);
-    if (!n) return TD_OK;
-    if (is_device_ptr(src)) {
-        TD_HIP(hipMemcpyAsync(h.data(), src, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx().stream));
-        TD_HIP(hipStreamSynchronize(ctx().stream));
-    } else {
-        memcpy(h.data(), src, sizeof(int32_t) * n);
-    }
-    return TD_OK;
+    return outputs_finish(o, k, d_err, [fn](int e) {
+        if (e & ERR_POOL_RANGE)
+            return fail(TD_ERANGE, "%s: a pool cost, or a pool weight K - cost (K = floor(m/2) * cost span + 1), leaves the solver's "
+                        "integer range", fn);
+        if (e)
+            return fail(TD_EINTERNAL, "%s: a model failed (error word 0x%x: 1 defensive loop cap, 2 inconsistent state, 4 certificate "
+                        "violated, 8 weight range)", fn, e);
+        return (int)TD_OK;
+    });
 }
 
 }  // namespace
+
+size_t td::lds_budget()
+{
+    static size_t cap = 0;
+    static int device = -1;   // the answer is this device's: td_shutdown and a td_init elsewhere ask again
+    if (device != ctx().device) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx().device) != hipSuccess || v <= 0) {
+            (void)hipGetLastError();
+            v = 64 * 1024;
+        }
+        cap = std::min<size_t>((size_t)v, 160 * 1024) - 1024;
+        device = ctx().device;
+    }
+    return cap;
+}
 
 extern "C" {
 
@@ -402,14 +354,13 @@ int td_match_batched(int batch, int n, const int32_t *ns, const int32_t *weight,
     Out o[6] = {{mate, sizeof(int32_t) * B * N},          {total, sizeof(int64_t) * B},
                 {dual_bound, sizeof(int64_t) * B},       {dual_vertex, sizeof(int64_t) * B * N},
                 {blossom_parent, sizeof(int32_t) * B * 2 * N}, {dual_blossom, sizeof(int64_t) * B * N}};
-    size_t err_off;
-    if ((rc = outputs_prepare(o, 6, &err_off))) return rc;
+    int *d_err;
+    if ((rc = outputs_prepare(g_res, o, 6, &d_err))) return rc;
     bool lds;
     unsigned char *ws;
     size_t per;
     int grid;
     if ((rc = state_plan(batch, nmax, &lds, &ws, &per, &grid))) return rc;
-    int *d_err = (int *)((char *)g_res.p + err_off);
 #define TD_MATCH_ARGS                                                                                                               \
     batch, n, (const int32_t *)d_ns, (const int32_t *)d_w, ws, per, (int32_t *)o[0].dptr(), (int64_t *)o[1].dptr(),                 \
         (int64_t *)o[2].dptr(), (int64_t *)o[3].dptr(), (int32_t *)o[4].dptr(), (int64_t *)o[5].dptr(), d_err
@@ -420,7 +371,7 @@ int td_match_batched(int batch, int n, const int32_t *ns, const int32_t *weight,
         k_match_batched<false><<<grid, 64, 0, c.stream>>>(TD_MATCH_ARGS);
     }
 #undef TD_MATCH_ARGS
-    return outputs_finish(fn, o, 6, err_off);
+    return match_finish(fn, o, 6, d_err);
 }
 
 }  // extern "C"
@@ -444,15 +395,13 @@ int pool2_batched_impl(const char *fn, int batch, int n, const int32_t *off, con
     int rc;
     std::vector<int32_t> h_off;
     if ((rc = host_copy(off, (size_t)batch + 1, h_off))) return rc;
-    if (h_off[0] != 0) return fail(TD_EINVAL, "%s: off[0] = %d, not 0", fn, h_off[0]);
-    int nmax = 0;
-    for (int b = 0; b < batch; b++) {
-        const int m = h_off[b + 1] - h_off[b];
-        if (m < 0) return fail(TD_EINVAL, "%s: off decreases at model %d (%d -> %d)", fn, b, h_off[b], h_off[b + 1]);
-        if (m > n) return fail(TD_EINVAL, "%s: model %d has %d customers, more than n = %d", fn, b, m, n);
-        nmax = std::max(nmax, m);
-    }
-    const size_t tot_c = (size_t)h_off[batch];
+    Ragged rg;
+    if ((rc = ragged_check(fail, fn, "off", "model", h_off.data(), batch, &rg, [&](int b, int m) {
+            return m > n ? fail(TD_EINVAL, "%s: model %d has %d customers, more than n = %d", fn, b, m, n) : 0;
+        })))
+        return rc;
+    const int nmax = rg.longest;
+    const size_t tot_c = (size_t)rg.total;
     if (tot_c && (!from || !to)) return fail(TD_EINVAL, "%s: null from / to", fn);
     const void *d_optv = nullptr, *d_mlv = nullptr;
     if (opt_v) {
@@ -484,27 +433,26 @@ int pool2_batched_impl(const char *fn, int batch, int n, const int32_t *off, con
     const size_t B = (size_t)batch, H = (size_t)(n / 2);
     Out o[6] = {{cust_a, sizeof(int32_t) * B * H}, {cust_b, sizeof(int32_t) * B * H}, {plan, sizeof(int32_t) * B * H},
                 {cost, sizeof(int32_t) * B * H},   {n_pools, sizeof(int32_t) * B},    {total, sizeof(int64_t) * B}};
-    size_t err_off;
-    if ((rc = outputs_prepare(o, 6, &err_off))) return rc;
-    int *d_err = (int *)((char *)g_res.p + err_off);
+    int *d_err;
+    if ((rc = outputs_prepare(g_res, o, 6, &d_err))) return rc;
     // models in chunks whose pair-cost slabs take at most 256 MiB
     const size_t NN = std::max<size_t>((size_t)n * n, 1);
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(B, ((size_t)256 << 20) / (sizeof(int32_t) * NN)));
     const size_t Q = (size_t)chunk, Hs = std::max<size_t>(H, 1);
-    const size_t b_pc = align256(sizeof(int32_t) * Q * NN), b_ns = align256(sizeof(int32_t) * Q), b_k = align256(sizeof(int64_t) * Q),
-                 b_mate = align256(sizeof(int32_t) * Q * (size_t)std::max(n, 1)), b_tot = align256(sizeof(int64_t) * Q),
-                 b_pair = align256(sizeof(int32_t) * Q * Hs);
-    if ((rc = ensure(g_pool, b_pc + 2 * b_ns + b_k + b_mate + b_tot + 2 * b_pair + b_ns))) return rc;
-    char *p = (char *)g_pool.p;
-    int32_t *pc = (int32_t *)p;
-    int32_t *d_ns = (int32_t *)(p += b_pc);     // sizes as the greedy sees them
-    int32_t *d_nsm = (int32_t *)(p += b_ns);    // sizes as k_pool_match sees them
-    int64_t *d_K = (int64_t *)(p += b_ns);
-    int32_t *d_mate = (int32_t *)(p += b_k);
-    int64_t *d_tot = (int64_t *)(p += b_mate);
-    int32_t *d_rows = (int32_t *)(p += b_tot);
-    int32_t *d_cols = (int32_t *)(p += b_pair);
-    int32_t *d_np = (int32_t *)(p += b_pair);
+    int32_t *pc, *d_ns, *d_nsm, *d_mate, *d_rows, *d_cols, *d_np;
+    int64_t *d_K, *d_tot;
+    if ((rc = carve_buf(g_pool, [&](Carve &c) {
+            pc = c.take<int32_t>(Q * NN);
+            d_ns = c.take<int32_t>(Q);    // sizes as the greedy sees them
+            d_nsm = c.take<int32_t>(Q);   // sizes as k_pool_match sees them
+            d_K = c.take<int64_t>(Q);
+            d_mate = c.take<int32_t>(Q * (size_t)std::max(n, 1));
+            d_tot = c.take<int64_t>(Q);
+            d_rows = c.take<int32_t>(Q * Hs);
+            d_cols = c.take<int32_t>(Q * Hs);
+            d_np = c.take<int32_t>(Q);
+        })))
+        return rc;
     bool lds = false;
     unsigned char *ws = nullptr;
     size_t per = 0;
@@ -532,7 +480,7 @@ int pool2_batched_impl(const char *fn, int batch, int n, const int32_t *off, con
                                                         (int32_t *)o[0].dptr(), (int32_t *)o[1].dptr(), (int32_t *)o[2].dptr(),
                                                         (int32_t *)o[3].dptr(), (int32_t *)o[4].dptr(), (int64_t *)o[5].dptr());
     }
-    return outputs_finish(fn, o, 6, err_off);
+    return match_finish(fn, o, 6, d_err);
 }
 
 }  // namespace

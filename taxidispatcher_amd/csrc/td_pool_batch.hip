@@ -21,7 +21,7 @@
 #include <utility>
 #include <vector>
 
-#include "td_common.h"
+#include "td_stage.h"
 #include "td_pool_core.h"
 
 using namespace td;
@@ -394,21 +394,6 @@ __global__ void k_pooln_batched_copy(int batch, int per_model, const int32_t *__
 Buf g_slab, g_stage, g_err;
 std::vector<int32_t> g_h;
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int host_copy(const int32_t *src, size_t n, std::vector<int32_t> &h)
-{
-    h.resize(n);
-    if (!n) return TD_OK;
-    if (is_device_ptr(src)) {
-        TD_HIP(hipMemcpyAsync(h.data(), src, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx().stream));
-        TD_HIP(hipStreamSynchronize(ctx().stream));
-    } else {
-        memcpy(h.data(), src, sizeof(int32_t) * n);
-    }
-    return TD_OK;
-}
-
 }  // namespace
 
 void td::pool_batch_release_workspace()
@@ -435,32 +420,38 @@ extern "C" int td_pool_n_batched(int k, int batch, int n, const int32_t *off, co
     if (!n_pools || (n / k > 0 && !pools)) return fail(TD_EINVAL, "%s: null output array", fn);
     int rc;
     if ((rc = host_copy(off, (size_t)batch + 1, g_h))) return rc;
-    if (g_h[0] != 0) return fail(TD_EINVAL, "%s: off[0] = %d, not 0", fn, g_h[0]);
-    for (int b = 0; b < batch; b++) {
-        const int m = g_h[b + 1] - g_h[b];
-        if (m < 0) return fail(TD_EINVAL, "%s: off decreases at model %d (%d -> %d)", fn, b, g_h[b], g_h[b + 1]);
-        if (m > n) return fail(TD_EINVAL, "%s: model %d has %d requests, more than n = %d", fn, b, m, n);
-    }
-    const size_t B = (size_t)batch, R = (size_t)g_h[batch], rec = (size_t)(2 * k + 1), per = (size_t)(n / k) * rec;
+    Ragged rg;
+    if ((rc = ragged_check(fail, fn, "off", "model", g_h.data(), batch, &rg, [&](int b, int m) {
+            return m > n ? fail(TD_EINVAL, "%s: model %d has %d requests, more than n = %d", fn, b, m, n) : 0;
+        })))
+        return rc;
+    const size_t B = (size_t)batch, R = (size_t)rg.total, rec = (size_t)(2 * k + 1), per = (size_t)(n / k) * rec;
     if (R && (!from || !to || !max_wait || !max_loss)) return fail(TD_EINVAL, "%s: null request array", fn);
     // one staging block, grown in 4 MiB steps: host inputs, then the results of every model
     const int32_t *h_in[6] = {off, from, to, max_wait, max_loss, first};
     const size_t n_in[6] = {B + 1, R, R, R, R, first ? 2 * B : 0};
-    size_t o_in[6], at = 0;
-    for (int q = 0; q < 6; q++) {
-        o_in[q] = at;
-        if (n_in[q] && !is_device_ptr(h_in[q])) at += align256(sizeof(int32_t) * n_in[q]);
-    }
-    const size_t o_pools = at, o_np = o_pools + align256(sizeof(int32_t) * B * per), o_nh = o_np + align256(sizeof(int32_t) * B),
-                 o_tot = o_nh + align256(sizeof(int64_t) * B), bytes = o_tot + align256(sizeof(int64_t) * B);
-    if ((rc = ensure(g_stage, (bytes + ((size_t)4 << 20) - 1) & ~(((size_t)4 << 20) - 1)))) return rc;
+    bool stage[6];
+    for (int q = 0; q < 6; q++) stage[q] = n_in[q] && !is_device_ptr(h_in[q]);
+    int32_t *s_in[6], *s_pools, *s_np;
+    long long *s_nh, *s_tot;
+    auto layout = [&](Carve &cv) {
+        for (int q = 0; q < 6; q++) s_in[q] = cv.take<int32_t>(stage[q] ? n_in[q] : 0);
+        s_pools = cv.take<int32_t>(B * per);
+        s_np = cv.take<int32_t>(B);
+        s_nh = cv.take<long long>(B);
+        s_tot = cv.take<long long>(B);
+    };
+    Carve size;
+    layout(size);
+    if ((rc = ensure(g_stage, (size.at + ((size_t)4 << 20) - 1) & ~(((size_t)4 << 20) - 1)))) return rc;
+    Carve block(g_stage.p);
+    layout(block);
     const int32_t *d_in[6];
     for (int q = 0; q < 6; q++) {
         d_in[q] = h_in[q];
-        if (n_in[q] && !is_device_ptr(h_in[q])) {
-            int32_t *dst = (int32_t *)((char *)g_stage.p + o_in[q]);
-            TD_HIP(hipMemcpyAsync(dst, q == 0 ? g_h.data() : h_in[q], sizeof(int32_t) * n_in[q], hipMemcpyHostToDevice, c.stream));
-            d_in[q] = dst;
+        if (stage[q]) {
+            TD_HIP(hipMemcpyAsync(s_in[q], q == 0 ? g_h.data() : h_in[q], sizeof(int32_t) * n_in[q], hipMemcpyHostToDevice, c.stream));
+            d_in[q] = s_in[q];
         }
     }
     const void *d_dist = nullptr;
@@ -471,8 +462,6 @@ extern "C" int td_pool_n_batched(int k, int batch, int n, const int32_t *off, co
     if ((rc = ensure(g_err, 256))) return rc;
     PnbErr *d_err = (PnbErr *)g_err.p;
     TD_HIP(hipMemsetAsync(d_err, 0, sizeof(PnbErr), c.stream));
-    int32_t *s_pools = (int32_t *)((char *)g_stage.p + o_pools), *s_np = (int32_t *)((char *)g_stage.p + o_np);
-    long long *s_nh = (long long *)((char *)g_stage.p + o_nh), *s_tot = (long long *)((char *)g_stage.p + o_tot);
     const int grid = std::min(batch, grid_cap);
     {
         ProfScope ps(TD_K_LCM);

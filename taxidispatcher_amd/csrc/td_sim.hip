@@ -60,33 +60,15 @@ struct Head {
     int32_t n_dem, n_sup, n_dem2, n_ks, n_kd;
 };
 
-struct td_sim {
+struct td_sim : SimDev, SimPin {   // td_sim_layout.h: every device array of the handle, and the pinned block
     World w;
     int max_non_lcm = 0;
     int cap = 1;                 // capacity of every per-tick list: max(n_cabs, n_req, 1)
     int words = 0;               // of one stand bitset
-    Buf mem;                     // every device array of the handle
-    Head *head = nullptr;        // device: Ctl and the per-tick list sizes
+    Buf mem;                     // the device block
+    Head *head = nullptr;        // = head_blk
     Ctl *ctl = nullptr;          // = &head->ctl
-    uint32_t *bits = nullptr;    // cab bits, then request bits: the batched layout at b == 0
-    // a table world: the table (= w.dist), the neighbour bit matrices [n_stands][words], the near bitsets (laid out like bits)
-    int32_t *dist = nullptr;
-    uint32_t *nb_dem = nullptr, *nb_sup = nullptr, *near = nullptr;
-    int32_t *blockcnt = nullptr;
-    // temp lists: demand before pooling, supply, demand after pooling, kept lists
-    int32_t *dem_idx, *dem_from, *dem_to;
-    int32_t *sup_cab, *sup_to;
-    int32_t *d2_idx, *d2_from, *d2_partner, *d2_plan, *d2_cost;
-    int32_t *ks_cab, *ks_to;
-    int32_t *kd_idx, *kd_from, *kd_partner, *kd_plan, *kd_cost;
-    int32_t *isb, *ainfo;                       // analyzePool: is a B customer / first plan as the A customer
-    int32_t *pl_a, *pl_b, *pl_plan, *pl_cost;   // td_pool2's plan list
-    int32_t *pair_cab, *pair_dem;               // first pair of a cab / request
-    int32_t *in_rows, *in_cols, *in_r2c;        // this tick's decisions
-    int32_t *tmp;                               // td_sim_state: client ids
-    // pinned host block: the head's read-back, then td_tick's host results for td_sim_step
-    void *pin = nullptr;
-    int32_t *h_rows, *h_cols, *h_kc, *h_kd, *h_r2c;
+    void *pin = nullptr;         // the pinned block: the head's read-back at its front
     // sequencing
     int last_t = -1;
     bool begun = false;          // a tick with demand waits for td_sim_apply
@@ -108,9 +90,8 @@ struct td_sim {
 
 namespace {
 
-constexpr int HEAD_INTS = 64;   // ints reserved for the head block
 constexpr int SIM_POOL_OPT_NMAX = 2048;   // largest model of td_pool2_batched: the optimum of a tick is one such model
-static_assert(sizeof(Head) <= sizeof(int32_t) * HEAD_INTS && sizeof(Head) <= 256, "the head fits its device block and the pinned block's front");
+static_assert(sizeof(Head) <= sizeof(int32_t) * SIM_HEAD_INTS && sizeof(Head) <= SIM_PIN_HEAD, "the head fits its device block and the pinned block's front");
 
 // world 0's segment of a list: it begins at 0; its size is the host's (n), or still on the device (dev non-null: a kept list)
 struct Seg1 {
@@ -422,100 +403,32 @@ int sim_create(int n_cabs, int n_stands, int drop_time, int max_non_lcm, int32_t
     const size_t nr = (size_t)std::max(n_req, 1), nc = (size_t)n_cabs, cap = std::max(nr, nc), words = (size_t)(n_stands + 31) / 32;
     s->cap = (int)cap;
     s->words = (int)words;
-    const size_t ns = (size_t)n_stands, table_ints = dist ? ns * ns + 2 * ns * words + 2 * words : 0;
-    const size_t ints = table_ints + HEAD_INTS + 2 * words + (cap + CB - 1) / CB + 9 * nr + 5 * nc + 3 * nr + 2 * nc + 5 * nr + 2 * nc + 5 * nr + 2 * nr + 4 * (nr / 2 + 1) +
-                        nc + nr + 3 * cap + cap + 64;
-    rc = ensure(s->mem, sizeof(int32_t) * ints);
+    const SimDims dims{nc, nr, cap, words, (cap + CB - 1) / CB, (size_t)n_stands, dist != nullptr};
+    rc = carve_buf(s->mem, [&](Carve &cv) { sim_layout(cv, dims, *s); });
     if (rc) {
         delete s;
         return rc;
     }
-    int32_t *p = (int32_t *)s->mem.p;
-    auto take = [&](size_t k) {
-        int32_t *r = p;
-        p += k;
-        return r;
-    };
-    s->head = (Head *)take(HEAD_INTS);
+    s->head = (Head *)s->head_blk;
     s->ctl = &s->head->ctl;
-    // the cab bits and the request bits must stay adjacent, in this order (and so the two near bitsets): the kernels address
-    // them as world 0 of the batched layout, and sim_begin clears both with ONE memset
-    s->bits = (uint32_t *)take(2 * words);
-    if (dist) {
-        s->near = (uint32_t *)take(2 * words);
-        s->nb_dem = (uint32_t *)take(ns * words);
-        s->nb_sup = (uint32_t *)take(ns * words);
-        s->dist = take(ns * ns);
-    }
-    s->blockcnt = take((cap + CB - 1) / CB);
     World &w = s->w;
-    w.n_cabs = n_cabs;
-    w.n_req = n_req;
-    w.n_stands = n_stands;
-    w.drop_time = drop_time;
-    w.big_cost = big_cost;
-    w.dist = s->dist;
-    int32_t *rid = take(nr), *rfrom = take(nr), *rto = take(nr), *rat = take(nr);
-    w.r_id = rid;
-    w.r_from = rfrom;
-    w.r_to = rto;
-    w.r_at = rat;
-    w.r_cab = take(nr);
-    w.r_pick = take(nr);
-    w.r_pid = take(nr);
-    w.r_plan = take(nr);
-    w.r_pcost = take(nr);
-    w.c_from = take(nc);
-    w.c_to = take(nc);
-    w.c_clnt = take(nc);
-    w.c_onb = take(nc);
-    w.c_start = take(nc);
-    s->dem_idx = take(nr);
-    s->dem_from = take(nr);
-    s->dem_to = take(nr);
-    s->sup_cab = take(nc);
-    s->sup_to = take(nc);
-    s->d2_idx = take(nr);
-    s->d2_from = take(nr);
-    s->d2_partner = take(nr);
-    s->d2_plan = take(nr);
-    s->d2_cost = take(nr);
-    s->ks_cab = take(nc);
-    s->ks_to = take(nc);
-    s->kd_idx = take(nr);
-    s->kd_from = take(nr);
-    s->kd_partner = take(nr);
-    s->kd_plan = take(nr);
-    s->kd_cost = take(nr);
-    s->isb = take(nr);
-    s->ainfo = take(nr);
-    s->pl_a = take(nr / 2 + 1);
-    s->pl_b = take(nr / 2 + 1);
-    s->pl_plan = take(nr / 2 + 1);
-    s->pl_cost = take(nr / 2 + 1);
-    s->pair_cab = take(nc);
-    s->pair_dem = take(nr);
-    s->in_rows = take(cap);
-    s->in_cols = take(cap);
-    s->in_r2c = take(cap);
-    s->tmp = take(cap);
+    w = World{n_cabs, n_req, n_stands, drop_time, big_cost};
+    set_tables(w, *s, s->dist);
     auto bail = [&](int code) {
         td_sim_destroy(s);
         return code;
     };
-    hipError_t e = hipHostMalloc(&s->pin, 256 + sizeof(int32_t) * 5 * cap, hipHostMallocDefault);
+    Carve pin_size;
+    sim_pin_layout(pin_size, dims, *s);
+    hipError_t e = hipHostMalloc(&s->pin, pin_size.at, hipHostMallocDefault);
     if (e != hipSuccess) {
         s->pin = nullptr;
         return bail(hip_fail(e, "hipHostMalloc(td_sim)"));
     }
-    int32_t *hp = (int32_t *)((char *)s->pin + 256);
-    s->h_rows = hp;
-    s->h_cols = hp + cap;
-    s->h_kc = hp + 2 * cap;
-    s->h_kd = hp + 3 * cap;
-    s->h_r2c = hp + 4 * cap;
-    if ((e = hipMemsetAsync(s->ctl, 0, sizeof(int32_t) * HEAD_INTS, c.stream)) != hipSuccess) return bail(hip_fail(e, "hipMemsetAsync"));
-    int32_t *dst[4] = {rid, rfrom, rto, rat};
+    Carve pin(s->pin);
+    sim_pin_layout(pin, dims, *s);
+    if ((e = hipMemsetAsync(s->ctl, 0, sizeof(int32_t) * SIM_HEAD_INTS, c.stream)) != hipSuccess) return bail(hip_fail(e, "hipMemsetAsync"));
+    int32_t *dst[4] = {s->r_id, s->r_from, s->r_to, s->r_at};
     for (int q = 0; q < 4 && n_req; q++)
         if ((e = hipMemcpyAsync(dst[q], h.data() + (size_t)q * n_req, sizeof(int32_t) * (size_t)n_req, hipMemcpyHostToDevice, c.stream)) != hipSuccess)
             return bail(hip_fail(e, "hipMemcpyAsync(request table)"));

@@ -17,7 +17,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "td_common.h"
+#include "td_sim_layout.h"   // (brings td_stage.h and the HIP runtime)
 #include "td_sim_core.h"
 
 #ifndef TD_NEAR_WPG
@@ -672,6 +672,15 @@ inline int get(int32_t *dst, const int32_t *src, size_t n)
     return TD_OK;
 }
 
+// the world's tables where the handle's layout put them; dist == nullptr: the world lives on the line
+inline void set_tables(World &w, const WorldDev &d, const int32_t *dist)
+{
+    w.dist = dist;
+    w.r_id = d.r_id, w.r_from = d.r_from, w.r_to = d.r_to, w.r_at = d.r_at;
+    w.r_cab = d.r_cab, w.r_pick = d.r_pick, w.r_pid = d.r_pid, w.r_plan = d.r_plan, w.r_pcost = d.r_pcost;
+    w.c_from = d.c_from, w.c_to = d.c_to, w.c_clnt = d.c_clnt, w.c_onb = d.c_onb, w.c_start = d.c_start;
+}
+
 // the request file on the host once: h = ids, from, to, at behind one another (n_req each; host or device sources)
 inline int load_requests(int n_req, const int32_t *id, const int32_t *from, const int32_t *to, const int32_t *at, std::vector<int32_t> &h)
 {
@@ -743,19 +752,18 @@ inline int ev_setup(EvLog &ev, uint32_t kinds, int64_t capacity, int B, size_t n
 {
     ev_off(ev);
     if (!kinds) return TD_OK;
-    const size_t chunks = (vmax + CB - 1) / CB, slots = nc + nr + 2 * (nc + nr) + 2 * nc;
-    const size_t ints = 8 + 8 * (size_t)capacity + 4 * slots + (size_t)B * chunks + (size_t)B + 16;
-    int rc = td::ensure(ev.mem, sizeof(int32_t) * ints);
+    const size_t chunks = (vmax + CB - 1) / CB;
+    int rc = td::carve_buf(ev.mem, [&](td::Carve &c) {
+        ev.ctl = c.take<EvCtl>(1);
+        ev.log = c.take<int4>(2 * (size_t)capacity);
+        ev.st_arr = c.take<int4>(nc);
+        ev.st_drop = c.take<int4>(nr);
+        ev.st_pairs = c.take<int4>(2 * (nc + nr));
+        ev.st_sol = c.take<int4>(2 * nc);
+        ev.cnt = c.take<int32_t>((size_t)B * chunks);
+        ev.woff = c.take<int32_t>((size_t)B);
+    });
     if (rc) return rc;
-    int32_t *p = (int32_t *)ev.mem.p;
-    ev.ctl = (EvCtl *)p;
-    ev.log = (int4 *)(p + 8);
-    ev.st_arr = ev.log + 2 * (size_t)capacity;
-    ev.st_drop = ev.st_arr + nc;
-    ev.st_pairs = ev.st_drop + nr;
-    ev.st_sol = ev.st_pairs + 2 * (nc + nr);
-    ev.cnt = (int32_t *)(ev.st_sol + 2 * nc);
-    ev.woff = ev.cnt + (size_t)B * chunks;
     ev.chunks = (int)chunks;
     ev.cap = capacity;
     hipError_t e = hipMemsetAsync(ev.ctl, 0, sizeof(EvCtl), td::ctx().stream);

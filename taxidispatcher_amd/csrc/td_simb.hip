@@ -48,8 +48,6 @@ using namespace tdsim;
 
 namespace {
 constexpr int SIMB_NMAX = 2048;   // largest model of td_tick_batched / td_pool2_batched
-constexpr int N_OFF = 7;          // offset arrays of the head block
-constexpr int N_PER = 4;          // per-world words of the head block
 }  // namespace
 
 // decisions of a tick: packed ragged arrays from the caller (stride == 0), or td_tick_batched's strided outputs
@@ -94,7 +92,7 @@ struct SimbPlans {
     __device__ __forceinline__ int base(int b) const { return ragged ? pl_off[b] >> 1 : b * pool_h; }
 };
 
-struct td_simb {
+struct td_simb : SimbDev, SimbPin {   // td_sim_layout.h: every device array of the handle, and the pinned block
     World w;                     // the concatenated tables
     int B = 0, max_non_lcm = 0;
     int words = 0;               // of one stand bitset
@@ -103,33 +101,11 @@ struct td_simb {
     size_t pool_cap = 0, in_cap = 0;
     std::vector<int32_t> cab_off, req_off;   // host copies
     Buf mem;
-    // head block (device) and its pinned mirror: Ctl[B], the error word, the offset arrays, the per-world words
-    int32_t *head = nullptr;
+    // head block (device) and its pinned mirror h_head: Ctl[B], the error word, the offset arrays, the per-world words
+    int32_t *head = nullptr;     // = ctl_blk
     size_t head_ints = 0;
     Ctl *ctl = nullptr;
-    int32_t *gerr = nullptr;
-    int32_t *dem_off, *sup_off, *pl_off, *d2_off, *tk_off, *ks_off, *kd_off;
-    int32_t *n_pools, *tk_np, *tk_lm, *tk_rest;
-    int32_t *d_cab_off = nullptr, *d_req_off = nullptr;
-    uint32_t *bits = nullptr;    // world b: cab bits at (2 b) * words, request bits at (2 b + 1) * words
-    // a table batch: the table (= w.dist), the neighbour bit matrices [n_stands][words] and the near bitsets, laid out like bits
-    int32_t *dist = nullptr;
-    uint32_t *nb_dem = nullptr, *nb_sup = nullptr, *near = nullptr;
-    int32_t *cnt_a, *cnt_b;
-    int32_t *dem_idx, *dem_from, *dem_to, *pl_from, *pl_to;
-    int32_t *sup_cab, *sup_to;
-    int32_t *d2_idx, *d2_from, *d2_partner, *d2_plan, *d2_cost, *tk_from;
-    int32_t *ks_cab, *ks_to;
-    int32_t *kd_idx, *kd_from, *kd_partner, *kd_plan, *kd_cost;
-    int32_t *isb, *ainfo;
-    int32_t *pa, *pb, *pp, *pc;                 // the pool calls' plan lists
-    int64_t *p_total, *tk_total;
-    int32_t *pair_cab, *pair_dem;
-    int32_t *in_rows, *in_cols, *in_r2c, *in_pair_off, *in_r2c_off, *in_solved;
-    int32_t *tk_rows, *tk_cols, *tk_r2c;        // td_tick_batched's strided outputs
-    int32_t *tmp;
     void *pin = nullptr;
-    int32_t *h_head = nullptr, *h_stage = nullptr;
     // sequencing
     int last_t = -1;
     bool begun = false;
@@ -141,14 +117,12 @@ struct td_simb {
     // td_simb_pooling: the policy of every world from the next begin on.  pool_set == false: the handle pools as it always did
     bool pool_set = false, has_none = false;
     std::vector<int32_t> pool_mode, pool_opt;   // TD_POOL_*; 1 where the mode is TD_POOL_OPTIMAL
-    std::vector<double> pool_ml;
-    int32_t *d_none = nullptr;                  // device [B]: 1 = the world is left out of the pool lists (read only when has_none)
+    std::vector<double> pool_ml;                // (d_none is read only when has_none)
     std::vector<int32_t> h_npool, h_pbase;      // this tick's plans per world and where they begin in pa / pb / pp / pc
     // td_simb_dispatch: the dispatch policy of every world from the next begin on.  disp_set == false: the handle dispatches as it
     // always did, through td_tick_batched and the one-number instantiations of the world kernels
     bool disp_set = false;
-    std::vector<int32_t> disp_mode, disp_mnl, disp_parts;   // host mirrors: what td_dispatch_batched is handed
-    int32_t *d_rule = nullptr;                              // device [B]: rule(b), read by the world kernels when disp_set
+    std::vector<int32_t> disp_mode, disp_mnl, disp_parts;   // host mirrors: what td_dispatch_batched is handed; d_rule[b] = rule(b)
     // the model size above which the LCM ran in world b (LcmRuleB of td_sim_world.h)
     int rule(int b) const
     {
@@ -233,20 +207,6 @@ __global__ __launch_bounds__(CB) void k_scatter(const int32_t *__restrict__ off,
 
 inline int nchunks(int n) { return std::max(1, (n + CB - 1) / CB); }
 
-// host copy of n values (host or device source)
-int host_copy(const int32_t *src, size_t n, std::vector<int32_t> &h)
-{
-    h.resize(n);
-    if (!n) return TD_OK;
-    if (is_device_ptr(src)) {
-        TD_HIP(hipMemcpyAsync(h.data(), src, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx().stream));
-        TD_HIP(hipStreamSynchronize(ctx().stream));
-    } else {
-        memcpy(h.data(), src, sizeof(int32_t) * n);
-    }
-    return TD_OK;
-}
-
 // the head block on the host: every world's Ctl, the error word, the offset arrays, the per-world words, in ONE copy
 int read_head(td_simb *s)
 {
@@ -301,7 +261,7 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     int rc;
     for (int q = 0; q < 4 * B; q++) info[q] = 0;
     // this tick's offsets and per-world words start from zero; the sums and the error word stay
-    TD_HIP(hipMemsetAsync(s->dem_off, 0, sizeof(int32_t) * ((size_t)N_OFF * (B + 1) + (size_t)N_PER * B), c.stream));
+    TD_HIP(hipMemsetAsync(s->dem_off, 0, sizeof(int32_t) * (SIMB_N_OFF * (B + 1) + SIMB_N_PER * B), c.stream));
     TD_HIP(hipMemsetAsync(s->bits, 0, sizeof(uint32_t) * 2 * (size_t)s->words * B, c.stream));
     const size_t shm = sizeof(uint32_t) * (size_t)s->words;
     const int gc = nchunks(s->max_cabs), gr = nchunks(s->max_req);
@@ -532,16 +492,13 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
 // offsets [B + 1] from the caller: start at 0, never decrease, world b's segment at most cap(b) long
 int check_offsets(const td_simb *s, const char *what, const std::vector<int32_t> &h, int *longest)
 {
-    *longest = 0;
-    if (h[0] != 0) return fail(TD_EINVAL, "td_simb_apply: %s[0] = %d, not 0", what, h[0]);
-    for (int b = 0; b < s->B; b++) {
-        const int m = h[b + 1] - h[b];
+    Ragged rg;
+    int rc = ragged_check(fail, "td_simb_apply", what, "world", h.data(), s->B, &rg, [&](int b, int m) {
         const int cap = std::max(std::max(s->cab_off[b + 1] - s->cab_off[b], s->req_off[b + 1] - s->req_off[b]), 1);
-        if (m < 0) return fail(TD_EINVAL, "td_simb_apply: %s decreases at world %d (%d -> %d)", what, b, h[b], h[b + 1]);
-        if (m > cap) return fail(TD_EINVAL, "td_simb_apply: world %d's segment of %s has %d entries, more than %d", b, what, m, cap);
-        *longest = std::max(*longest, m);
-    }
-    return TD_OK;
+        return m > cap ? fail(TD_EINVAL, "td_simb_apply: world %d's segment of %s has %d entries, more than %d", b, what, m, cap) : 0;
+    });
+    *longest = rg.longest;
+    return rc;
 }
 
 }  // namespace
@@ -566,19 +523,20 @@ static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_
     int rc;
     std::vector<int32_t> hc, ho;
     if ((rc = host_copy(n_cabs, (size_t)B, hc)) || (rc = host_copy(req_off, (size_t)B + 1, ho))) return rc;
-    if (ho[0] != 0) return fail(TD_EINVAL, "td_simb_create: req_off[0] = %d, not 0", ho[0]);
+    Ragged rg;
+    if ((rc = ragged_check(fail, "td_simb_create", "req_off", "world", ho.data(), B, &rg, [&](int b, int) {
+            return hc[b] < 1 || hc[b] > SIMB_NMAX ? fail(TD_EINVAL, "td_simb_create: world %d has %d cabs, outside 1 .. %d", b, hc[b], SIMB_NMAX) : 0;
+        })))
+        return rc;
     std::vector<int32_t> cab_off((size_t)B + 1, 0);
-    int max_cabs = 0, max_req = 0;
+    int max_cabs = 0;
     size_t in_cap = 0;
     for (int b = 0; b < B; b++) {
-        if (hc[b] < 1 || hc[b] > SIMB_NMAX) return fail(TD_EINVAL, "td_simb_create: world %d has %d cabs, outside 1 .. %d", b, hc[b], SIMB_NMAX);
-        if (ho[b + 1] < ho[b]) return fail(TD_EINVAL, "td_simb_create: req_off decreases at world %d (%d -> %d)", b, ho[b], ho[b + 1]);
         cab_off[b + 1] = cab_off[b] + hc[b];
         max_cabs = std::max(max_cabs, hc[b]);
-        max_req = std::max(max_req, ho[b + 1] - ho[b]);
         in_cap += (size_t)std::max(std::max(hc[b], ho[b + 1] - ho[b]), 1);
     }
-    const int n_req = ho[B], nc_tot = cab_off[B];
+    const int max_req = rg.longest, n_req = rg.total, nc_tot = cab_off[B];
     if (n_req && (!req_id || !req_from || !req_to || !req_at)) return fail(TD_EINVAL, "null request array");
     // the request files on the host once: ids unique within a world and not negative, stands inside the line, times not negative
     std::vector<int32_t> h;
@@ -607,129 +565,34 @@ static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_
     s->pool_mode.assign((size_t)B, TD_POOL_GREEDY);
     s->pool_ml.assign((size_t)B, 0.0);
     for (std::vector<int64_t> *v : {&s->lcm_used, &s->max_model, &s->max_solver, &s->max_pool_mem, &s->max_pool}) v->assign((size_t)B, 0);
-    const size_t nb = (size_t)B, nr = (size_t)std::max(n_req, 1), nc = (size_t)nc_tot, words = (size_t)s->words;
-    const size_t n_cnt = nb * (size_t)nchunks(std::max(max_cabs, max_req));
+    const size_t nb = (size_t)B, nr = (size_t)std::max(n_req, 1), nc = (size_t)nc_tot;
     s->pool_cap = std::max(nb * (size_t)s->hcap, nr / 2 + 1);
-    const size_t tk_cap = nb * (size_t)s->ncap;
-    s->head_ints = 16 * nb + 16 + (size_t)N_OFF * (nb + 1) + (size_t)N_PER * nb;
-    const size_t ns = (size_t)n_stands, table_ints = dist ? ns * ns + 2 * ns * words + 2 * words * nb : 0;   // table, matrices, near bitsets
-    const size_t ints = table_ints + s->head_ints + 2 * (nb + 1) + 2 * words * nb + 2 * n_cnt + 9 * nr + 5 * nc   // head, offsets, bits, counts, tables
-                        + 5 * nr + 2 * nc + 6 * nr + 2 * nc + 5 * nr + 2 * nr                        // dem / pl, sup, d2 / tk, ks, kd, isb / ainfo
-                        + 4 * s->pool_cap + 4 * nb + nc + nr                                         // plans, two int64 [B], pair maps
-                        + 3 * in_cap + 2 * (nb + 1) + nb + 3 * tk_cap + std::max<size_t>(max_cabs, 1) + 2 * nb + 64;   // .., tmp, d_none, d_rule
-    rc = ensure(s->mem, sizeof(int32_t) * ints);
+    const SimbDims dims{nb, nc, nr, (size_t)s->words, (size_t)n_stands, nb * (size_t)nchunks(std::max(max_cabs, max_req)), s->pool_cap, in_cap,
+                        nb * (size_t)s->ncap, std::max<size_t>(max_cabs, 1), dist != nullptr};
+    s->head_ints = dims.head_ints();
+    rc = carve_buf(s->mem, [&](Carve &cv) { simb_layout(cv, dims, *s); });
     if (rc) {
         delete s;
         return rc;
     }
-    int32_t *p = (int32_t *)s->mem.p;
-    auto take = [&](size_t k) {
-        int32_t *r = p;
-        p += k;
-        return r;
-    };
-    s->p_total = (int64_t *)take(2 * nb);   // the 64-bit arrays first: 8-byte aligned, and so is the head (Ctl holds 64-bit sums)
-    s->tk_total = (int64_t *)take(2 * nb);
-    s->head = p;
-    s->ctl = (Ctl *)take(16 * nb);
-    s->gerr = take(16);
-    s->dem_off = take(nb + 1);   // the seven offset arrays and the four per-world arrays are one block (zeroed per tick)
-    s->sup_off = take(nb + 1);
-    s->pl_off = take(nb + 1);
-    s->d2_off = take(nb + 1);
-    s->tk_off = take(nb + 1);
-    s->ks_off = take(nb + 1);
-    s->kd_off = take(nb + 1);
-    s->n_pools = take(nb);
-    s->tk_np = take(nb);
-    s->tk_lm = take(nb);
-    s->tk_rest = take(nb);
-    s->d_cab_off = take(nb + 1);
-    s->d_req_off = take(nb + 1);
-    s->bits = (uint32_t *)take(2 * words * nb);
-    s->cnt_a = take(n_cnt);
-    s->cnt_b = take(n_cnt);
+    s->head = (int32_t *)s->ctl_blk;
+    s->ctl = (Ctl *)s->ctl_blk;
     World &w = s->w;
-    w.n_cabs = nc_tot;
-    w.n_req = n_req;
-    w.n_stands = n_stands;
-    w.drop_time = drop_time;
-    w.big_cost = big_cost;
-    if (dist) {   // one city for the whole batch
-        s->near = (uint32_t *)take(2 * words * nb);
-        s->nb_dem = (uint32_t *)take(ns * words);
-        s->nb_sup = (uint32_t *)take(ns * words);
-        s->dist = take(ns * ns);
-    }
-    w.dist = s->dist;   // nullptr: the worlds of the batch live on the line
-    int32_t *rid = take(nr), *rfrom = take(nr), *rto = take(nr), *rat = take(nr);
-    w.r_id = rid;
-    w.r_from = rfrom;
-    w.r_to = rto;
-    w.r_at = rat;
-    w.r_cab = take(nr);
-    w.r_pick = take(nr);
-    w.r_pid = take(nr);
-    w.r_plan = take(nr);
-    w.r_pcost = take(nr);
-    w.c_from = take(nc);
-    w.c_to = take(nc);
-    w.c_clnt = take(nc);
-    w.c_onb = take(nc);
-    w.c_start = take(nc);
-    s->dem_idx = take(nr);
-    s->dem_from = take(nr);
-    s->dem_to = take(nr);
-    s->pl_from = take(nr);
-    s->pl_to = take(nr);
-    s->sup_cab = take(nc);
-    s->sup_to = take(nc);
-    s->d2_idx = take(nr);
-    s->d2_from = take(nr);
-    s->d2_partner = take(nr);
-    s->d2_plan = take(nr);
-    s->d2_cost = take(nr);
-    s->tk_from = take(nr);
-    s->ks_cab = take(nc);
-    s->ks_to = take(nc);
-    s->kd_idx = take(nr);
-    s->kd_from = take(nr);
-    s->kd_partner = take(nr);
-    s->kd_plan = take(nr);
-    s->kd_cost = take(nr);
-    s->isb = take(nr);
-    s->ainfo = take(nr);
-    s->pa = take(s->pool_cap);
-    s->pb = take(s->pool_cap);
-    s->pp = take(s->pool_cap);
-    s->pc = take(s->pool_cap);
-    s->pair_cab = take(nc);
-    s->pair_dem = take(nr);
-    s->in_rows = take(in_cap);
-    s->in_cols = take(in_cap);
-    s->in_r2c = take(in_cap);
-    s->in_pair_off = take(nb + 1);
-    s->in_r2c_off = take(nb + 1);
-    s->in_solved = take(nb);
-    s->tk_rows = take(tk_cap);
-    s->tk_cols = take(tk_cap);
-    s->tk_r2c = take(tk_cap);
-    s->tmp = take(std::max<size_t>(max_cabs, 1));
-    s->d_none = take(nb);
-    s->d_rule = take(nb);
+    w = World{nc_tot, n_req, n_stands, drop_time, big_cost};
+    set_tables(w, *s, s->dist);
     auto bail = [&](int code) {
         td_simb_destroy(s);
         return code;
     };
-    // pinned: the head's mirror, then a stage for the offsets / flags of td_simb_apply and the initial tables
-    const size_t stage_ints = std::max<size_t>(3 * (nb + 1), 2 * (nb + 1) + 5 * nc + 5 * nr);
-    hipError_t e = hipHostMalloc(&s->pin, sizeof(int32_t) * (s->head_ints + stage_ints + 16), hipHostMallocDefault);
+    Carve pin_size;
+    simb_pin_layout(pin_size, dims, *s);
+    hipError_t e = hipHostMalloc(&s->pin, pin_size.at, hipHostMallocDefault);
     if (e != hipSuccess) {
         s->pin = nullptr;
         return bail(hip_fail(e, "hipHostMalloc(td_simb)"));
     }
-    s->h_head = (int32_t *)s->pin;
-    s->h_stage = s->h_head + s->head_ints;
+    Carve pin(s->pin);
+    simb_pin_layout(pin, dims, *s);
     // the initial world, made on the host: cab c of a world stands at c % n_stands (initSupply :565-573), no request is assigned
     int32_t *st = s->h_stage;
     memcpy(st, cab_off.data(), sizeof(int32_t) * (nb + 1));
@@ -756,8 +619,8 @@ static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_
                {w.c_to, ic + nc, nc},                 {w.c_clnt, ic + 2 * nc, nc},          {w.c_onb, ic + 3 * nc, nc},
                {w.c_start, ic + 4 * nc, nc},          {w.r_cab, ir, nr},                    {w.r_pick, ir + nr, nr},
                {w.r_pid, ir + 2 * nr, nr},            {w.r_plan, ir + 3 * nr, nr},          {w.r_pcost, ir + 4 * nr, nr},
-               {rid, h.data(), (size_t)n_req},        {rfrom, h.data() + (size_t)n_req, (size_t)n_req},
-               {rto, h.data() + (size_t)2 * n_req, (size_t)n_req}, {rat, h.data() + (size_t)3 * n_req, (size_t)n_req}};
+               {s->r_id, h.data(), (size_t)n_req},     {s->r_from, h.data() + (size_t)n_req, (size_t)n_req},
+               {s->r_to, h.data() + (size_t)2 * n_req, (size_t)n_req}, {s->r_at, h.data() + (size_t)3 * n_req, (size_t)n_req}};
     for (const Up &u : ups)
         if (u.n && (e = hipMemcpyAsync(u.dst, u.src, sizeof(int32_t) * u.n, hipMemcpyHostToDevice, c.stream)) != hipSuccess)
             return bail(hip_fail(e, "hipMemcpyAsync(td_simb tables)"));
