@@ -55,7 +55,20 @@ TD_API const char *td_last_error(void);
  * ready in that stream's order: a caller working on another stream either shares its stream
  * with td_set_stream or fences with its own synchronisation / td_synchronize. Entry points that
  * return values to the host (td_assign, td_lcm, td_pool2, td_count_sum) return after their
- * results are complete. */
+ * results are complete.
+ * The builders (td_cost_build, td_cost_build_rows, td_gen_uniform) do NOT wait for the stream
+ * when the destination and every array argument they were given (positions, ids, the distance
+ * table) are device memory: the call returns with its kernels queued, and the next entry point
+ * (td_assign, td_lcm, ...) queues behind them without a host round trip in between. Launch
+ * errors are still reported by the call, execution errors by the next call that synchronises.
+ * If ANY of those pointers is host memory (a pinned host pointer counts as host) the call waits:
+ * a host destination is complete on return, a host array may be reused or freed on return.
+ * Lifetime: the device inputs of a call that did not wait must stay valid and unmodified, and
+ * its output must not be written by anyone else, until the library's stream has passed the
+ * call: that is td_synchronize or any entry point that returns values to the host.
+ * While the library runs on its own stream, a builder that does not wait also makes the default
+ * (null) stream wait for it on the device: work queued on the default stream after the call sees
+ * the whole output. Work on any other stream needs the fence above. */
 TD_API int td_set_stream(void *hip_stream); /* run on the caller's stream (NULL -> library stream) */
 TD_API int td_synchronize(void);
 /* Device bytes currently held in the library's grow-only workspaces (the default solver, handles, shards, staging and

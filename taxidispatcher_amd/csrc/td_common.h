@@ -45,6 +45,7 @@ struct Ctx {
     int n_pend = 0;
     hipEvent_t ev_pool[8192];
     int n_ev = 0, ev_next = 0;
+    hipEvent_t ev_built = nullptr;   // end of the last no-wait builder call on the library's own stream (td_core.hip: builder_end)
     int64_t stats[16] = {0};
 };
 
@@ -66,7 +67,8 @@ int copy_in(void *dst, const void *src, size_t bytes);
 // td_line.hip: sorted matching + certificate pass for line-metric matrices (tried first by td_assign)
 //   line_probe_launch  queues the O(n) probe; *skip_dev = device word that is non-zero unless the probe refuses;
 //                      clear_words non-null: the probe also zeroes clear_words[0 .. nclear) (td_assign's control words)
-//   line_probe_wait    waits for the probe alone (its call number in the pinned verdict block, not the stream) and returns its verdict:
+//   line_probe_wait    waits for the probe alone (its call number in the pinned verdict block, not the stream; the probe runs behind
+//                      whatever the caller queued in front of td_assign, a no-wait cost build included) and returns its verdict:
 //                      0 refused, 1 plausible, 2 constant trailing columns (retry on the transpose),
 //                      3 plausible with *k constant rows (the unbalanced model)
 //   line_finish        keys, sort, prices, certificate pass; *accepted = 1: *r2c_dev / *total are proven optimal;
@@ -88,7 +90,8 @@ int build_assign_device(const int32_t *d_cab, int n_s, const int32_t *d_dem, int
 int lcm_hinted(int n, const int32_t *cost, int32_t mask, int32_t threshold, int stop_value_on, int32_t stop_value, int stop_size,
                int64_t sum_below, int max_pairs, int32_t *rows, int32_t *cols, int32_t *n_pairs, int64_t *total, int32_t *last_min,
                int hint_vmin, int hint_vmax);
-// td_core.hip: td_cost_build for device-resident library buffers, without the trailing stream synchronisation (td_tick)
+// td_core.hip: td_cost_build for device-resident library buffers: no wait for the stream, as the public entry points with
+// device arrays, and no ordering of the default stream behind it (td_tick: nobody outside the library sees the buffer)
 int cost_build_async(const int32_t *cab_to, int n_s, const int32_t *dem_from, int n_d, const int32_t *dist, int S, int32_t fill,
                      int32_t threshold, int32_t *cost);
 // td_lcm.hip: td_tick's LCM of a thresholded |a - b| model on <= 64 stands straight from the position arrays (no matrix);

@@ -397,6 +397,7 @@ int td_init(int device)
     c.pin_in_cap = 1 << 20;
     c.pin_in_off = 0;
     TD_HIP(hipHostMalloc(&c.pin_in, c.pin_in_cap, hipHostMallocDefault));
+    TD_HIP(hipEventCreateWithFlags(&c.ev_built, hipEventDisableTiming));
     c.inited = true;
     c.err[0] = 0;
     return TD_OK;
@@ -419,6 +420,8 @@ void td_shutdown(void)
     for (Buf *b : bufs) buf_free(*b);
     for (int i = 0; i < c.n_ev; i++) (void)hipEventDestroy(c.ev_pool[i]);
     c.n_ev = c.ev_next = c.n_pend = 0;
+    if (c.ev_built) (void)hipEventDestroy(c.ev_built);
+    c.ev_built = nullptr;
     if (c.pinned) (void)hipHostFree(c.pinned);
     c.pinned = nullptr;
     if (c.pin_in) (void)hipHostFree(c.pin_in);
@@ -489,9 +492,30 @@ int td_last_stats(int64_t *out, int n)
     return TD_OK;
 }
 
+// The end of a builder call (td_cost_build, td_cost_build_rows, td_gen_uniform; the header's stream rule).
+// wait: the destination or an array argument is host memory (a pinned pointer counts as host), so the caller may reuse
+// the array, or read the destination, the moment the call returns.  Otherwise everything is device memory and the call
+// returns with its kernels queued: the next entry point queues behind them without a host round trip in between.
+// On the library's own stream the default (null) stream is also made to wait for the builder ON THE DEVICE, so work a
+// caller queues on the default stream after the call (a torch operation on the output) still sees the whole output.
+// (The event is a barrier packet behind the builder's kernel: td_assign's first kernel starts 7 us after a 16 384^2 write
+// instead of 17 - 24 us after it with the host wait.  The kernel's own completion signal as the event, hipExtLaunchKernelGGL's
+// stop event, measured 5 us and the same step time: profiles/front_gap/README.md.)
+static int builder_end(bool wait)
+{
+    Ctx &c = ctx();
+    if (wait) {
+        TD_HIP(hipStreamSynchronize(c.stream));
+    } else if (c.stream == c.own_stream) {
+        TD_HIP(hipEventRecord(c.ev_built, c.stream));
+        TD_HIP(hipStreamWaitEvent(nullptr, c.ev_built, 0));
+    }
+    return TD_OK;
+}
+
 static int cost_build_impl(const int32_t *cab_to, const int32_t *cab_id, int n_s, const int32_t *dem_from,
                            const int32_t *dem_id, int n_d, const int32_t *dist, int S, int32_t fill, int32_t threshold,
-                           int by_id, int row0, int nrows, int32_t *cost, bool nosync = false)
+                           int by_id, int row0, int nrows, int32_t *cost, bool internal = false)
 {
     TD_REQUIRE_INIT();
     Ctx &c = ctx();
@@ -506,6 +530,7 @@ static int cost_build_impl(const int32_t *cab_to, const int32_t *cab_id, int n_s
     if (by_id && (!cab_id || !dem_id)) return fail(TD_EINVAL, "by_id needs cab_id and dem_id");
     const void *d_cab = nullptr, *d_cid = nullptr, *d_dem = nullptr, *d_did = nullptr, *d_dist = nullptr;
     int rc;
+    bool host_arg = false;   // an array argument or the destination is host memory: the call waits for the stream
     // position arrays are tiny (<= 256 KiB); stage them when they are host pointers
     if (n_s && (rc = ensure(c.stage_a, sizeof(int32_t) * 2 * (size_t)std::max(n_s, 1)))) return rc;
     if (n_d && (rc = ensure(c.stage_b, sizeof(int32_t) * 2 * (size_t)std::max(n_d, 1)))) return rc;
@@ -518,6 +543,7 @@ static int cost_build_impl(const int32_t *cab_to, const int32_t *cab_id, int n_s
             *out = src;
             return TD_OK;
         }
+        host_arg = true;
         char *dst = (char *)buf.p + off;
         TD_HIP(hipMemcpyAsync(dst, src, sizeof(int32_t) * (size_t)cnt, hipMemcpyHostToDevice, c.stream));
         *out = dst;
@@ -529,6 +555,7 @@ static int cost_build_impl(const int32_t *cab_to, const int32_t *cab_id, int n_s
     if ((rc = stage(dem_id, n_d, c.stage_b, sizeof(int32_t) * (size_t)n_d, &d_did))) return rc;
     if (dist) {
         if ((rc = to_device(dist, sizeof(int32_t) * (size_t)S * S, c.stage_c, &d_dist))) return rc;
+        if (d_dist != dist) host_arg = true;
     }
     const bool out_dev = is_device_ptr(cost);
     int32_t *d_cost = cost;
@@ -573,14 +600,14 @@ static int cost_build_impl(const int32_t *cab_to, const int32_t *cab_id, int n_s
     if (!out_dev) {
         TD_HIP(hipMemcpyAsync(cost, d_cost, cbytes, hipMemcpyDeviceToHost, c.stream));
     }
-    if (!(nosync && out_dev)) TD_HIP(hipStreamSynchronize(c.stream));
-    return TD_OK;
+    if (internal && out_dev && !host_arg) return TD_OK;
+    return builder_end(host_arg || !out_dev);
 }
 
 }   // extern "C"
 
-// td_tick's cost builds: every array is a library buffer on the device and the next kernel is queued on the same stream,
-// so the call returns without waiting (the public entry points wait: their callers may release the arrays at once)
+// td_tick's cost builds: every array is a library buffer on the device and the next kernel is queued on the same stream
+// (the public entry points with device arrays return the same way, and also order the default stream behind the build)
 int td::cost_build_async(const int32_t *cab_to, int n_s, const int32_t *dem_from, int n_d, const int32_t *dist, int S, int32_t fill,
                          int32_t threshold, int32_t *cost)
 {
@@ -634,8 +661,7 @@ int td_gen_uniform(int n, uint64_t seed, int32_t lo, int32_t hi, int row0, int n
     }
     TD_HIP(hipGetLastError());
     if (!out_dev) TD_HIP(hipMemcpyAsync(cost, d_cost, cbytes, hipMemcpyDeviceToHost, c.stream));
-    TD_HIP(hipStreamSynchronize(c.stream));
-    return TD_OK;
+    return builder_end(!out_dev);
 }
 
 int td_expand_x(int n, const int32_t *row_to_col, uint8_t *x)

@@ -59,7 +59,10 @@ class HipShard:
             _ffi.check(self.lib.td_set_stream(ctypes.c_void_p(self.stream.cuda_stream)))
             HipShard._stream_owner = self
         self.n, self.row0, self.nrows = n, row0, nrows
-        self._cost = cost_rows  # keep alive: the library reads it again for the total
+        # keep alive: the library reads it again for the total.  The rows may still be being written by a cost build that
+        # did not wait (device rows): every reader is a library call on the library's stream, queued behind the build, and
+        # td_set_stream above waited for the stream it left.
+        self._cost = cost_rows
         h = ctypes.c_void_p()
         _ffi.check(self.lib.td_shard_create(n, row0, nrows, _ffi.addr(cost_rows) if nrows else None,
                                             ctypes.byref(h)))
@@ -159,6 +162,12 @@ class HipShard:
         ptr = ctypes.c_void_p()
         nbytes = ctypes.c_uint64()
         _ffi.check(self.lib.td_shard_cc(self.h, ctypes.byref(ptr), ctypes.byref(nbytes)))
+        if not self.shared_stream:
+            # td_shard_cc may have queued the rest of the narrow copy, behind a compress pass that itself runs behind a
+            # cost build that did not wait (td_gen_uniform / td_cost_build_rows into device rows): the exchange that
+            # carries the handle runs on torch's stream, and a peer must not map rows that are still being written.
+            # (On the shared stream the all-gather of the handles is queued behind all of that.)
+            _ffi.check(self.lib.td_synchronize())
         buf = (ctypes.c_ubyte * 64)()
         rc = self.lib.td_ipc_export(ptr, buf)
         ok = rc == 0

@@ -42,6 +42,7 @@ for n in [1000, 4096, 16384]:
     for rep in range(3):
         t0 = time.time()
         _ffi.check(lib.td_gen_uniform(n, 1, 10, 40, 0, n, cost.data_ptr()))
+        _ffi.check(lib.td_synchronize())   # a device destination is not waited for: time the write, not its launch
         t1 = time.time()
         r2c, tot, dual = td.assign(cost, n, want_dual=True)
         t2 = time.time()

@@ -8,7 +8,9 @@ A step runs from one k_gen_uniform to the last k_final before the next.  Prints 
 every kernel's time in launch order, of the time from the end of k_gen_uniform to the start of the compress pass, and of
 the time from the end of the compress pass to the end of k_final.  The k_hop_* launches carry the number of their two-hop
 pass (a pass ends with its k_hop_match, whichever kernels it is made of: four while k_hop_esc made the masks of tight
-free columns, three since k_hop_table tests them itself), and every pass gets a line with its sum.
+free columns, three since k_hop_table tests them itself), and every pass gets a line with its sum.  The last two lines: the
+idle time in front of k_gen_uniform (end of the step before's last k_final -> start of the cost write: the host round
+trip at the end of td_assign) and the launches per step (profiles/front_gap/README.md).
 """
 import csv
 import re
@@ -33,7 +35,10 @@ def main():
             steps.append(cur)
         if cur is not None:
             cur.append(k)
-    steps = [s for s in steps if any(k[0].startswith("k_final") for k in s)][drop:]
+    steps = [s for s in steps if any(k[0].startswith("k_final") for k in s)]
+    # end of the step before (its last k_final) -> start of this step's cost write: the host round trip at the end of td_assign
+    prev_end = {id(s): max(k[2] for k in p if k[0].startswith("k_final")) for p, s in zip(steps, steps[1:])}
+    steps = steps[drop:]
     shape = [k[0] for k in steps[-1]]
     steps = [s for s in steps if [k[0] for k in s] == shape]   # (the steps that launched the same sequence)
 
@@ -60,6 +65,10 @@ def main():
     print("end of compress -> end of k_final           %s" % stat([s[fi][2] - s[ci][2] for s in steps]))
     print("start of k_gen_uniform -> end of k_final    %s" % stat([s[fi][2] - s[0][1] for s in steps]))
     print("sum of kernel times                         %s" % stat([sum(k[2] - k[1] for k in s) for s in steps]))
+    gaps = [s[0][1] - prev_end[id(s)] for s in steps if id(s) in prev_end]
+    if gaps:
+        print("end of k_final of the step before -> start of k_gen_uniform %s" % stat(gaps))
+    print("launches per step                           %d" % len(shape))
 
 
 if __name__ == "__main__":
