@@ -566,6 +566,51 @@ TD_API int td_simb_pooling(td_simb *s, const int32_t *mode /* [B], NULL = greedy
 TD_API int td_sim_pools(td_sim *s, int max_pools, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n);
 TD_API int td_simb_pools(td_simb *s, int world, int max_pools, int32_t *cust_a, int32_t *cust_b, int32_t *plan, int32_t *cost, int32_t *n);
 
+/* ---- pools of up to four in a world ---------------------------------------------------------------------------
+ * td_sim_pooling_n replaces the world's pair policy from the next begin on (the specification: Simulator(pool_n=, pool_wait=,
+ * pool_loss=)); a later td_sim_pooling puts the world back on a pair policy.  findPool is then a cascade over the tick's
+ * demand list: stage k = k_hi, k_hi - 1, .., k_lo runs on the requests no earlier stage pooled, in list order, and is exactly
+ * td_pool_n(k, ...) on that list with max_wait and max_loss_pct for every request, every request a possible first pick-up, the
+ * world's table or |a - b|; a list shorter than k yields nothing.  The tick's plans are the stages' records in stage order.
+ * analyzePool: every member of a record but its first pick-up leaves the demand and is assigned with it (one second
+ * passenger and one pick-up counted per such member); the first pick-up stays, carries the cost, and its cab is kept busy for
+ * the cost as with a pair.  There is no route model.  td_sim_state on the OPT path: d_pool_id = the second pick-up's id,
+ * d_pool_plan = the pool's size, d_pool_cost = the cost (the LCM path copies no pool info, as with pairs).
+ * max_POOL_size: the most plans of a tick, all stages; max_POOL_MEM_size: the most happy plans of a tick, summed over its stages.
+ * The first call allocates the wider partner columns and the stage lists for the handle; nothing is allocated per tick.
+ * TD_EINVAL, the policy unchanged: sizes outside 2 <= k_lo <= k_hi <= 4, a negative wait or loss, max_happy above 2^22
+ * (td_pool_n_batched's limit; <= 0: the default of the call underneath), a call while a tick with demand waits for its apply,
+ * k_hi > 2 on a handle that logs.
+ * Limits per tick, from the calls underneath: up to 512 requests before pooling a stage is td_pool_n_batched's device code on
+ * the one model, up to 2047 td_pool_n with the whole list as first pick-ups (inputs and records stay on the device either
+ * way); more than 2047: TD_EINVAL from begin.  More happy plans in a stage than max_happy, or a plan cost above 16383:
+ * TD_ERANGE from begin.  After any of these the handle is left as TD_POOL_OPTIMAL's paragraph above states it.
+ * td_sim_pools_n: the plans of the tick last begun in plan order (stage order, then td_pool_n's order): a record is 9 ints,
+ * 4 pick-ups, 4 drop-offs (-1 behind the pool's size), the cost; members are indices into that tick's demand list before
+ * pooling; size[i] is 2 .. 4; host or device destinations.  More plans than max_pools: TD_EINVAL with *n set, nothing copied.
+ * td_sim_pools on a world under this policy is TD_EINVAL (the message names td_sim_pools_n), and td_sim_pools_n on a pair
+ * world likewise.
+ * The event log is cut on purpose: the apply stages own two staging slots per thread and a pool of four needs four, so
+ * td_sim_log with a non-zero mask on a world with k_hi > 2 is TD_EINVAL ("not built").  With k_hi == 2 the log works: a pool
+ * is a pair, and the records are the specification's.
+ * td_simb_pooling_n gives every world of a batch its own such policy: four arrays [B], host or device; k_hi[b] == 0: world b
+ * keeps the policy it has (a pair policy of td_simb_pooling, or an earlier one of this call).  td_simb_pooling puts every
+ * world back on a pair policy.  The pool call sees every world of the policy at once: round k = 4, 3, 2 is ONE launch of
+ * td_pool_n_batched's workgroup-per-model core over the worlds whose cascade has a stage of k (a world of another policy,
+ * without supply or with fewer than two requests is an empty model), then one launch for the records and marks and one
+ * compaction pass for all worlds: at most three rounds a tick, whatever B is.  A world with more than 512 requests before
+ * pooling in a tick: TD_EINVAL from begin, the message names the world and the count; max_happy and the cost limit as above,
+ * the message names the world.  td_simb_pools_n(world) / td_simb_pools(world) refuse a world of the other kind.
+ * The event log of a batch follows the single world's rule: td_simb_log with a non-zero mask while some world has k_hi > 2, and
+ * td_simb_pooling_n that gives a world k_hi > 2 on a batch that logs, are TD_EINVAL ("not built"); with k_hi == 2 in every
+ * record world the log works and a world's records are the specification's.  A pair world above 2048 requests before pooling
+ * is pooled world by world as in a batch of pair worlds, whatever the record worlds beside it do. */
+TD_API int td_sim_pooling_n(td_sim *s, int k_hi, int k_lo, int max_wait, int max_loss_pct, int64_t max_happy);
+TD_API int td_simb_pooling_n(td_simb *s, const int32_t *k_hi, const int32_t *k_lo, const int32_t *max_wait, const int32_t *max_loss_pct,
+                             int64_t max_happy);
+TD_API int td_sim_pools_n(td_sim *s, int max_pools, int32_t *records /* max_pools x 9 */, int32_t *size, int32_t *n);
+TD_API int td_simb_pools_n(td_simb *s, int world, int max_pools, int32_t *records /* max_pools x 9 */, int32_t *size, int32_t *n);
+
 /* ---- the dispatch policy of a world ------------------------------------------------------------------------------
  * Until *_dispatch is called a world dispatches as Simulator.java:163-208 does, "the LCM down to max_non_lcm, then the
  * optimum", with the max_non_lcm it was created with, through the calls and kernels it always used.  td_sim_dispatch sets one

@@ -106,6 +106,10 @@ SIGNATURES = {
     "td_sim_pools": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_int32)]),
     "td_simb_pools": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p,
                                      ctypes.POINTER(ctypes.c_int32)]),
+    "td_sim_pooling_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "td_sim_pools_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_int32)]),
+    "td_simb_pooling_n": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int64]),
+    "td_simb_pools_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_int32)]),
     "td_pool2": (ctypes.c_int, [ctypes.c_int, c_i32p, c_i32p, c_i32p, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p,
                                 ctypes.POINTER(ctypes.c_int32)]),
     "td_pool2_loss": (ctypes.c_int, [ctypes.c_int, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_double, c_i32p, c_i32p, c_i32p, c_i32p,

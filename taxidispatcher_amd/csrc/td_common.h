@@ -109,6 +109,11 @@ void match_release_workspace();
 void pool_release_workspace();
 // td_pool_batch.hip: frees td_pool_n_batched's key slab and staging (td_shutdown)
 void pool_batch_release_workspace();
+// td_pool_batch.hip: td_pool_n_batched's core on device arrays with a size per model, for the worlds of td_simb_pooling_n
+int pool_n_worlds(int k, int batch, int n, const int32_t *off, const int32_t *cnt, const int32_t *k_hi, const int32_t *k_lo,
+                  const int32_t *from, const int32_t *to, const int32_t *wait, const int32_t *loss, const int32_t *dist, int S,
+                  int64_t max_happy, int32_t *pools, int32_t *n_pools, long long *n_happy, long long *total, int *over_model,
+                  long long *over_count);
 void prof_begin(int k);
 void prof_end(int k);
 void prof_flush();

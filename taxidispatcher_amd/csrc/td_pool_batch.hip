@@ -204,7 +204,16 @@ __device__ __forceinline__ unsigned char pnb_perm_codes(std::integer_sequence<in
     return code[qi];
 }
 
-template <int K>
+// V: the models are worlds (td::pool_n_worlds): model b's requests lie at off[b], sel.cnt[b] of them, and only where the world's
+// cascade has a stage of K (sel.k_lo[b] <= K <= sel.k_hi[b]), else the model is empty; wait / loss hold one rule per model
+template <bool V>
+struct PnbSel {};
+template <>
+struct PnbSel<true> {
+    const int32_t *cnt, *k_hi, *k_lo;
+};
+
+template <int K, bool V = false>
 __global__ __launch_bounds__(PNB_T) void k_pooln_batched(int batch, int n, const int32_t *__restrict__ off,
                                                          const int32_t *__restrict__ from, const int32_t *__restrict__ to,
                                                          const int32_t *__restrict__ wait, const int32_t *__restrict__ loss,
@@ -212,7 +221,7 @@ __global__ __launch_bounds__(PNB_T) void k_pooln_batched(int batch, int n, const
                                                          unsigned long long cap, unsigned long long *__restrict__ slab,
                                                          int32_t *__restrict__ pools, int32_t *__restrict__ n_pools,
                                                          long long *__restrict__ n_happy, long long *__restrict__ total,
-                                                         PnbErr *__restrict__ err)
+                                                         PnbErr *__restrict__ err, PnbSel<V> sel)
 {
     __shared__ PnbShared<K> sh;
     __shared__ unsigned char s_perm[24];
@@ -222,7 +231,12 @@ __global__ __launch_bounds__(PNB_T) void k_pooln_batched(int batch, int n, const
     if (tid < NP) s_perm[tid] = pnb_perm_codes<K>(std::make_integer_sequence<int, NP>{}, tid);
     const size_t rec = (size_t)(2 * K + 1), stride = (size_t)(n / K) * rec;
     for (int b = blockIdx.x; b < batch; b += gridDim.x) {
-        const int o = off[b], nb = off[b + 1] - o;
+        const int o = off[b];
+        int nb;
+        if constexpr (V)
+            nb = sel.k_lo[b] <= K && K <= sel.k_hi[b] ? max(0, min(sel.cnt[b], min(n, PNB_MAXN))) : 0;
+        else
+            nb = off[b + 1] - o;
         int f0 = 0, f1 = nb;
         if (first) {
             f0 = max(first[2 * b], 0);
@@ -234,8 +248,8 @@ __global__ __launch_bounds__(PNB_T) void k_pooln_batched(int batch, int n, const
             const int32_t f = from[o + i], t = to[o + i];
             sh.req[i] = f;
             sh.req[PNB_MAXN + i] = t;
-            sh.req[2 * PNB_MAXN + i] = wait[o + i];
-            sh.req[3 * PNB_MAXN + i] = loss[o + i];
+            sh.req[2 * PNB_MAXN + i] = wait[V ? b : o + i];
+            sh.req[3 * PNB_MAXN + i] = loss[V ? b : o + i];
             bad = bad || (dist && ((uint32_t)f >= (uint32_t)S || (uint32_t)t >= (uint32_t)S));
         }
         if (tid < K - 1) sh.qn[tid] = 0;
@@ -402,6 +416,54 @@ void td::pool_batch_release_workspace()
     for (Buf *b : bs) buf_free(*b);
 }
 
+// td_pool_n_batched's workgroup-per-model core for the world layer (td_simb_pooling_n): every array is the caller's and on the
+// device, model b = the cnt[b] requests at off[b] (at most n <= 512 each), one wait / loss per model, a model outside
+// k_lo[b] <= k <= k_hi[b] is empty; records go to pools + b * (n / k) * (2 k + 1) as they are.  One launch whatever the batch.
+// TD_ERANGE with *over_model / *over_count set: that model has more happy plans than max_happy (*over_model = -1: a cost).
+int td::pool_n_worlds(int k, int batch, int n, const int32_t *off, const int32_t *cnt, const int32_t *k_hi, const int32_t *k_lo,
+                      const int32_t *from, const int32_t *to, const int32_t *wait, const int32_t *loss, const int32_t *dist, int S,
+                      int64_t max_happy, int32_t *pools, int32_t *n_pools, long long *n_happy, long long *total, int *over_model,
+                      long long *over_count)
+{
+    Ctx &c = ctx();
+    const char *fn = "td_pool_n_batched";
+    *over_model = -1;
+    *over_count = 0;
+    if (k < 2 || k > 4 || batch < 1 || n < 0 || n > PNB_MAXN || max_happy > PNB_MAX_HAPPY) return fail(TD_EINVAL, "%s: bad world call", fn);
+    if (max_happy <= 0) max_happy = PNB_DEF_HAPPY;
+    int rc;
+    const int grid_cap = (int)std::max<size_t>(1, std::min<size_t>((size_t)PNB_GRID, PNB_SLAB_BYTES / (sizeof(unsigned long long) * (size_t)max_happy)));
+    if ((rc = ensure(g_slab, sizeof(unsigned long long) * (size_t)max_happy * (size_t)grid_cap))) return rc;
+    if ((rc = ensure(g_err, 256))) return rc;
+    PnbErr *d_err = (PnbErr *)g_err.p;
+    TD_HIP(hipMemsetAsync(d_err, 0, sizeof(PnbErr), c.stream));
+    const int grid = std::min(batch, grid_cap);
+    const PnbSel<true> sel{cnt, k_hi, k_lo};
+    {
+        ProfScope ps(TD_K_LCM);
+#define TD_PNW(KV)                                                                                                                  \
+    k_pooln_batched<KV, true><<<grid, PNB_T, 0, c.stream>>>(batch, n, off, from, to, wait, loss, dist, S, nullptr, (unsigned long long)max_happy, \
+                                                            (unsigned long long *)g_slab.p, pools, n_pools, n_happy, total, d_err, sel)
+        if (k == 2) TD_PNW(2);
+        else if (k == 3) TD_PNW(3);
+        else TD_PNW(4);
+#undef TD_PNW
+        TD_HIP(hipGetLastError());
+    }
+    TD_HIP(hipMemcpyAsync(c.pinned, d_err, sizeof(PnbErr), hipMemcpyDeviceToHost, c.stream));
+    TD_HIP(hipStreamSynchronize(c.stream));
+    const PnbErr e = *(const PnbErr *)c.pinned;
+    if (e.bad) return fail(TD_EINVAL, "%s: model %d has a stand outside the %d x %d distance table", fn, batch - e.bad, S, S);
+    if (e.cost) return fail(TD_ERANGE, "%s: a plan cost does not fit 14 bits", fn);
+    if (e.over) {
+        *over_model = batch - e.over;
+        TD_HIP(hipMemcpyAsync(over_count, n_happy + *over_model, sizeof(long long), hipMemcpyDeviceToHost, c.stream));
+        TD_HIP(hipStreamSynchronize(c.stream));
+        return fail(TD_ERANGE, "%s: model %d has %lld happy plans, more than max_happy = %lld", fn, *over_model, *over_count, (long long)max_happy);
+    }
+    return TD_OK;
+}
+
 extern "C" int td_pool_n_batched(int k, int batch, int n, const int32_t *off, const int32_t *from, const int32_t *to,
                                  const int32_t *max_wait, const int32_t *max_loss, const int32_t *dist, int S, const int32_t *first,
                                  int64_t max_happy, int32_t *pools, int32_t *n_pools, int64_t *n_happy, int64_t *total)
@@ -468,7 +530,7 @@ extern "C" int td_pool_n_batched(int k, int batch, int n, const int32_t *off, co
 #define TD_PNB(KV)                                                                                                               \
     k_pooln_batched<KV><<<grid, PNB_T, 0, c.stream>>>(batch, n, d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], (const int32_t *)d_dist, S, \
                                                       d_in[5], (unsigned long long)max_happy, (unsigned long long *)g_slab.p, s_pools, \
-                                                      s_np, s_nh, s_tot, d_err)
+                                                      s_np, s_nh, s_tot, d_err, PnbSel<false>{})
         if (k == 2) TD_PNB(2);
         else if (k == 3) TD_PNB(3);
         else TD_PNB(4);

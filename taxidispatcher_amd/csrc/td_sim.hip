@@ -17,6 +17,10 @@
 //           td_pool2 (device lists)      findPool; under td_sim_pooling: td_pool2_loss (the candidate rule), td_pool2_batched on
 //                                        the one model (the optimum), or nothing (TD_POOL_NONE: the demand is copied as it is)
 //           k_pool_mark, k_count / k_scatter   analyzePool: B customers out, A customers annotated, order kept
+//           under td_sim_pooling_n (sim_begin_pool_n): per stage k = k_hi .. k_lo the pool call on the device lists
+//           (td_pool_n_batched on the one model, td_pool_n above 512 requests), k_pool_records (the stage's records as the
+//           tick's, and analyzePool's marks), k_count / k_scatter (the rest for the next stage); then k_count / k_scatter
+//           with PoolEmitN: the first pick-up carries up to three partners, the size and the cost
 //   apply   k_pair_map                   first pair per cab / per request (setdefault), indices checked
 //           k_apply_pairs                analyzePairs' two loops, one thread per cab / request of the model
 //           k_count / k_scatter  x 2     the kept lists, ordered: what row_to_col indexes
@@ -58,6 +62,17 @@ using namespace tdsim;
 struct Head {
     Ctl ctl;
     int32_t n_dem, n_sup, n_dem2, n_ks, n_kd;
+    int32_t n_stage;   // td_sim_pooling_n: the requests the last stage compaction kept; begin checks it against the pool counts
+};
+
+// what td_sim_pooling_n adds to a handle, allocated by its first call: nothing of it is touched per tick by another policy
+struct PoolNDev {
+    int32_t *wait = nullptr, *loss = nullptr;        // the world's scalar rule, once per request slot
+    int32_t *st_from[2], *st_to[2], *st_map[2];      // a stage's request list and its positions in the tick's demand list
+    int32_t *used = nullptr;                         // a stage's requests that its pools took
+    int32_t *out = nullptr;                          // a stage's records as the pool call writes them
+    int32_t *recs = nullptr, *size = nullptr;        // the tick's plans: 9 ints each, and their sizes
+    int32_t *d2_more[2], *kd_more[2];                // the third and fourth pick-up of the demand after pooling / the kept demand
 };
 
 struct td_sim : SimDev, SimPin {   // td_sim_layout.h: every device array of the handle, and the pinned block
@@ -77,6 +92,11 @@ struct td_sim : SimDev, SimPin {   // td_sim_layout.h: every device array of the
     int n_pooled = 0;            // the customers findPool looked at in this tick: the demand, or 0 where it did not run
     int pool_mode = TD_POOL_GREEDY;   // td_sim_pooling: the policy from the next begin on
     double max_loss = 0.0;            // <= 0: every ordered pair is a candidate
+    // td_sim_pooling_n: pools of pn_hi down to pn_lo from the next begin on; pn_hi == 0: the pair policy above holds
+    int pn_hi = 0, pn_lo = 0, pn_wait = 0, pn_loss = 0;
+    int64_t pn_max_happy = 0;
+    PoolNDev pn;
+    Buf pn_mem;
     // td_sim_dispatch: the dispatch method from the next begin on.  The world kernels take the LCM rule as one number
     // ("the LCM ran when the model is larger than it"), so a policy is that number: lcm_rule() below.
     int disp_mode = TD_DISPATCH_LCM_OPT, disp_parts = 4;
@@ -111,6 +131,76 @@ struct Plans1 {
     __device__ int count(int) const { return k; }
     __device__ int base(int) const { return 0; }
 };
+
+// td_sim_pooling_n, one stage of the cascade: record p of the pool call (2 K + 1 ints, members = positions in the stage's list)
+// becomes plan base + p of the tick (9 ints, members = positions in the tick's demand list through `map`; nullptr: the first
+// stage, whose list is the demand list).  analyzePool's marks with it: every member but the first pick-up leaves (isb), the
+// first pick-up gets its plan (ainfo), and the stage's list forgets all of them (used).  pl_a / pl_b: first and second
+// pick-up, where the event log reads a pair.  A member outside its list raises the error word.
+__global__ __launch_bounds__(256) void k_pool_records(int K, int np, int base, int cap_plans, int m_stage, int n_dem,
+                                                      const int32_t *__restrict__ out, const int32_t *__restrict__ map,
+                                                      int32_t *__restrict__ recs, int32_t *__restrict__ size, int32_t *__restrict__ pl_a,
+                                                      int32_t *__restrict__ pl_b, int32_t *__restrict__ used, int32_t *__restrict__ isb,
+                                                      int32_t *__restrict__ ainfo, int32_t *gerr)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= np) return;
+    if (base + p >= cap_plans) {
+        atomicMax(gerr, 1);
+        return;
+    }
+    const int32_t *r = out + (size_t)p * (size_t)(2 * K + 1);
+    int pick[4] = {-1, -1, -1, -1}, drop[4] = {-1, -1, -1, -1};
+    bool bad = false;
+    for (int i = 0; i < K; i++) {
+        const int a = r[i], d = r[K + i];
+        if (a < 0 || a >= m_stage || d < 0 || d >= m_stage) {
+            bad = true;
+            continue;
+        }
+        pick[i] = map ? map[a] : a;
+        drop[i] = map ? map[d] : d;
+        bad = bad || pick[i] < 0 || pick[i] >= n_dem || drop[i] < 0 || drop[i] >= n_dem;
+    }
+    if (bad) {
+        atomicMax(gerr, 1);
+        return;
+    }
+    int32_t *o = recs + (size_t)9 * (size_t)(base + p);
+    for (int i = 0; i < 4; i++) {
+        o[i] = pick[i];
+        o[4 + i] = drop[i];
+    }
+    o[8] = r[2 * K];
+    size[base + p] = K;
+    pl_a[base + p] = pick[0];
+    pl_b[base + p] = pick[1];
+    atomicMin(&ainfo[pick[0]], base + p);
+    for (int i = 0; i < K; i++) {
+        used[r[i]] = 1;
+        if (i) isb[pick[i]] = 1;
+    }
+}
+
+// the requests a stage leaves to the next one, in list order, with their positions in the tick's demand list
+struct StageEmit {
+    const int32_t *from, *to, *map;
+    int32_t *from2, *to2, *map2;
+    __device__ void operator()(int o, int, int i, int) const
+    {
+        from2[o] = from[i];
+        to2[o] = to[i];
+        map2[o] = map ? map[i] : i;
+    }
+};
+
+__global__ __launch_bounds__(256) void k_fill2(int n, int32_t *__restrict__ a, int va, int32_t *__restrict__ b, int vb)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    a[i] = va;
+    b[i] = vb;
+}
 
 // this tick's decisions as td_sim_apply got them
 struct Dec1 {
@@ -208,6 +298,86 @@ int sim_ev_tick_done(td_sim *s)
     return sim_ev_flush(s, phase);
 }
 
+constexpr int SIM_POOL_N_NMAX = 2047;   // td_pool_n's largest model
+constexpr int SIM_POOL_NB_NMAX = 512;   // td_pool_n_batched's
+
+// findPool and analyzePool of a tick under td_sim_pooling_n (the specification: Simulator.find_pool_n / analyze_pool_n).  The
+// cascade runs on the device lists: stage k is td_pool_n_batched's device code on the one model (up to 512 requests) or
+// td_pool_n with every request as a possible first pick-up (up to 2047), each with device inputs and a device destination;
+// k_pool_records translates and marks, one compaction hands the rest to the next stage.  The host learns a stage's pool
+// count from the pool call itself and derives the next list's size from it: a stage adds no read-back of its own.
+int sim_begin_pool_n(td_sim *s, int t, int32_t info[4])
+{
+    Ctx &c = ctx();
+    const int n = s->n_dem;
+    const PoolNDev &pn = s->pn;
+    int rc;
+    if (n > SIM_POOL_N_NMAX)
+        return fail(TD_EINVAL, "td_sim_begin: world 0 has %d requests before pooling in tick %d, more than the %d td_pool_n takes", n, t,
+                    SIM_POOL_N_NMAX);
+    s->n_pooled = n;
+    TD_HIP(hipMemsetAsync(s->isb, 0, sizeof(int32_t) * (size_t)n, c.stream));
+    TD_HIP(hipMemsetAsync(s->ainfo, 0x7f, sizeof(int32_t) * (size_t)n, c.stream));
+    const int cap_plans = std::max(s->w.n_req, 1) / 2 + 1, S = s->dist ? s->w.n_stands : 0;   // what pl_a / pl_b hold; recs and size hold no less
+    int total = 0, m = n, cur = 0, m_left = -1;   // m_left: what the last compaction between two stages must have counted
+    int64_t happy = 0;
+    const int32_t *from = s->dem_from, *to = s->dem_to, *map = nullptr;
+    for (int k = s->pn_hi; k >= s->pn_lo && n >= 2; k--) {
+        if (m < k) continue;   // a stage list shorter than its k yields no pools
+        int32_t np = 0;
+        int64_t nh = 0;
+        if (m <= SIM_POOL_NB_NMAX) {
+            const int32_t off[2] = {0, m};
+            rc = td_pool_n_batched(k, 1, m, off, from, to, pn.wait, pn.loss, s->dist, S, nullptr, s->pn_max_happy, pn.out, &np, &nh, nullptr);
+        } else {
+            rc = td_pool_n(k, m, from, to, pn.wait, pn.loss, s->dist, S, 0, m, s->pn_max_happy, m / k + 1, pn.out, &np, &nh);
+        }
+        if (rc) return rc;
+        happy += nh;
+        if (np <= 0) continue;
+        if (np > m / k) return fail(TD_EINTERNAL, "td_sim_begin: %d pools of %d among %d requests", np, k, m);
+        TD_HIP(hipMemsetAsync(pn.used, 0, sizeof(int32_t) * (size_t)m, c.stream));
+        k_pool_records<<<(np + 255) / 256, 256, 0, c.stream>>>(k, np, total, cap_plans, m, n, pn.out, map, pn.recs, pn.size, s->pl_a, s->pl_b,
+                                                              pn.used, s->isb, s->ainfo, &s->ctl->err);
+        TD_HIP(hipGetLastError());
+        total += np;
+        if (k > s->pn_lo) {   // the requests this stage did not pool, in list order, for the next one
+            if ((rc = compact(s, m, PoolPred{pn.used}, StageEmit{from, to, map, pn.st_from[cur], pn.st_to[cur], pn.st_map[cur]}, &s->head->n_stage)))
+                return rc;
+            from = pn.st_from[cur], to = pn.st_to[cur], map = pn.st_map[cur];
+            cur ^= 1;
+            m -= k * np;   // pools of a stage share no request
+            m_left = m;
+        }
+    }
+    if (n >= 2) {
+        s->max_pool_mem = std::max(s->max_pool_mem, happy);
+        s->max_pool = std::max(s->max_pool, (int64_t)total);
+    }
+    s->n_pool = total;
+    const Seg1 dem{n, nullptr};
+    if (s->pn_hi > 2)
+        rc = compact(s, n, PoolPred{s->isb},
+                     PoolEmitN<3, Seg1>{dem, total, s->dem_idx, s->dem_from, s->ainfo, pn.recs, pn.size, s->d2_idx, s->d2_from, s->d2_partner,
+                                        s->d2_plan, s->d2_cost, {pn.d2_more[0], pn.d2_more[1]}},
+                     &s->head->n_dem2);
+    else
+        rc = compact(s, n, PoolPred{s->isb},
+                     PoolEmitN<1, Seg1>{dem, total, s->dem_idx, s->dem_from, s->ainfo, pn.recs, pn.size, s->d2_idx, s->d2_from, s->d2_partner,
+                                        s->d2_plan, s->d2_cost, {nullptr, nullptr}},
+                     &s->head->n_dem2);
+    if (rc) return rc;
+    Head h;
+    if ((rc = read_head(s, &h))) return rc;
+    if (h.ctl.err) return fail(TD_EINTERNAL, "td_sim: a pool record names a customer outside the demand list");
+    if (m_left >= 0 && h.n_stage != m_left)
+        return fail(TD_EINTERNAL, "td_sim_begin: a stage of tick %d left %d requests on the device, %d by the pool counts", t, h.n_stage, m_left);
+    s->n_dem2 = h.n_dem2;
+    info[3] = h.n_dem2;
+    s->max_model = std::max(s->max_model, (int64_t)std::max(s->n_sup, s->n_dem2));
+    return TD_OK;
+}
+
 int sim_begin(td_sim *s, int t, int32_t info[4])
 {
     Ctx &c = ctx();
@@ -260,6 +430,7 @@ int sim_begin(td_sim *s, int t, int32_t info[4])
     // findPool on the device lists, the plans stay on the device
     int32_t k = 0;
     const int n = h.n_dem;
+    if (s->pn_hi) return sim_begin_pool_n(s, t, info);
     const bool find = s->pool_mode != TD_POOL_NONE;   // NONE: no findPool; the demand list is copied below as it is, no mark set
     if (find) s->n_pooled = n;
     if (find && n >= 2) {
@@ -313,6 +484,9 @@ int sim_apply(td_sim *s, int n_pairs, const int32_t *rows, const int32_t *cols, 
         return sim_ev_tick_done(s);
     }
     const bool log = s->ev.kinds != 0;
+    // pools of three or four: the partner columns behind the first travel with the apply kernels (such a handle never logs)
+    const bool more = s->pn_hi > 2;
+    auto px3 = [&] { return MorePartners<3>{{s->pn.d2_more[0], s->pn.d2_more[1]}, {s->pn.kd_more[0], s->pn.kd_more[1]}}; };
     if (log && (rc = ev_clear_apply(s->ev, (size_t)n_s, (size_t)n_d))) return rc;
     const bool lcm = n > mnl.v;
     if (lcm && !solved) *opt_count = -1;
@@ -325,37 +499,43 @@ int sim_apply(td_sim *s, int n_pairs, const int32_t *rows, const int32_t *cols, 
         TD_HIP(hipMemsetAsync(s->pair_cab, 0x7f, sizeof(int32_t) * (size_t)n_s, c.stream));
         TD_HIP(hipMemsetAsync(s->pair_dem, 0x7f, sizeof(int32_t) * (size_t)n_d, c.stream));
         if (n_pairs > 0) k_pair_map<<<(n_pairs + 255) / 256, 256, 0, c.stream>>>(dec, mnl, sup, d2, s->pair_cab, s->pair_dem, gerr);
-        auto pairs = [&](auto ev) {
+        auto pairs = [&](auto ev, auto px) {
             k_apply_pairs<<<nblocks(n_s + n_d), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, s->pair_cab, s->pair_dem, s->sup_cab,
-                                                                 s->sup_to, s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, gerr, ev);
+                                                                 s->sup_to, s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, gerr, ev, px);
         };
-        if (log)
-            pairs(EvOn{s->ev.st_pairs});
+        if (more)
+            pairs(EvOff{}, px3());
+        else if (log)
+            pairs(EvOn{s->ev.st_pairs}, MorePartners<1>{});
         else
-            pairs(EvOff{});
+            pairs(EvOff{}, MorePartners<1>{});
         TD_HIP(hipGetLastError());
         if ((rc = compact(s, n_s, KeptPred<Seg1>{s->pair_cab, sup, d2, mnl}, KeptSupEmit{s->sup_cab, s->sup_to, s->ks_cab, s->ks_to},
                           &s->head->n_ks)))
             return rc;
-        if ((rc = compact(s, n_d, KeptPred<Seg1>{s->pair_dem, sup, d2, mnl},
-                          KeptDemEmit{s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan,
-                                      s->kd_cost},
-                          &s->head->n_kd)))
-            return rc;
+        const KeptDemEmit ke{s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost};
+        if (more)
+            rc = compact(s, n_d, KeptPred<Seg1>{s->pair_dem, sup, d2, mnl},
+                         KeptDemEmitN<3>{ke, {s->pn.d2_more[0], s->pn.d2_more[1]}, {s->pn.kd_more[0], s->pn.kd_more[1]}}, &s->head->n_kd);
+        else
+            rc = compact(s, n_d, KeptPred<Seg1>{s->pair_dem, sup, d2, mnl}, ke, &s->head->n_kd);
+        if (rc) return rc;
     }
     if (!lcm || solved) {
         if ((rc = put(s->in_r2c, r2c, (size_t)nr))) return rc;
         // the kernel takes the kept lists where the LCM ran (their sizes are on the device), else the whole model
         const Seg1 ks{0, &s->head->n_ks}, kd{0, &s->head->n_kd};
-        auto solution = [&](auto ev) {
+        auto solution = [&](auto ev, auto px) {
             k_apply_solution<<<nblocks(n_s), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, ks, kd, s->sup_cab, s->sup_to, s->d2_idx, s->d2_from,
                                                               s->d2_partner, s->d2_plan, s->d2_cost, s->ks_cab, s->ks_to, s->kd_idx, s->kd_from,
-                                                              s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, gerr, ev);
+                                                              s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, gerr, ev, px);
         };
-        if (log)
-            solution(EvOn{s->ev.st_sol});
+        if (more)
+            solution(EvOff{}, px3());
+        else if (log)
+            solution(EvOn{s->ev.st_sol}, MorePartners<1>{});
         else
-            solution(EvOff{});
+            solution(EvOff{}, MorePartners<1>{});
         TD_HIP(hipGetLastError());
     }
     Head h;
@@ -465,6 +645,7 @@ extern "C" int td_sim_destroy(td_sim *s)
     if (!s) return TD_OK;
     if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
     buf_free(s->mem);
+    buf_free(s->pn_mem);
     ev_off(s->ev);
     if (s->pin) (void)hipHostFree(s->pin);
     delete s;
@@ -490,6 +671,56 @@ extern "C" int td_sim_pooling(td_sim *s, int mode, double max_loss)
     if (s->begun) return fail(TD_EINVAL, "td_sim_pooling: tick %d still waits for td_sim_apply", s->last_t);
     s->pool_mode = mode;
     s->max_loss = max_loss;
+    s->pn_hi = s->pn_lo = 0;   // back on a pair policy
+    return TD_OK;
+}
+
+extern "C" int td_sim_pooling_n(td_sim *s, int k_hi, int k_lo, int max_wait, int max_loss_pct, int64_t max_happy)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (!(2 <= k_lo && k_lo <= k_hi && k_hi <= 4)) return fail(TD_EINVAL, "td_sim_pooling_n: k_hi = %d, k_lo = %d outside 2 <= k_lo <= k_hi <= 4", k_hi, k_lo);
+    if (max_wait < 0 || max_loss_pct < 0) return fail(TD_EINVAL, "td_sim_pooling_n: max_wait = %d, max_loss_pct = %d: nothing negative", max_wait, max_loss_pct);
+    if (max_happy > ((int64_t)1 << 22)) return fail(TD_EINVAL, "td_sim_pooling_n: max_happy = %lld above %lld", (long long)max_happy, 1ll << 22);
+    if (s->begun) return fail(TD_EINVAL, "td_sim_pooling_n: tick %d still waits for td_sim_apply", s->last_t);
+    if (k_hi > 2 && s->ev.kinds)
+        return fail(TD_EINVAL, "td_sim_pooling_n: not built: the event log of pools of three and four (the handle logs; k_hi = 2 can be logged)");
+    Ctx &c = ctx();
+    PoolNDev &pn = s->pn;
+    if (!s->pn_mem.p) {   // the handle's, from the first call on: nothing is allocated per tick
+        const size_t cap = (size_t)s->cap, plans = cap / 2 + 1;
+        PoolNDev d;
+        int rc = carve_buf(s->pn_mem, [&](Carve &cv) {
+            for (int32_t **a : {&d.wait, &d.loss, &d.st_from[0], &d.st_from[1], &d.st_to[0], &d.st_to[1], &d.st_map[0], &d.st_map[1], &d.used,
+                                &d.d2_more[0], &d.d2_more[1], &d.kd_more[0], &d.kd_more[1]})
+                *a = cv.take<int32_t>(cap);
+            d.out = cv.take<int32_t>(3 * cap + 9);   // (m / k) records of 2 k + 1 ints: at most 2.5 m
+            d.recs = cv.take<int32_t>(9 * plans);
+            d.size = cv.take<int32_t>(plans);
+        });
+        if (rc) return rc;
+        pn = d;
+    }
+    k_fill2<<<(s->cap + 255) / 256, 256, 0, c.stream>>>(s->cap, pn.wait, max_wait, pn.loss, max_loss_pct);
+    TD_HIP(hipGetLastError());
+    s->pn_hi = k_hi, s->pn_lo = k_lo, s->pn_wait = max_wait, s->pn_loss = max_loss_pct, s->pn_max_happy = max_happy;
+    return TD_OK;
+}
+
+extern "C" int td_sim_pools_n(td_sim *s, int max_pools, int32_t *records, int32_t *size, int32_t *n)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !n) return fail(TD_EINVAL, "null argument");
+    if (!s->pn_hi) return fail(TD_EINVAL, "td_sim_pools_n: the world pools pairs (td_sim_pooling): read them with td_sim_pools");
+    if (max_pools < 0) return fail(TD_EINVAL, "td_sim_pools_n: negative max_pools");
+    const int k = s->n_pool;
+    *n = k;
+    if (k > max_pools) return fail(TD_EINVAL, "td_sim_pools_n: %d plans, more than max_pools = %d", k, max_pools);
+    if (k == 0) return TD_OK;
+    if (!records || !size) return fail(TD_EINVAL, "null destination");
+    int rc;
+    if ((rc = get(records, s->pn.recs, (size_t)9 * k)) || (rc = get(size, s->pn.size, (size_t)k))) return rc;
+    TD_HIP(hipStreamSynchronize(ctx().stream));
     return TD_OK;
 }
 
@@ -512,6 +743,7 @@ extern "C" int td_sim_pools(td_sim *s, int max_pools, int32_t *cust_a, int32_t *
 {
     TD_REQUIRE_INIT();
     if (!s || !n) return fail(TD_EINVAL, "null argument");
+    if (s->pn_hi) return fail(TD_EINVAL, "td_sim_pools: the world pools up to %d (td_sim_pooling_n): read the records with td_sim_pools_n", s->pn_hi);
     if (max_pools < 0) return fail(TD_EINVAL, "td_sim_pools: negative max_pools");
     const int k = s->n_pool;
     *n = k;
@@ -627,6 +859,8 @@ extern "C" int td_sim_log(td_sim *s, uint32_t kinds, int64_t capacity)
     if (kinds & ~TD_EV_ALL) return fail(TD_EINVAL, "td_sim_log: kinds = 0x%x has bits outside 1 .. 11", kinds);
     if (kinds && (capacity <= 0 || capacity > INT_MAX)) return fail(TD_EINVAL, "td_sim_log: capacity = %lld outside 1 .. 2^31 - 1", (long long)capacity);
     if (s->begun) return fail(TD_EINVAL, "td_sim_log: tick %d still waits for td_sim_apply", s->last_t);
+    if (kinds && s->pn_hi > 2)
+        return fail(TD_EINVAL, "td_sim_log: not built: the event log of pools of three and four (td_sim_pooling_n with k_hi = %d)", s->pn_hi);
     const size_t nc = (size_t)s->w.n_cabs, nr = (size_t)s->w.n_req;
     return ev_setup(s->ev, kinds, capacity, 1, nc, nr, nc + nr + 2 + nr + nr / 2 + 2 * (nc + nr) + 2 * nc);
 }

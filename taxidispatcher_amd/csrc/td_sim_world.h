@@ -282,6 +282,48 @@ struct PoolEmit {
         if (o2 >= 0) tk_from[o2] = dem_from[d];
     }
 };
+// ---- pools of up to four (td_sim_pooling_n).  A plan is a record of 9 ints: 4 pick-ups (-1 behind the pool's size), 4
+// drop-offs, the cost; its members are positions in the tick's demand list.  The first pick-up stays in the demand and carries
+// the size (in the plan column) and the cost; the second pick-up is its `partner`, the third and fourth lie in two more
+// columns.  NP = the partners a customer can carry: 1 while every pool is a pair (the columns of a pair world are enough),
+// 3 with pools of three or four.
+template <int NP>
+struct MorePartners {   // the partner columns behind the first: of the demand after pooling, of the kept demand
+    const int32_t *d[NP - 1], *kd[NP - 1];
+};
+template <>
+struct MorePartners<1> {};
+
+// analyzePool for records: ainfo = the record of a first pick-up (k_pool_records marked it), every other member has left
+template <int NP, class S>
+struct PoolEmitN {
+    S dem;
+    int n_rec;
+    const int32_t *dem_idx, *dem_from, *ainfo, *recs, *size;
+    int32_t *idx, *from, *partner, *plan, *cost, *more[2];
+    __device__ void operator()(int o, int, int d, int b) const
+    {
+        idx[o] = dem_idx[d];
+        from[o] = dem_from[d];
+        const int p = ainfo[d];
+        const bool a = p >= 0 && p < n_rec;
+        const int32_t *r = recs + (size_t)9 * (a ? p : 0);
+        int d0, n_dem;
+        dem(b, &d0, &n_dem);
+        auto member = [&](int q) {   // k_pool_records raised the error word for a member outside the list; never index by it
+            const int m = a ? r[q] : -1;
+            return m >= 0 && m < n_dem ? dem_idx[d0 + m] : -1;
+        };
+        partner[o] = member(1);
+        if constexpr (NP > 1) {
+            more[0][o] = member(2);
+            more[1][o] = member(3);
+        }
+        plan[o] = a ? size[p] : -1;
+        cost[o] = a ? r[8] : 0;
+    }
+};
+
 // the cabs / requests of an LCM world that are in no pair (analyzePairs' supply2 / demand2)
 template <class S, class L = LcmRule1>
 struct KeptPred {
@@ -315,6 +357,19 @@ struct KeptDemEmit {
         partner2[o] = partner[d];
         plan2[o] = plan[d];
         cost2[o] = cost[d];
+    }
+};
+// the same with the NP - 1 partner columns behind the first: from the demand after pooling (more) to the kept demand (more2)
+template <int NP>
+struct KeptDemEmitN {
+    KeptDemEmit kept;
+    const int32_t *more[NP - 1];
+    int32_t *more2[NP - 1];
+    __device__ void operator()(int o, int o2, int d, int b) const
+    {
+        kept(o, o2, d, b);
+#pragma unroll
+        for (int q = 0; q < NP - 1; q++) more2[q][o] = more[q][d];
     }
 };
 
@@ -404,13 +459,16 @@ __global__ __launch_bounds__(256) void k_pair_map(D dec, L max_non_lcm, S sup, S
 // request stores is world-local: cab minus where the world's fleet begins.
 // ev: EvOff, or EvOn on the pairs stage (cleared by the host before the launch): thread l of world b owns slots
 // 2 (s0 + d0 + l) and + 1, so the cab loop's records precede the request loop's and :654 precedes the same request's :432.
-template <class D, class S, class EV, class L>
+// px: the partner columns behind the first (NP = 3: a world of td_*_pooling_n with pools of three or four, never logged)
+template <class D, class S, class EV, class L, int NP>
 __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, L max_non_lcm, S cabs, S sup, S d2,
                                                     const int32_t *__restrict__ pair_cab, const int32_t *__restrict__ pair_dem,
                                                     const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
                                                     const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_partner,
-                                                    const int32_t *__restrict__ d_cost, Ctl *ctl, const int32_t *gerr, EV ev)
+                                                    const int32_t *__restrict__ d_cost, Ctl *ctl, const int32_t *gerr, EV ev,
+                                                    MorePartners<NP> px)
 {
+    static_assert(NP == 1 || !EV::on, "the apply stages own two staging slots per thread: a pool of four needs four");
     __shared__ int s_red[16];
     if (block_err(gerr)) return;
     const int b = blockIdx.y;
@@ -443,6 +501,17 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, L max
                 numb = 1;
                 if constexpr (EV::on) ev.put(slot + 1, TD_EV_POOLED_SECOND, EV_LCM, w.r_id[d_partner[d]], cab, -1);
             }
+            if constexpr (NP > 1) {
+#pragma unroll
+                for (int q = 0; q < NP - 1; q++) {
+                    const int o = px.d[q][d];
+                    if (o > -1) {   // assignPooled once per other member
+                        w.r_cab[o] = cab;
+                        second++;
+                        numb++;
+                    }
+                }
+            }
         }
     }
     const int tn = block_sum(numb, s_red), tp = block_sum(ptime, s_red), ts = block_sum(second, s_red);
@@ -458,7 +527,7 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, L max
 // cabs and the lists are copies), so that test is not repeated.
 // ev: EvOff, or EvOn on the solution stage (cleared by the host before the launch): cab l of world b's model owns slots
 // 2 (s0 + l) and + 1 with s0 = where the world's SUPPLY list begins (a kept list is no longer): :432 first, then :448 / :486.
-template <class D, class S, class EV, class L>
+template <class D, class S, class EV, class L, int NP>
 __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, L max_non_lcm, S cabs, S sup, S d2, S ks, S kd,
                                                        const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
                                                        const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_from,
@@ -467,8 +536,9 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, L 
                                                        const int32_t *__restrict__ ks_to, const int32_t *__restrict__ kd_idx,
                                                        const int32_t *__restrict__ kd_from, const int32_t *__restrict__ kd_partner,
                                                        const int32_t *__restrict__ kd_plan, const int32_t *__restrict__ kd_cost, Ctl *ctl,
-                                                       const int32_t *gerr, EV ev)
+                                                       const int32_t *gerr, EV ev, MorePartners<NP> px)
 {
+    static_assert(NP == 1 || !EV::on, "the apply stages own two staging slots per thread: a pool of four needs four");
     __shared__ int s_red[16];
     if (block_err(gerr)) return;
     const int b = blockIdx.y;
@@ -511,6 +581,17 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, L 
                     w.r_pcost[idx] = l_cost[e];
                     numb = 1;
                     if constexpr (EV::on) ev.put(slot0 + 2 * l, TD_EV_POOLED_SECOND, EV_OPT, w.r_id[partner], cab - c0, -1);
+                }
+                if constexpr (NP > 1) {
+#pragma unroll
+                    for (int q = 0; q < NP - 1; q++) {
+                        const int o = (lcm ? px.kd[q] : px.d[q])[e];
+                        if (o > -1) {   // assignPooled once per other member; the table keeps the second pick-up's id
+                            w.r_cab[o] = cab - c0;
+                            second++;
+                            numb++;
+                        }
+                    }
                 }
                 dispatch(w, t, cab, l_to[s], idx, partner, l_cost[e], numb, ptime, ev, slot0 + 2 * l + 1, EV_OPT, cab - c0);
             }

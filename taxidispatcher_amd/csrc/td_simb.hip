@@ -92,7 +92,38 @@ struct SimbPlans {
     __device__ __forceinline__ int base(int b) const { return ragged ? pl_off[b] >> 1 : b * pool_h; }
 };
 
+// td_simb_pooling_n: what the first call adds to a handle; a world with hi[b] == 0 keeps its pair policy.  The stage lists lie
+// where the world's demand list lies (dem_off[b]), cnt[b] entries long; world b's records at b * stride.
+struct SimbPoolN {
+    bool set = false;            // some world pools records
+    int any3 = 0;                // some world has k_hi > 2: the apply kernels carry three partners
+    std::vector<int32_t> hi, lo, wait, loss;
+    int64_t max_happy = 0;
+    int stride = 1, nmax = 1;    // plans per world in recs / size; the largest stage list (<= 512)
+    Buf mem;
+    int32_t *d_hi = nullptr, *d_lo, *d_wait, *d_loss;   // [B]
+    int32_t *cnt[2], *np;                               // [B]: the stage list's size (ping-pong), the stage's pools
+    int32_t *rec_base = nullptr;                        // [B]: where a record world's pairs lie in pa / pb, for the event log (k_hi == 2)
+    std::vector<int32_t> h_cnt, h_base;                 // this tick's first stage sizes and rec_base on the host
+    long long *nh, *happy, *tot;                        // [B]: the stage's happy plans, the tick's, the stage's cost
+    int32_t *st_from[2], *st_to[2], *st_map[2], *used;  // the stage lists and their positions in the world's demand list
+    int32_t *out;                                       // a stage's records as the pool call writes them
+    int32_t *recs, *size;                               // the tick's plans: 9 ints each, and their sizes
+    int32_t *d2_more[2], *kd_more[2];                   // the third and fourth pick-up of the demand after pooling / the kept demand
+};
+
+// the plan lists as the event log reads them in a batch with record worlds (td_simb_pooling_n, k_hi == 2 everywhere): a record
+// world pooled its whole demand list and mirrors its pairs in pa / pb at rec_base[b]
+struct SimbPlansN {
+    SimbPlans pl;
+    const int32_t *k_hi, *dem_off, *rec_base;
+    __device__ __forceinline__ int n_act(int b) const { return k_hi[b] ? dem_off[b + 1] - dem_off[b] : pl.n_act(b); }
+    __device__ __forceinline__ int count(int b) const { return pl.count(b); }
+    __device__ __forceinline__ int base(int b) const { return k_hi[b] ? rec_base[b] : pl.base(b); }
+};
+
 struct td_simb : SimbDev, SimbPin {   // td_sim_layout.h: every device array of the handle, and the pinned block
+    SimbPoolN pn;
     World w;                     // the concatenated tables
     int B = 0, max_non_lcm = 0;
     int words = 0;               // of one stand bitset
@@ -205,6 +236,139 @@ __global__ __launch_bounds__(CB) void k_scatter(const int32_t *__restrict__ off,
     if (f && pos < cap) emit(off_out[b] + pos, two ? off_out2[b] + pos : -1, lo + l, b);
 }
 
+// ---- td_simb_pooling_n: the cascade of every world at once.  The stage lists lie where the worlds' demand lists lie.
+struct PnArgs {
+    const int32_t *dem_off, *dem_from, *dem_to;
+    int32_t *cnt[2], *np, *n_rec;
+    long long *nh, *happy;
+    int32_t *st_from[2], *st_to[2], *st_map[2], *used;
+};
+
+// One compaction pass per stage for all worlds, one workgroup per world (a stage list holds at most 512 requests): the
+// requests no pool of the stage took stay, in list order, with their positions in the world's demand list; the world's plan
+// and happy-plan counts move on.  ident: the demand list itself becomes the first stage's list.
+__global__ __launch_bounds__(CB) void k_pn_compact(PnArgs a, int cur, int ident)
+{
+    __shared__ int s_red[16];
+    const int b = blockIdx.x, d0 = a.dem_off[b], n_dem = a.dem_off[b + 1] - d0;
+    const int m = min(max(a.cnt[ident ? 0 : cur][b], 0), n_dem);
+    const int32_t *sf = ident ? a.dem_from : a.st_from[cur], *st = ident ? a.dem_to : a.st_to[cur], *sm = a.st_map[cur];
+    const int nxt = ident ? 0 : cur ^ 1;
+    int kept = 0;
+    for (int i0 = 0; i0 < m; i0 += CB) {
+        const int i = i0 + threadIdx.x;
+        bool f = false;
+        if (i < m) {
+            f = !a.used[d0 + i];
+            a.used[d0 + i] = 0;   // the next stage starts from a clean list
+        }
+        int tot;
+        const int o = d0 + kept + block_rank(f, s_red, &tot);
+        if (f) {
+            a.st_from[nxt][o] = sf[d0 + i];
+            a.st_to[nxt][o] = st[d0 + i];
+            a.st_map[nxt][o] = ident ? i : sm[d0 + i];
+        }
+        kept += tot;
+    }
+    if (threadIdx.x == 0 && !ident) {
+        a.cnt[nxt][b] = kept;
+        a.n_rec[b] += a.np[b];
+        a.happy[b] += a.nh[b];
+        a.np[b] = 0;
+    }
+}
+
+// k_pool_mark for records, a stage of every world: record p of world b's pool call (2 K + 1 ints, members = positions in the
+// stage list) becomes plan n_rec[b] + p of the world's tick (9 ints, members = positions in the demand list).  Every member but
+// the first pick-up gets the leave mark, the first its plan index, the stage list forgets all of them.  A member outside
+// the list raises the error word.  rec_base non-null: the pair is mirrored in pl_a / pl_b for the event log.
+__global__ __launch_bounds__(256) void k_pn_records(int K, int nmax, int cur, int stride, PnArgs a, const int32_t *__restrict__ out,
+                                                    int32_t *__restrict__ recs, int32_t *__restrict__ size, int32_t *__restrict__ isb,
+                                                    int32_t *__restrict__ ainfo, const int32_t *__restrict__ rec_base,
+                                                    int32_t *__restrict__ pl_a, int32_t *__restrict__ pl_b, int32_t *gerr)
+{
+    const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.np[b] || p >= nmax / K) return;
+    const int d0 = a.dem_off[b], n_dem = a.dem_off[b + 1] - d0, m = min(a.cnt[cur][b], n_dem), base = a.n_rec[b];
+    if (base < 0 || base + p >= stride) {
+        atomicMax(gerr, 1);
+        return;
+    }
+    const int32_t *r = out + ((size_t)b * (size_t)(nmax / K) + (size_t)p) * (size_t)(2 * K + 1), *map = a.st_map[cur] + d0;
+    int pick[4] = {-1, -1, -1, -1}, drop[4] = {-1, -1, -1, -1};
+    bool bad = false;
+    for (int i = 0; i < K; i++) {
+        const int u = r[i], v = r[K + i];
+        if (u < 0 || u >= m || v < 0 || v >= m) {
+            bad = true;
+            continue;
+        }
+        pick[i] = map[u];
+        drop[i] = map[v];
+        bad = bad || pick[i] < 0 || pick[i] >= n_dem || drop[i] < 0 || drop[i] >= n_dem;
+    }
+    if (bad) {
+        atomicMax(gerr, 1);
+        return;
+    }
+    const size_t q = (size_t)b * (size_t)stride + (size_t)(base + p);
+    int32_t *o = recs + 9 * q;
+    for (int i = 0; i < 4; i++) {
+        o[i] = pick[i];
+        o[4 + i] = drop[i];
+    }
+    o[8] = r[2 * K];
+    size[q] = K;
+    if (rec_base) {   // the handle logs (every pool is a pair): first and second pick-up where the event log reads a pair
+        const int e = rec_base[b] + base + p;   // base + p < n_dem / 2: inside the world's slice of pa / pb
+        pl_a[e] = pick[0];
+        pl_b[e] = pick[1];
+    }
+    atomicMin(&ainfo[d0 + pick[0]], base + p);
+    for (int i = 0; i < K; i++) {
+        a.used[d0 + r[i]] = 1;
+        if (i) isb[d0 + pick[i]] = 1;
+    }
+}
+
+// analyzePool of a batch that mixes policies: a pair world's customer through PoolEmit, a record world's through its records
+template <int NP>
+struct PoolEmitB {
+    PoolEmit<SimbPlans, SegOff> pair;
+    const int32_t *k_hi, *recs, *size;
+    int stride;
+    int32_t *more[2];
+    __device__ void operator()(int o, int o2, int d, int b) const
+    {
+        if (!k_hi[b]) {
+            pair(o, o2, d, b);
+            if constexpr (NP > 1) more[0][o] = more[1][o] = -1;
+            return;
+        }
+        pair.idx[o] = pair.dem_idx[d];
+        pair.from[o] = pair.dem_from[d];
+        const int p = pair.ainfo[d];
+        const bool a = p >= 0 && p < min(pair.pl.count(b), stride);
+        const size_t q = (size_t)b * (size_t)stride + (size_t)(a ? p : 0);
+        const int32_t *r = recs + 9 * q;
+        int d0, n_dem;
+        pair.dem(b, &d0, &n_dem);
+        auto member = [&](int j) {   // k_pn_records raised the error word for a member outside the list; never index by it
+            const int m = a ? r[j] : -1;
+            return m >= 0 && m < n_dem ? pair.dem_idx[d0 + m] : -1;
+        };
+        pair.partner[o] = member(1);
+        if constexpr (NP > 1) {
+            more[0][o] = member(2);
+            more[1][o] = member(3);
+        }
+        pair.plan[o] = a ? size[q] : -1;
+        pair.cost[o] = a ? r[8] : 0;
+        if (o2 >= 0) pair.tk_from[o2] = pair.dem_from[d];
+    }
+};
+
 inline int nchunks(int n) { return std::max(1, (n + CB - 1) / CB); }
 
 // the head block on the host: every world's Ctl, the error word, the offset arrays, the per-world words, in ONE copy
@@ -235,9 +399,18 @@ int simb_ev_flush(td_simb *s, int phase)
         const size_t nc = (size_t)(s->cab_off[b + 1] - s->cab_off[b]), nr = (size_t)(s->req_off[b + 1] - s->req_off[b]), ns = (size_t)s->n_sup[b];
         vmax = std::max(vmax, nc + nr + 2 + s->n_dem[b] + s->n_dem[b] / 2 + 2 * (ns + s->n_d2[b]) + 2 * ns);
     }
+    const SimbPlans pl{s->pool_h, s->pool_ragged, s->pl_off, s->n_pools};
+    if (s->pn.set)
+        return with_rule(s, [&](auto rule) {
+            const EvSrc<SegOff, SimbPlansN, decltype(rule)> src{s->w, SegOff{s->d_cab_off}, SegOff{s->d_req_off}, SegOff{s->dem_off}, SegOff{s->sup_off},
+                                                                SegOff{s->d2_off}, SimbPlansN{pl, s->pn.d_hi, s->dem_off, s->pn.rec_base}, rule,
+                                                                s->last_t, phase, e.kinds, e.st_arr, e.st_drop, e.st_pairs, e.st_sol, s->dem_idx, s->pa,
+                                                                s->pb};
+            return ev_flush(s->ev, src, s->B, vmax);
+        });
     return with_rule(s, [&](auto rule) {
         const EvSrc<SegOff, SimbPlans, decltype(rule)> src{s->w, SegOff{s->d_cab_off}, SegOff{s->d_req_off}, SegOff{s->dem_off}, SegOff{s->sup_off},
-                                                           SegOff{s->d2_off}, SimbPlans{s->pool_h, s->pool_ragged, s->pl_off, s->n_pools}, rule,
+                                                           SegOff{s->d2_off}, pl, rule,
                                                            s->last_t, phase, e.kinds, e.st_arr, e.st_drop, e.st_pairs, e.st_sol, s->dem_idx, s->pa,
                                                            s->pb};
         return ev_flush(s->ev, src, s->B, vmax);
@@ -251,6 +424,75 @@ int simb_ev_tick_done(td_simb *s)
     const int phase = s->ev.begin_flushed ? 2 : 3;
     s->ev.begin_flushed = false;
     return simb_ev_flush(s, phase);
+}
+
+constexpr int SIMB_POOL_N_NMAX = 512;   // td_pool_n_batched's largest model
+
+// findPool of the worlds under td_simb_pooling_n, after the pair worlds' (the specification: Simulator.find_pool_n in every
+// such world).  Round k = 4, 3, 2 serves every world whose cascade has a stage of k, so a world's stages run k_hi down to k_lo
+// and a tick has at most three pool launches whatever B is; a world of another policy, without supply or with fewer than
+// two requests is an empty model.  Marks go to isb / ainfo, the plan count of a world to n_pools[b] (read with the head).
+// the first stage's list of every record world (0: the world does not pool in this tick) and the rounds the tick needs;
+// a world beyond the pool call's model is refused before anything is pooled
+int simb_pool_n_sizes(td_simb *s, int t)
+{
+    SimbPoolN &pn = s->pn;
+    pn.nmax = 0;
+    for (int b = 0; b < s->B; b++) {
+        const int m = pn.hi[b] && s->n_sup[b] > 0 && s->n_dem[b] >= 2 ? s->n_dem[b] : 0;
+        if (m > SIMB_POOL_N_NMAX)
+            return fail(TD_EINVAL, "td_simb_begin: world %d has %d requests before pooling in tick %d, more than the %d td_pool_n_batched takes", b, m, t,
+                        SIMB_POOL_N_NMAX);
+        pn.h_cnt[b] = m;
+        pn.nmax = std::max(pn.nmax, m);
+    }
+    return TD_OK;
+}
+
+int simb_pool_n(td_simb *s, int t)
+{
+    Ctx &c = ctx();
+    SimbPoolN &pn = s->pn;
+    const int B = s->B, nmax = pn.nmax;
+    const bool log = s->ev.kinds != 0;
+    if (nmax == 0) return TD_OK;
+    bool round[5] = {false, false, false, false, false};
+    for (int b = 0; b < B; b++)
+        for (int k = pn.lo[b]; pn.h_cnt[b] && k <= pn.hi[b]; k++) round[k] = true;
+    // h_stage (pinned, at least 3 (B + 1) ints) serves twice, ordered on the stream: 2 B ints up (sizes, rec_base), then B 64-bit
+    // happy-plan counts down.  The per-world pair path queued an upload from it: that one has to be over first.
+    if (s->pool_ragged) TD_HIP(hipStreamSynchronize(c.stream));
+    int32_t *st = s->h_stage;
+    memcpy(st, pn.h_cnt.data(), sizeof(int32_t) * B);
+    memcpy(st + B, pn.h_base.data(), sizeof(int32_t) * B);
+    TD_HIP(hipMemcpyAsync(pn.cnt[0], st, sizeof(int32_t) * 2 * B, hipMemcpyHostToDevice, c.stream));   // cnt[0] and rec_base are one block
+    const size_t nd_tot = (size_t)h_of(s, s->dem_off)[B];
+    TD_HIP(hipMemsetAsync(pn.np, 0, sizeof(int32_t) * B, c.stream));
+    TD_HIP(hipMemsetAsync(pn.happy, 0, sizeof(long long) * B, c.stream));
+    TD_HIP(hipMemsetAsync(pn.used, 0, sizeof(int32_t) * nd_tot, c.stream));
+    const PnArgs a{s->dem_off, s->dem_from, s->dem_to, {pn.cnt[0], pn.cnt[1]}, pn.np, s->n_pools, pn.nh, pn.happy,
+                   {pn.st_from[0], pn.st_from[1]}, {pn.st_to[0], pn.st_to[1]}, {pn.st_map[0], pn.st_map[1]}, pn.used};
+    k_pn_compact<<<B, CB, 0, c.stream>>>(a, 0, 1);
+    TD_HIP(hipGetLastError());
+    int cur = 0;
+    for (int k = 4; k >= 2; k--) {
+        if (!round[k]) continue;
+        int over = -1, rc;
+        long long count = 0;
+        rc = pool_n_worlds(k, B, nmax, s->dem_off, pn.cnt[cur], pn.d_hi, pn.d_lo, pn.st_from[cur], pn.st_to[cur], pn.d_wait, pn.d_loss, s->dist,
+                           s->dist ? s->w.n_stands : 0, pn.max_happy, pn.out, pn.np, pn.nh, pn.tot, &over, &count);
+        if (rc == TD_ERANGE && over >= 0)
+            return fail(TD_ERANGE, "td_simb_begin: world %d has %lld happy plans of %d in tick %d, more than max_happy", over, count, k, t);
+        if (rc) return rc;
+        k_pn_records<<<dim3((std::max(1, nmax / k) + 255) / 256, B), 256, 0, c.stream>>>(k, nmax, cur, pn.stride, a, pn.out, pn.recs, pn.size, s->isb,
+                                                                                       s->ainfo, log ? pn.rec_base : nullptr, s->pa, s->pb, s->gerr);
+        k_pn_compact<<<B, CB, 0, c.stream>>>(a, cur, 0);
+        TD_HIP(hipGetLastError());
+        cur ^= 1;
+    }
+    // the happy plans of the tick per world, for max_POOL_MEM_size: read after the head's synchronisation
+    TD_HIP(hipMemcpyAsync(st, pn.happy, sizeof(long long) * B, hipMemcpyDeviceToHost, c.stream));
+    return TD_OK;
 }
 
 int simb_begin(td_simb *s, int t, int32_t *info)
@@ -305,6 +547,15 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     }
     if (hd[B] == 0) return simb_ev_tick_done(s);   // Simulator.java:160 in every world: nothing to do in this tick
     s->begun = true;
+    // the record worlds' sizes first: their pairs are mirrored for the event log at the stride of the pair worlds' plans
+    int n_all = max_act;
+    if (s->pn.set) {
+        if ((rc = simb_pool_n_sizes(s, t))) return rc;
+        if (log && max_act <= SIMB_NMAX) {
+            n_all = std::max(max_act, s->pn.nmax);
+            s->pool_h = std::max(1, n_all / 2);
+        }
+    }
     // findPool for the worlds with supply, the plans stay on the device
     if (max_act >= 2) {
         if (s->pool_set)   // the optimum of a world is ONE model of the batched call: refused before anything is pooled
@@ -316,11 +567,11 @@ int simb_begin(td_simb *s, int t, int32_t *info)
             if (hp[b + 1] - hp[b] >= 2) s->max_pool_mem[b] = std::max(s->max_pool_mem[b], (int64_t)s->n_dem[b] * (s->n_dem[b] - 1));
         const int S = s->dist ? w.n_stands : 0;
         if (max_act <= SIMB_NMAX) {
-            s->pool_h = std::max(1, max_act / 2);
+            s->pool_h = std::max(1, n_all / 2);
             if (!s->pool_set)
-                rc = td_pool2_batched(B, max_act, hp, s->pl_from, s->pl_to, s->dist, S, 0.0, 0, s->pa, s->pb, s->pp, s->pc, s->n_pools, s->p_total);
+                rc = td_pool2_batched(B, n_all, hp, s->pl_from, s->pl_to, s->dist, S, 0.0, 0, s->pa, s->pb, s->pp, s->pc, s->n_pools, s->p_total);
             else   // one call for every policy of the batch: its launches do not depend on B or on the mix
-                rc = td_pool2_batched_v(B, max_act, hp, s->pl_from, s->pl_to, s->dist, S, s->pool_ml.data(), s->pool_opt.data(), s->pa, s->pb, s->pp, s->pc,
+                rc = td_pool2_batched_v(B, n_all, hp, s->pl_from, s->pl_to, s->dist, S, s->pool_ml.data(), s->pool_opt.data(), s->pa, s->pb, s->pp, s->pc,
                                         s->n_pools, s->p_total);
             if (rc) return rc;
         } else if (s->pool_set) {
@@ -363,15 +614,31 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     const SegOff dem{s->dem_off};
     if (max_act >= 2)
         k_pool_mark<<<dim3((max_act / 2 + 255) / 256, B), 256, 0, c.stream>>>(pl, dem, s->pa, s->pb, s->isb, s->ainfo, s->gerr);
+    if (s->pn.set) {
+        // where a record world mirrors its pairs: its slot of the strided plan lists, or, beside the packed lists of the per-world
+        // pair path (at most pl_off[B] / 2 plans), packed behind them: together never more than half the requests
+        int at = (hp[B] >> 1) + 1;
+        for (int b = 0; b < B; b++) {
+            s->pn.h_base[b] = s->pool_ragged ? at : b * s->pool_h;
+            if (s->pn.hi[b]) at += s->n_dem[b] >> 1;
+        }
+        if ((rc = simb_pool_n(s, t))) return rc;
+    }
     const dim3 grid_d(nchunks(max_dem), B);
     const PoolPred pp{s->isb};
     k_count<SegOff, PoolPred><<<grid_d, CB, 0, c.stream>>>(dem, pp, s->cnt_a);
     k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, (int)grid_d.x, nullptr, 0, 0, s->sup_off, s->d2_off, nullptr, s->tk_off);
-    k_scatter<PoolPred, PoolEmit<SimbPlans, SegOff>><<<grid_d, CB, 0, c.stream>>>(
-        s->dem_off, pp,
-        PoolEmit<SimbPlans, SegOff>{pl, dem, s->dem_idx, s->dem_from, s->ainfo, s->pb, s->pp, s->pc, s->d2_idx, s->d2_from, s->d2_partner,
-                                    s->d2_plan, s->d2_cost, s->tk_from},
-        s->cnt_a, s->d2_off, s->tk_off);
+    const PoolEmit<SimbPlans, SegOff> pe{pl, dem, s->dem_idx, s->dem_from, s->ainfo, s->pb, s->pp, s->pc, s->d2_idx, s->d2_from, s->d2_partner,
+                                         s->d2_plan, s->d2_cost, s->tk_from};
+    const SimbPoolN &pn = s->pn;
+    if (!pn.set)
+        k_scatter<PoolPred, PoolEmit<SimbPlans, SegOff>><<<grid_d, CB, 0, c.stream>>>(s->dem_off, pp, pe, s->cnt_a, s->d2_off, s->tk_off);
+    else if (pn.any3)
+        k_scatter<PoolPred, PoolEmitB<3>><<<grid_d, CB, 0, c.stream>>>(
+            s->dem_off, pp, PoolEmitB<3>{pe, pn.d_hi, pn.recs, pn.size, pn.stride, {pn.d2_more[0], pn.d2_more[1]}}, s->cnt_a, s->d2_off, s->tk_off);
+    else
+        k_scatter<PoolPred, PoolEmitB<1>><<<grid_d, CB, 0, c.stream>>>(s->dem_off, pp, PoolEmitB<1>{pe, pn.d_hi, pn.recs, pn.size, pn.stride, {nullptr, nullptr}},
+                                                                     s->cnt_a, s->d2_off, s->tk_off);
     TD_HIP(hipGetLastError());
     if ((rc = read_head(s))) return rc;
     if (*h_of(s, s->gerr)) {
@@ -385,6 +652,16 @@ int simb_begin(td_simb *s, int t, int32_t *info)
         s->h_npool[b] = m >= 2 ? std::min(std::max(hn[b], 0), m / 2) : 0;
         s->h_pbase[b] = s->pool_ragged ? hp[b] >> 1 : b * s->pool_h;
         s->n_d2[b] = h2[b + 1] - h2[b];
+        if (s->pn.set && s->pn.hi[b]) {   // a record world: its plans of all stages, and the happy plans behind them
+            const bool ran = s->pn.nmax > 0 && s->n_sup[b] > 0 && s->n_dem[b] >= 2;
+            s->h_npool[b] = ran ? std::min(std::max(hn[b], 0), s->pn.stride) : 0;
+            if (ran) {
+                long long happy;
+                memcpy(&happy, s->h_stage + 2 * (size_t)b, sizeof(happy));
+                s->max_pool_mem[b] = std::max(s->max_pool_mem[b], (int64_t)happy);
+                s->max_pool[b] = std::max(s->max_pool[b], (int64_t)s->h_npool[b]);
+            }
+        }
         if (s->n_dem[b] == 0) continue;
         info[4 * b] = 1;
         info[4 * b + 1] = s->n_dem[b];
@@ -421,6 +698,9 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
     const int32_t *hs = h_of(s, s->sup_off), *h2 = h_of(s, s->d2_off);
     const SegOff cabs{s->d_cab_off}, sup{s->sup_off}, d2{s->d2_off};
     const bool log = s->ev.kinds != 0;
+    // pools of three or four in some world: the partner columns behind the first travel with the apply kernels (such a handle never logs)
+    const bool more = s->pn.set && s->pn.any3;
+    const MorePartners<3> px3{{s->pn.d2_more[0], s->pn.d2_more[1]}, {s->pn.kd_more[0], s->pn.kd_more[1]}};
     if (log && (rc = ev_clear_apply(s->ev, (size_t)hs[B], (size_t)h2[B]))) return rc;
     rc = with_rule(s, [&](auto mnl) -> int {
     using L = decltype(mnl);
@@ -429,14 +709,16 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
         TD_HIP(hipMemsetAsync(s->pair_dem, 0x7f, sizeof(int32_t) * (size_t)h2[B], c.stream));
         if (max_pairs > 0)
             k_pair_map<<<dim3((max_pairs + 255) / 256, B), 256, 0, c.stream>>>(dec, mnl, sup, d2, s->pair_cab, s->pair_dem, s->gerr);
-        auto pairs = [&](auto ev) {
+        auto pairs = [&](auto ev, auto px) {
             k_apply_pairs<<<dim3(nchunks(max_sd), B), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, s->pair_cab, s->pair_dem, s->sup_cab, s->sup_to,
-                                                                       s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, s->gerr, ev);
+                                                                       s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, s->gerr, ev, px);
         };
-        if (log)
-            pairs(EvOn{s->ev.st_pairs});
+        if (more)
+            pairs(EvOff{}, px3);
+        else if (log)
+            pairs(EvOn{s->ev.st_pairs}, MorePartners<1>{});
         else
-            pairs(EvOff{});
+            pairs(EvOff{}, MorePartners<1>{});
         const dim3 grid_s(nchunks(max_s), B), grid_d(nchunks(max_d), B);
         const KeptPred<SegOff, L> ps{s->pair_cab, sup, d2, mnl}, pd{s->pair_dem, sup, d2, mnl};
         k_count<SegOff, KeptPred<SegOff, L>><<<grid_s, CB, 0, c.stream>>>(sup, ps, s->cnt_a);
@@ -444,20 +726,25 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
         k_offsets<<<1, CB, 0, c.stream>>>(B, s->cnt_a, (int)grid_s.x, s->cnt_b, (int)grid_d.x, 0, nullptr, s->ks_off, s->kd_off, nullptr);
         k_scatter<KeptPred<SegOff, L>, KeptSupEmit><<<grid_s, CB, 0, c.stream>>>(s->sup_off, ps, KeptSupEmit{s->sup_cab, s->sup_to, s->ks_cab, s->ks_to},
                                                                             s->cnt_a, s->ks_off, nullptr);
-        k_scatter<KeptPred<SegOff, L>, KeptDemEmit><<<grid_d, CB, 0, c.stream>>>(
-            s->d2_off, pd, KeptDemEmit{s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost},
-            s->cnt_b, s->kd_off, nullptr);
+        const KeptDemEmit ke{s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost};
+        if (more)
+            k_scatter<KeptPred<SegOff, L>, KeptDemEmitN<3>><<<grid_d, CB, 0, c.stream>>>(
+                s->d2_off, pd, KeptDemEmitN<3>{ke, {s->pn.d2_more[0], s->pn.d2_more[1]}, {s->pn.kd_more[0], s->pn.kd_more[1]}}, s->cnt_b, s->kd_off, nullptr);
+        else
+            k_scatter<KeptPred<SegOff, L>, KeptDemEmit><<<grid_d, CB, 0, c.stream>>>(s->d2_off, pd, ke, s->cnt_b, s->kd_off, nullptr);
     }
-    auto solution = [&](auto ev) {
+    auto solution = [&](auto ev, auto px) {
         k_apply_solution<<<dim3(nchunks(max_s), B), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, SegOff{s->ks_off}, SegOff{s->kd_off}, s->sup_cab,
                                                                      s->sup_to, s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->ks_cab,
                                                                      s->ks_to, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, s->gerr,
-                                                                     ev);
+                                                                     ev, px);
     };
-    if (any_sup && log)
-        solution(EvOn{s->ev.st_sol});
+    if (any_sup && more)
+        solution(EvOff{}, px3);
+    else if (any_sup && log)
+        solution(EvOn{s->ev.st_sol}, MorePartners<1>{});
     else if (any_sup)
-        solution(EvOff{});
+        solution(EvOff{}, MorePartners<1>{});
     return TD_OK;
     });
     if (rc) return rc;
@@ -561,7 +848,9 @@ static int simb_create(int batch, const int32_t *n_cabs, int n_stands, int drop_
     s->ncap = std::max(1, std::min(SIMB_NMAX, std::max(max_cabs, max_req)));
     s->hcap = std::max(1, std::min(SIMB_NMAX, max_req) / 2);
     s->in_cap = in_cap;
-    for (std::vector<int32_t> *v : {&s->n_dem, &s->n_sup, &s->n_d2, &s->pool_opt, &s->h_npool, &s->h_pbase}) v->assign((size_t)B, 0);
+    for (std::vector<int32_t> *v : {&s->n_dem, &s->n_sup, &s->n_d2, &s->pool_opt, &s->h_npool, &s->h_pbase, &s->pn.hi, &s->pn.lo, &s->pn.wait, &s->pn.loss,
+                                    &s->pn.h_cnt, &s->pn.h_base})
+        v->assign((size_t)B, 0);
     s->pool_mode.assign((size_t)B, TD_POOL_GREEDY);
     s->pool_ml.assign((size_t)B, 0.0);
     for (std::vector<int64_t> *v : {&s->lcm_used, &s->max_model, &s->max_solver, &s->max_pool_mem, &s->max_pool}) v->assign((size_t)B, 0);
@@ -651,6 +940,7 @@ extern "C" int td_simb_destroy(td_simb *s)
     if (!s) return TD_OK;
     if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
     buf_free(s->mem);
+    buf_free(s->pn.mem);
     ev_off(s->ev);
     if (s->pin) (void)hipHostFree(s->pin);
     delete s;
@@ -693,6 +983,102 @@ extern "C" int td_simb_pooling(td_simb *s, const int32_t *mode, const double *ma
     for (size_t b = 0; b < B; b++) s->pool_opt[b] = hm[b] == TD_POOL_OPTIMAL;
     s->has_none = none;
     s->pool_set = true;
+    // every world is back on a pair policy
+    s->pn.set = false;
+    s->pn.any3 = 0;
+    for (std::vector<int32_t> *v : {&s->pn.hi, &s->pn.lo, &s->pn.wait, &s->pn.loss}) v->assign(B, 0);
+    return TD_OK;
+}
+
+extern "C" int td_simb_pooling_n(td_simb *s, const int32_t *k_hi, const int32_t *k_lo, const int32_t *max_wait, const int32_t *max_loss_pct,
+                                 int64_t max_happy)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !k_hi || !k_lo || !max_wait || !max_loss_pct) return fail(TD_EINVAL, "td_simb_pooling_n: null argument");
+    if (s->begun) return fail(TD_EINVAL, "td_simb_pooling_n: tick %d still waits for td_simb_apply", s->last_t);
+    if (max_happy > ((int64_t)1 << 22)) return fail(TD_EINVAL, "td_simb_pooling_n: max_happy = %lld above %lld", (long long)max_happy, 1ll << 22);
+    const size_t B = (size_t)s->B;
+    SimbPoolN &pn = s->pn;
+    int rc;
+    std::vector<int32_t> hh, hl, hw, hs;
+    if ((rc = host_copy(k_hi, B, hh)) || (rc = host_copy(k_lo, B, hl)) || (rc = host_copy(max_wait, B, hw)) || (rc = host_copy(max_loss_pct, B, hs)))
+        return rc;
+    bool any = false;
+    int any3 = 0;
+    for (size_t b = 0; b < B; b++) {
+        if (hh[b] == 0) {   // world b keeps the policy it has
+            hh[b] = pn.hi[b], hl[b] = pn.lo[b], hw[b] = pn.wait[b], hs[b] = pn.loss[b];
+        } else {
+            if (!(2 <= hl[b] && hl[b] <= hh[b] && hh[b] <= 4))
+                return fail(TD_EINVAL, "td_simb_pooling_n: k_hi[%zu] = %d, k_lo[%zu] = %d outside 2 <= k_lo <= k_hi <= 4", b, hh[b], b, hl[b]);
+            if (hw[b] < 0 || hs[b] < 0)
+                return fail(TD_EINVAL, "td_simb_pooling_n: max_wait[%zu] = %d, max_loss_pct[%zu] = %d: nothing negative", b, hw[b], b, hs[b]);
+        }
+        any = any || hh[b];
+        any3 = any3 || hh[b] > 2;
+    }
+    if (any3 && s->ev.kinds)
+        return fail(TD_EINVAL, "td_simb_pooling_n: not built: the event log of pools of three and four (the handle logs; k_hi = 2 can be logged)");
+    if (!pn.mem.p) {   // the handle's, from the first call on: nothing is allocated per tick
+        const size_t nr = (size_t)std::max(s->nr_tot, 1), ncap = (size_t)std::max(1, std::min(SIMB_POOL_N_NMAX, s->max_req));
+        const size_t stride = std::max<size_t>(1, ncap / 2);
+        SimbPoolN d;
+        rc = carve_buf(pn.mem, [&](Carve &cv) {
+            for (long long **a : {&d.nh, &d.happy, &d.tot}) *a = cv.take<long long>(B);
+            for (int32_t **a : {&d.d_hi, &d.d_lo, &d.d_wait, &d.d_loss, &d.cnt[0], &d.rec_base, &d.cnt[1], &d.np}) *a = cv.take<int32_t>(B);   // cnt[0], rec_base: one upload
+            for (int32_t **a : {&d.st_from[0], &d.st_from[1], &d.st_to[0], &d.st_to[1], &d.st_map[0], &d.st_map[1], &d.used, &d.d2_more[0], &d.d2_more[1],
+                                &d.kd_more[0], &d.kd_more[1]})
+                *a = cv.take<int32_t>(nr);
+            d.out = cv.take<int32_t>(B * 3 * ncap + 16);   // per world (n / k) records of 2 k + 1 ints: at most 2.5 n
+            d.recs = cv.take<int32_t>(9 * B * stride);
+            d.size = cv.take<int32_t>(B * stride);
+        });
+        if (rc) return rc;
+        pn.d_hi = d.d_hi, pn.d_lo = d.d_lo, pn.d_wait = d.d_wait, pn.d_loss = d.d_loss, pn.np = d.np, pn.rec_base = d.rec_base, pn.nh = d.nh, pn.happy = d.happy, pn.tot = d.tot;
+        pn.used = d.used, pn.out = d.out, pn.recs = d.recs, pn.size = d.size;
+        for (int q = 0; q < 2; q++)
+            pn.cnt[q] = d.cnt[q], pn.st_from[q] = d.st_from[q], pn.st_to[q] = d.st_to[q], pn.st_map[q] = d.st_map[q], pn.d2_more[q] = d.d2_more[q],
+            pn.kd_more[q] = d.kd_more[q];
+        pn.stride = (int)stride;
+    }
+    // the worlds of this policy leave the pair lists as a world without pooling does (k_offsets' gate)
+    std::vector<int32_t> none(B);
+    bool gate = false;
+    for (size_t b = 0; b < B; b++) {
+        none[b] = hh[b] || (s->pool_set && s->pool_mode[b] == TD_POOL_NONE);
+        gate = gate || none[b];
+    }
+    TD_HIP(hipMemcpyAsync(s->d_none, none.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx().stream));
+    TD_HIP(hipMemcpyAsync(pn.d_hi, hh.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx().stream));
+    TD_HIP(hipMemcpyAsync(pn.d_lo, hl.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx().stream));
+    TD_HIP(hipMemcpyAsync(pn.d_wait, hw.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx().stream));
+    TD_HIP(hipMemcpyAsync(pn.d_loss, hs.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx().stream));
+    TD_HIP(hipStreamSynchronize(ctx().stream));
+    s->has_none = gate;
+    pn.hi = hh, pn.lo = hl, pn.wait = hw, pn.loss = hs;
+    pn.set = any;
+    pn.any3 = any3;
+    pn.max_happy = max_happy;
+    return TD_OK;
+}
+
+extern "C" int td_simb_pools_n(td_simb *s, int world, int max_pools, int32_t *records, int32_t *size, int32_t *n)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !n) return fail(TD_EINVAL, "null argument");
+    if (world < 0 || world >= s->B) return fail(TD_EINVAL, "td_simb_pools_n: world %d outside 0 .. %d", world, s->B - 1);
+    if (!s->pn.set || !s->pn.hi[world])
+        return fail(TD_EINVAL, "td_simb_pools_n: world %d pools pairs (td_simb_pooling): read them with td_simb_pools", world);
+    if (max_pools < 0) return fail(TD_EINVAL, "td_simb_pools_n: negative max_pools");
+    const int k = s->h_npool[world];
+    *n = k;
+    if (k > max_pools) return fail(TD_EINVAL, "td_simb_pools_n: world %d has %d plans, more than max_pools = %d", world, k, max_pools);
+    if (k == 0) return TD_OK;
+    if (!records || !size) return fail(TD_EINVAL, "null destination");
+    const size_t q = (size_t)world * (size_t)s->pn.stride;
+    int rc;
+    if ((rc = get(records, s->pn.recs + 9 * q, (size_t)9 * k)) || (rc = get(size, s->pn.size + q, (size_t)k))) return rc;
+    TD_HIP(hipStreamSynchronize(ctx().stream));
     return TD_OK;
 }
 
@@ -734,6 +1120,8 @@ extern "C" int td_simb_pools(td_simb *s, int world, int max_pools, int32_t *cust
     TD_REQUIRE_INIT();
     if (!s || !n) return fail(TD_EINVAL, "null argument");
     if (world < 0 || world >= s->B) return fail(TD_EINVAL, "td_simb_pools: world %d outside 0 .. %d", world, s->B - 1);
+    if (s->pn.set && s->pn.hi[world])
+        return fail(TD_EINVAL, "td_simb_pools: world %d pools up to %d (td_simb_pooling_n): read the records with td_simb_pools_n", world, s->pn.hi[world]);
     if (max_pools < 0) return fail(TD_EINVAL, "td_simb_pools: negative max_pools");
     const int k = s->h_npool[world];
     *n = k;
@@ -894,6 +1282,8 @@ extern "C" int td_simb_log(td_simb *s, uint32_t kinds, int64_t capacity)
     if (kinds & ~TD_EV_ALL) return fail(TD_EINVAL, "td_simb_log: kinds = 0x%x has bits outside 1 .. 11", kinds);
     if (kinds && (capacity <= 0 || capacity > INT_MAX)) return fail(TD_EINVAL, "td_simb_log: capacity = %lld outside 1 .. 2^31 - 1", (long long)capacity);
     if (s->begun) return fail(TD_EINVAL, "td_simb_log: tick %d still waits for td_simb_apply", s->last_t);
+    if (kinds && s->pn.set && s->pn.any3)
+        return fail(TD_EINVAL, "td_simb_log: not built: the event log of pools of three and four (a world under td_simb_pooling_n has k_hi > 2)");
     const size_t nc = (size_t)s->max_cabs, nr = (size_t)s->max_req;
     return ev_setup(s->ev, kinds, capacity, s->B, (size_t)s->nc_tot, (size_t)s->nr_tot, nc + nr + 2 + nr + nr / 2 + 2 * (nc + nr) + 2 * nc);
 }

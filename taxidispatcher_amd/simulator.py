@@ -73,6 +73,35 @@ def pool_mode(pool):
     return POOL_MODES[pool]
 
 
+def pool_n_sizes(pool_n):
+    """pool_n as the worlds take it -> None (the pool= policy holds) or (k_hi, k_lo); a bare k means (k, k).  ValueError
+    unless 2 <= k_lo <= k_hi <= 4."""
+    if pool_n is None:
+        return None
+    if isinstance(pool_n, (list, tuple, np.ndarray)):
+        if len(pool_n) != 2:
+            raise ValueError("pool_n=%r: None, k or (k_hi, k_lo)" % (pool_n,))
+        hi, lo = pool_n
+    else:
+        hi = lo = pool_n
+    if isinstance(hi, bool) or isinstance(lo, bool) or int(hi) != hi or int(lo) != lo:
+        raise ValueError("pool_n=%r: the sizes must be integers" % (pool_n,))
+    hi, lo = int(hi), int(lo)
+    if not 2 <= lo <= hi <= 4:
+        raise ValueError("pool_n=%r: 2 <= k_lo <= k_hi <= 4 is required" % (pool_n,))
+    return hi, lo
+
+
+def pool_n_rule(pool_wait, pool_loss):
+    """pool_wait / pool_loss of a pool_n policy -> two ints, each at least 0 (ValueError)"""
+    out = []
+    for what, v in (("pool_wait", pool_wait), ("pool_loss", pool_loss)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 0:
+            raise ValueError("%s=%r: an integer, at least 0" % (what, v))
+        out.append(int(v))
+    return tuple(out)
+
+
 from .dispatch import DISPATCH_MODES   # the one table: TD_DISPATCH_LCM_OPT / _OPT / _LCM / _SPLIT by name
 
 
@@ -86,14 +115,15 @@ def dispatch_mode(dispatch):
 class HipBackend:
     """cost build / LCM / optimal assignment on the GPU through the C ABI; dist: a stand-to-stand table (None = |a - b|).
     pool / max_loss: the policy find_pool follows when the caller names none ("greedy": dispatch.find_pool, "optimal":
-    dispatch.find_pool_optimal; max_loss=None: every ordered pair is a candidate)."""
+    dispatch.find_pool_optimal; max_loss=None: every ordered pair is a candidate).  max_happy: the most happy plans of one
+    find_pool_n stage (0: the default of the pool call underneath)."""
 
-    def __init__(self, dist=None, pool="greedy", max_loss=None):
+    def __init__(self, dist=None, pool="greedy", max_loss=None, max_happy=0):
         from . import dispatch
         self.d = dispatch
         self.dist = None if dist is None else check_dist(dist)
         pool_mode(pool)
-        self.pool, self.max_loss = pool, max_loss
+        self.pool, self.max_loss, self.max_happy = pool, max_loss, int(max_happy)
 
     def calculate_cost(self, cab_to, dem_from):
         return self.d.cost_build(cab_to, dem_from, self.dist, fill=BIG_COST, threshold=DROP_TIME)[1]
@@ -118,6 +148,17 @@ class HipBackend:
         if optimal:
             return self.d.find_pool_optimal(frm, to, self.dist, max_loss)
         return self.d.find_pool(frm, to, self.dist, max_loss)
+
+    def find_pool_n(self, k, frm, to, wait, loss):
+        """pools of k among the requests (td_pool_n: every request may be the first pick-up) -> (records [m, 2k+1] of
+        pick-ups, drop-offs, cost in td_pool_n's order, happy plans before de-duplication); up to 512 requests through
+        td_pool_n_batched on the one model, above through td_pool_n"""
+        frm, to, wait, loss = (np.asarray(a, np.int32).reshape(-1) for a in (frm, to, wait, loss))
+        rows = np.stack([np.arange(frm.size, dtype=np.int32), frm, to, wait, loss], axis=1)
+        if frm.size <= self.d.POOL_N_BATCHED_NMAX:
+            recs, nh = self.d.pool_n_batched(k, [rows], self.dist, max_happy=self.max_happy)
+            return np.asarray(recs[0]), int(np.asarray(nh).reshape(-1)[0])
+        return self.d.find_pool_n(k, rows, self.dist, max_happy=self.max_happy)
 
 
 class HipTickBackend(HipBackend):
@@ -187,11 +228,30 @@ class Simulator:
     "lcm+opt" with its own max_non_lcm; "opt": the LCM never runs; "lcm": the LCM with stop size 0, run to its end, with
     supply always, and the solver never (the line ends after the pairs, total_LCM_used counts the tick); "split":
     backend.split(cab_to, dem_from, parts) on the whole model, applied by analyze_solution (method OPT), max_solver_size takes
-    the whole model size."""
+    the whole model size.
+    pool_n / pool_wait / pool_loss: pools of up to four, the specification of td_sim_pooling_n.  pool_n=None: nothing above
+    changes.  pool_n = k or (k_hi, k_lo), 2 <= k_lo <= k_hi <= 4, replaces the pool= policy: find_pool runs a cascade over the
+    tick's demand list, stage k = k_hi, k_hi - 1, .., k_lo on the requests no earlier stage pooled (list order kept).  Stage k
+    is backend.find_pool_n(k, from, to, wait, loss) = td_pool_n(k, ...) on that list with max_wait = pool_wait and max_loss =
+    pool_loss (percent) for every request, every request a possible first pick-up, the world's table or |a - b|; a list
+    shorter than k yields nothing.  The tick's plans are the stages' records in stage order, as (pick-ups, drop-offs, cost)
+    with indices into the tick's demand list.  analyze_pool: every member of a record but its first pick-up leaves the
+    demand; the first pick-up stays and carries field 3 = the id of the second pick-up, field 4 = the pool's size, field 5 =
+    the cost; the other members (pick-up order) travel beside it.  Where such a customer is dispatched, _assign_pooled runs
+    once per other member in pick-up order, so total_second_passengers and total_pickup_numb grow by one per other member.
+    What reaches the request table: on the LCM path (analyze_pairs) d_cab of every member and d_pick of the first pick-up,
+    and no pool info; on the OPT path (analyze_solution) those and d_pool_id = the second pick-up's id, d_pool_plan = the
+    size, d_pool_cost = the cost, on the first pick-up's row.  The cab stays busy for the cost through cheat_a_bit, as with a
+    pair; there is no route model.  max_POOL_size: the most pools of a tick, all stages together; max_POOL_MEM_size: the most
+    happy plans before de-duplication of a tick, summed over its stages.  Events: EV_POOL carries the total, one EV_POOL_PAIR
+    (customer = the first pick-up, aux = the member) and one EV_POOLED_SECOND per other member."""
 
     def __init__(self, demand_rows, backend=None, n_cabs=N_CABS, on_solver_instance=None, dist=None, events=False, pool="greedy",
-                 max_loss=None, dispatch="lcm+opt", max_non_lcm=None, parts=4):
+                 max_loss=None, dispatch="lcm+opt", max_non_lcm=None, parts=4, pool_n=None, pool_wait=0, pool_loss=0):
         pool_mode(pool)
+        self.pool_n = pool_n_sizes(pool_n)
+        self.pool_wait, self.pool_loss = pool_n_rule(pool_wait, pool_loss)
+        self._others = {}        # pool_n: the first pick-up's id -> the ids of the pool's other members, of this tick
         dispatch_mode(dispatch)
         if max_non_lcm is not None and int(max_non_lcm) < 0:
             raise ValueError("max_non_lcm=%r is negative" % (max_non_lcm,))
@@ -327,8 +387,66 @@ class Simulator:
             self._ev(t, EV_POOL_PAIR, customer=temp_demand[p[0]][0], aux=temp_demand[p[1]][0])   # :746
         return out
 
+    # findPool under pool_n: the cascade; -> [(pick-ups, drop-offs, cost)] with indices into temp_demand, in plan order
+    def find_pool_n(self, temp_demand, t=None):
+        n = len(temp_demand)
+        if n < 2:
+            self._ev(t, EV_POOL, aux=0)
+            return []
+        frm = np.array([r[1] for r in temp_demand], np.int64)
+        to = np.array([r[2] for r in temp_demand], np.int64)
+        k_hi, k_lo = self.pool_n
+        live = np.arange(n)      # the requests no earlier stage pooled, in list order
+        out, happy = [], 0
+        for k in range(k_hi, k_lo - 1, -1):
+            m = int(live.size)
+            if m < k:
+                continue
+            recs, nh = self.be.find_pool_n(k, frm[live], to[live], np.full(m, self.pool_wait, np.int32), np.full(m, self.pool_loss, np.int32))
+            happy += int(nh)
+            gone = np.zeros(m, bool)
+            for r in np.asarray(recs, np.int64).reshape(-1, 2 * k + 1).tolist():
+                out.append((tuple(int(live[i]) for i in r[:k]), tuple(int(live[i]) for i in r[k:2 * k]), int(r[2 * k])))
+                gone[r[:k]] = True
+            live = live[~gone]
+        self.m["max_POOL_MEM_size"] = max(self.m["max_POOL_MEM_size"], happy)
+        self.m["max_POOL_size"] = max(self.m["max_POOL_size"], len(out))
+        self._ev(t, EV_POOL, aux=len(out))
+        for picks, _, _ in out:
+            for other in picks[1:]:
+                self._ev(t, EV_POOL_PAIR, customer=temp_demand[picks[0]][0], aux=temp_demand[other][0])
+        return out
+
+    # analyzePool for records: -> (the demand after pooling, {first pick-up's id: the other members' ids in pick-up order})
+    @staticmethod
+    def analyze_pool_n(pool, temp_demand):
+        leaves = {d for picks, _, _ in pool for d in picks[1:]}
+        first = {}
+        for picks, _, cost in pool:
+            first.setdefault(picks[0], (picks[1:], len(picks), cost))
+        out, others = [], {}
+        for d, r in enumerate(temp_demand):
+            if d in leaves:
+                continue
+            cust = [r[0], r[1], r[2], -1, -1, 0]
+            if d in first:
+                rest, size, cost = first[d]
+                cust[3], cust[4], cust[5] = temp_demand[rest[0]][0], size, cost
+                others[r[0]] = tuple(temp_demand[o][0] for o in rest)
+            out.append(cust)
+        return out, others
+
+    # the customers assigned with a dispatched customer: its pool's other members in pick-up order
+    def _pool_members(self, cust):
+        if cust[3] == -1:
+            return ()
+        return self._others.get(cust[0], (cust[3],)) if self.pool_n is not None else (cust[3],)
+
     # findPool + analyzePool under the world's policy; "none": the demand as it is, in the model's six-field form
     def _pooled(self, temp_demand, t):
+        if self.pool_n is not None:
+            out, self._others = self.analyze_pool_n(self.find_pool_n(temp_demand, t), temp_demand)
+            return out
         if self.pool == "none":
             return [[r[0], r[1], r[2], -1, -1, 0] for r in temp_demand]
         return self.analyze_pool(self.find_pool(temp_demand, t), temp_demand)
@@ -410,8 +528,8 @@ class Simulator:
                 self.d_cab[c2] = cab_id
                 self._ev(t, EV_ASSIGNED_LCM, customer=cust[0], cab=cab_id)                    # :654
                 self.d_pick[c2] = t
-                if cust[3] > -1:
-                    self._assign_pooled(cust[3], cab_id, t, EV_LCM)
+                for other in self._pool_members(cust):
+                    self._assign_pooled(other, cab_id, t, EV_LCM)
                     self.m["total_pickup_numb"] += 1
                 # NOTE: pool info is NOT copied into demand[] on the LCM path (only :391-396 does)
             else:
@@ -429,10 +547,11 @@ class Simulator:
                 d = self.id2idx[cust[0]]
                 self.d_cab[d] = sup[0]
                 self.d_pick[d] = t
-                if cust[3] > -1:
-                    self._assign_pooled(cust[3], sup[0], t, EV_OPT)
-                    self.d_pool_id[d], self.d_pool_plan[d], self.d_pool_cost[d] = cust[3], cust[4], cust[5]
+                for other in self._pool_members(cust):
+                    self._assign_pooled(other, sup[0], t, EV_OPT)
                     self.m["total_pickup_numb"] += 1
+                if cust[3] > -1:
+                    self.d_pool_id[d], self.d_pool_plan[d], self.d_pool_cost[d] = cust[3], cust[4], cust[5]
                 self._dispatch(t, sup, cust, EV_OPT)
         return total
 
@@ -603,6 +722,15 @@ def format_events(records, world=None):
     return lines
 
 
+def _read_pools_n(sim, call, n_req):
+    """td_sim_pools_n / td_simb_pools_n -> [(pick-ups, drop-offs, cost)] in plan order"""
+    cap = max(n_req // 2, 1)
+    recs, size = np.empty((cap, 9), np.int32), np.empty(cap, np.int32)
+    k = sim._ct.c_int32(0)
+    sim._ffi.check(call(cap, sim._ffi.addr(recs), sim._ffi.addr(size), sim._ct.byref(k)))
+    return [(tuple(int(v) for v in recs[i, :size[i]]), tuple(int(v) for v in recs[i, 4:4 + size[i]]), int(recs[i, 8])) for i in range(k.value)]
+
+
 def _read_pools(sim, call, n_req):
     cap = max(n_req // 2, 1)
     a, b, plan, cost = (np.empty(cap, np.int32) for _ in range(4))
@@ -660,7 +788,10 @@ class DeviceSimulator(_DeviceEvents):
     pool / max_loss: the pooling policy as `Simulator` takes it (td_sim_pooling); `pools()` reads the plans of the tick last
     begun (td_sim_pools).
     dispatch / parts: the dispatch policy as `Simulator` takes it (td_sim_dispatch, with the world's max_non_lcm); None: the
-    world never calls td_sim_dispatch and dispatches as it always did."""
+    world never calls td_sim_dispatch and dispatches as it always did.
+    pool_n / pool_wait / pool_loss / max_happy: pools of up to four as `Simulator` takes them (td_sim_pooling_n; max_happy: the
+    most happy plans of one stage, 0 = the default of the pool call underneath); `pools_n()` reads the records of the tick
+    last begun (td_sim_pools_n), `set_pool_n` changes the policy between two ticks.  None: td_sim_pooling_n is never called."""
 
     M_KEYS = ("total_dropped", "total_pickup_time", "total_pickup_numb", "total_LCM_used", "max_model_size", "max_solver_size",
               "max_POOL_MEM_size", "max_POOL_size", "total_second_passengers")
@@ -668,11 +799,13 @@ class DeviceSimulator(_DeviceEvents):
     REQ_KEYS = ("d_cab", "d_pick", "d_pool_id", "d_pool_plan", "d_pool_cost")
 
     def __init__(self, demand_rows, n_cabs=None, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None, events=None,
-                 event_capacity=None, pool="greedy", max_loss=None, dispatch=None, parts=4):
+                 event_capacity=None, pool="greedy", max_loss=None, dispatch=None, parts=4, pool_n=None, pool_wait=0, pool_loss=0, max_happy=0):
         import ctypes
         mode = pool_mode(pool)
         if dispatch is not None:
             dispatch_mode(dispatch)
+        pool_n_sizes(pool_n)
+        pool_n_rule(pool_wait, pool_loss)
         from . import _ffi
         self._ffi, self._ct = _ffi, ctypes
         self._lib = _ffi.lib()
@@ -705,9 +838,29 @@ class DeviceSimulator(_DeviceEvents):
         self.pool, self.max_loss = pool, max_loss
         if pool != "greedy" or max_loss is not None:      # a default world never calls td_sim_pooling
             _ffi.check(self._lib.td_sim_pooling(self._h, mode, 0.0 if max_loss is None else float(max_loss)))
+        self.pool_n = None
+        if pool_n is not None:                            # a default world never calls td_sim_pooling_n
+            self.set_pool_n(pool_n, pool_wait, pool_loss, max_happy)
         self.dispatch, self.parts = "lcm+opt", int(parts)
         if dispatch is not None:                          # a default world never calls td_sim_dispatch
             self.set_dispatch(dispatch, self.max_non_lcm, parts)
+
+    def set_pool_n(self, pool_n, pool_wait=0, pool_loss=0, max_happy=0):
+        """td_sim_pooling_n: pools of k_hi down to k_lo (pool_n = k or (k_hi, k_lo)) under pool_wait / pool_loss, from the next
+        begin on; pool_n=None: td_sim_pooling with the handle's pool= policy, back on pairs"""
+        if pool_n is None:
+            self._ffi.check(self._lib.td_sim_pooling(self._h, pool_mode(self.pool), 0.0 if self.max_loss is None else float(self.max_loss)))
+            self.pool_n = None
+            return
+        hi, lo = pool_n_sizes(pool_n)
+        wait, loss = pool_n_rule(pool_wait, pool_loss)
+        self._ffi.check(self._lib.td_sim_pooling_n(self._h, hi, lo, wait, loss, int(max_happy)))
+        self.pool_n, self.pool_wait, self.pool_loss, self.max_happy = (hi, lo), wait, loss, int(max_happy)
+
+    def pools_n(self):
+        """the plans of the tick last begun under pool_n: a list of (pick-ups, drop-offs, cost), the members indices into that
+        tick's demand list before pooling, in plan order (Simulator.find_pool_n's list)"""
+        return _read_pools_n(self, lambda *a: self._lib.td_sim_pools_n(self._h, *a), self.n_req)
 
     def set_dispatch(self, dispatch, max_non_lcm=None, parts=4):
         """td_sim_dispatch: the dispatch method ("lcm+opt", "opt", "lcm", "split"), its max_non_lcm (None: as it is) and the
@@ -861,7 +1014,10 @@ class DeviceSimulatorBatch(_DeviceEvents):
     its world, and within a tick world 0's records come first.  The default capacity, 4 * (all cabs + all requests) + 64 * B,
     holds any one tick of the batch.
     pool / max_loss: the pooling policy, one for the batch or a list with one entry per world (td_simb_pooling; None in a
-    max_loss list: every ordered pair in that world); `pools(b)` reads world b's plans of the tick last begun."""
+    max_loss list: every ordered pair in that world); `pools(b)` reads world b's plans of the tick last begun.
+    pool_n / pool_wait / pool_loss / max_happy: pools of up to four per world (td_simb_pooling_n): a list with one entry per
+    world (k, (k_hi, k_lo), or None: the world keeps its pool= policy) or one value for all; `pools_n(b)` reads world b's
+    records, `set_pool_n` changes the policies between two ticks.  A batch that logs events takes such policies with k_hi = 2 only."""
 
     M_KEYS, CAB_KEYS, REQ_KEYS = DeviceSimulator.M_KEYS, DeviceSimulator.CAB_KEYS, DeviceSimulator.REQ_KEYS
     format_line = staticmethod(DeviceSimulator.format_line)
@@ -869,7 +1025,8 @@ class DeviceSimulatorBatch(_DeviceEvents):
     # dispatch / max_non_lcm / parts: the dispatch policy per world (td_simb_dispatch), each a list with one entry per world or one
     # value for all; dispatch=None with a scalar max_non_lcm: the batch never calls td_simb_dispatch and dispatches as it always did
     def __init__(self, demand_rows_list, n_cabs_list, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None,
-                 events=None, event_capacity=None, pool="greedy", max_loss=None, dispatch=None, parts=4):
+                 events=None, event_capacity=None, pool="greedy", max_loss=None, dispatch=None, parts=4, pool_n=None, pool_wait=0, pool_loss=0,
+                 max_happy=0):
         import ctypes
         n_cabs_list = list(n_cabs_list)
         nb = len(n_cabs_list)
@@ -930,6 +1087,9 @@ class DeviceSimulatorBatch(_DeviceEvents):
         if any(p != "greedy" for p in pools) or any(x is not None for x in losses):      # a default batch never calls td_simb_pooling
             ml = np.array([0.0 if x is None else float(x) for x in losses], np.float64)
             _ffi.check(self._lib.td_simb_pooling(self._h, _ffi.addr(modes), _ffi.addr(ml)))
+        self.pool_n = [None] * nb
+        if pool_n is not None and not (isinstance(pool_n, list) and all(k is None for k in pool_n)):      # a default batch never calls td_simb_pooling_n
+            self.set_pool_n(pool_n, pool_wait, pool_loss, max_happy)
         self.dispatch, self.max_non_lcms, self.parts = ["lcm+opt"] * nb, [self.max_non_lcm] * nb, [4] * nb
         if dispatch is not None:                          # a default batch never calls td_simb_dispatch
             self.set_dispatch(dispatch, mnl_list, parts)
@@ -944,6 +1104,39 @@ class DeviceSimulatorBatch(_DeviceEvents):
         arrs = [np.array([dispatch_mode(d) for d in ds], np.int32), np.array(ms, np.int32), np.array(ps, np.int32)]
         self._ffi.check(self._lib.td_simb_dispatch(self._h, *[self._ffi.addr(a) for a in arrs]))
         self.dispatch, self.max_non_lcms, self.parts = ds, [int(v) for v in ms], [int(v) for v in ps]
+
+    def set_pool_n(self, pool_n, pool_wait=0, pool_loss=0, max_happy=0):
+        """td_simb_pooling_n: pools of up to four per world, from the next begin on.  pool_n / pool_wait / pool_loss: a list with
+        one entry per world, or one value for all worlds; a pool_n entry of None keeps that world's policy as it is.  pool_n=None
+        (not a list): td_simb_pooling with the batch's pool= policies, every world back on pairs."""
+        nb = self.batch
+        if pool_n is None:
+            modes = np.array([pool_mode(p) for p in self.pool], np.int32)
+            ml = np.array([0.0 if x is None else float(x) for x in self.max_loss], np.float64)
+            self._ffi.check(self._lib.td_simb_pooling(self._h, self._ffi.addr(modes), self._ffi.addr(ml)))
+            self.pool_n = [None] * nb
+            return
+        # a list of length 2 of ints is ONE (k_hi, k_lo) for all worlds only when it is a tuple; a list is per world
+        sizes = list(pool_n) if isinstance(pool_n, list) else [pool_n] * nb
+        per = lambda v: list(v) if isinstance(v, (list, np.ndarray)) else [v] * nb
+        waits, losses = per(pool_wait), per(pool_loss)
+        if not len(sizes) == len(waits) == len(losses) == nb:
+            raise ValueError("pool_n / pool_wait / pool_loss: %d / %d / %d entries for %d worlds" % (len(sizes), len(waits), len(losses), nb))
+        hi, lo, wt, ls = (np.zeros(nb, np.int32) for _ in range(4))
+        for b in range(nb):
+            k = pool_n_sizes(sizes[b])
+            if k is None:
+                continue
+            hi[b], lo[b] = k
+            wt[b], ls[b] = pool_n_rule(waits[b], losses[b])
+        self._ffi.check(self._lib.td_simb_pooling_n(self._h, *[self._ffi.addr(a) for a in (hi, lo, wt, ls)], int(max_happy)))
+        for b in range(nb):
+            if hi[b]:
+                self.pool_n[b] = (int(hi[b]), int(lo[b]))
+
+    def pools_n(self, b):
+        """world b's records of the tick last begun under pool_n, as DeviceSimulator.pools_n lists them"""
+        return _read_pools_n(self, lambda *a: self._lib.td_simb_pools_n(self._h, int(b), *a), self.n_req[b])
 
     def pools(self, b):
         """world b's plans of the tick last begun, as DeviceSimulator.pools lists them"""

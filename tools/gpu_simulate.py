@@ -17,7 +17,12 @@ requests before pooling (the committed demand file has such ticks at 1300 cabs a
 Simulator(dispatch=...) with --world host); with --cabs a,b,c each may be a list a,b,c with one entry per world, and a single
 value holds for every world, e.g. --cabs 400,400,400 --dispatch lcm,opt,split --max-non-lcm 0,16,600 --parts 4.  A split world,
 and in a batch an optimum-alone world, refuses a tick whose model has more than 1024 cabs or requests, which the committed
-demand reaches at 1300 cabs."""
+demand reaches at 1300 cabs.
+--pool-n K_HI,K_LO (or K), --pool-wait W, --pool-loss L, --max-happy H: pools of up to four (Simulator(pool_n=...) with --world host,
+td_sim_pooling_n with --world device) instead of the --pool policy: the cascade of td_pool_n stages K_HI .. K_LO under a pick-up
+path of at most W and rides at most L percent longer.  This tool runs one such world; --cabs N with a single N then sets its fleet size (batches
+of such worlds: DeviceSimulatorBatch(pool_n=[...]), tools/sim_pool_n_time.py).  A tick with more than 2047 requests before pooling, or a stage with more happy plans than H,
+is refused, and the tool says which tick."""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -33,9 +38,41 @@ ap.add_argument("--max-loss", default=None, metavar="X[,...]", help="the candida
 ap.add_argument("--dispatch", default=None, metavar="lcm+opt|opt|lcm|split[,...]", help="the dispatch method; a list goes with a --cabs list")
 ap.add_argument("--max-non-lcm", default=None, metavar="N[,...]", help="max_non_lcm under lcm+opt; a list goes with a --cabs list")
 ap.add_argument("--parts", default="4", metavar="P[,...]", help="the split's number of stand ranges; a list goes with a --cabs list")
+ap.add_argument("--pool-n", default=None, metavar="K_HI,K_LO", help="pools of up to four: the stage sizes, largest first (one world only)")
+ap.add_argument("--pool-wait", type=int, default=0, metavar="W", help="with --pool-n: the longest pick-up path before a member boards")
+ap.add_argument("--pool-loss", type=int, default=0, metavar="L", help="with --pool-n: percent a pooled ride may exceed the direct one")
+ap.add_argument("--max-happy", type=int, default=0, metavar="H", help="with --pool-n: the most happy plans of one stage (0: the pool call's default)")
 args = ap.parse_args()
+pool_n, n_cabs_1 = {}, {}
+if args.pool_n:
+    try:
+        sizes = tuple(int(v) for v in args.pool_n.split(","))
+        pool_n = dict(pool_n=simulator.pool_n_sizes(sizes[0] if len(sizes) == 1 else sizes), pool_wait=args.pool_wait, pool_loss=args.pool_loss)
+        simulator.pool_n_rule(args.pool_wait, args.pool_loss)
+    except ValueError as e:
+        ap.error("--pool-n %s: %s" % (args.pool_n, e))
+    if args.cabs and "," in args.cabs:
+        ap.error("--pool-n serves one world here; for a batch see tools/sim_pool_n_time.py")
+    if args.cabs:
+        n_cabs_1, args.cabs = dict(n_cabs=int(args.cabs)), None
 if args.cabs and args.world != "device":
     ap.error("--cabs needs --world device")
+
+
+def run_120(sim):
+    """sim.run(120); a --pool-n world runs tick by tick, so that a tick past the policy's limits is named when it is refused"""
+    if not pool_n:
+        return sim.run(120)
+    for t in range(120):
+        try:
+            line = sim.tick(t)
+        except td.TdError as e:
+            sys.exit("tick %d refused: %s" % (t, e))
+        if line is not None:
+            sim.log.append(line)
+    return sim.log
+
+
 policy = {}
 if args.dispatch or args.max_non_lcm is not None:
     n_w = len(args.cabs.split(",")) if args.cabs else 1
@@ -121,12 +158,15 @@ if args.world == "device" and args.cabs:
         print(sim.metrics_text(b, total_simul_time=int(dt)))
     sys.exit(0)
 if args.world == "device":
-    sim = simulator.DeviceSimulator(rows, dist=dist, events=True if args.events else None, pool=pools[0], max_loss=losses[0], **policy)
+    if pool_n:
+        pool_n["max_happy"] = args.max_happy
+    sim = simulator.DeviceSimulator(rows, dist=dist, events=True if args.events else None, pool=pools[0], max_loss=losses[0], **policy, **pool_n,
+                                    **n_cabs_1)
     t0 = time.time()
     if args.events:
         records, log = run_logged(sim, 120), sim.log
     else:
-        log = sim.run(120)
+        log = run_120(sim)
     dt = time.time() - t0
     if args.events:
         write_events(args.events, records)
@@ -134,7 +174,8 @@ if args.world == "device":
     print("\n".join(log[-3:]))
     print(sim.metrics_text(total_simul_time=int(dt)))
     sys.exit(0)
-sim = simulator.Simulator(rows, dist=dist, events=bool(args.events), pool=pools[0], max_loss=losses[0], **policy)
+sim = simulator.Simulator(rows, backend=simulator.HipBackend(dist, max_happy=args.max_happy) if pool_n else None, dist=dist, events=bool(args.events), pool=pools[0],
+                          max_loss=losses[0], **policy, **pool_n, **({"n_cabs": n_cabs_1["n_cabs"]} if n_cabs_1 else {}))
 t0 = time.time()
 per = {"pool": 0.0, "cost": 0.0, "lcm": 0.0, "solve": 0.0}
 be = sim.be
@@ -144,7 +185,7 @@ def timed(name, fn):
     return w
 be.find_pool = timed("pool", be.find_pool); be.calculate_cost = timed("cost", be.calculate_cost)
 be.lcm = timed("lcm", be.lcm); be.solve = timed("solve", be.solve)
-log = sim.run(120)
+log = run_120(sim)
 dt = time.time() - t0
 if args.events:
     write_events(args.events, sim.events)
