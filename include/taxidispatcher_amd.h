@@ -934,7 +934,34 @@ TD_API int td_profile_reset(void);
  *  1024  accepted (always equal to word [8])
  *   Word [12] is set to 0 when td_assign is entered, filled in as the attempt proceeds and kept when the general solver
  *   takes over, so a refusal can be read too.  After a transposed retry bits 2, 8 and 16..512 describe the probe and the
- *   finish on the transpose.  The sharded entry points (td_line_shard_*) do not set it. */
+ *   finish on the transpose.  The sharded entry points (td_line_shard_*) do not set it.
+ * [13] = finisher_path, which finishers the last td_assign launched for the rows the bidding rounds left free, as a bit set
+ *   (FP_* below; DESIGN.md section 2, step 4 has the selection):
+ *     1  FP_FOREST          k_forest launched              2  FP_FOREST_NONE    k_forest's turn, but 0 rows were free
+ *     4  FP_FOREST_REFUSED  its cooperative launch returned an error (the finishers below took over)
+ *     8  FP_PSAP            at least one group of speculative k_sap batches with k_pcommit
+ *    16  FP_SAPX            k_sapx launched               32  FP_SAPX_REFUSED   its cooperative launch returned an error
+ *    64  FP_SAP8_BATCH      k_sap8's speculative batches 128  FP_SAP8           k_sap8
+ *   bits 8..12              CH, the 16-byte chunks per thread of the single-workgroup search that was launched (1 .. 16)
+ *  8192  FP_SAP512          the 512-thread k_sap       16384  FP_SAP            the generic (1024-thread) k_sap
+ * 32768  FP_NOLDS           that search kept owner[] / pred[] in global memory (npad * 8 bytes > 150 KiB)
+ *   bits 16..31             speculative batches launched (k_sap in SPEC mode or k_sap8, each with its k_pcommit)
+ *   Word [13] is set to 0 when td_assign is entered and again before the finisher of each cell width's attempt, so it
+ *   describes the attempt that delivered the answer (0: the rounds left no row, or the line-metric path answered). */
+#define TD_FP_FOREST 1
+#define TD_FP_FOREST_NONE 2
+#define TD_FP_FOREST_REFUSED 4
+#define TD_FP_PSAP 8
+#define TD_FP_SAPX 16
+#define TD_FP_SAPX_REFUSED 32
+#define TD_FP_SAP8_BATCH 64
+#define TD_FP_SAP8 128
+#define TD_FP_CH_SHIFT 8
+#define TD_FP_CH_MASK 0x1f00
+#define TD_FP_SAP512 8192
+#define TD_FP_SAP 16384
+#define TD_FP_NOLDS 32768
+#define TD_FP_BATCH_SHIFT 16
 TD_API int td_last_stats(int64_t *out, int n);
 
 #ifdef __cplusplus

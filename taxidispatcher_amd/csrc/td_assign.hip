@@ -3635,6 +3635,11 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
     const size_t shm = lds ? st : 0;
     if (CH * E > 64) return fail(TD_ERANGE, "n=%d too large for the single-workgroup finisher", n);
     ProfScope ps(TD_K_SAP);
+    int64_t &fpath = ctx().stats[13];   // finisher_path: which of the finishers below are launched (FP_*, td_common.h)
+    auto fp_batches = [&](int nb) {     // bits 16..31: speculative batches, saturating
+        const int64_t sum = std::min<int64_t>(0xffff, (fpath >> FP_BATCH_SHIFT) + nb);
+        fpath = (fpath & ((1ll << FP_BATCH_SHIFT) - 1)) | (sum << FP_BATCH_SHIFT);
+    };
     k_freelist<<<1, 1024, 0, ctx().stream>>>(n, r2c_full, (int *)sv.list.p, (int *)sv.misc.p);
     // ---- 4-byte rows of n >= TD_FOREST_MIN_N: the incremental shortest-path forest over all CUs (td_forest.h)
     if constexpr (sizeof(CT) == 4) {
@@ -3644,7 +3649,10 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
             {   // nothing left for a finisher (thresholded models, easy instances): no cooperative launch for it
                 TD_HIP(hipMemcpyAsync(c.pinned, (int *)sv.misc.p + CTL_NFREE, sizeof(int), hipMemcpyDeviceToHost, c.stream));
                 TD_HIP(hipStreamSynchronize(c.stream));
-                if (((int *)c.pinned)[0] == 0) return TD_OK;
+                if (((int *)c.pinned)[0] == 0) {
+                    fpath |= FP_FOREST_NONE;
+                    return TD_OK;
+                }
             }
             typedef typename std::conditional<sizeof(PT) == 4, int, long long>::type LT;
             const size_t off_base = (sizeof(FoShared) + 255) / 256 * 256;
@@ -3678,6 +3686,7 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
             else TD_FO_LAUNCH(128, 512);
 #undef TD_FO_LAUNCH
             if (le == hipSuccess) {
+                fpath |= FP_FOREST;
                 TD_HIP(hipGetLastError());
                 if (getenv("TD_DEBUG")) {
                     long long st[16];
@@ -3689,6 +3698,7 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
                 return TD_OK;
             }
             (void)hipGetLastError();   // refused: the finishers below do the job
+            fpath |= FP_FOREST_REFUSED;
         }
     }
     // ---- speculative parallel searches first (a few batches), the serial workgroup mops up
@@ -3747,6 +3757,8 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
                                                            (int *)sv.misc.p, raise, recs, 0, PS_G, IsNP<CT>::value ? g_np_plimit : 0ll);
             }
             launched += nb;
+            fpath |= FP_PSAP | ((int64_t)CH << FP_CH_SHIFT);
+            fp_batches(nb);
             TD_HIP(hipGetLastError());
             int left = 0;
             if ((rc = read_nfree(&left))) return rc;
@@ -3789,6 +3801,7 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
             const hipError_t le = hipLaunchCooperativeKernel((const void *)k_sapx<CT, TXsel, NGsel>, dim3(KX), dim3(TXsel * NGsel), kargs, 0, c.stream);
             if (le == hipSuccess) launched_x = true;
             else (void)hipGetLastError();
+            fpath |= launched_x ? FP_SAPX : FP_SAPX_REFUSED;
         }
         if (launched_x) {
             Ctx &c = ctx();
@@ -3826,7 +3839,10 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
                     k_pcommit<int32_t><<<1, 1024, cshm, c.stream>>>(n, (int32_t *)sv.price.p, (int *)sv.owner.p, r2c_full,
                                                                     (int *)sv.list.p, (int *)sv.misc.p, raise, recs, 0, g_psap8_grid);
                 }
+                fpath |= FP_SAP8_BATCH;
+                fp_batches(g_psap8_batches);
             }
+            fpath |= FP_SAP8 | ((int64_t)CH << FP_CH_SHIFT) | (lds ? 0 : FP_NOLDS);
             if (lds) {
                 if (shm > 48 * 1024)
                     (void)hipFuncSetAttribute((const void *)k_sap8<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
@@ -3859,6 +3875,7 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
             else if (ch5 == 2) { TD_SAP5(2) }
             else { TD_SAP5(4) }
 #undef TD_SAP5
+            fpath |= FP_SAP512 | ((int64_t)ch5 << FP_CH_SHIFT) | (lds ? 0 : FP_NOLDS);
             TD_HIP(hipGetLastError());
             return TD_OK;
         }
@@ -3879,6 +3896,7 @@ int sv_finish_t(Solver &sv, const ShardTab &tab, int *r2c_full)
         default: return fail(TD_ERANGE, "n=%d too large for the single-workgroup finisher", n);
     }
 #undef TD_SAP
+    fpath |= FP_SAP | ((int64_t)CH << FP_CH_SHIFT) | (lds ? 0 : FP_NOLDS);
     TD_HIP(hipGetLastError());
     return TD_OK;
 }
@@ -4110,7 +4128,8 @@ int sv_readback_parse(Solver &sv, const char *pin, int64_t *total, int64_t *dual
     if (getenv("TD_DEBUG")) {
         fprintf(stderr, "[td] n=%d bpc=%d progress per round:", sv.n, sv.bpc);
         for (int r = 0; r < max_rounds && r < 48; r++) fprintf(stderr, " %d", hctl[CTL_PROG + r]);
-        fprintf(stderr, " | parallel-sap %d | serial-sap rows %d steps %d\n", hctl[CTL_PACC], hctl[CTL_NFREE], hctl[CTL_STEPS]);
+        fprintf(stderr, " | parallel-sap %d | serial-sap rows %d steps %d | finisher_path 0x%llx\n", hctl[CTL_PACC], hctl[CTL_NFREE], hctl[CTL_STEPS],
+                (unsigned long long)c.stats[13]);
     }
     c.stats[0] = rounds;
     c.stats[1] = 0;
@@ -4690,6 +4709,7 @@ int step_finish(Solver &sv, Call &cl, Next &next)
     tab.rps = n;
     tab.count = 1;
     sv.placed = false;
+    cl.c.stats[13] = 0;   // finisher_path describes this attempt: a void attempt at a narrower width has launched finishers too
     if (!cl.all_placed) TD_DISPATCH(sv, sv_finish_t, sv, tab, (int *)sv.r2c.p);
     if (rc) return rc;
     if (sv.defer_const && !sv.placed) {
@@ -4783,6 +4803,7 @@ int assign_impl(Solver &sv, const AssignHint &hint, int n, const int32_t *cost, 
     TD_REQUIRE_INIT();
     Ctx &c = ctx();
     c.stats[12] = 0;   // line_path: filled in as the line attempt proceeds, kept when the general solver takes over
+    c.stats[13] = 0;   // finisher_path: sv_finish_t ORs in what it launches
     read_tunables();
     if (n < 0) return fail(TD_EINVAL, "n < 0");
     Call cl{c, n, hint, row_to_col, total, dual_bound};

@@ -76,6 +76,10 @@ int copy_in(void *dst, const void *src, size_t bytes);
 // td_last_stats word 12 (line_path): what the last td_assign's line attempt did (the public header lists the bits)
 enum { LP_PROBE = 1, LP_BALANCED = 2, LP_TRANSPOSE = 4, LP_UNBAL = 8, LP_QROW2 = 16, LP_I2SEARCH = 32, LP_I2COLQ = 64, LP_REV = 128,
        LP_VEC = 256, LP_WIDE = 512, LP_ACCEPTED = 1024 };
+// td_last_stats word 13 (finisher_path): which finishers the last td_assign's sv_finish_t launched (the public header lists the bits)
+enum { FP_FOREST = 1, FP_FOREST_NONE = 2, FP_FOREST_REFUSED = 4, FP_PSAP = 8, FP_SAPX = 16, FP_SAPX_REFUSED = 32, FP_SAP8_BATCH = 64,
+       FP_SAP8 = 128, FP_CH_SHIFT = 8 /* bits 8..12: CH */, FP_SAP512 = 1 << 13, FP_SAP = 1 << 14, FP_NOLDS = 1 << 15,
+       FP_BATCH_SHIFT = 16 /* bits 16..31: speculative batches launched */ };
 int line_probe_launch(int n, const int32_t *d_cost, const long long **skip_dev, int *clear_words = nullptr, int nclear = 0);
 int line_probe_wait(int *mode, int *k, int *suspicious = nullptr /* the 1-byte attempt is void: the probe made the queued pass a no-op */,
                     int *shape3 = nullptr /* int[4]: estimated constant columns / rows, row 0 too wide for one byte, value of the last column */);

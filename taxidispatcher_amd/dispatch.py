@@ -222,6 +222,14 @@ def last_stats():
     return d
 
 
+def finisher_path():
+    """td_last_stats word 13: which finishers the last td_assign launched for the rows its bidding rounds left free, as a bit
+    set (the TD_FP_* bits of the header).  Not a key of last_stats(): recorded comparisons of that dict stay valid."""
+    out = (ctypes.c_int64 * 16)()
+    _ffi.check(_ffi.lib().td_last_stats(out, 16))
+    return int(out[13])
+
+
 # ----------------------------------------------------------------------------------------
 # reference-shaped API
 # ----------------------------------------------------------------------------------------
