@@ -947,7 +947,18 @@ TD_API int td_profile_reset(void);
  * 32768  FP_NOLDS           that search kept owner[] / pred[] in global memory (npad * 8 bytes > 150 KiB)
  *   bits 16..31             speculative batches launched (k_sap in SPEC mode or k_sap8, each with its k_pcommit)
  *   Word [13] is set to 0 when td_assign is entered and again before the finisher of each cell width's attempt, so it
- *   describes the attempt that delivered the answer (0: the rounds left no row, or the line-metric path answered). */
+ *   describes the attempt that delivered the answer (0: the rounds left no row, or the line-metric path answered).
+ * [14] = match_path, what the last td_match_batched / td_pool2_batched / td_pool2_batched_v launched, as a bit set (MP_* below;
+ *   DESIGN.md 3.5 has the placement rule and the chunk size):
+ *     1  MP_LDS        the solver's per-model state (align256(152 n + 64) bytes, n the longest model) lay in LDS
+ *     2  MP_WS         ... in slices of the library workspace, one per workgroup (it did not fit the LDS budget)
+ *     4  MP_POOL       entered as a pool call (td_pool2_batched / td_pool2_batched_v)
+ *     8  MP_GREEDY     the greedy was launched           16  MP_MATCH   k_pool_match (the optimum) was launched
+ *    32  MP_PER_MODEL  per-model policy arrays were given (td_pool2_batched_v)
+ *   bits 8..23         chunks launched, saturating at 65535 (pool calls: ceil(batch / chunk); td_match_batched: 1)
+ *   Bits 1 and 2 are set by td_match_batched always and by a pool call only with MP_MATCH.  Word [14] is set to 0 when one of
+ *   the three is entered and filled in before it returns, refused calls included once the launches were made (TD_ERANGE,
+ *   TD_EINTERNAL); an argument error or a batch of 0 leaves it 0.  It is defined only right after such a call. */
 #define TD_FP_FOREST 1
 #define TD_FP_FOREST_NONE 2
 #define TD_FP_FOREST_REFUSED 4
@@ -962,6 +973,14 @@ TD_API int td_profile_reset(void);
 #define TD_FP_SAP 16384
 #define TD_FP_NOLDS 32768
 #define TD_FP_BATCH_SHIFT 16
+#define TD_MP_LDS 1
+#define TD_MP_WS 2
+#define TD_MP_POOL 4
+#define TD_MP_GREEDY 8
+#define TD_MP_MATCH 16
+#define TD_MP_PER_MODEL 32
+#define TD_MP_CHUNK_SHIFT 8
+#define TD_MP_CHUNK_MAX 0xffff
 TD_API int td_last_stats(int64_t *out, int n);
 
 #ifdef __cplusplus

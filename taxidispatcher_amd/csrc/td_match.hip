@@ -328,6 +328,7 @@ int td_match_batched(int batch, int n, const int32_t *ns, const int32_t *weight,
     TD_REQUIRE_INIT();
     Ctx &c = ctx();
     const char *fn = "td_match_batched";
+    c.stats[14] = 0;   // match_path (TD_MP_*): filled in below once the launch is decided
     if (batch < 0) return fail(TD_EINVAL, "%s: batch = %d < 0", fn, batch);
     if (n < 0 || n > MATCH_NMAX) return fail(TD_EINVAL, "%s: n = %d outside [0, %d]", fn, n, MATCH_NMAX);
     if (batch == 0) return TD_OK;
@@ -361,6 +362,7 @@ int td_match_batched(int batch, int n, const int32_t *ns, const int32_t *weight,
     size_t per;
     int grid;
     if ((rc = state_plan(batch, nmax, &lds, &ws, &per, &grid))) return rc;
+    c.stats[14] = (lds ? TD_MP_LDS : TD_MP_WS) | 1 << TD_MP_CHUNK_SHIFT;
 #define TD_MATCH_ARGS                                                                                                               \
     batch, n, (const int32_t *)d_ns, (const int32_t *)d_w, ws, per, (int32_t *)o[0].dptr(), (int64_t *)o[1].dptr(),                 \
         (int64_t *)o[2].dptr(), (int64_t *)o[3].dptr(), (int32_t *)o[4].dptr(), (int64_t *)o[5].dptr(), d_err
@@ -386,6 +388,7 @@ int pool2_batched_impl(const char *fn, int batch, int n, const int32_t *off, con
                        int32_t *plan, int32_t *cost, int32_t *n_pools, int64_t *total)
 {
     Ctx &c = ctx();
+    c.stats[14] = 0;   // match_path (TD_MP_*): filled in below as the launches are decided and made
     if (batch < 0) return fail(TD_EINVAL, "%s: batch = %d < 0", fn, batch);
     if (n < 0 || n > MATCH_NMAX) return fail(TD_EINVAL, "%s: n = %d outside [0, %d]", fn, n, MATCH_NMAX);
     if (dist && (S <= 0 || S > 46340)) return fail(TD_EINVAL, "%s: S = %d outside [1, 46340] with a distance table", fn, S);
@@ -459,7 +462,11 @@ int pool2_batched_impl(const char *fn, int batch, int n, const int32_t *off, con
     int mgrid = 0;
     if (run_match && (rc = state_plan(chunk, nmax, &lds, &ws, &per, &mgrid))) return rc;
     const size_t shm_fin = sizeof(int32_t) * 3 * (H + 1);
+    int64_t path = TD_MP_POOL | (opt_v ? TD_MP_PER_MODEL : 0) | (run_greedy ? TD_MP_GREEDY : 0);
+    if (run_match) path |= TD_MP_MATCH | (lds ? TD_MP_LDS : TD_MP_WS);
+    int64_t chunks = 0;
     for (int b0 = 0; b0 < batch; b0 += chunk) {
+        chunks++;
         const int nq = std::min(chunk, batch - b0);
         const int grid = std::min(nq, 1 << 20);
         k_pool_costs<<<grid, 256, 0, c.stream>>>(nq, b0, n, optimal, (const int32_t *)d_optv, (const int32_t *)d_off, (const int32_t *)d_from,
@@ -480,6 +487,7 @@ int pool2_batched_impl(const char *fn, int batch, int n, const int32_t *off, con
                                                         (int32_t *)o[0].dptr(), (int32_t *)o[1].dptr(), (int32_t *)o[2].dptr(),
                                                         (int32_t *)o[3].dptr(), (int32_t *)o[4].dptr(), (int64_t *)o[5].dptr());
     }
+    c.stats[14] = path | std::min<int64_t>(chunks, TD_MP_CHUNK_MAX) << TD_MP_CHUNK_SHIFT;
     return match_finish(fn, o, 6, d_err);
 }
 

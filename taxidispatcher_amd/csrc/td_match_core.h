@@ -109,6 +109,26 @@ TDM_HD int E1(int e) { return e & 4095; }
 TDM_HD int flip(int e) { return (e & 4095) << 12 | e >> 12; }
 TDM_HD uint64_t pack(int64_t v, int idx) { return (uint64_t)v << 24 | (uint64_t)(uint32_t)idx; }
 
+// Path counters of the host build (tools/match_proto.cpp's test build defines TDM_TRACE; td_match.hip never does, and
+// without the macro the hooks expand to nothing): which control paths a solve walked, how often, how far.
+#ifdef TDM_TRACE
+struct Trace {
+    long long blossom_formed, leaves_max;                                    // add_blossom: count, most leaves at formation
+    long long aug_blossom, aug_fwd, aug_back, aug_nested;                    // augment_blossom: items, walk direction, child blossoms
+    long long expand_end, expand_end_nested;                                 // end-of-stage expansions, zero-dual sub-blossoms freed with them
+    long long expand_T, relabel_fwd, relabel_back, relabel_steps_max;        // delta-4 expansions, the relabel walk's direction and length
+    long long sub_vertex_T, sub_blossom_T;                                   // a reached child of an expanded T-blossom becomes T
+    long long reach_in_T;                                                    // scan: a vertex inside a T-blossom marked reached
+    long long delta1, delta2, delta3, delta4, substage_max, augmentations;   // run: the delta choice, the longest stage
+};
+inline Trace g_trace{};
+#define TDM_COUNT(f) (++tdm::g_trace.f)
+#define TDM_MAX(f, v) (tdm::g_trace.f = (long long)(v) > tdm::g_trace.f ? (long long)(v) : tdm::g_trace.f)
+#else
+#define TDM_COUNT(f) ((void)0)
+#define TDM_MAX(f, v) ((void)0)
+#endif
+
 // per-model state: n vertices, 2n nodes; carve() lays it out in `bytes(n)` bytes (LDS or a workspace slice)
 struct St {
     int32_t *mate, *inb, *pathb, *freeb, *stk, *tmp;              // n
@@ -309,6 +329,8 @@ struct Match {
             qt += popc(mq);
             nl += popc(ml);
         }
+        TDM_COUNT(blossom_formed);
+        TDM_MAX(leaves_max, nl);
         x = bb;
         g = 0;
         do {
@@ -363,7 +385,11 @@ struct Match {
                     return;
                 }
             }
-            if (t >= n) s.stk[sp++] = t << 12 | v;
+            TDM_COUNT(aug_blossom);
+            if (t >= n) {
+                s.stk[sp++] = t << 12 | v;
+                TDM_COUNT(aug_nested);
+            }
             int i = 0;
             for (int x = s.head[b]; x != t; x = s.nxt[x])
                 if (++i > 2 * n) {
@@ -371,6 +397,10 @@ struct Match {
                     return;
                 }
             const bool fwd = i & 1;
+            if (i > 0) {
+                if (fwd) TDM_COUNT(aug_fwd);
+                else TDM_COUNT(aug_back);
+            }
             for (int tc = t, g2 = 0; tc != s.head[b];) {
                 if (++g2 > n) {
                     err |= ERR_CAP;
@@ -407,6 +437,7 @@ struct Match {
 
     TDM_HD void augment_matching(int v, int w)
     {
+        TDM_COUNT(augmentations);
         for (int side = 0; side < 2; side++) {
             int sv = side ? w : v, j = side ? v : w;
             for (int g = 0;; g++) {
@@ -434,6 +465,7 @@ struct Match {
         // children become top-level (at the end of a stage, zero-dual sub-blossoms are expanded as well)
         int sp = 0;
         s.stk[sp++] = b;
+        if (endstage) TDM_COUNT(expand_end);
         while (sp > 0) {
             const int x = s.stk[--sp];
             int c = s.head[x], g = 0;
@@ -448,7 +480,10 @@ struct Match {
                 }
                 c = s.nxt[c];
             } while (c != s.head[x] && ++g <= 2 * n);
-            if (x != b) free_blossom(x);
+            if (x != b) {
+                free_blossom(x);
+                TDM_COUNT(expand_end_nested);
+            }
         }
         for (int u0 = 0; u0 < n; u0 += W) {
             const int u = u0 + lane();
@@ -468,6 +503,12 @@ struct Match {
                     return;
                 }
             const bool fwd = j & 1;
+            TDM_COUNT(expand_T);
+            TDM_MAX(relabel_steps_max, j);
+            if (j > 0) {
+                if (fwd) TDM_COUNT(relabel_fwd);
+                else TDM_COUNT(relabel_back);
+            }
             int v = E0(s.lend[b]), w = E1(s.lend[b]), tc = entry, g = 0;
             while (tc != s.head[b] && !err) {
                 const int q = fwd ? E1(s.ced[tc]) : E0(s.ced[s.prv[tc]]);
@@ -509,6 +550,8 @@ struct Match {
                     rv = k == NONE ? -1 : (int)k;
                 }
                 if (rv >= 0) {   // a vertex reached from outside: the sub-blossom becomes T
+                    if (x < n) TDM_COUNT(sub_vertex_T);
+                    else TDM_COUNT(sub_blossom_T);
                     s.label[rv] = 0;
                     s.label[s.mate[s.base[x]]] = 0;
                     assign_label(rv, 2, E0(s.lend[rv]));
@@ -547,6 +590,7 @@ struct Match {
                 } else if (s.label[ww] == 0) {   // inside a T-blossom: mark it reached
                     s.label[ww] = 2;
                     s.lend[ww] = E(v, ww);
+                    TDM_COUNT(reach_in_T);
                 }
             }
         }
@@ -634,6 +678,7 @@ struct Match {
             bool aug = false;
             for (int sub = 0;; sub++) {
                 if (sub > 4 * n + 8) return err | ERR_CAP;
+                TDM_MAX(substage_max, sub);
                 while (qh < qt && !aug && !err) aug = scan(s.queue[qh++]);
                 if (err) return err;
                 if (aug) break;
@@ -685,6 +730,10 @@ struct Match {
                     arg = (int)(k4 & M24);
                 }
                 if (delta < 0) return err | ERR_STATE;
+                if (type == 1) TDM_COUNT(delta1);
+                else if (type == 2) TDM_COUNT(delta2);
+                else if (type == 3) TDM_COUNT(delta3);
+                else TDM_COUNT(delta4);
                 for (int x = lane(); x < n2; x += W) {
                     if (x < n) {
                         const int lb = s.label[s.inb[x]];

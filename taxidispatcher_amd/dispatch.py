@@ -230,6 +230,16 @@ def finisher_path():
     return int(out[13])
 
 
+def match_path():
+    """td_last_stats word 14: what the last match_batched / pool2_batched launched, as a bit set (the TD_MP_* bits of the
+    header): 1 solver state in LDS, 2 in workspace slices, 4 a pool call, 8 the greedy launched, 16 k_pool_match launched,
+    32 per-model policy arrays given; bits 8..23 the chunks launched (saturating).  Not a key of last_stats(): recorded
+    comparisons of that dict stay valid."""
+    out = (ctypes.c_int64 * 16)()
+    _ffi.check(_ffi.lib().td_last_stats(out, 16))
+    return int(out[14])
+
+
 # ----------------------------------------------------------------------------------------
 # reference-shaped API
 # ----------------------------------------------------------------------------------------
@@ -913,7 +923,7 @@ def match_batched(weights, ns=None, want_dual=False):
     return (mate, total, bound, (y, par, z)) if want_dual else (mate, total, bound)
 
 
-def pool2_batched(froms, tos, distances=None, max_loss=None, optimal=True):
+def pool2_batched(froms, tos, distances=None, max_loss=None, optimal=True, n=None):
     """td_pool2_batched: pools of two for B ragged models in one call, one shared distance table (None: |a - b|).
     froms / tos: ragged lists as in pack_ragged (the same model sizes on both sides).  max_loss=None: every ordered pair is a
     candidate (Simulator.java:691); else pool_opt_min.py:58-64's loss tests.  optimal=False: the reference's greedy in its
@@ -921,14 +931,21 @@ def pool2_batched(froms, tos, distances=None, max_loss=None, optimal=True):
     max_loss and optimal may also be lists with one entry per model (None in a max_loss list: every ordered pair for that
     model): td_pool2_batched_v, the same launches whatever the mix; model b comes out exactly as a uniform call on it alone.
     Returns (cust_a, cust_b, plan, cost: int32[B, n // 2], n_pools int32[B], total int64[B]); model b's pools are the first
-    n_pools[b] entries of its rows; customer indices are positions within the model."""
+    n_pools[b] entries of its rows; customer indices are positions within the model.
+    n: the stride of the pair-cost slab and of the outputs (default: the longest model); refused when below the longest model
+    or above MATCH_NMAX.  A larger n answers the same, with fewer models per 256 MiB chunk."""
     lib = _ffi.lib()
     fv, fo, fh = _ragged(froms, "froms")
     tv, _, th = _ragged(tos, "tos")
     if not np.array_equal(fh, th):
         raise _ffi.TdError("froms and tos must describe the same models (equal offsets)")
     batch = int(fh.size - 1)
-    n = int(np.diff(fh).max()) if batch else 0
+    longest = int(np.diff(fh).max()) if batch else 0
+    if n is None:
+        n = longest
+    elif int(n) < longest or int(n) > MATCH_NMAX:
+        raise _ffi.TdError("n = %d: below the longest model (%d customers) or above %d" % (int(n), longest, MATCH_NMAX))
+    n = int(n)
     dptr, S, keep = _dist_arg(distances)
     half = n // 2
     a, b, plan, cost = (_out((batch, half), np.int32) for _ in range(4))

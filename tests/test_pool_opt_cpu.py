@@ -182,7 +182,10 @@ def proto(tmp_path_factory):
     return exe
 
 
-def _run_proto(exe, mats):
+def _run_proto(exe, mats, trace=False):
+    """per graph (err, total, bound, mate, y, parent, z); a build with -DTDM_TRACE prints a sixth line per graph, the path
+    counters, returned as an eighth entry"""
+    lines = 6 if trace else 5
     inp = [str(len(mats))]
     for W in mats:
         inp.append(str(W.shape[0]))
@@ -190,8 +193,8 @@ def _run_proto(exe, mats):
     out = subprocess.run([exe], input="\n".join(inp), capture_output=True, text=True, check=True).stdout.split("\n")
     res = []
     for t in range(len(mats)):
-        err, tot, bnd = map(int, out[5 * t].split())
-        vals = [list(map(int, out[5 * t + r].split())) for r in range(1, 5)]
+        err, tot, bnd = map(int, out[lines * t].split())
+        vals = [list(map(int, out[lines * t + r].split())) for r in range(1, lines)]
         res.append((err, tot, bnd, *vals))
     return res
 

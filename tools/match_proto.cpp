@@ -1,6 +1,8 @@
 // Host build of the blossom solver of td_match.hip (csrc/td_match_core.h, W = 1): reads graphs as text from stdin
 // (count, then per graph n and the n x n weight matrix, row-major) and prints per graph "err total bound", the mates,
 // the vertex duals, the blossom parents of the 2n nodes and the blossom duals z (doubled, as td_match_batched exports them).
+// Built with -DTDM_TRACE it prints a sixth line per graph: the path counters of tdm::Trace, in TRACE_FIELDS' order
+// (tests/test_match_paths_cpu.py reads them by that order; tests/match_path_cases.py names them).
 //   g++ -O2 -std=c++17 -I taxidispatcher_amd/csrc tools/match_proto.cpp -o match_proto
 #include <cstdio>
 #include <vector>
@@ -17,6 +19,13 @@ struct Mat {
     }
 };
 
+#ifdef TDM_TRACE
+#define TRACE_FIELDS(X)                                                                                                           \
+    X(blossom_formed) X(leaves_max) X(aug_blossom) X(aug_fwd) X(aug_back) X(aug_nested) X(expand_end) X(expand_end_nested)        \
+    X(expand_T) X(relabel_fwd) X(relabel_back) X(relabel_steps_max) X(sub_vertex_T) X(sub_blossom_T) X(reach_in_T) X(delta1)      \
+    X(delta2) X(delta3) X(delta4) X(substage_max) X(augmentations)
+#endif
+
 int main()
 {
     int T;
@@ -29,6 +38,9 @@ int main()
             if (scanf("%d", &x) != 1) return 1;
         std::vector<unsigned char> mem(tdm::bytes(n > 0 ? n : 1) + 64);
         const Mat m{w.data(), n};
+#ifdef TDM_TRACE
+        tdm::g_trace = tdm::Trace{};
+#endif
         tdm::Match<Mat> M(tdm::carve(mem.data(), n), m, n);
         int err = n > 0 ? M.run() : 0;
         int64_t total = 0, bound = 0;
@@ -42,6 +54,12 @@ int main()
         printf("\n");
         for (int i = n; i < 2 * n; i++) printf("%lld ", (long long)(M.s.base[i] >= 0 ? 2 * M.s.dual[i] : 0));
         printf("\n");
+#ifdef TDM_TRACE
+#define X(f) printf("%lld ", tdm::g_trace.f);
+        TRACE_FIELDS(X)
+#undef X
+        printf("\n");
+#endif
     }
     return 0;
 }
