@@ -609,6 +609,14 @@ TD_API int td_sim_pooling_n(td_sim *s, int k_hi, int k_lo, int max_wait, int max
 TD_API int td_simb_pooling_n(td_simb *s, const int32_t *k_hi, const int32_t *k_lo, const int32_t *max_wait, const int32_t *max_loss_pct,
                              int64_t max_happy);
 TD_API int td_sim_pools_n(td_sim *s, int max_pools, int32_t *records /* max_pools x 9 */, int32_t *size, int32_t *n);
+/* td_sim_pool_buffer: with plan_buffer > 0 every stage of a world under td_sim_pooling_n is
+ * td_pool_n_banded(k, ..., plan_buffer, ...) on the device lists, whatever the list's size up to 2047: the same records, and
+ * begin no longer returns TD_ERANGE for the number of happy plans (max_happy is not looked at; the cost limit stays).
+ * max_POOL_MEM_size stays the sum of the stages' true happy counts.  0 restores the calls above.  TD_EINVAL, nothing changed:
+ * a NULL handle, a negative value, a value below 24 * 2047 (the room td_pool_n_banded needs for the largest tick), a call
+ * while a tick waits for its apply.  The setting survives td_sim_pooling and td_sim_pooling_n and takes effect at the next
+ * begin; a handle that never calls it launches exactly what it did before the call existed. */
+TD_API int td_sim_pool_buffer(td_sim *s, int64_t plan_buffer);
 TD_API int td_simb_pools_n(td_simb *s, int world, int max_pools, int32_t *records /* max_pools x 9 */, int32_t *size, int32_t *n);
 
 /* ---- the dispatch policy of a world ------------------------------------------------------------------------------
@@ -739,6 +747,27 @@ TD_API int td_pool_n(int k, int n, const int32_t *from, const int32_t *to, const
                      int64_t max_happy, int max_pools, int32_t *pools, int32_t *n_pools, int64_t *n_happy);
 TD_API int td_pool_merge(int k, int n_requests, int n_in, const int32_t *pools_in /* n_in * (2k+1) */,
                          int sort_by_cost, int max_pools, int32_t *pools_out, int32_t *n_out);
+
+/* ---- f-4 in a bounded plan buffer --------------------------------------
+ * td_pool_n_banded: td_pool_n's arguments, rules and answer (host or device arrays, the first-pick-up slice, k = 2..4,
+ *   n <= 2047, the empty cases, TD_ERANGE for a plan cost above 16383 with n_happy still set): pools[0 .. n_pools) and n_pools
+ *   are, record for record, what td_pool_n returns on the same input with room for every happy plan, and n_happy is the true
+ *   number of happy plans.  It never fails for the number of happy plans.
+ *   plan_buffer: the most plan keys the call holds at once (<= 0: 4 Mi).  The keys' ascending order is the reference's stable
+ *   sort and the de-duplication only reads them in that order, so it runs over consecutive key intervals ("bands"), each
+ *   enumerated, sorted and scanned on its own with the set of used requests carried along; a plan with a used request is
+ *   never stored.  A band is the longest run of costs that fits; where one cost alone does not fit it is cut at the first
+ *   pick-up, then the second, and so on: one value of the last digit but one holds at most (n - k + 1) k! <= 24 n plans, so
+ *   the only new refusal is plan_buffer < 24 n (TD_EINVAL, the message has both numbers, no output written).  Workspace
+ *   grows with plan_buffer (two key arrays and the sort's scratch), not with the plan count; time grows with the bands:
+ *   every band costs one counting pass per level it is cut at and one enumeration pass.
+ *   stats (may be NULL): [0] bands, [1] enumeration passes in all, counting passes included, [2] the deepest level a band was
+ *   cut at (0: at a cost, l: at pick-up l - 1; at most k - 1), [3] the most keys held in one band.  All 0 in the empty cases.
+ */
+TD_API int td_pool_n_banded(int k, int n, const int32_t *from, const int32_t *to, const int32_t *max_wait,
+                            const int32_t *max_loss, const int32_t *dist, int S, int first0, int first1,
+                            int64_t plan_buffer, int max_pools, int32_t *pools, int32_t *n_pools,
+                            int64_t *n_happy, int64_t stats[4] /* may be NULL */);
 
 /* ---- f-4 for MANY models per call ------------------------------------------------------
  * td_pool_n_batched: B ragged models, model b = requests [off[b], off[b+1]) of the concatenated from / to / max_wait /

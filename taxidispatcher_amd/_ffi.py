@@ -107,6 +107,7 @@ SIGNATURES = {
     "td_simb_pools": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p,
                                      ctypes.POINTER(ctypes.c_int32)]),
     "td_sim_pooling_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "td_sim_pool_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     "td_sim_pools_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_int32)]),
     "td_simb_pooling_n": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int64]),
     "td_simb_pools_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_int32)]),
@@ -122,6 +123,9 @@ SIGNATURES = {
     "td_pool_n": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int,
                                  ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_i32p, ctypes.POINTER(ctypes.c_int32),
                                  ctypes.POINTER(ctypes.c_int64)]),
+    "td_pool_n_banded": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_i32p, ctypes.POINTER(ctypes.c_int32),
+                                        ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
     "td_pool_merge": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p, ctypes.c_int, ctypes.c_int, c_i32p,
                                      ctypes.POINTER(ctypes.c_int32)]),
     "td_pool_n_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int,

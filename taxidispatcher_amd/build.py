@@ -10,7 +10,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = [os.path.join(HERE, "csrc", f) for f in ("td_core.hip", "td_assign.hip", "td_lcm.hip", "td_pool.hip", "td_pool_batch.hip", "td_line.hip", "td_tick.hip",
+SRC = [os.path.join(HERE, "csrc", f) for f in ("td_core.hip", "td_assign.hip", "td_lcm.hip", "td_pool.hip", "td_pool_band.hip", "td_pool_batch.hip", "td_line.hip", "td_tick.hip",
                                                "td_batch.hip", "td_match.hip", "td_sim.hip", "td_simb.hip")]
 # every header a source may include: a header added later is part of the staleness check without being listed here
 HDR = sorted(glob.glob(os.path.join(HERE, "csrc", "*.h")) + glob.glob(os.path.join(ROOT, "include", "*.h")))

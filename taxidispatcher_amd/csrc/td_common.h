@@ -111,6 +111,8 @@ void pool2_greedy_launch(int batch, int n, const int32_t *d_ns, const int32_t *d
 void match_release_workspace();
 // td_pool.hip: frees td_pool_n / td_pool_merge's workspace (td_shutdown)
 void pool_release_workspace();
+// td_pool_band.hip: frees td_pool_n_banded's workspace (td_shutdown)
+void pool_band_release_workspace();
 // td_pool_batch.hip: frees td_pool_n_batched's key slab and staging (td_shutdown)
 void pool_batch_release_workspace();
 // td_pool_batch.hip: td_pool_n_batched's core on device arrays with a size per model, for the worlds of td_simb_pooling_n

@@ -414,6 +414,7 @@ void td_shutdown(void)
     batch_release_workspace();
     match_release_workspace();
     pool_release_workspace();
+    pool_band_release_workspace();
     pool_batch_release_workspace();
     Buf *bufs[] = {&c.stage_a, &c.stage_b, &c.stage_c, &c.stage_d, &c.stage_out, &c.cc,
                    &c.misc,    &c.lcm_a,   &c.lcm_b,   &c.lcm_c,   &c.lcm_d};

@@ -153,11 +153,7 @@ template <bool FROM_KEY>
 __device__ __forceinline__ void pn_requests(int k, int n, unsigned long long key, const int32_t *recs, int *c)
 {
     if (FROM_KEY) {
-        unsigned long long s = (key & PN_SEQ_MASK) / 24ull;
-        for (int i = 3; i >= 0; i--) {
-            c[i] = (int)(s % (unsigned long long)n);
-            s /= (unsigned long long)n;
-        }
+        pn_key_requests(n, key, c);
     } else {
         const int32_t *r = recs + (size_t)(key & 0xFFFFFFFFull) * (size_t)(2 * k + 1);
         for (int i = 0; i < k; i++) c[i] = r[i];

@@ -1,4 +1,4 @@
-// td_pool_core.h — what td_pool_n (td_pool.hip) and td_pool_n_batched (td_pool_batch.hip) share: the plan key, the k!
+// td_pool_core.h — what td_pool_n (td_pool.hip), td_pool_n_banded (td_pool_band.hip) and td_pool_n_batched (td_pool_batch.hip) share: the plan key, the k!
 // drop-off orders, the distance and the happiness / cost test of pool_n.c:101-153.  One definition, so both calls answer alike.
 //
 //   key = cost << 50 | sequence number;  sequence number = (((p0 * n + p1) * n + p2) * n + p3) * 24 + drop-off order, the
@@ -42,6 +42,16 @@ constexpr PnOrder pn_order(int k, int qi)
     PnOrder o{{0, 0, 0, 0}};
     pn_perm(k, qi, o.q);
     return o;
+}
+
+// the pick-ups behind a key (radix n; the slots behind the pool's size decode to 0)
+__device__ __forceinline__ void pn_key_requests(int n, unsigned long long key, int *c)
+{
+    unsigned long long s = (key & PN_SEQ_MASK) / 24ull;
+    for (int i = 3; i >= 0; i--) {
+        c[i] = (int)(s % (unsigned long long)n);
+        s /= (unsigned long long)n;
+    }
 }
 
 __device__ __forceinline__ int pn_d(const int32_t *dist, int S, int a, int b)

@@ -18,7 +18,8 @@
 //                                        the one model (the optimum), or nothing (TD_POOL_NONE: the demand is copied as it is)
 //           k_pool_mark, k_count / k_scatter   analyzePool: B customers out, A customers annotated, order kept
 //           under td_sim_pooling_n (sim_begin_pool_n): per stage k = k_hi .. k_lo the pool call on the device lists
-//           (td_pool_n_batched on the one model, td_pool_n above 512 requests), k_pool_records (the stage's records as the
+//           (td_pool_n_batched on the one model, td_pool_n above 512 requests; td_pool_n_banded for every stage once
+//           td_sim_pool_buffer set a plan buffer), k_pool_records (the stage's records as the
 //           tick's, and analyzePool's marks), k_count / k_scatter (the rest for the next stage); then k_count / k_scatter
 //           with PoolEmitN: the first pick-up carries up to three partners, the size and the cost
 //   apply   k_pair_map                   first pair per cab / per request (setdefault), indices checked
@@ -95,6 +96,7 @@ struct td_sim : SimDev, SimPin {   // td_sim_layout.h: every device array of the
     // td_sim_pooling_n: pools of pn_hi down to pn_lo from the next begin on; pn_hi == 0: the pair policy above holds
     int pn_hi = 0, pn_lo = 0, pn_wait = 0, pn_loss = 0;
     int64_t pn_max_happy = 0;
+    int64_t pn_buffer = 0;       // td_sim_pool_buffer: > 0: every stage is td_pool_n_banded with this plan buffer
     PoolNDev pn;
     Buf pn_mem;
     // td_sim_dispatch: the dispatch method from the next begin on.  The world kernels take the LCM rule as one number
@@ -326,7 +328,9 @@ int sim_begin_pool_n(td_sim *s, int t, int32_t info[4])
         if (m < k) continue;   // a stage list shorter than its k yields no pools
         int32_t np = 0;
         int64_t nh = 0;
-        if (m <= SIM_POOL_NB_NMAX) {
+        if (s->pn_buffer > 0) {
+            rc = td_pool_n_banded(k, m, from, to, pn.wait, pn.loss, s->dist, S, 0, m, s->pn_buffer, m / k + 1, pn.out, &np, &nh, nullptr);
+        } else if (m <= SIM_POOL_NB_NMAX) {
             const int32_t off[2] = {0, m};
             rc = td_pool_n_batched(k, 1, m, off, from, to, pn.wait, pn.loss, s->dist, S, nullptr, s->pn_max_happy, pn.out, &np, &nh, nullptr);
         } else {
@@ -704,6 +708,18 @@ extern "C" int td_sim_pooling_n(td_sim *s, int k_hi, int k_lo, int max_wait, int
     k_fill2<<<(s->cap + 255) / 256, 256, 0, c.stream>>>(s->cap, pn.wait, max_wait, pn.loss, max_loss_pct);
     TD_HIP(hipGetLastError());
     s->pn_hi = k_hi, s->pn_lo = k_lo, s->pn_wait = max_wait, s->pn_loss = max_loss_pct, s->pn_max_happy = max_happy;
+    return TD_OK;
+}
+
+extern "C" int td_sim_pool_buffer(td_sim *s, int64_t plan_buffer)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (plan_buffer < 0 || (plan_buffer > 0 && plan_buffer < (int64_t)24 * SIM_POOL_N_NMAX))
+        return fail(TD_EINVAL, "td_sim_pool_buffer: plan_buffer = %lld: 0, or at least 24 * %d = %d", (long long)plan_buffer, SIM_POOL_N_NMAX,
+                    24 * SIM_POOL_N_NMAX);
+    if (s->begun) return fail(TD_EINVAL, "td_sim_pool_buffer: tick %d still waits for td_sim_apply", s->last_t);
+    s->pn_buffer = plan_buffer;
     return TD_OK;
 }
 

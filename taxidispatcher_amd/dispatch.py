@@ -31,6 +31,7 @@ Reference map (file:line in boguszjelinski/taxidispatcher):
     pool2_batched         greedy (pool_opt_min.py:81-102) or optimal (:114-122) pools of two of many ragged models per call
     find_pool_optimal     find_pool's format, optimal pools
     pool_gap              pool_opt_min.py as two calls
+    find_pool_n_banded    pool_n.c (pools of 2..4) of one model in a bounded plan buffer, any number of happy plans
     pool_n_batched        pool_n.c (pools of 2..4) of many models of at most 512 requests per call
     find_pool_fanout      findpool.c as two calls: the 8 children as one batch, then the merge
 """
@@ -432,6 +433,35 @@ def find_pool_n(k, demand, distances=None, child=None, children=8, max_happy=0):
                              int(first1), int(max_happy), cap, _ffi.addr(out), ctypes.byref(m), ctypes.byref(nh)))
     del keep
     return out[:m.value].copy(), int(nh.value)
+
+
+def find_pool_n_banded(k, demand, distances=None, child=None, children=8, plan_buffer=0):
+    """td_pool_n_banded: find_pool_n's answer with at most plan_buffer plan keys held at once (0: 4 Mi; at least 24 * len(demand)),
+    whatever the number of happy plans.  demand / distances / child / children as find_pool_n takes them.  Returns (records,
+    number of happy plans, stats): stats = (bands, enumeration passes, the deepest level a band was cut at, the most keys of
+    one band)."""
+    lib = _ffi.lib()
+    if not 2 <= int(k) <= 4:
+        raise _ffi.TdError("pool size %d (2..4)" % int(k))
+    d = _ffi.as_i32(np.asarray(demand).reshape(len(demand), -1))
+    n = int(d.shape[0])
+    frm, to, wait, loss = (np.ascontiguousarray(d[:, c]) for c in (1, 2, 3, 4))
+    if child is None:
+        first0, first1 = 0, n
+    else:
+        step = n // children + 1
+        first0 = step * child
+        first1 = min(n, first0 + step)
+    dptr, S, keep = _dist_arg(distances)
+    cap = max(1, n // k + 1)
+    out = np.zeros((cap, 2 * k + 1), np.int32)
+    m = ctypes.c_int32(0)
+    nh = ctypes.c_int64(0)
+    stats = np.zeros(4, np.int64)
+    _ffi.check(lib.td_pool_n_banded(int(k), n, _ffi.addr(frm), _ffi.addr(to), _ffi.addr(wait), _ffi.addr(loss), dptr, S, int(first0),
+                                    int(first1), int(plan_buffer), cap, _ffi.addr(out), ctypes.byref(m), ctypes.byref(nh), _ffi.addr(stats)))
+    del keep
+    return out[:m.value].copy(), int(nh.value), tuple(int(v) for v in stats)
 
 
 def merge_pools(k, n_requests, lists):

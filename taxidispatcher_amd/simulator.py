@@ -92,6 +92,18 @@ def pool_n_sizes(pool_n):
     return hi, lo
 
 
+POOL_BUFFER_MIN = 24 * 2047   # td_sim_pool_buffer: the room td_pool_n_banded needs for the largest tick
+
+
+def pool_buffer_size(pool_buffer):
+    """pool_buffer of a world -> an int: 0 (off) or at least 24 * 2047 (ValueError)"""
+    if isinstance(pool_buffer, bool) or not isinstance(pool_buffer, (int, np.integer)):
+        raise ValueError("pool_buffer=%r: an integer" % (pool_buffer,))
+    if pool_buffer < 0 or 0 < pool_buffer < POOL_BUFFER_MIN:
+        raise ValueError("pool_buffer=%r: 0, or at least 24 * 2047 = %d" % (pool_buffer, POOL_BUFFER_MIN))
+    return int(pool_buffer)
+
+
 def pool_n_rule(pool_wait, pool_loss):
     """pool_wait / pool_loss of a pool_n policy -> two ints, each at least 0 (ValueError)"""
     out = []
@@ -116,14 +128,16 @@ class HipBackend:
     """cost build / LCM / optimal assignment on the GPU through the C ABI; dist: a stand-to-stand table (None = |a - b|).
     pool / max_loss: the policy find_pool follows when the caller names none ("greedy": dispatch.find_pool, "optimal":
     dispatch.find_pool_optimal; max_loss=None: every ordered pair is a candidate).  max_happy: the most happy plans of one
-    find_pool_n stage (0: the default of the pool call underneath)."""
+    find_pool_n stage (0: the default of the pool call underneath).  pool_buffer > 0: every find_pool_n stage is
+    td_pool_n_banded with this plan buffer (the specification of td_sim_pool_buffer) and max_happy is not looked at."""
 
-    def __init__(self, dist=None, pool="greedy", max_loss=None, max_happy=0):
+    def __init__(self, dist=None, pool="greedy", max_loss=None, max_happy=0, pool_buffer=0):
         from . import dispatch
         self.d = dispatch
         self.dist = None if dist is None else check_dist(dist)
         pool_mode(pool)
         self.pool, self.max_loss, self.max_happy = pool, max_loss, int(max_happy)
+        self.pool_buffer = pool_buffer_size(pool_buffer)
 
     def calculate_cost(self, cab_to, dem_from):
         return self.d.cost_build(cab_to, dem_from, self.dist, fill=BIG_COST, threshold=DROP_TIME)[1]
@@ -152,9 +166,11 @@ class HipBackend:
     def find_pool_n(self, k, frm, to, wait, loss):
         """pools of k among the requests (td_pool_n: every request may be the first pick-up) -> (records [m, 2k+1] of
         pick-ups, drop-offs, cost in td_pool_n's order, happy plans before de-duplication); up to 512 requests through
-        td_pool_n_batched on the one model, above through td_pool_n"""
+        td_pool_n_batched on the one model, above through td_pool_n; with pool_buffer all through td_pool_n_banded"""
         frm, to, wait, loss = (np.asarray(a, np.int32).reshape(-1) for a in (frm, to, wait, loss))
         rows = np.stack([np.arange(frm.size, dtype=np.int32), frm, to, wait, loss], axis=1)
+        if self.pool_buffer > 0:
+            return self.d.find_pool_n_banded(k, rows, self.dist, plan_buffer=self.pool_buffer)[:2]
         if frm.size <= self.d.POOL_N_BATCHED_NMAX:
             recs, nh = self.d.pool_n_batched(k, [rows], self.dist, max_happy=self.max_happy)
             return np.asarray(recs[0]), int(np.asarray(nh).reshape(-1)[0])
@@ -791,7 +807,10 @@ class DeviceSimulator(_DeviceEvents):
     world never calls td_sim_dispatch and dispatches as it always did.
     pool_n / pool_wait / pool_loss / max_happy: pools of up to four as `Simulator` takes them (td_sim_pooling_n; max_happy: the
     most happy plans of one stage, 0 = the default of the pool call underneath); `pools_n()` reads the records of the tick
-    last begun (td_sim_pools_n), `set_pool_n` changes the policy between two ticks.  None: td_sim_pooling_n is never called."""
+    last begun (td_sim_pools_n), `set_pool_n` changes the policy between two ticks.  None: td_sim_pooling_n is never called.
+    pool_buffer: > 0: every stage of a pool_n world is td_pool_n_banded with this plan buffer (td_sim_pool_buffer; at least
+    24 * 2047), so no tick is refused for its number of happy plans; `set_pool_buffer` changes it between two ticks, 0 switches
+    it off.  0: td_sim_pool_buffer is never called."""
 
     M_KEYS = ("total_dropped", "total_pickup_time", "total_pickup_numb", "total_LCM_used", "max_model_size", "max_solver_size",
               "max_POOL_MEM_size", "max_POOL_size", "total_second_passengers")
@@ -799,9 +818,11 @@ class DeviceSimulator(_DeviceEvents):
     REQ_KEYS = ("d_cab", "d_pick", "d_pool_id", "d_pool_plan", "d_pool_cost")
 
     def __init__(self, demand_rows, n_cabs=None, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None, events=None,
-                 event_capacity=None, pool="greedy", max_loss=None, dispatch=None, parts=4, pool_n=None, pool_wait=0, pool_loss=0, max_happy=0):
+                 event_capacity=None, pool="greedy", max_loss=None, dispatch=None, parts=4, pool_n=None, pool_wait=0, pool_loss=0, max_happy=0,
+                 pool_buffer=0):
         import ctypes
         mode = pool_mode(pool)
+        pool_buffer = pool_buffer_size(pool_buffer)
         if dispatch is not None:
             dispatch_mode(dispatch)
         pool_n_sizes(pool_n)
@@ -841,6 +862,9 @@ class DeviceSimulator(_DeviceEvents):
         self.pool_n = None
         if pool_n is not None:                            # a default world never calls td_sim_pooling_n
             self.set_pool_n(pool_n, pool_wait, pool_loss, max_happy)
+        self.pool_buffer = 0
+        if pool_buffer:                                   # a default world never calls td_sim_pool_buffer
+            self.set_pool_buffer(pool_buffer)
         self.dispatch, self.parts = "lcm+opt", int(parts)
         if dispatch is not None:                          # a default world never calls td_sim_dispatch
             self.set_dispatch(dispatch, self.max_non_lcm, parts)
@@ -856,6 +880,12 @@ class DeviceSimulator(_DeviceEvents):
         wait, loss = pool_n_rule(pool_wait, pool_loss)
         self._ffi.check(self._lib.td_sim_pooling_n(self._h, hi, lo, wait, loss, int(max_happy)))
         self.pool_n, self.pool_wait, self.pool_loss, self.max_happy = (hi, lo), wait, loss, int(max_happy)
+
+    def set_pool_buffer(self, pool_buffer):
+        """td_sim_pool_buffer: the plan buffer of td_pool_n_banded for every stage of a pool_n world, from the next begin on; 0:
+        the stages run as they did without it"""
+        self._ffi.check(self._lib.td_sim_pool_buffer(self._h, int(pool_buffer)))
+        self.pool_buffer = int(pool_buffer)
 
     def pools_n(self):
         """the plans of the tick last begun under pool_n: a list of (pick-ups, drop-offs, cost), the members indices into that

@@ -22,7 +22,9 @@ demand reaches at 1300 cabs.
 td_sim_pooling_n with --world device) instead of the --pool policy: the cascade of td_pool_n stages K_HI .. K_LO under a pick-up
 path of at most W and rides at most L percent longer.  This tool runs one such world; --cabs N with a single N then sets its fleet size (batches
 of such worlds: DeviceSimulatorBatch(pool_n=[...]), tools/sim_pool_n_time.py).  A tick with more than 2047 requests before pooling, or a stage with more happy plans than H,
-is refused, and the tool says which tick."""
+is refused, and the tool says which tick.
+--pool-buffer N (with --pool-n): every stage runs through td_pool_n_banded with a plan buffer of N keys (td_sim_pool_buffer /
+HipBackend(pool_buffer=N); at least 24 * 2047 = 49128): the same plans, and no tick is refused for its number of happy plans."""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -42,8 +44,16 @@ ap.add_argument("--pool-n", default=None, metavar="K_HI,K_LO", help="pools of up
 ap.add_argument("--pool-wait", type=int, default=0, metavar="W", help="with --pool-n: the longest pick-up path before a member boards")
 ap.add_argument("--pool-loss", type=int, default=0, metavar="L", help="with --pool-n: percent a pooled ride may exceed the direct one")
 ap.add_argument("--max-happy", type=int, default=0, metavar="H", help="with --pool-n: the most happy plans of one stage (0: the pool call's default)")
+ap.add_argument("--pool-buffer", type=int, default=0, metavar="N", help="with --pool-n: the plan buffer of td_pool_n_banded for every stage (0: off)")
 args = ap.parse_args()
 pool_n, n_cabs_1 = {}, {}
+if args.pool_buffer:
+    if not args.pool_n:
+        ap.error("--pool-buffer goes with --pool-n")
+    try:
+        simulator.pool_buffer_size(args.pool_buffer)
+    except ValueError as e:
+        ap.error("--pool-buffer %d: %s" % (args.pool_buffer, e))
 if args.pool_n:
     try:
         sizes = tuple(int(v) for v in args.pool_n.split(","))
@@ -160,6 +170,7 @@ if args.world == "device" and args.cabs:
 if args.world == "device":
     if pool_n:
         pool_n["max_happy"] = args.max_happy
+        pool_n["pool_buffer"] = args.pool_buffer
     sim = simulator.DeviceSimulator(rows, dist=dist, events=True if args.events else None, pool=pools[0], max_loss=losses[0], **policy, **pool_n,
                                     **n_cabs_1)
     t0 = time.time()
@@ -174,7 +185,7 @@ if args.world == "device":
     print("\n".join(log[-3:]))
     print(sim.metrics_text(total_simul_time=int(dt)))
     sys.exit(0)
-sim = simulator.Simulator(rows, backend=simulator.HipBackend(dist, max_happy=args.max_happy) if pool_n else None, dist=dist, events=bool(args.events), pool=pools[0],
+sim = simulator.Simulator(rows, backend=simulator.HipBackend(dist, max_happy=args.max_happy, pool_buffer=args.pool_buffer) if pool_n else None, dist=dist, events=bool(args.events), pool=pools[0],
                           max_loss=losses[0], **policy, **pool_n, **({"n_cabs": n_cabs_1["n_cabs"]} if n_cabs_1 else {}))
 t0 = time.time()
 per = {"pool": 0.0, "cost": 0.0, "lcm": 0.0, "solve": 0.0}
