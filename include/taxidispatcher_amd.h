@@ -324,11 +324,13 @@ TD_API int td_lcm_shard_take(td_lcm_shard *s, int row, int col);
 /* The same result in ROUNDS of locally dominant cells instead of one exchange per pick (Simulator.java:523-549 takes up
  * to 700 picks per tick): a live cell that is the first minimum of its row AND of its column under the order (value, row,
  * column) is taken by the sequential greedy before anything else of its row or column, so all of them are taken at once.
- * Per round: round_colmin (per column the smallest live cell below `limit` of this shard's rows, key = (value << 32) | global
- * row as a SIGNED int64, INT64_MAX = none) -> MIN all-reduce of the n keys -> round_apply (taken[c] = the key of a row whose
- * first minimum is its column's minimum, INT64_MIN = none) -> MAX all-reduce -> round_commit (mask the taken columns
- * everywhere, retire the taken rows, re-scan the rows that lost their cached column).  The picks sorted by (value, row, column)
- * are td_lcm's pair list; the stop rules are applied to that order by the host driver (sharded.py lcm_sharded).  Vectors
+ * Per round: round_colmin (per column the smallest live cell below `limit` of this shard's rows, INT64_MAX = none) -> MIN
+ * all-reduce of the n keys -> round_apply (taken[c] = the key of a row whose first minimum is its column's minimum,
+ * INT64_MIN = none) -> MAX all-reduce -> round_commit (mask the taken columns everywhere, retire the taken rows, re-scan the
+ * rows that lost their cached column).  A key is (value << 32) | (global row + 1) as a SIGNED int64, ordered like (value,
+ * row): value = key >> 32, row = (key & 0xFFFFFFFF) - 1.  Its low word is 1 .. 2^31, so neither sentinel is the key of a
+ * cell, whatever int32 value the cell holds (-2^31 in row 0 included).  The picks sorted by (value, row, column) are
+ * td_lcm's pair list; the stop rules are applied to that order by the host driver (sharded.py lcm_sharded).  Vectors
  * may be host or device memory. */
 TD_API int td_lcm_shard_round_colmin(td_lcm_shard *s, int64_t limit, int64_t *colmin);
 TD_API int td_lcm_shard_round_apply(td_lcm_shard *s, int64_t limit, const int64_t *colmin, int64_t *taken);

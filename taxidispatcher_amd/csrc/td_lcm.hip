@@ -26,6 +26,9 @@ __device__ __forceinline__ unsigned long long lcm_key(int32_t v, int col)
     return ((unsigned long long)((uint32_t)v ^ 0x80000000u) << 32) | (uint32_t)col;
 }
 __device__ __forceinline__ int32_t lcm_val(unsigned long long k) { return (int32_t)((uint32_t)(k >> 32) ^ 0x80000000u); }
+// transport key of the sharded rounds (k_lcmsh_colmin / _apply / _commit): signed, ordered like (value, global row)
+__device__ __forceinline__ long long lcmr_key(int32_t v, int grow) { return ((long long)v << 32) | (long long)((uint32_t)grow + 1u); }
+__device__ __forceinline__ int lcmr_row(long long k) { return (int)((uint32_t)k - 1u); }
 
 // first minimum of one row among unmasked candidate columns, by one wavefront
 __device__ __forceinline__ unsigned long long lcm_scan_row(const int32_t *__restrict__ rp, int n, int lane,
@@ -1047,8 +1050,9 @@ __global__ __launch_bounds__(256) void k_lcmsh_rescan(int n, int nrows, int col,
 // A live cell that is the first minimum of its row AND of its column under the reference's order (value, row,
 // column) is taken by the sequential greedy before anything else of its row or column, so ALL such cells can
 // be taken in one round; the rounds end when no candidate is left and the picks, sorted by that order, are the
-// sequential greedy's picks in its order.  Transport keys are SIGNED: (value << 32) | row, so a MIN / MAX
-// all-reduce of int64 vectors orders them like (value, row).
+// sequential greedy's picks in its order.  Transport keys are SIGNED: (value << 32) | (global row + 1), so a MIN / MAX
+// all-reduce of int64 vectors orders them like (value, row).  The low word of a cell's key is 1 .. 2^31: never 0 (INT64_MIN,
+// "not taken", would be value -2^31 in row 0 without the + 1) and never 2^32 - 1 (INT64_MAX, "no candidate").
 constexpr long long LCMR_NONE_MIN = LLONG_MAX;   // column without a candidate (MIN all-reduce)
 constexpr long long LCMR_NONE_MAX = LLONG_MIN;   // column not taken in this round (MAX all-reduce)
 
@@ -1065,7 +1069,7 @@ __global__ __launch_bounds__(256) void k_lcmsh_colmin(int n, int nrows, int row0
             if (rowbest[r] == LCM_INF) continue;   // taken, or no candidate left in the row (uniform over the workgroup)
             const int32_t v = cost[(int64_t)r * n + c];
             if ((long long)v < limit) {
-                const long long k = ((long long)v << 32) | (long long)(uint32_t)(row0 + r);
+                const long long k = lcmr_key(v, row0 + r);
                 best = k < best ? k : best;
             }
         }
@@ -1085,7 +1089,7 @@ __global__ __launch_bounds__(256) void k_lcmsh_apply(int n, int nrows, int row0,
     const int32_t v = lcm_val(k);
     if ((long long)v >= limit) return;
     const int c = (int)(uint32_t)k;
-    const long long mine = ((long long)v << 32) | (long long)(uint32_t)(row0 + r);
+    const long long mine = lcmr_key(v, row0 + r);
     if (colmin[c] == mine) taken[c] = mine;   // one writer per column: the column's minimum is unique
 }
 
@@ -1104,7 +1108,7 @@ __global__ __launch_bounds__(256) void k_lcmsh_commit(int n, int nrows, int row0
     const long long t = taken[c];
     if (t == LCMR_NONE_MAX) return;
     atomicOr(&colmask[c >> 5], 1u << (c & 31));
-    const int r = (int)(uint32_t)t - row0;
+    const int r = lcmr_row(t) - row0;
     if (r >= 0 && r < nrows) rowbest[r] = LCM_INF;
 }
 

@@ -877,7 +877,7 @@ def lcm_sharded(shards, dist, n, mask, threshold=-1, stop_value_on=0, stop_value
     ROUNDS of locally dominant cells: a live cell that is the first minimum of its row and
     of its column under the reference's order (value, row, column) is taken by the sequential greedy before
     anything else of its row or column, so every round takes all of them at once — two all-reduces of n
-    int64 keys per round (MIN of the column minima, MAX of the taken keys) and a few tens of rounds per
+    int64 keys `(value << 32) | (global row + 1)` per round (MIN of the column minima, MAX of the taken keys) and a few tens of rounds per
     tick instead of one exchange per pick (~700).  The picks, sorted by the reference's order, ARE the
     sequential greedy's picks in its order; the stop rules are then applied to that sequence.  The vectors
     live on the shards' device, so the collectives run on whatever backend owns it (RCCL for HIP shards).
@@ -926,7 +926,7 @@ def lcm_sharded(shards, dist, n, mask, threshold=-1, stop_value_on=0, stop_value
     keys = picked.cpu().numpy()
     cols_all = np.nonzero(keys != LCM_NONE_MAX)[0]
     vals = keys[cols_all] >> 32
-    rows_all = keys[cols_all] & 0xFFFFFFFF
+    rows_all = (keys[cols_all] & 0xFFFFFFFF) - 1     # the key's low word is global row + 1: no cell packs to a sentinel
     order = np.lexsort((cols_all, rows_all, vals))      # the reference's order: value, then row, then column
     iters = n if max_pairs is None else min(n, max_pairs)
     pairs_r, pairs_c = [], []

@@ -337,7 +337,10 @@ class ModelShard:
 
 
 class ModelLcmShard:
-    """numpy model of td_lcm_shard_* (one rank's rows of the sharded lowest-cost method)."""
+    """numpy model of td_lcm_shard_* (one rank's rows of the sharded lowest-cost method).  Transport keys of the rounds as on
+    the device: (value << 32) | (global_row + 1) as a signed int64, so that no cell packs to NONE_MIN / NONE_MAX."""
+
+    NO_CELL = 2**62      # above every int32 value: a masked or non-candidate cell in the row scans
 
     def __init__(self, n, row0, nrows, cost_rows, stop_value_on=0, stop_value=0):
         self.n, self.row0, self.nrows = n, row0, nrows
@@ -346,56 +349,62 @@ class ModelLcmShard:
         self.row_live = np.ones(nrows, bool)
         self.col_live = np.ones(n, bool)
 
+    def _first_minima(self):
+        """(live local rows that still have a candidate, its value and column: the FIRST minimum, smallest column)"""
+        rows = np.nonzero(self.row_live)[0]
+        ok = np.broadcast_to(self.col_live, (rows.size, self.n))
+        if self.limit is not None:
+            ok = ok & (self.c[rows] < self.limit)
+        seen = np.where(ok, self.c[rows], self.NO_CELL)
+        j = np.argmin(seen, axis=1) if rows.size else np.zeros(0, np.int64)
+        v = seen[np.arange(rows.size), j]
+        has = v < self.NO_CELL
+        return rows[has], v[has], j[has]
+
     def local_min(self):
-        best = (2**63 - 1, -1, -1)
-        for i in np.nonzero(self.row_live)[0]:
-            row = np.where(self.col_live, self.c[i], 2**62)
-            if self.limit is not None:
-                row = np.where(row < self.limit, row, 2**62)
-            j = int(np.argmin(row))                     # first minimum: smallest column
-            if row[j] < 2**62:
-                best = min(best, (int(row[j]), self.row0 + int(i), j))
-        return best
+        rows, v, j = self._first_minima()
+        if not rows.size:
+            return (2**63 - 1, -1, -1)
+        k = np.lexsort((rows, v))[0]                    # smallest value, then smallest row
+        return (int(v[k]), self.row0 + int(rows[k]), int(j[k]))
 
     def take(self, row, col):
         if self.row0 <= row < self.row0 + self.nrows:
             self.row_live[row - self.row0] = False
         self.col_live[col] = False
 
-    # ---- rounds of locally dominant cells (td_lcm_shard_round_*): torch int64 vectors on the CPU
+    # ---- rounds of locally dominant cells (td_lcm_shard_round_*): int64 vectors on the CPU (torch tensors or numpy arrays)
     device = "cpu"
     NONE_MIN, NONE_MAX = 2**63 - 1, -2**63
 
-    def _row_first_min(self, i):
-        row = np.where(self.col_live, self.c[i], 2**62)
-        if self.limit is not None:
-            row = np.where(row < self.limit, row, 2**62)
-        j = int(np.argmin(row))
-        return (int(row[j]), j) if row[j] < 2**62 else None
+    def _keys(self, values, local_rows):
+        return (np.asarray(values, np.int64) << 32) | (self.row0 + np.asarray(local_rows, np.int64) + 1)
+
+    @staticmethod
+    def _np(vec):
+        return vec if isinstance(vec, np.ndarray) else vec.numpy()
 
     def round_colmin(self, limit, out):
         res = np.full(self.n, self.NONE_MIN, np.int64)
-        for i in np.nonzero(self.row_live)[0]:
-            if self._row_first_min(i) is None:      # no candidate left in the row: it sits out (like rowbest == INF)
-                continue
-            ok = self.col_live & (self.c[i] < limit)
-            keys = (self.c[i] << 32) | (self.row0 + int(i))
-            res = np.where(ok, np.minimum(res, keys), res)
-        out.copy_(__import__("torch").from_numpy(res))
+        rows, _, _ = self._first_minima()               # a row without a candidate sits out (like rowbest == INF)
+        if rows.size:
+            ok = self.col_live[None, :] & (self.c[rows] < limit)
+            keys = np.where(ok, self._keys(self.c[rows], rows[:, None]), self.NONE_MIN)
+            res = keys.min(axis=0)
+        self._np(out)[:] = res
 
     def round_apply(self, limit, colmin, out):
-        cm = colmin.numpy()
+        cm = self._np(colmin)
         res = np.full(self.n, self.NONE_MAX, np.int64)
-        for i in np.nonzero(self.row_live)[0]:
-            fm = self._row_first_min(i)
-            if fm is None or fm[0] >= limit:
-                continue
-            key = (fm[0] << 32) | (self.row0 + int(i))
-            if cm[fm[1]] == key:
-                res[fm[1]] = key
-        out.copy_(__import__("torch").from_numpy(res))
+        rows, v, j = self._first_minima()
+        below = v < limit
+        rows, v, j = rows[below], v[below], j[below]
+        key = self._keys(v, rows)
+        mine = cm[j] == key                             # one row per column at most: the column's minimum is unique
+        res[j[mine]] = key[mine]
+        self._np(out)[:] = res
 
     def round_commit(self, taken):
-        t = taken.numpy()
+        t = self._np(taken)
         for c in np.nonzero(t != self.NONE_MAX)[0]:
-            self.take(int(t[c] & 0xFFFFFFFF), int(c))
+            self.take(int(t[c] & 0xFFFFFFFF) - 1, int(c))
