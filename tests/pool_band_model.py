@@ -115,8 +115,16 @@ def scan_all(k, cost, p, qi):
     return recs
 
 
-def banded(k, n, cost, p, qi, plan_buffer=0, max_pools=None):
-    """the host loop of td_pool_n_banded on the plan list -> (records, n_happy, (bands, passes, deepest level, most keys))"""
+CHUNK = 1024      # k_band_greedy: keys per chunk
+
+
+def banded(k, n, cost, p, qi, plan_buffer=0, max_pools=None, trace=None):
+    """the host loop of td_pool_n_banded on the plan list -> (records, n_happy, (bands, passes, deepest level, most keys)).
+    trace: a list that gets one dict per band: lo, hi, level (the digit it was cut at), expect (its keys), first_bins (the size
+    of the first non-empty bin at each level it passed through), prefix (the key of the digits fixed above the cut), kept (the
+    positions of the kept plans among the band's keys in ascending order), kills_later (per kept plan: a key of a LATER chunk
+    of 1024 of the same band shares a request with it, so k_band_greedy must carry the bitmap from chunk to chunk), rows
+    (the band's keys as indices into the plan list)."""
     room = DEFAULT_BUFFER if plan_buffer <= 0 else int(plan_buffer)
     assert room >= 24 * n
     perms = list(itertools.permutations(range(k)))
@@ -136,10 +144,12 @@ def banded(k, n, cost, p, qi, plan_buffer=0, max_pools=None):
         if not live.any() or n - int(used.sum()) < k or len(recs) >= max_pools:
             break
         level, prefix, sel, bins = 0, 0, live, 1 << 14
+        first_bins = []
         while True:
             vals = digits[level][sel]
             hist = np.bincount(vals, minlength=bins)
             b0 = int(vals.min())
+            first_bins.append(int(hist[b0]))
             if hist[b0] <= room:
                 expect, b1 = 0, b0
                 while b1 < bins and expect + int(hist[b1]) <= room:
@@ -161,15 +171,24 @@ def banded(k, n, cost, p, qi, plan_buffer=0, max_pools=None):
         assert len(band) == expect, (len(band), expect)
         passes += 1
         most = max(most, expect)
-        for i in band.tolist():
+        kept_at = []
+        for at, i in enumerate(band.tolist()):
             if n - int(used.sum()) < k or len(recs) >= max_pools:
                 break
             mem = p[i, :k].tolist()
             if used[mem].any():
                 continue
             used[mem] = True
+            kept_at.append(at)
             recs.append(mem + [mem[j] for j in perms[int(qi[i])]] + [int(cost[i])])
         bands += 1
+        if trace is not None:
+            kills = []
+            for at in kept_at:
+                later = band[(at // CHUNK + 1) * CHUNK:]
+                kills.append(bool(np.isin(p[later, :k], p[band[at], :k]).any()))
+            trace.append(dict(lo=lo, hi=hi, level=level, expect=expect, first_bins=first_bins, prefix=prefix, kept=kept_at,
+                              kills_later=kills, rows=band))
         if hi == END:      # nothing lies above: no further count
             break
         lo = hi
