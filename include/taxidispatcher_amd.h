@@ -619,6 +619,14 @@ TD_API int td_sim_pools_n(td_sim *s, int max_pools, int32_t *records /* max_pool
  * while a tick waits for its apply.  The setting survives td_sim_pooling and td_sim_pooling_n and takes effect at the next
  * begin; a handle that never calls it launches exactly what it did before the call existed. */
 TD_API int td_sim_pool_buffer(td_sim *s, int64_t plan_buffer);
+/* td_simb_pool_buffer: the same for a batch of worlds.  With plan_buffer > 0 every round k = 4, 3, 2 of a tick
+ * is ONE launch of td_pool_n_banded_batched's core over the worlds instead of td_pool_n_batched's: the same records, still at
+ * most three pool launches a tick, begin is no longer TD_ERANGE for a world's number of happy plans (max_happy is not looked
+ * at; the cost limit and the 512 requests of a world stay), max_POOL_MEM_size stays the sum of the true happy counts.  0
+ * restores td_pool_n_batched's core.  TD_EINVAL, the handle unchanged: a NULL handle, a negative value, a value in
+ * 1 .. 24 * 512 - 1, a value above 2^22, a call while a tick waits for its apply.  The setting survives td_simb_pooling and
+ * td_simb_pooling_n and takes effect at the next begin; a batch that never calls it launches exactly what it did before. */
+TD_API int td_simb_pool_buffer(td_simb *s, int64_t plan_buffer);
 TD_API int td_simb_pools_n(td_simb *s, int world, int max_pools, int32_t *records /* max_pools x 9 */, int32_t *size, int32_t *n);
 
 /* ---- the dispatch policy of a world ------------------------------------------------------------------------------
@@ -806,6 +814,34 @@ TD_API int td_pool_n_batched(int k, int batch, int n, const int32_t *off,
                              const int32_t *from, const int32_t *to, const int32_t *max_wait, const int32_t *max_loss,
                              const int32_t *dist, int S, const int32_t *first /* [2*batch] or NULL */,
                              int64_t max_happy, int32_t *pools, int32_t *n_pools, int64_t *n_happy, int64_t *total);
+
+/* ---- f-4 for MANY models per call in a bounded plan slab ----------------
+ * td_pool_n_banded_batched: td_pool_n_batched's arguments, layout, staging and rules (host or device memory for every array,
+ *   batch == 0 a no-op, a refused call writes no output), with td_pool_n_banded's band loop run inside the workgroup: model
+ *   b's records, n_pools[b] and total[b] are what td_pool_n_batched writes for model b with room for every plan, n_happy[b]
+ *   is the true number of happy plans, and the call is never refused for the number of happy plans.  One launch; no host
+ *   round trip, sort call or launch per band or per model.
+ *   plan_buffer: the most plan keys a workgroup holds at once (<= 0: 65536; at most 2^22).  Plan storage is (workgroups in
+ *   flight) x plan_buffer 8-byte keys, workgroups in flight = min(1024, 1 GiB / (8 plan_buffer)), plus 128 KiB of cost
+ *   counters per workgroup in flight; grow-only, counted by td_workspace_bytes, released by td_shutdown.
+ *   stats (may be NULL): [4 * batch], model b's four numbers at 4 b as td_pool_n_banded defines them: bands, enumeration
+ *   passes in all, the deepest level a band was cut at, the most keys held in one band.  All 0 for an empty model.
+ *   TD_EINVAL, every output unwritten: td_pool_n_batched's refusals (k, batch, n, the offsets, a model larger than n, a null
+ *   required array, dist with S <= 0, a stand outside the table), plan_buffer above 2^22, and plan_buffer below 24 x the
+ *   requests of some model (the message names the first such model and both numbers).  TD_ERANGE: a happy plan's cost is
+ *   negative or above 16383.
+ *   When to use which, measured on one MI355X (host clock, host arrays): lists that fit are answered faster by
+ *   td_pool_n_batched (one walk instead of at least two): 1000 x 100: 1.08 / 1.13 / 1.71 times its time at k = 2 / 3 / 4,
+ *   64 x 256: 1.23 / 1.91 / 2.82.  64 models of 256 requests with 0.6 / 1.1 million plans each (k = 3 / 4), buffer 65 536:
+ *   1.25 / 3.82 times td_pool_n_batched(max_happy = 2^22) on its 32 workgroups, and 7.2 / 2.7 times faster than a loop of
+ *   td_pool_n_banded.  So: td_pool_n_batched while every list fits a max_happy up to 2^22; this call when some model may not
+ *   fit or the slab must stay small; td_pool_n_banded for one model.
+ */
+TD_API int td_pool_n_banded_batched(int k, int batch, int n, const int32_t *off,
+                                    const int32_t *from, const int32_t *to, const int32_t *max_wait, const int32_t *max_loss,
+                                    const int32_t *dist, int S, const int32_t *first /* [2*batch] or NULL */,
+                                    int64_t plan_buffer, int32_t *pools, int32_t *n_pools, int64_t *n_happy, int64_t *total,
+                                    int64_t *stats /* [4*batch] or NULL */);
 
 /* ---- a-7 objective evaluation  (greedy_opt.py:21-29 count_sum) ---------------------- */
 TD_API int td_count_sum(int n, const int32_t *cost, const int32_t *row_to_col, int64_t big_cost,

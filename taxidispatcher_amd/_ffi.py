@@ -108,6 +108,7 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_int32)]),
     "td_sim_pooling_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "td_sim_pool_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    "td_simb_pool_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     "td_sim_pools_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_int32)]),
     "td_simb_pooling_n": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int64]),
     "td_simb_pools_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_int32)]),
@@ -130,6 +131,8 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_int32)]),
     "td_pool_n_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int,
                                          c_i32p, ctypes.c_int64, c_i32p, c_i32p, c_i32p, c_i32p]),
+    "td_pool_n_banded_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p,
+                                                ctypes.c_int, c_i32p, ctypes.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
     "td_count_sum": (ctypes.c_int, [ctypes.c_int, c_i32p, c_i32p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
                                     ctypes.POINTER(ctypes.c_int32)]),
     "td_gen_uniform": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int,

@@ -120,6 +120,10 @@ int pool_n_worlds(int k, int batch, int n, const int32_t *off, const int32_t *cn
                   const int32_t *from, const int32_t *to, const int32_t *wait, const int32_t *loss, const int32_t *dist, int S,
                   int64_t max_happy, int32_t *pools, int32_t *n_pools, long long *n_happy, long long *total, int *over_model,
                   long long *over_count);
+// td_pool_batch.hip: the same with td_pool_n_banded_batched's kernel (plan_buffer keys per workgroup, no refusal for the plan count)
+int pool_n_worlds_banded(int k, int batch, int n, const int32_t *off, const int32_t *cnt, const int32_t *k_hi, const int32_t *k_lo,
+                         const int32_t *from, const int32_t *to, const int32_t *wait, const int32_t *loss, const int32_t *dist, int S,
+                         int64_t plan_buffer, int32_t *pools, int32_t *n_pools, long long *n_happy, long long *total);
 void prof_begin(int k);
 void prof_end(int k);
 void prof_flush();

@@ -99,6 +99,7 @@ struct SimbPoolN {
     int any3 = 0;                // some world has k_hi > 2: the apply kernels carry three partners
     std::vector<int32_t> hi, lo, wait, loss;
     int64_t max_happy = 0;
+    int64_t buffer = 0;          // td_simb_pool_buffer: > 0: every round is td_pool_n_banded_batched's core with this plan buffer
     int stride = 1, nmax = 1;    // plans per world in recs / size; the largest stage list (<= 512)
     Buf mem;
     int32_t *d_hi = nullptr, *d_lo, *d_wait, *d_loss;   // [B]
@@ -479,8 +480,12 @@ int simb_pool_n(td_simb *s, int t)
         if (!round[k]) continue;
         int over = -1, rc;
         long long count = 0;
-        rc = pool_n_worlds(k, B, nmax, s->dem_off, pn.cnt[cur], pn.d_hi, pn.d_lo, pn.st_from[cur], pn.st_to[cur], pn.d_wait, pn.d_loss, s->dist,
-                           s->dist ? s->w.n_stands : 0, pn.max_happy, pn.out, pn.np, pn.nh, pn.tot, &over, &count);
+        if (pn.buffer > 0)
+            rc = pool_n_worlds_banded(k, B, nmax, s->dem_off, pn.cnt[cur], pn.d_hi, pn.d_lo, pn.st_from[cur], pn.st_to[cur], pn.d_wait, pn.d_loss,
+                                      s->dist, s->dist ? s->w.n_stands : 0, pn.buffer, pn.out, pn.np, pn.nh, pn.tot);
+        else
+            rc = pool_n_worlds(k, B, nmax, s->dem_off, pn.cnt[cur], pn.d_hi, pn.d_lo, pn.st_from[cur], pn.st_to[cur], pn.d_wait, pn.d_loss, s->dist,
+                               s->dist ? s->w.n_stands : 0, pn.max_happy, pn.out, pn.np, pn.nh, pn.tot, &over, &count);
         if (rc == TD_ERANGE && over >= 0)
             return fail(TD_ERANGE, "td_simb_begin: world %d has %lld happy plans of %d in tick %d, more than max_happy", over, count, k, t);
         if (rc) return rc;
@@ -1059,6 +1064,18 @@ extern "C" int td_simb_pooling_n(td_simb *s, const int32_t *k_hi, const int32_t 
     pn.set = any;
     pn.any3 = any3;
     pn.max_happy = max_happy;
+    return TD_OK;
+}
+
+extern "C" int td_simb_pool_buffer(td_simb *s, int64_t plan_buffer)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (plan_buffer < 0 || (plan_buffer > 0 && plan_buffer < (int64_t)24 * SIMB_POOL_N_NMAX) || plan_buffer > ((int64_t)1 << 22))
+        return fail(TD_EINVAL, "td_simb_pool_buffer: plan_buffer = %lld: 0, or 24 * %d = %d .. %lld", (long long)plan_buffer, SIMB_POOL_N_NMAX,
+                    24 * SIMB_POOL_N_NMAX, 1ll << 22);
+    if (s->begun) return fail(TD_EINVAL, "td_simb_pool_buffer: tick %d still waits for td_simb_apply", s->last_t);
+    s->pn.buffer = plan_buffer;
     return TD_OK;
 }
 

@@ -524,14 +524,39 @@ def pool_n_batched(k, demands, distances=None, firsts=None, max_happy=0):
     return [pools[b, :int(m[b])].copy() for b in range(batch)], nh
 
 
-def find_pool_fanout(k, demand, distances=None, children=8):
+def pool_n_banded_batched(k, demands, distances=None, firsts=None, plan_buffer=0, stats=False):
+    """td_pool_n_banded_batched: pool_n_batched's arguments and answer with at most plan_buffer plan keys held per workgroup
+    (0: 65536; at least 24 * the largest model, at most 2^22), whatever a model's number of happy plans.  Returns (records per
+    model, int64[B] happy plans per model), and with stats=True a third value: int64[B, 4], per model (bands, enumeration
+    passes, the deepest level a band was cut at, the most keys of one band)."""
+    lib = _ffi.lib()
+    if not 2 <= int(k) <= 4:
+        raise _ffi.TdError("pool size %d (2..4)" % int(k))
+    off, frm, to, wait, loss, first, batch, n = pack_pool_n(demands, firsts)
+    dptr, S, keep = _dist_arg(distances)
+    per = n // int(k)
+    pools = _out((batch, per, 2 * int(k) + 1), np.int32)
+    m, nh, st = _out((batch,), np.int32), _out((batch,), np.int64), _out((batch, 4), np.int64)
+    _ffi.check(lib.td_pool_n_banded_batched(int(k), batch, n, _ffi.addr(off), _ffi.addr(frm), _ffi.addr(to), _ffi.addr(wait), _ffi.addr(loss),
+                                            dptr, S, _ffi.addr(first), int(plan_buffer), _ffi.addr(pools), _ffi.addr(m), _ffi.addr(nh), None,
+                                            _ffi.addr(st) if stats else None))
+    del keep
+    lists = [pools[b, :int(m[b])].copy() for b in range(batch)]
+    return (lists, nh, st) if stats else (lists, nh)
+
+
+def find_pool_fanout(k, demand, distances=None, children=8, plan_buffer=None):
     """findpool.c as two calls: its `children` first-pick-up slices (pool_n.c:243-246) as one batch of `children` models of
-    the same demand, then the merge (findpool.c:73-98,166-172).  Returns the merged int32 array [m, 2k+1]."""
+    the same demand, then the merge (findpool.c:73-98,166-172).  Returns the merged int32 array [m, 2k+1].  plan_buffer: the
+    children go through pool_n_banded_batched with this buffer (0: its default) instead of pool_n_batched."""
     d = np.asarray(demand).reshape(len(demand), -1)
     n = int(d.shape[0])
     step = n // children + 1
     firsts = [(step * c, min(n, step * c + step)) for c in range(children)]
-    lists, _ = pool_n_batched(k, [d] * children, distances, firsts)
+    if plan_buffer is None:
+        lists, _ = pool_n_batched(k, [d] * children, distances, firsts)
+    else:
+        lists, _ = pool_n_banded_batched(k, [d] * children, distances, firsts, plan_buffer)
     return merge_pools(k, n, lists)
 
 

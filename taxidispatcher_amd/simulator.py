@@ -93,14 +93,19 @@ def pool_n_sizes(pool_n):
 
 
 POOL_BUFFER_MIN = 24 * 2047   # td_sim_pool_buffer: the room td_pool_n_banded needs for the largest tick
+POOL_BUFFER_BATCH_MIN = 24 * 512   # td_simb_pool_buffer: a world of a batch pools at most 512 requests
+POOL_BUFFER_BATCH_MAX = 1 << 22    # ... and a workgroup's slab is at most td_pool_n_batched's largest
 
 
-def pool_buffer_size(pool_buffer):
-    """pool_buffer of a world -> an int: 0 (off) or at least 24 * 2047 (ValueError)"""
+def pool_buffer_size(pool_buffer, largest=2047, most=None):
+    """pool_buffer of a world -> an int: 0 (off) or at least 24 * largest (2047; a world of a batch: 512) and at most `most`
+    (ValueError)"""
     if isinstance(pool_buffer, bool) or not isinstance(pool_buffer, (int, np.integer)):
         raise ValueError("pool_buffer=%r: an integer" % (pool_buffer,))
-    if pool_buffer < 0 or 0 < pool_buffer < POOL_BUFFER_MIN:
-        raise ValueError("pool_buffer=%r: 0, or at least 24 * 2047 = %d" % (pool_buffer, POOL_BUFFER_MIN))
+    if pool_buffer < 0 or 0 < pool_buffer < 24 * largest:
+        raise ValueError("pool_buffer=%r: 0, or at least 24 * %d = %d" % (pool_buffer, largest, 24 * largest))
+    if most is not None and pool_buffer > most:
+        raise ValueError("pool_buffer=%r: at most %d" % (pool_buffer, most))
     return int(pool_buffer)
 
 
@@ -1047,7 +1052,10 @@ class DeviceSimulatorBatch(_DeviceEvents):
     max_loss list: every ordered pair in that world); `pools(b)` reads world b's plans of the tick last begun.
     pool_n / pool_wait / pool_loss / max_happy: pools of up to four per world (td_simb_pooling_n): a list with one entry per
     world (k, (k_hi, k_lo), or None: the world keeps its pool= policy) or one value for all; `pools_n(b)` reads world b's
-    records, `set_pool_n` changes the policies between two ticks.  A batch that logs events takes such policies with k_hi = 2 only."""
+    records, `set_pool_n` changes the policies between two ticks.  A batch that logs events takes such policies with k_hi = 2 only.
+    pool_buffer: > 0: every pool round of the pool_n worlds is td_pool_n_banded_batched's kernel with this plan buffer per
+    workgroup (td_simb_pool_buffer; 24 * 512 .. 2^22), so no tick is refused for a world's number of happy plans;
+    `set_pool_buffer` changes it between two ticks, 0 switches it off.  0: td_simb_pool_buffer is never called."""
 
     M_KEYS, CAB_KEYS, REQ_KEYS = DeviceSimulator.M_KEYS, DeviceSimulator.CAB_KEYS, DeviceSimulator.REQ_KEYS
     format_line = staticmethod(DeviceSimulator.format_line)
@@ -1056,8 +1064,9 @@ class DeviceSimulatorBatch(_DeviceEvents):
     # value for all; dispatch=None with a scalar max_non_lcm: the batch never calls td_simb_dispatch and dispatches as it always did
     def __init__(self, demand_rows_list, n_cabs_list, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None,
                  events=None, event_capacity=None, pool="greedy", max_loss=None, dispatch=None, parts=4, pool_n=None, pool_wait=0, pool_loss=0,
-                 max_happy=0):
+                 max_happy=0, pool_buffer=0):
         import ctypes
+        pool_buffer = pool_buffer_size(pool_buffer, 512, POOL_BUFFER_BATCH_MAX)
         n_cabs_list = list(n_cabs_list)
         nb = len(n_cabs_list)
         mnl_list = None
@@ -1120,6 +1129,9 @@ class DeviceSimulatorBatch(_DeviceEvents):
         self.pool_n = [None] * nb
         if pool_n is not None and not (isinstance(pool_n, list) and all(k is None for k in pool_n)):      # a default batch never calls td_simb_pooling_n
             self.set_pool_n(pool_n, pool_wait, pool_loss, max_happy)
+        self.pool_buffer = 0
+        if pool_buffer:                                   # a default batch never calls td_simb_pool_buffer
+            self.set_pool_buffer(pool_buffer)
         self.dispatch, self.max_non_lcms, self.parts = ["lcm+opt"] * nb, [self.max_non_lcm] * nb, [4] * nb
         if dispatch is not None:                          # a default batch never calls td_simb_dispatch
             self.set_dispatch(dispatch, mnl_list, parts)
@@ -1134,6 +1146,12 @@ class DeviceSimulatorBatch(_DeviceEvents):
         arrs = [np.array([dispatch_mode(d) for d in ds], np.int32), np.array(ms, np.int32), np.array(ps, np.int32)]
         self._ffi.check(self._lib.td_simb_dispatch(self._h, *[self._ffi.addr(a) for a in arrs]))
         self.dispatch, self.max_non_lcms, self.parts = ds, [int(v) for v in ms], [int(v) for v in ps]
+
+    def set_pool_buffer(self, pool_buffer):
+        """td_simb_pool_buffer: the plan buffer per workgroup of every pool round of the pool_n worlds, from the next begin on;
+        0: the rounds run as they did without it"""
+        self._ffi.check(self._lib.td_simb_pool_buffer(self._h, int(pool_buffer)))
+        self.pool_buffer = int(pool_buffer)
 
     def set_pool_n(self, pool_n, pool_wait=0, pool_loss=0, max_happy=0):
         """td_simb_pooling_n: pools of up to four per world, from the next begin on.  pool_n / pool_wait / pool_loss: a list with

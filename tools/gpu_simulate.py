@@ -24,7 +24,10 @@ path of at most W and rides at most L percent longer.  This tool runs one such w
 of such worlds: DeviceSimulatorBatch(pool_n=[...]), tools/sim_pool_n_time.py).  A tick with more than 2047 requests before pooling, or a stage with more happy plans than H,
 is refused, and the tool says which tick.
 --pool-buffer N (with --pool-n): every stage runs through td_pool_n_banded with a plan buffer of N keys (td_sim_pool_buffer /
-HipBackend(pool_buffer=N); at least 24 * 2047 = 49128): the same plans, and no tick is refused for its number of happy plans."""
+HipBackend(pool_buffer=N); at least 24 * 2047 = 49128): the same plans, and no tick is refused for its number of happy plans.
+--pool-n with --world device --cabs a,b,c: every world of the batch under that cascade (td_simb_pooling_n; a world may have at most
+512 requests before pooling in a tick), and --pool-buffer N then sets td_simb_pool_buffer (24 * 512 = 12288 .. 2^22): the pool
+rounds run through td_pool_n_banded_batched's kernel and no tick is refused for a world's number of happy plans."""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -51,7 +54,10 @@ if args.pool_buffer:
     if not args.pool_n:
         ap.error("--pool-buffer goes with --pool-n")
     try:
-        simulator.pool_buffer_size(args.pool_buffer)
+        if args.cabs and "," in args.cabs:
+            simulator.pool_buffer_size(args.pool_buffer, 512, simulator.POOL_BUFFER_BATCH_MAX)
+        else:
+            simulator.pool_buffer_size(args.pool_buffer)
     except ValueError as e:
         ap.error("--pool-buffer %d: %s" % (args.pool_buffer, e))
 if args.pool_n:
@@ -61,9 +67,9 @@ if args.pool_n:
         simulator.pool_n_rule(args.pool_wait, args.pool_loss)
     except ValueError as e:
         ap.error("--pool-n %s: %s" % (args.pool_n, e))
-    if args.cabs and "," in args.cabs:
-        ap.error("--pool-n serves one world here; for a batch see tools/sim_pool_n_time.py")
-    if args.cabs:
+    if args.cabs and "," in args.cabs and args.world != "device":
+        ap.error("--pool-n with several fleets needs --world device")
+    if args.cabs and "," not in args.cabs:
         n_cabs_1, args.cabs = dict(n_cabs=int(args.cabs)), None
 if args.cabs and args.world != "device":
     ap.error("--cabs needs --world device")
@@ -149,10 +155,20 @@ def run_logged(sim, ticks):
 if args.world == "device" and args.cabs:
     fleets = [int(v) for v in args.cabs.split(",")]
     sim = simulator.DeviceSimulatorBatch([rows] * len(fleets), fleets, dist=dist, events=True if args.events else None, pool=pools, max_loss=losses,
-                                         **policy)
+                                         **policy, **pool_n, **(dict(max_happy=args.max_happy, pool_buffer=args.pool_buffer) if pool_n else {}))
     t0 = time.time()
     if args.events:
         records, logs = run_logged(sim, 120), sim.logs
+    elif pool_n:      # tick by tick, so that a tick past the policy's limits is named when it is refused
+        logs = sim.logs
+        for t in range(120):
+            try:
+                out = sim.tick(t)
+            except td.TdError as e:
+                sys.exit("tick %d refused: %s" % (t, e))
+            for b, line in enumerate(out or []):
+                if line is not None:
+                    logs[b].append(line)
     else:
         logs = sim.run(120)
     dt = time.time() - t0
