@@ -629,6 +629,33 @@ TD_API int td_sim_pool_buffer(td_sim *s, int64_t plan_buffer);
 TD_API int td_simb_pool_buffer(td_simb *s, int64_t plan_buffer);
 TD_API int td_simb_pools_n(td_simb *s, int world, int max_pools, int32_t *records /* max_pools x 9 */, int32_t *size, int32_t *n);
 
+/* ---- the route model of a world -----------------------------------------------------------------------------------
+ * Without it a pooled cab is busy for the pool's cost through cheat_a_bit and ends at a stand nobody asked for.  With
+ * td_sim_route(s, 1) a cab that is dispatched to a customer with a pool record drives the record (the specification:
+ * Simulator(route=True)): its stops are the pick-ups in order, then the drop-offs in order, which is the path the record's
+ * cost prices.  Standing at the first pick-up it serves stop 0 at the dispatch tick and advances; otherwise it heads there as
+ * before and the arrival serves stop 0.  Advancing serves every stop at the stand just reached (a pick-up sets d_pick, a
+ * drop-off sets d_drop), then starts for the next stop's stand; with no stop left the cab is free at this stand in this tick.
+ * The route lives in the cab, so the LCM path drives a pool as the OPT path does.  Every existing metric is counted where it
+ * was.  A customer without a record behaves as before.
+ * td_sim_route: on != 0 takes effect from the next begin; the first such call allocates the route storage (8 stop words and a
+ * position per cab, the drop-off tick per request, one record column per list, four counters; td_workspace_bytes counts it,
+ * td_sim_destroy returns it) and nothing is allocated per tick.  on == 0 stops handing out routes; cabs that are mid-route
+ * finish theirs.  TD_EINVAL, nothing changed: a call while a tick waits for its apply, on != 0 on a handle without a
+ * td_sim_pooling_n policy or on a handle that logs.  While routes are on td_sim_pooling (back to pairs) is TD_EINVAL, and
+ * td_sim_log with a non-zero mask is TD_EINVAL ("not built") on any handle that has route storage.
+ * td_sim_route_state: d_drop [n_req] (-1 until dropped off), the position [n_cabs] = the stops of the cab's list already
+ * served, the stop words [8 * n_cabs]: request index * 2 + (1: drop-off, 0: pick-up), -1 behind the list; a finished list stays
+ * until the cab gets the next one.  Host or device destinations, NULL to skip.  td_sim_route_metrics: drop_numb, ride_time =
+ * the sum of d_drop - d_pick over the dropped-off members, solo_time = the sum of their direct ways, max_over_loss = the
+ * largest ride * 100 - solo * (100 + max_loss_pct) seen (INT64_MIN before the first drop-off; <= 0 iff every driven ride
+ * keeps the loss rule).  Both are TD_EINVAL on a handle that never had routes.  td_sim_state and td_sim_metrics keep their
+ * layouts.  A handle that never calls td_sim_route launches the kernels it launched before; a batch has no routes. */
+#define TD_SIM_N_ROUTE_METRICS 4
+TD_API int td_sim_route(td_sim *s, int on);
+TD_API int td_sim_route_state(td_sim *s, int32_t *r_drop, int32_t *c_pos, int32_t *c_stops /* 8 * n_cabs */);
+TD_API int td_sim_route_metrics(td_sim *s, int64_t out[TD_SIM_N_ROUTE_METRICS]);
+
 /* ---- the dispatch policy of a world ------------------------------------------------------------------------------
  * Until *_dispatch is called a world dispatches as Simulator.java:163-208 does, "the LCM down to max_non_lcm, then the
  * optimum", with the max_non_lcm it was created with, through the calls and kernels it always used.  td_sim_dispatch sets one

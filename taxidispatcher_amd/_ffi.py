@@ -108,6 +108,9 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_int32)]),
     "td_sim_pooling_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "td_sim_pool_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    "td_sim_route": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "td_sim_route_state": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p]),
+    "td_sim_route_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "td_simb_pool_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     "td_sim_pools_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_int32)]),
     "td_simb_pooling_n": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int64]),

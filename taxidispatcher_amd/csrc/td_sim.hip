@@ -47,6 +47,11 @@
 //   nb_sup[s] bit s'  <=>  dist[s][s'] < drop_time   (cab at s, a request starting at s': a ROW)
 // A line world (dist == nullptr) launches exactly what it launched before.
 //
+// The route model (td_sim_route): off by default, and then every kernel above runs in its RouteOff instantiation.
+// With routes on, the last compaction of sim_begin_pool_n and the kept-demand compaction carry the record index of a first
+// pick-up as one more column (WithRec / KeptRec), k_apply_pairs / k_apply_solution hand the dispatched cab its stop list and
+// k_arrive drives it (td_sim_core.h: route_give, route_advance); no launch is added per tick.
+//
 // The event log (td_sim_log / td_sim_events): off by default, and then every kernel above runs in its EvOff
 // instantiation and nothing else is queued.  With the log on, k_arrive, k_dem_count, k_apply_pairs and k_apply_solution write
 // their records into fixed staging slots, and the call that ends a tick queues ONE ordered flush (td_sim_world.h: k_ev_count,
@@ -74,6 +79,13 @@ struct PoolNDev {
     int32_t *out = nullptr;                          // a stage's records as the pool call writes them
     int32_t *recs = nullptr, *size = nullptr;        // the tick's plans: 9 ints each, and their sizes
     int32_t *d2_more[2], *kd_more[2];                // the third and fourth pick-up of the demand after pooling / the kept demand
+};
+
+// what td_sim_route adds to a handle, allocated by its first call with on != 0
+struct RouteDev {
+    int32_t *stops = nullptr, *pos = nullptr, *r_drop = nullptr;   // 8 stop words and a position per cab, the drop-off tick per request
+    int32_t *d2_rec = nullptr, *kd_rec = nullptr;                  // the record of each customer of the demand after pooling / the kept demand
+    long long *cnt = nullptr;                                      // drop_numb, ride_time, solo_time, max_over_loss
 };
 
 struct td_sim : SimDev, SimPin {   // td_sim_layout.h: every device array of the handle, and the pinned block
@@ -106,6 +118,12 @@ struct td_sim : SimDev, SimPin {   // td_sim_layout.h: every device array of the
     // at least one row); INT_MAX where it never does
     int lcm_rule() const { return disp_mode == TD_DISPATCH_LCM_OPT ? max_non_lcm : disp_mode == TD_DISPATCH_LCM ? -1 : INT_MAX; }
     EvLog ev;                    // td_sim_log
+    // td_sim_route: route_on: the apply kernels hand out routes from the next begin on; rt_mem.p: the handle has route
+    // storage, and k_arrive drives what is in it (cabs mid-route finish theirs after on = 0)
+    bool route_on = false;
+    RouteDev rt;
+    Buf rt_mem;
+    RouteOn route() const { return RouteOn{rt.stops, rt.pos, rt.r_drop, rt.cnt, pn_loss, pn.recs, dem_idx, rt.d2_rec, rt.kd_rec}; }
     // the host side of Simulator.m
     int64_t lcm_used = 0, max_model = 0, max_solver = 0, max_pool_mem = 0, max_pool = 0;
 };
@@ -220,6 +238,17 @@ struct Dec1 {
         *nr = solved ? n_r2c : 0;
     }
 };
+
+// the route storage's first state: no stop anywhere, nobody dropped off, the counters empty
+__global__ __launch_bounds__(256) void k_route_init(int n_cabs, int n_req, int32_t *__restrict__ stops, int32_t *__restrict__ pos,
+                                                    int32_t *__restrict__ r_drop, long long *__restrict__ cnt)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 8 * n_cabs) stops[i] = -1;
+    if (i < n_cabs) pos[i] = 0;
+    if (i < n_req) r_drop[i] = -1;
+    if (i < 4) cnt[i] = i == 3 ? INT64_MIN : 0;
+}
 
 __global__ __launch_bounds__(256) void k_init_fleet(World w)
 {
@@ -360,16 +389,16 @@ int sim_begin_pool_n(td_sim *s, int t, int32_t info[4])
     }
     s->n_pool = total;
     const Seg1 dem{n, nullptr};
+    auto pooled = [&](auto emit) {   // with routes the record of a first pick-up travels beside its columns
+        if (s->route_on) return compact(s, n, PoolPred{s->isb}, WithRec<decltype(emit)>{emit, s->ainfo, total, s->rt.d2_rec}, &s->head->n_dem2);
+        return compact(s, n, PoolPred{s->isb}, emit, &s->head->n_dem2);
+    };
     if (s->pn_hi > 2)
-        rc = compact(s, n, PoolPred{s->isb},
-                     PoolEmitN<3, Seg1>{dem, total, s->dem_idx, s->dem_from, s->ainfo, pn.recs, pn.size, s->d2_idx, s->d2_from, s->d2_partner,
-                                        s->d2_plan, s->d2_cost, {pn.d2_more[0], pn.d2_more[1]}},
-                     &s->head->n_dem2);
+        rc = pooled(PoolEmitN<3, Seg1>{dem, total, s->dem_idx, s->dem_from, s->ainfo, pn.recs, pn.size, s->d2_idx, s->d2_from, s->d2_partner,
+                                       s->d2_plan, s->d2_cost, {pn.d2_more[0], pn.d2_more[1]}});
     else
-        rc = compact(s, n, PoolPred{s->isb},
-                     PoolEmitN<1, Seg1>{dem, total, s->dem_idx, s->dem_from, s->ainfo, pn.recs, pn.size, s->d2_idx, s->d2_from, s->d2_partner,
-                                        s->d2_plan, s->d2_cost, {nullptr, nullptr}},
-                     &s->head->n_dem2);
+        rc = pooled(PoolEmitN<1, Seg1>{dem, total, s->dem_idx, s->dem_from, s->ainfo, pn.recs, pn.size, s->d2_idx, s->d2_from, s->d2_partner,
+                                       s->d2_plan, s->d2_cost, {nullptr, nullptr}});
     if (rc) return rc;
     Head h;
     if ((rc = read_head(s, &h))) return rc;
@@ -397,9 +426,11 @@ int sim_begin(td_sim *s, int t, int32_t info[4])
     const bool log = s->ev.kinds != 0;
     s->n_pool = s->n_pooled = 0;
     if (log)
-        k_arrive<<<nblocks(w.n_cabs), CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOn{s->ev.st_arr});
+        k_arrive<<<nblocks(w.n_cabs), CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOn{s->ev.st_arr}, RouteOff{});
+    else if (s->rt_mem.p)   // a handle with route storage never logs
+        k_arrive<<<nblocks(w.n_cabs), CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOff{}, s->route());
     else
-        k_arrive<<<nblocks(w.n_cabs), CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOff{});
+        k_arrive<<<nblocks(w.n_cabs), CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOff{}, RouteOff{});
     k_flags<<<nblocks(w.n_cabs), CB, shm, c.stream>>>(cabs, w.n_stands, w.c_to, w.c_clnt, s->bits, 0);
     if (s->dist) k_near_b<<<near_grid(1, words), CB, near_lds(words), c.stream>>>(1, w.n_stands, words, s->nb_dem, s->bits, s->near, 0);
     if (w.n_req > 0) {
@@ -490,6 +521,8 @@ int sim_apply(td_sim *s, int n_pairs, const int32_t *rows, const int32_t *cols, 
     const bool log = s->ev.kinds != 0;
     // pools of three or four: the partner columns behind the first travel with the apply kernels (such a handle never logs)
     const bool more = s->pn_hi > 2;
+    // routes (td_sim_route): the apply kernels hand out stop lists; only a tick that pooled by records has the record column
+    const bool route = s->route_on && s->pn_hi > 0;
     auto px3 = [&] { return MorePartners<3>{{s->pn.d2_more[0], s->pn.d2_more[1]}, {s->pn.kd_more[0], s->pn.kd_more[1]}}; };
     if (log && (rc = ev_clear_apply(s->ev, (size_t)n_s, (size_t)n_d))) return rc;
     const bool lcm = n > mnl.v;
@@ -503,43 +536,54 @@ int sim_apply(td_sim *s, int n_pairs, const int32_t *rows, const int32_t *cols, 
         TD_HIP(hipMemsetAsync(s->pair_cab, 0x7f, sizeof(int32_t) * (size_t)n_s, c.stream));
         TD_HIP(hipMemsetAsync(s->pair_dem, 0x7f, sizeof(int32_t) * (size_t)n_d, c.stream));
         if (n_pairs > 0) k_pair_map<<<(n_pairs + 255) / 256, 256, 0, c.stream>>>(dec, mnl, sup, d2, s->pair_cab, s->pair_dem, gerr);
-        auto pairs = [&](auto ev, auto px) {
+        auto pairs = [&](auto ev, auto px, auto rt) {
             k_apply_pairs<<<nblocks(n_s + n_d), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, s->pair_cab, s->pair_dem, s->sup_cab,
-                                                                 s->sup_to, s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, gerr, ev, px);
+                                                                 s->sup_to, s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, gerr, ev, px, rt);
         };
-        if (more)
-            pairs(EvOff{}, px3());
+        if (route && more)
+            pairs(EvOff{}, px3(), s->route());
+        else if (route)
+            pairs(EvOff{}, MorePartners<1>{}, s->route());
+        else if (more)
+            pairs(EvOff{}, px3(), RouteOff{});
         else if (log)
-            pairs(EvOn{s->ev.st_pairs}, MorePartners<1>{});
+            pairs(EvOn{s->ev.st_pairs}, MorePartners<1>{}, RouteOff{});
         else
-            pairs(EvOff{}, MorePartners<1>{});
+            pairs(EvOff{}, MorePartners<1>{}, RouteOff{});
         TD_HIP(hipGetLastError());
         if ((rc = compact(s, n_s, KeptPred<Seg1>{s->pair_cab, sup, d2, mnl}, KeptSupEmit{s->sup_cab, s->sup_to, s->ks_cab, s->ks_to},
                           &s->head->n_ks)))
             return rc;
         const KeptDemEmit ke{s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost};
+        auto kept = [&](auto emit) {   // with routes the record column travels to the kept demand too
+            if (route) return compact(s, n_d, KeptPred<Seg1>{s->pair_dem, sup, d2, mnl}, KeptRec<decltype(emit)>{emit, s->rt.d2_rec, s->rt.kd_rec}, &s->head->n_kd);
+            return compact(s, n_d, KeptPred<Seg1>{s->pair_dem, sup, d2, mnl}, emit, &s->head->n_kd);
+        };
         if (more)
-            rc = compact(s, n_d, KeptPred<Seg1>{s->pair_dem, sup, d2, mnl},
-                         KeptDemEmitN<3>{ke, {s->pn.d2_more[0], s->pn.d2_more[1]}, {s->pn.kd_more[0], s->pn.kd_more[1]}}, &s->head->n_kd);
+            rc = kept(KeptDemEmitN<3>{ke, {s->pn.d2_more[0], s->pn.d2_more[1]}, {s->pn.kd_more[0], s->pn.kd_more[1]}});
         else
-            rc = compact(s, n_d, KeptPred<Seg1>{s->pair_dem, sup, d2, mnl}, ke, &s->head->n_kd);
+            rc = kept(ke);
         if (rc) return rc;
     }
     if (!lcm || solved) {
         if ((rc = put(s->in_r2c, r2c, (size_t)nr))) return rc;
         // the kernel takes the kept lists where the LCM ran (their sizes are on the device), else the whole model
         const Seg1 ks{0, &s->head->n_ks}, kd{0, &s->head->n_kd};
-        auto solution = [&](auto ev, auto px) {
+        auto solution = [&](auto ev, auto px, auto rt) {
             k_apply_solution<<<nblocks(n_s), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, ks, kd, s->sup_cab, s->sup_to, s->d2_idx, s->d2_from,
                                                               s->d2_partner, s->d2_plan, s->d2_cost, s->ks_cab, s->ks_to, s->kd_idx, s->kd_from,
-                                                              s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, gerr, ev, px);
+                                                              s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, gerr, ev, px, rt);
         };
-        if (more)
-            solution(EvOff{}, px3());
+        if (route && more)
+            solution(EvOff{}, px3(), s->route());
+        else if (route)
+            solution(EvOff{}, MorePartners<1>{}, s->route());
+        else if (more)
+            solution(EvOff{}, px3(), RouteOff{});
         else if (log)
-            solution(EvOn{s->ev.st_sol}, MorePartners<1>{});
+            solution(EvOn{s->ev.st_sol}, MorePartners<1>{}, RouteOff{});
         else
-            solution(EvOff{}, MorePartners<1>{});
+            solution(EvOff{}, MorePartners<1>{}, RouteOff{});
         TD_HIP(hipGetLastError());
     }
     Head h;
@@ -650,6 +694,7 @@ extern "C" int td_sim_destroy(td_sim *s)
     if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
     buf_free(s->mem);
     buf_free(s->pn_mem);
+    buf_free(s->rt_mem);
     ev_off(s->ev);
     if (s->pin) (void)hipHostFree(s->pin);
     delete s;
@@ -673,6 +718,7 @@ extern "C" int td_sim_pooling(td_sim *s, int mode, double max_loss)
     if (mode < TD_POOL_NONE || mode > TD_POOL_OPTIMAL) return fail(TD_EINVAL, "td_sim_pooling: mode = %d outside 0 .. 2", mode);
     if (max_loss != max_loss) return fail(TD_EINVAL, "td_sim_pooling: max_loss is not a number");
     if (s->begun) return fail(TD_EINVAL, "td_sim_pooling: tick %d still waits for td_sim_apply", s->last_t);
+    if (s->route_on) return fail(TD_EINVAL, "td_sim_pooling: routes are on (td_sim_route) and pairs have no drop-off order to drive; switch them off first");
     s->pool_mode = mode;
     s->max_loss = max_loss;
     s->pn_hi = s->pn_lo = 0;   // back on a pair policy
@@ -877,6 +923,7 @@ extern "C" int td_sim_log(td_sim *s, uint32_t kinds, int64_t capacity)
     if (s->begun) return fail(TD_EINVAL, "td_sim_log: tick %d still waits for td_sim_apply", s->last_t);
     if (kinds && s->pn_hi > 2)
         return fail(TD_EINVAL, "td_sim_log: not built: the event log of pools of three and four (td_sim_pooling_n with k_hi = %d)", s->pn_hi);
+    if (kinds && s->rt_mem.p) return fail(TD_EINVAL, "td_sim_log: not built: the event log of routed worlds (the handle has routes, td_sim_route)");
     const size_t nc = (size_t)s->w.n_cabs, nr = (size_t)s->w.n_req;
     return ev_setup(s->ev, kinds, capacity, 1, nc, nr, nc + nr + 2 + nr + nr / 2 + 2 * (nc + nr) + 2 * nc);
 }
@@ -892,4 +939,67 @@ extern "C" int td_sim_events(td_sim *s, int64_t max_records, int32_t *records, i
         s->ev.begin_flushed = true;
     }
     return ev_drain(s->ev, "td_sim_events", max_records, records, n, lost);
+}
+
+extern "C" int td_sim_route(td_sim *s, int on)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (s->begun) return fail(TD_EINVAL, "td_sim_route: tick %d still waits for td_sim_apply", s->last_t);
+    if (!on) {   // no new routes; the cabs that are mid-route finish theirs
+        s->route_on = false;
+        return TD_OK;
+    }
+    if (!s->pn_hi) return fail(TD_EINVAL, "td_sim_route: the world pools pairs, which have no drop-off order to drive; set a td_sim_pooling_n policy first");
+    if (s->ev.kinds) return fail(TD_EINVAL, "td_sim_route: not built: the event log of routed worlds (the handle logs)");
+    if (!s->rt_mem.p) {   // the handle's, from the first call on: nothing is allocated per tick
+        Ctx &c = ctx();
+        const size_t nc = (size_t)s->w.n_cabs, nr = (size_t)std::max(s->w.n_req, 1), cap = (size_t)s->cap;
+        RouteDev d;
+        int rc = carve_buf(s->rt_mem, [&](Carve &cv) {
+            d.stops = (int32_t *)cv.take<int4>(2 * nc);   // a cab's eight words are two 16-byte vectors
+            d.cnt = cv.take<long long>(4);
+            d.pos = cv.take<int32_t>(nc);
+            d.r_drop = cv.take<int32_t>(nr);
+            d.d2_rec = cv.take<int32_t>(cap);
+            d.kd_rec = cv.take<int32_t>(cap);
+        });
+        if (rc) return rc;
+        s->rt = d;
+        const int n = (int)std::max<size_t>(std::max(8 * nc, nr), 4);   // the four counters are the first four threads'
+        k_route_init<<<(n + 255) / 256, 256, 0, c.stream>>>(s->w.n_cabs, s->w.n_req, d.stops, d.pos, d.r_drop, d.cnt);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            buf_free(s->rt_mem);
+            s->rt = RouteDev();
+            return hip_fail(e, "td_sim_route launch");
+        }
+    }
+    s->route_on = true;
+    return TD_OK;
+}
+
+extern "C" int td_sim_route_state(td_sim *s, int32_t *r_drop, int32_t *c_pos, int32_t *c_stops)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (!s->rt_mem.p) return fail(TD_EINVAL, "td_sim_route_state: the handle has no routes (td_sim_route)");
+    int rc;
+    if ((rc = get(r_drop, s->rt.r_drop, (size_t)s->w.n_req)) || (rc = get(c_pos, s->rt.pos, (size_t)s->w.n_cabs)) ||
+        (rc = get(c_stops, s->rt.stops, (size_t)8 * s->w.n_cabs)))
+        return rc;
+    TD_HIP(hipStreamSynchronize(ctx().stream));
+    return TD_OK;
+}
+
+extern "C" int td_sim_route_metrics(td_sim *s, int64_t out[TD_SIM_N_ROUTE_METRICS])
+{
+    TD_REQUIRE_INIT();
+    if (!s || !out) return fail(TD_EINVAL, "null argument");
+    if (!s->rt_mem.p) return fail(TD_EINVAL, "td_sim_route_metrics: the handle has no routes (td_sim_route)");
+    static_assert(sizeof(long long) == sizeof(int64_t), "the counters are read back as they lie");
+    TD_HIP(hipMemcpyAsync(s->pin, s->rt.cnt, sizeof(int64_t) * TD_SIM_N_ROUTE_METRICS, hipMemcpyDeviceToHost, ctx().stream));
+    TD_HIP(hipStreamSynchronize(ctx().stream));
+    for (int q = 0; q < TD_SIM_N_ROUTE_METRICS; q++) out[q] = ((const int64_t *)s->pin)[q];
+    return TD_OK;
 }

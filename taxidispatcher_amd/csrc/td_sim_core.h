@@ -54,6 +54,28 @@ struct EvOn {
     }
 };
 
+// ---- the route model (td_sim_route).  A routed cab drives its pool's plan: 8 stop words per cab, a stop word
+// = request index * 2 + (1: drop-off, 0: pick-up), -1 = no stop, and the position of the next stop to serve.  The rules take
+// the route as a template parameter the way they take the event log's emitter: RouteOff is empty and compiles to nothing (the
+// instantiation of every handle that never asked for routes, and of every batch), RouteOn holds the handle's route storage.
+struct RouteOff {
+    static constexpr bool on = false;
+    struct Acc {};
+};
+struct RouteAcc {   // what one thread's served drop-offs add to the route counters
+    long long drops = 0, ride = 0, solo = 0, over = INT64_MIN;
+};
+struct RouteOn {
+    static constexpr bool on = true;
+    using Acc = RouteAcc;
+    int32_t *stops, *pos, *r_drop;   // [8 n_cabs], [n_cabs], [n_req]
+    long long *cnt;                  // drop_numb, ride_time, solo_time, max_over_loss
+    int loss;                        // the policy's max_loss_pct
+    // what a dispatching thread builds a stop list from: the tick's 9-int records, the tick's demand list (a record's members
+    // are positions in it), and the record of each customer of the demand after pooling / of the kept demand (-1: none)
+    const int32_t *recs, *dem_idx, *d_rec, *kd_rec;
+};
+
 // Simulator.java:469-474
 __host__ __device__ inline int cheat_a_bit(int frm, int cost, int n_stands)
 {
@@ -111,12 +133,90 @@ static __global__ __launch_bounds__(256) void k_nb_build(int n_stands, int words
     if (bad) atomicMax(err, 3);
 }
 
+// Simulator._advance: cab c has just reached stand `cur` at tick t with the stop words s[8] and `pos` stops served.  Every stop
+// at this stand is served now (a zero-length leg); then the cab starts for the next stop's stand, or, with none left, is free
+// here in this tick.  The loop is unrolled over the eight words, which stay in registers; `go` ends it at the first stop elsewhere.
+__device__ __forceinline__ void route_advance(const World &w, const RouteOn &rt, int t, int c, int cur, const int (&s)[8], int pos, RouteAcc &acc)
+{
+    bool go = true;
+    int next = -1;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        if (go && i >= pos) {
+            const int wd = s[i];
+            if (wd < 0) {
+                go = false;
+            } else {
+                const int req = wd >> 1, drop = wd & 1;
+                const int st = drop ? w.r_to[req] : w.r_from[req];
+                if (st != cur) {
+                    next = st;
+                    go = false;
+                } else if (drop) {
+                    const long long ride = t - w.r_pick[req], solo = way(w, w.r_from[req], st);
+                    const long long over = ride * 100 - solo * (100 + rt.loss);
+                    rt.r_drop[req] = t;
+                    acc.drops++;
+                    acc.ride += ride;
+                    acc.solo += solo;
+                    acc.over = over > acc.over ? over : acc.over;
+                    pos = i + 1;
+                } else {
+                    w.r_pick[req] = t;
+                    pos = i + 1;
+                }
+            }
+        }
+    }
+    rt.pos[c] = pos;
+    w.c_from[c] = cur;
+    if (next >= 0) {
+        w.c_to[c] = next;
+        w.c_onb[c] = 1;
+        w.c_start[c] = t;
+    } else {   // today's "cab is free" state
+        w.c_to[c] = cur;
+        w.c_clnt[c] = -1;
+        w.c_onb[c] = 0;
+        w.c_start[c] = -1;
+    }
+}
+
+// the stop words of record `rec` into s and into the cab's list (two 16-byte stores): the path pn_check prices, the pick-ups in
+// order, then the drop-offs in order (k of each in the record, -1 behind them; members are positions in the tick's demand list)
+__device__ __forceinline__ void route_give(const RouteOn &rt, int cab, int rec, int (&s)[8])
+{
+    const int32_t *r = rt.recs + (size_t)9 * rec;
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) k += r[i] >= 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) s[i] = i < k ? 2 * rt.dem_idx[r[i]] : i < 2 * k ? 2 * rt.dem_idx[r[4 + i - k]] + 1 : -1;
+    ((int4 *)rt.stops)[2 * (size_t)cab] = make_int4(s[0], s[1], s[2], s[3]);
+    ((int4 *)rt.stops)[2 * (size_t)cab + 1] = make_int4(s[4], s[5], s[6], s[7]);
+}
+
+// the cab's stop words in registers (two 16-byte loads); true when a stop is left at its position
+__device__ __forceinline__ bool route_load(const RouteOn &rt, int c, int (&s)[8], int *pos)
+{
+    const int4 a = ((const int4 *)rt.stops)[2 * (size_t)c], b = ((const int4 *)rt.stops)[2 * (size_t)c + 1];
+    s[0] = a.x, s[1] = a.y, s[2] = a.z, s[3] = a.w, s[4] = b.x, s[5] = b.y, s[6] = b.z, s[7] = b.w;
+    const int p = rt.pos[c];
+    *pos = p;
+    int at = -1;
+#pragma unroll
+    for (int i = 0; i < 8; i++) at = i == p ? s[i] : at;
+    return at >= 0;
+}
+
 // Simulator.java:220-254 for ONE cab; returns 1 when a passenger was picked up.  c = the cab's row in the fleet table,
 // cab_no = the number the request table stores for it (the same thing in one world; world-local in a batch of worlds).
 // The cab's record (:233 picked up, :251 free, or none) goes to `slot` of ev: every cab writes its slot in every tick.
-template <class EV>
-__device__ inline int arrive_as(const World &w, int t, int c, int cab_no, const EV &ev, int slot)
+// rt: RouteOff, or RouteOn: a cab with stops left serves the stop it has reached and advances (acc: its drop-offs' counters)
+template <class EV, class R>
+__device__ inline int arrive_as(const World &w, int t, int c, int cab_no, const EV &ev, int slot, const R &rt, typename R::Acc &acc)
 {
+    static_assert(!(EV::on && R::on), "the event log of routed worlds is not built");
     const int f = w.c_from[c], to = w.c_to[c];
     ev.put(slot, 0, 0, -1, -1, -1);
     if (f == to || way(w, f, to) != t - w.c_start[c]) return 0;
@@ -125,12 +225,26 @@ __device__ inline int arrive_as(const World &w, int t, int c, int cab_no, const 
         if (d < 0) return 0;
         if constexpr (EV::on) ev.put(slot, TD_EV_PICKED_UP, 0, w.r_id[d], cab_no, -1);
         w.r_cab[d] = cab_no;
+        if constexpr (R::on) {
+            int s[8], pos;
+            if (route_load(rt, c, s, &pos)) {   // the arrival serves stop 0 and advances; the pool info of the table is not looked at
+                route_advance(w, rt, t, c, to, s, pos, acc);
+                return 1;
+            }
+        }
         w.r_pick[d] = t;
         w.c_from[c] = w.r_from[d];
         w.c_to[c] = w.r_pid[d] == -1 ? w.r_to[d] : cheat_a_bit(w.r_from[d], w.r_pcost[d], w.n_stands);
         w.c_onb[c] = 1;
         w.c_start[c] = t;
         return 1;
+    }
+    if constexpr (R::on) {
+        int s[8], pos;
+        if (route_load(rt, c, s, &pos)) {
+            route_advance(w, rt, t, c, to, s, pos, acc);
+            return 0;
+        }
     }
     w.c_from[c] = to;
     w.c_clnt[c] = -1;
@@ -142,18 +256,31 @@ __device__ inline int arrive_as(const World &w, int t, int c, int cab_no, const 
 
 // Simulator.java:424-490 _dispatch for cab `cab` (standing at sup_to) and the customer (request idx, pool partner / cost).
 // The record (:448-465 or :486-487, with `method`) goes to `slot` of ev; cab_no is the cab's number as the log prints it.
-template <class EV>
+// rt / rec / acc: RouteOff, or RouteOn and the customer's record (-1: none, the customer behaves as without routes): the cab
+// receives the record's stop list; standing at the first pick-up it serves stop 0 now and advances, cheat_a_bit is not called
+template <class EV, class R>
 __device__ __forceinline__ void dispatch(const World &w, int t, int cab, int sup_to, int idx, int partner, int pcost, int &numb, int &ptime,
-                                         const EV &ev, int slot, int method, int cab_no)
+                                         const EV &ev, int slot, int method, int cab_no, const R &rt, int rec, typename R::Acc &acc)
 {
     const int cf = w.r_from[idx];
     int dn = 0, dp = 0;   // added to the counters once, below: no store through either reference inside a branch
+    bool routed = false;
+    if constexpr (R::on) routed = rec >= 0;
     if (sup_to == cf) {   // assignToCabAndGo
-        w.c_from[cab] = cf;
-        w.c_to[cab] = partner == -1 ? w.r_to[idx] : cheat_a_bit(cf, pcost, w.n_stands);
-        w.c_clnt[cab] = idx;
-        w.c_onb[cab] = 1;
-        w.c_start[cab] = t;
+        if (routed) {
+            if constexpr (R::on) {
+                int s[8];
+                route_give(rt, cab, rec, s);
+                w.c_clnt[cab] = idx;
+                route_advance(w, rt, t, cab, cf, s, 0, acc);
+            }
+        } else {
+            w.c_from[cab] = cf;
+            w.c_to[cab] = partner == -1 ? w.r_to[idx] : cheat_a_bit(cf, pcost, w.n_stands);
+            w.c_clnt[cab] = idx;
+            w.c_onb[cab] = 1;
+            w.c_start[cab] = t;
+        }
         dn = 1;
         if constexpr (EV::on) ev.put(slot, TD_EV_ASSIGNED_PICKED, method, w.r_id[idx], cab_no, partner == -1 ? -1 : w.r_id[partner]);
     } else if (way(w, sup_to, cf) < w.drop_time) {   // goToPickup
@@ -162,6 +289,13 @@ __device__ __forceinline__ void dispatch(const World &w, int t, int cab, int sup
         w.c_onb[cab] = 0;
         w.c_start[cab] = t;
         dp = way(w, w.c_from[cab], cf);
+        if constexpr (R::on) {
+            if (routed) {   // the arrival serves stop 0
+                int s[8];
+                route_give(rt, cab, rec, s);
+                rt.pos[cab] = 0;
+            }
+        }
         if constexpr (EV::on) ev.put(slot, TD_EV_HEADING, method, w.r_id[idx], cab_no, -1);
     }
     numb += dn;

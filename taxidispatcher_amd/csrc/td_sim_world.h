@@ -52,6 +52,35 @@ __device__ __forceinline__ T block_sum(T v, T *s_red)
     return tot;
 }
 
+// the route counters of a launch (td_sim_route): what the workgroup's threads served, one atomic per counter and workgroup.
+// RouteOff: nothing, and no LDS.  Every thread of the workgroup calls it.
+template <class R>
+__device__ __forceinline__ void route_flush(const R &rt, const typename R::Acc &acc)
+{
+    if constexpr (R::on) {
+        __shared__ long long s_rt[16];
+        const long long nd = block_sum(acc.drops, s_rt);
+        if (nd == 0) return;   // the same for the whole workgroup
+        const long long ride = block_sum(acc.ride, s_rt), solo = block_sum(acc.solo, s_rt);
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+        long long over = acc.over;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const long long u = __shfl_down(over, o);
+            over = u > over ? u : over;
+        }
+        if (lane == 0) s_rt[wv] = over;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int q = 1; q < nw; q++) over = s_rt[q] > over ? s_rt[q] : over;
+            atomicAdd((unsigned long long *)&rt.cnt[0], (unsigned long long)nd);
+            atomicAdd((unsigned long long *)&rt.cnt[1], (unsigned long long)ride);
+            atomicAdd((unsigned long long *)&rt.cnt[2], (unsigned long long)solo);
+            atomicMax(&rt.cnt[3], over);
+        }
+    }
+}
+
 // rank of this thread among the flagged threads of the workgroup (ascending thread order), *tot = how many
 __device__ __forceinline__ int block_rank(bool f, int *s_w, int *tot)
 {
@@ -126,14 +155,17 @@ struct SegOff {
 };
 
 // ev: the event log's emitter (td_sim_core.h): EvOff, or EvOn on the arrival stage, slot = the cab's row
-template <class S, class EV>
-__global__ __launch_bounds__(CB) void k_arrive(World w, S cabs, int t, Ctl *ctl, EV ev)
+// rt: the route model (td_sim_core.h): RouteOff, or RouteOn of a handle that has route storage
+template <class S, class EV, class R>
+__global__ __launch_bounds__(CB) void k_arrive(World w, S cabs, int t, Ctl *ctl, EV ev, R rt)
 {
     __shared__ int s_red[16];
     const int b = blockIdx.y, l = blockIdx.x * CB + threadIdx.x;
     int lo, n;
     cabs(b, &lo, &n);
-    const int got = l < n ? arrive_as(w, t, lo + l, l, ev, lo + l) : 0;
+    typename R::Acc acc;
+    const int got = l < n ? arrive_as(w, t, lo + l, l, ev, lo + l, rt, acc) : 0;
+    route_flush(rt, acc);
     const int tot = block_sum(got, s_red);
     if (threadIdx.x == 0) {
         if (blockIdx.x == 0) ctl[b].opt_count = 0;   // this tick's OPT count starts from zero
@@ -324,6 +356,35 @@ struct PoolEmitN {
     }
 };
 
+// ---- the route model (td_sim_route): the record of a first pick-up travels as one more column beside whatever the emitter E
+// writes, the way MorePartners carries the partner columns; the dispatching thread builds the stop list from the record.
+// (The record index and not the stops: one word per customer and list instead of eight, and the tick's records stay where
+// k_pool_records left them until the apply.)  Handles without routes keep their emitters, and so their kernels, as they are.
+template <class E>
+struct WithRec {   // the demand after pooling
+    E e;
+    const int32_t *ainfo;
+    int n_rec;
+    int32_t *rec;
+    __device__ void operator()(int o, int o2, int d, int b) const
+    {
+        e(o, o2, d, b);
+        const int p = ainfo[d];
+        rec[o] = p >= 0 && p < n_rec ? p : -1;
+    }
+};
+template <class E>
+struct KeptRec {   // the kept demand
+    E e;
+    const int32_t *rec;
+    int32_t *rec2;
+    __device__ void operator()(int o, int o2, int d, int b) const
+    {
+        e(o, o2, d, b);
+        rec2[o] = rec[d];
+    }
+};
+
 // the cabs / requests of an LCM world that are in no pair (analyzePairs' supply2 / demand2)
 template <class S, class L = LcmRule1>
 struct KeptPred {
@@ -460,13 +521,14 @@ __global__ __launch_bounds__(256) void k_pair_map(D dec, L max_non_lcm, S sup, S
 // ev: EvOff, or EvOn on the pairs stage (cleared by the host before the launch): thread l of world b owns slots
 // 2 (s0 + d0 + l) and + 1, so the cab loop's records precede the request loop's and :654 precedes the same request's :432.
 // px: the partner columns behind the first (NP = 3: a world of td_*_pooling_n with pools of three or four, never logged)
-template <class D, class S, class EV, class L, int NP>
+// rt: RouteOff, or RouteOn: the cab loop hands a pooled customer's cab its stop list
+template <class D, class S, class EV, class L, int NP, class R>
 __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, L max_non_lcm, S cabs, S sup, S d2,
                                                     const int32_t *__restrict__ pair_cab, const int32_t *__restrict__ pair_dem,
                                                     const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
                                                     const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_partner,
                                                     const int32_t *__restrict__ d_cost, Ctl *ctl, const int32_t *gerr, EV ev,
-                                                    MorePartners<NP> px)
+                                                    MorePartners<NP> px, R rt)
 {
     static_assert(NP == 1 || !EV::on, "the apply stages own two staging slots per thread: a pool of four needs four");
     __shared__ int s_red[16];
@@ -482,17 +544,23 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, L max
     const int l = blockIdx.x * CB + threadIdx.x;
     const int slot = 2 * (s0 + d0 + l);
     int numb = 0, ptime = 0, second = 0;
+    typename R::Acc acc;
     if (l < n_s) {
         const int p = pair_cab[s0 + l];
         if (p != NONE) {
             const int d = d0 + dec.cols[base + p];
-            dispatch(w, t, sup_cab[s0 + l], sup_to[s0 + l], d_idx[d], d_partner[d], d_cost[d], numb, ptime, ev, slot, EV_LCM, sup_cab[s0 + l] - c0);
+            int rec = -1;
+            if constexpr (R::on) rec = rt.d_rec[d];
+            dispatch(w, t, sup_cab[s0 + l], sup_to[s0 + l], d_idx[d], d_partner[d], d_cost[d], numb, ptime, ev, slot, EV_LCM, sup_cab[s0 + l] - c0, rt,
+                     rec, acc);
         }
     } else if (l < n_s + n_d) {
         const int d = d0 + l - n_s, p = pair_dem[d];
         if (p != NONE) {   // the request side is not guarded by the distance
             const int cab = sup_cab[s0 + dec.rows[base + p]] - c0, idx = d_idx[d];
             w.r_cab[idx] = cab;
+            // with routes the cab loop's thread of a standing cab stores r_pick[idx] too (route_advance serves stop 0 = this request
+            // at t): two threads, one value.  A change that makes the two values differ has to order the two stores
             w.r_pick[idx] = t;
             if constexpr (EV::on) ev.put(slot, TD_EV_ASSIGNED_LCM, 0, w.r_id[idx], cab, -1);
             if (d_partner[d] > -1) {
@@ -514,6 +582,7 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, L max
             }
         }
     }
+    route_flush(rt, acc);
     const int tn = block_sum(numb, s_red), tp = block_sum(ptime, s_red), ts = block_sum(second, s_red);
     if (threadIdx.x == 0) {
         if (tn) atomicAdd((unsigned long long *)&ctl[b].pickup_numb, (unsigned long long)tn);
@@ -527,7 +596,8 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, L max
 // cabs and the lists are copies), so that test is not repeated.
 // ev: EvOff, or EvOn on the solution stage (cleared by the host before the launch): cab l of world b's model owns slots
 // 2 (s0 + l) and + 1 with s0 = where the world's SUPPLY list begins (a kept list is no longer): :432 first, then :448 / :486.
-template <class D, class S, class EV, class L, int NP>
+// rt: RouteOff, or RouteOn, as k_apply_pairs takes it
+template <class D, class S, class EV, class L, int NP, class R>
 __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, L max_non_lcm, S cabs, S sup, S d2, S ks, S kd,
                                                        const int32_t *__restrict__ sup_cab, const int32_t *__restrict__ sup_to,
                                                        const int32_t *__restrict__ d_idx, const int32_t *__restrict__ d_from,
@@ -536,7 +606,7 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, L 
                                                        const int32_t *__restrict__ ks_to, const int32_t *__restrict__ kd_idx,
                                                        const int32_t *__restrict__ kd_from, const int32_t *__restrict__ kd_partner,
                                                        const int32_t *__restrict__ kd_plan, const int32_t *__restrict__ kd_cost, Ctl *ctl,
-                                                       const int32_t *gerr, EV ev, MorePartners<NP> px)
+                                                       const int32_t *gerr, EV ev, MorePartners<NP> px, R rt)
 {
     static_assert(NP == 1 || !EV::on, "the apply stages own two staging slots per thread: a pool of four needs four");
     __shared__ int s_red[16];
@@ -561,6 +631,7 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, L 
     const int32_t *l_partner = lcm ? kd_partner : d_partner, *l_plan = lcm ? kd_plan : d_plan, *l_cost = lcm ? kd_cost : d_cost;
     const int l = blockIdx.x * CB + threadIdx.x;
     int count = 0, numb = 0, ptime = 0, second = 0;
+    typename R::Acc acc;
     if (l < n_s) {
         const int s = s0 + l;
         const int c = l < nr ? dec.r2c[rb + l] : -1;
@@ -593,10 +664,13 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, L 
                         }
                     }
                 }
-                dispatch(w, t, cab, l_to[s], idx, partner, l_cost[e], numb, ptime, ev, slot0 + 2 * l + 1, EV_OPT, cab - c0);
+                int rec = -1;
+                if constexpr (R::on) rec = (lcm ? rt.kd_rec : rt.d_rec)[e];
+                dispatch(w, t, cab, l_to[s], idx, partner, l_cost[e], numb, ptime, ev, slot0 + 2 * l + 1, EV_OPT, cab - c0, rt, rec, acc);
             }
         }
     }
+    route_flush(rt, acc);
     const int tc = block_sum(count, s_red), tn = block_sum(numb, s_red), tp = block_sum(ptime, s_red), ts = block_sum(second, s_red);
     if (threadIdx.x == 0) {
         if (tc) atomicAdd(&ctl[b].opt_count, tc);

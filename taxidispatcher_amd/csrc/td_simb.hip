@@ -516,9 +516,9 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     const SegOff cabs{s->d_cab_off}, reqs{s->d_req_off};
     const bool log = s->ev.kinds != 0;
     if (log)
-        k_arrive<<<grid_c, CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOn{s->ev.st_arr});
+        k_arrive<<<grid_c, CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOn{s->ev.st_arr}, RouteOff{});
     else
-        k_arrive<<<grid_c, CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOff{});
+        k_arrive<<<grid_c, CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOff{}, RouteOff{});
     k_flags<<<grid_c, CB, shm, c.stream>>>(cabs, w.n_stands, w.c_to, w.c_clnt, s->bits, 0);
     const dim3 grid_n = near_grid(B, s->words);
     const size_t shm_n = near_lds(s->words);
@@ -716,7 +716,7 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
             k_pair_map<<<dim3((max_pairs + 255) / 256, B), 256, 0, c.stream>>>(dec, mnl, sup, d2, s->pair_cab, s->pair_dem, s->gerr);
         auto pairs = [&](auto ev, auto px) {
             k_apply_pairs<<<dim3(nchunks(max_sd), B), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, s->pair_cab, s->pair_dem, s->sup_cab, s->sup_to,
-                                                                       s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, s->gerr, ev, px);
+                                                                       s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, s->gerr, ev, px, RouteOff{});
         };
         if (more)
             pairs(EvOff{}, px3);
@@ -742,7 +742,7 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
         k_apply_solution<<<dim3(nchunks(max_s), B), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, SegOff{s->ks_off}, SegOff{s->kd_off}, s->sup_cab,
                                                                      s->sup_to, s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->ks_cab,
                                                                      s->ks_to, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, s->gerr,
-                                                                     ev, px);
+                                                                     ev, px, RouteOff{});
     };
     if (any_sup && more)
         solution(EvOff{}, px3);

@@ -92,6 +92,7 @@ def pool_n_sizes(pool_n):
     return hi, lo
 
 
+ROUTE_NONE_SEEN = -(1 << 63)  # route_m["max_over_loss"] before the first drop-off (td_sim_route_metrics: INT64_MIN)
 POOL_BUFFER_MIN = 24 * 2047   # td_sim_pool_buffer: the room td_pool_n_banded needs for the largest tick
 POOL_BUFFER_BATCH_MIN = 24 * 512   # td_simb_pool_buffer: a world of a batch pools at most 512 requests
 POOL_BUFFER_BATCH_MAX = 1 << 22    # ... and a workgroup's slab is at most td_pool_n_batched's largest
@@ -265,13 +266,29 @@ class Simulator:
     size, d_pool_cost = the cost, on the first pick-up's row.  The cab stays busy for the cost through cheat_a_bit, as with a
     pair; there is no route model.  max_POOL_size: the most pools of a tick, all stages together; max_POOL_MEM_size: the most
     happy plans before de-duplication of a tick, summed over its stages.  Events: EV_POOL carries the total, one EV_POOL_PAIR
-    (customer = the first pick-up, aux = the member) and one EV_POOLED_SECOND per other member."""
+    (customer = the first pick-up, aux = the member) and one EV_POOLED_SECOND per other member.
+    route: the route model, the specification of td_sim_route.  False: nothing above changes.  True (needs pool_n; with events:
+    ValueError "not built"): a cab dispatched to a customer with a pool record drives the record instead of cheat_a_bit.  Its
+    stops are from[p0], .., from[p(k-1)] (picks), to[q0], .., to[q(k-1)] (drops), the path the record's cost prices; c_stops[c]
+    holds them as words request index * 2 + (1: drop), -1 behind the list, c_pos[c] counts the stops served.  The route lives
+    in the cab and not in the request table, so it is driven on the LCM path as on the OPT path (the reference's asymmetry
+    for pool info does not apply to it).  _assign_to_cab_and_go serves stop 0 at t and advances; _go_to_pickup heads to
+    from[p0] as before, and the arrival serves stop 0 and advances.  _advance at tick t from the stand just reached: while the
+    next stop is at this stand, serve it (a pick sets d_pick[member] = t, a drop d_drop[member] = t: zero-length legs); with a
+    stop left the cab starts for its stand (c_from = here, c_to = there, c_start = t, on board), with none it is free here in
+    this tick.  Every existing metric is counted where it is counted without routes.  route_m: drop_numb, ride_time = the sum
+    of d_drop - d_pick over the dropped-off members, solo_time = the sum of their direct ways, max_over_loss = the largest
+    ride * 100 - solo * (100 + pool_loss) seen (ROUTE_NONE_SEEN before the first drop): <= 0 iff every driven ride keeps the loss
+    rule."""
 
     def __init__(self, demand_rows, backend=None, n_cabs=N_CABS, on_solver_instance=None, dist=None, events=False, pool="greedy",
-                 max_loss=None, dispatch="lcm+opt", max_non_lcm=None, parts=4, pool_n=None, pool_wait=0, pool_loss=0):
+                 max_loss=None, dispatch="lcm+opt", max_non_lcm=None, parts=4, pool_n=None, pool_wait=0, pool_loss=0, route=False):
         pool_mode(pool)
         self.pool_n = pool_n_sizes(pool_n)
         self.pool_wait, self.pool_loss = pool_n_rule(pool_wait, pool_loss)
+        self.route = False       # set_route: routes are handed out
+        self._has_routes = False # the world has route state (from the first set_route(True) on): cabs mid-route finish theirs
+        self._routes = {}        # route: the first pick-up's id -> (the stop words of its record, the record's cost), of this tick
         self._others = {}        # pool_n: the first pick-up's id -> the ids of the pool's other members, of this tick
         dispatch_mode(dispatch)
         if max_non_lcm is not None and int(max_non_lcm) < 0:
@@ -305,6 +322,73 @@ class Simulator:
                       max_model_size=0, max_solver_size=0, max_POOL_MEM_size=0, max_POOL_size=0,
                       total_second_passengers=0)
         self.log = []
+        if route:
+            self.set_route(True)
+
+    # ---- the route model (route=True)
+    def set_route(self, on):
+        """td_sim_route between two ticks: True hands routes out from the next tick on (the first time makes the route state),
+        False stops handing them out; cabs that are mid-route finish theirs"""
+        if on and self.pool_n is None:
+            raise ValueError("route=True needs a pool_n policy: pairs have no drop-off order to drive")
+        if on and self._events_on:
+            raise ValueError("not built: the event log of routed worlds")
+        if on and not self._has_routes:
+            nd = self.d_id.size
+            self.c_stops = np.full((self.n_cabs, 8), -1, np.int64)
+            self.c_pos = np.zeros(self.n_cabs, np.int64)
+            self.d_drop = np.full(nd, -1, np.int64)
+            self.route_m = dict(drop_numb=0, ride_time=0, solo_time=0, max_over_loss=ROUTE_NONE_SEEN)
+            self._has_routes = True
+        self.route = bool(on)
+
+    def _has_stops(self, c):
+        return self.c_pos[c] < 8 and self.c_stops[c, self.c_pos[c]] >= 0
+
+    def _routed(self, cust):
+        return self.route and cust[3] != -1 and cust[0] in self._routes
+
+    def _give_route(self, c, cust, method, how):
+        """cab c receives the stop list of cust's record (method: EV_LCM / EV_OPT, how: "standing" / "heading"; not used here)"""
+        words, _ = self._routes[cust[0]]
+        self.c_stops[c, :] = -1
+        self.c_stops[c, :len(words)] = words
+        self.c_pos[c] = 0
+
+    def _serve(self, t, d, drop):
+        if not drop:
+            self.d_pick[d] = t
+            return
+        ride, solo = t - int(self.d_pick[d]), int(self._way(int(self.d_from[d]), int(self.d_to[d])))
+        self.d_drop[d] = t
+        m = self.route_m
+        m["drop_numb"] += 1
+        m["ride_time"] += ride
+        m["solo_time"] += solo
+        m["max_over_loss"] = max(m["max_over_loss"], ride * 100 - solo * (100 + self.pool_loss))
+
+    def _advance(self, t, c, cur):
+        pos, nxt = int(self.c_pos[c]), -1
+        while pos < 8 and self.c_stops[c, pos] >= 0:
+            w = int(self.c_stops[c, pos])
+            d, drop = w >> 1, w & 1
+            stand = int(self.d_to[d] if drop else self.d_from[d])
+            if stand != cur:
+                nxt = stand
+                break
+            self._serve(t, d, drop)
+            pos += 1
+        self.c_pos[c] = pos
+        self.c_from[c] = cur
+        if nxt >= 0:
+            self.c_to[c] = nxt
+            self.c_onboard[c] = 1
+            self.c_start[c] = t
+        else:                       # the cab is free at this stand in this tick
+            self.c_to[c] = cur
+            self.c_clnt[c] = -1
+            self.c_onboard[c] = 0
+            self.c_start[c] = -1
 
     def _ev(self, t, kind, method=0, customer=-1, cab=-1, aux=-1):
         if self._events_on:
@@ -327,12 +411,17 @@ class Simulator:
                 self.d_pick[d] = t
                 self._ev(t, EV_PICKED_UP, customer=self.d_id[d], cab=c)                       # :233
                 self.m["total_pickup_numb"] += 1
+                if self._has_routes and self._has_stops(c):      # the arrival serves stop 0 and advances
+                    self._advance(t, c, int(self.d_from[d]))
+                    continue
                 self.c_from[c] = self.d_from[d]
                 self.c_to[c] = self.d_to[d] if self.d_pool_id[d] == -1 else cheat_a_bit(int(self.d_from[d]),
                                                                                        int(self.d_pool_cost[d]))
                 self.c_clnt[c] = self.d_id[d]
                 self.c_onboard[c] = 1
                 self.c_start[c] = t
+            elif self._has_routes and self._has_stops(c):    # a cab with stops left: serve the stop, then advance
+                self._advance(t, c, int(self.c_to[c]))
             else:
                 self.c_from[c] = self.c_to[c]
                 self.c_clnt[c] = -1
@@ -466,7 +555,13 @@ class Simulator:
     # findPool + analyzePool under the world's policy; "none": the demand as it is, in the model's six-field form
     def _pooled(self, temp_demand, t):
         if self.pool_n is not None:
-            out, self._others = self.analyze_pool_n(self.find_pool_n(temp_demand, t), temp_demand)
+            pool = self.find_pool_n(temp_demand, t)
+            out, self._others = self.analyze_pool_n(pool, temp_demand)
+            self._routes = {}
+            if self.route:       # the stops of each record, under its first pick-up: the path pn_check prices
+                idx = lambda p: self.id2idx[temp_demand[p][0]]
+                for picks, drops, cost in pool:
+                    self._routes.setdefault(temp_demand[picks[0]][0], ([2 * idx(p) for p in picks] + [2 * idx(q) + 1 for q in drops], cost))
             return out
         if self.pool == "none":
             return [[r[0], r[1], r[2], -1, -1, 0] for r in temp_demand]
@@ -506,6 +601,12 @@ class Simulator:
             self.m["total_second_passengers"] += 1
 
     def _assign_to_cab_and_go(self, t, c, cust, method=0):
+        if self._routed(cust):       # the cab stands at from[p0]: stop 0 is served at t and the cab advances; no cheat_a_bit
+            self._give_route(c, cust, method, "standing")
+            self.c_clnt[c] = cust[0]
+            self.m["total_pickup_numb"] += 1
+            self._advance(t, c, cust[1])
+            return
         self.c_from[c] = cust[1]
         self.c_to[c] = cust[2] if cust[3] == -1 else cheat_a_bit(int(self.c_from[c]), cust[5])
         self.c_clnt[c] = cust[0]
@@ -515,6 +616,8 @@ class Simulator:
         self._ev(t, EV_ASSIGNED_PICKED, method, customer=cust[0], cab=c, aux=cust[3])          # :448-465
 
     def _go_to_pickup(self, t, c, cust, method=0):
+        if self._routed(cust):       # heads to from[p0] as below; the arrival serves stop 0
+            self._give_route(c, cust, method, "heading")
         self.c_to[c] = cust[1]
         self.c_clnt[c] = cust[0]
         self.c_onboard[c] = 0
@@ -815,17 +918,25 @@ class DeviceSimulator(_DeviceEvents):
     last begun (td_sim_pools_n), `set_pool_n` changes the policy between two ticks.  None: td_sim_pooling_n is never called.
     pool_buffer: > 0: every stage of a pool_n world is td_pool_n_banded with this plan buffer (td_sim_pool_buffer; at least
     24 * 2047), so no tick is refused for its number of happy plans; `set_pool_buffer` changes it between two ticks, 0 switches
-    it off.  0: td_sim_pool_buffer is never called."""
+    it off.  0: td_sim_pool_buffer is never called.
+    route: True: a pooled cab drives its record as `Simulator(route=True)` specifies (td_sim_route; needs pool_n, and no
+    events: ValueError); `set_route` switches it between two ticks (cabs mid-route finish theirs), `route_state()` and
+    `route_metrics()` read what it adds.  False: td_sim_route is never called."""
 
     M_KEYS = ("total_dropped", "total_pickup_time", "total_pickup_numb", "total_LCM_used", "max_model_size", "max_solver_size",
               "max_POOL_MEM_size", "max_POOL_size", "total_second_passengers")
     CAB_KEYS = ("c_from", "c_to", "c_clnt", "c_onboard", "c_start")
     REQ_KEYS = ("d_cab", "d_pick", "d_pool_id", "d_pool_plan", "d_pool_cost")
+    ROUTE_M_KEYS = ("drop_numb", "ride_time", "solo_time", "max_over_loss")
 
     def __init__(self, demand_rows, n_cabs=None, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None, events=None,
                  event_capacity=None, pool="greedy", max_loss=None, dispatch=None, parts=4, pool_n=None, pool_wait=0, pool_loss=0, max_happy=0,
-                 pool_buffer=0):
+                 pool_buffer=0, route=False):
         import ctypes
+        if route and pool_n is None:
+            raise ValueError("route=True needs a pool_n policy: pairs have no drop-off order to drive")
+        if route and event_kinds_mask(events):
+            raise ValueError("not built: the event log of routed worlds")
         mode = pool_mode(pool)
         pool_buffer = pool_buffer_size(pool_buffer)
         if dispatch is not None:
@@ -873,6 +984,27 @@ class DeviceSimulator(_DeviceEvents):
         self.dispatch, self.parts = "lcm+opt", int(parts)
         if dispatch is not None:                          # a default world never calls td_sim_dispatch
             self.set_dispatch(dispatch, self.max_non_lcm, parts)
+        self.route = False
+        if route:                                         # a default world never calls td_sim_route
+            self.set_route(True)
+
+    def set_route(self, on):
+        """td_sim_route: hand routes out (or stop handing them out; cabs mid-route finish theirs) from the next begin on"""
+        self._ffi.check(self._lib.td_sim_route(self._h, int(bool(on))))
+        self.route = bool(on)
+
+    def route_state(self):
+        """td_sim_route_state under Simulator's names: d_drop [n_req], c_pos [n_cabs], c_stops [n_cabs, 8]"""
+        drop, pos = np.empty(max(self.n_req, 1), np.int32), np.empty(max(self.n_cabs, 1), np.int32)
+        stops = np.empty((max(self.n_cabs, 1), 8), np.int32)
+        self._ffi.check(self._lib.td_sim_route_state(self._h, *[self._ffi.addr(a) for a in (drop, pos, stops)]))
+        return dict(d_drop=drop[:self.n_req], c_pos=pos[:self.n_cabs], c_stops=stops[:self.n_cabs])
+
+    def route_metrics(self):
+        """td_sim_route_metrics: Simulator.route_m"""
+        out = np.zeros(len(self.ROUTE_M_KEYS), np.int64)
+        self._ffi.check(self._lib.td_sim_route_metrics(self._h, self._ffi.addr(out)))
+        return {k: int(v) for k, v in zip(self.ROUTE_M_KEYS, out)}
 
     def set_pool_n(self, pool_n, pool_wait=0, pool_loss=0, max_happy=0):
         """td_sim_pooling_n: pools of k_hi down to k_lo (pool_n = k or (k_hi, k_lo)) under pool_wait / pool_loss, from the next

@@ -27,7 +27,9 @@ is refused, and the tool says which tick.
 HipBackend(pool_buffer=N); at least 24 * 2047 = 49128): the same plans, and no tick is refused for its number of happy plans.
 --pool-n with --world device --cabs a,b,c: every world of the batch under that cascade (td_simb_pooling_n; a world may have at most
 512 requests before pooling in a tick), and --pool-buffer N then sets td_simb_pool_buffer (24 * 512 = 12288 .. 2^22): the pool
-rounds run through td_pool_n_banded_batched's kernel and no tick is refused for a world's number of happy plans."""
+rounds run through td_pool_n_banded_batched's kernel and no tick is refused for a world's number of happy plans.
+--route (with --pool-n, one world, no --events): a pooled cab drives its plan (Simulator(route=True) / td_sim_route) instead of
+being busy for the pool's cost through cheat_a_bit; after the run the four route counters and the mean ride / solo are printed."""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -48,8 +50,20 @@ ap.add_argument("--pool-wait", type=int, default=0, metavar="W", help="with --po
 ap.add_argument("--pool-loss", type=int, default=0, metavar="L", help="with --pool-n: percent a pooled ride may exceed the direct one")
 ap.add_argument("--max-happy", type=int, default=0, metavar="H", help="with --pool-n: the most happy plans of one stage (0: the pool call's default)")
 ap.add_argument("--pool-buffer", type=int, default=0, metavar="N", help="with --pool-n: the plan buffer of td_pool_n_banded for every stage (0: off)")
+ap.add_argument("--route", action="store_true", help="with --pool-n: a pooled cab drives its plan (one world, no --events)")
 args = ap.parse_args()
 pool_n, n_cabs_1 = {}, {}
+if args.route and (not args.pool_n or args.events or (args.cabs and "," in args.cabs)):
+    ap.error("--route goes with --pool-n, one world and no --events (batches and the event log of routed worlds are not built)")
+
+
+def print_route(m):
+    print("Route counters: dropped off %d, ride time %d, solo time %d, max over loss %s" % (
+        m["drop_numb"], m["ride_time"], m["solo_time"], m["max_over_loss"] if m["drop_numb"] else "none"))
+    if m["drop_numb"]:
+        print("Mean ride / solo: %.3f / %.3f" % (m["ride_time"] / m["drop_numb"], m["solo_time"] / m["drop_numb"]))
+
+
 if args.pool_buffer:
     if not args.pool_n:
         ap.error("--pool-buffer goes with --pool-n")
@@ -187,6 +201,7 @@ if args.world == "device":
     if pool_n:
         pool_n["max_happy"] = args.max_happy
         pool_n["pool_buffer"] = args.pool_buffer
+        pool_n["route"] = args.route
     sim = simulator.DeviceSimulator(rows, dist=dist, events=True if args.events else None, pool=pools[0], max_loss=losses[0], **policy, **pool_n,
                                     **n_cabs_1)
     t0 = time.time()
@@ -200,7 +215,11 @@ if args.world == "device":
     print("120 ticks in %.2f s (reference: 2603 s, README.md:45); world and path on the GPU, one td_sim_step call per tick" % dt)
     print("\n".join(log[-3:]))
     print(sim.metrics_text(total_simul_time=int(dt)))
+    if args.route:
+        print_route(sim.route_metrics())
     sys.exit(0)
+if pool_n:
+    pool_n["route"] = args.route
 sim = simulator.Simulator(rows, backend=simulator.HipBackend(dist, max_happy=args.max_happy, pool_buffer=args.pool_buffer) if pool_n else None, dist=dist, events=bool(args.events), pool=pools[0],
                           max_loss=losses[0], **policy, **pool_n, **({"n_cabs": n_cabs_1["n_cabs"]} if n_cabs_1 else {}))
 t0 = time.time()
@@ -219,3 +238,6 @@ if args.events:
 print("120 ticks in %.2f s (reference: 2603 s, README.md:45); path time on GPU incl. PCIe: %s" % (dt, {k: round(v, 3) for k, v in per.items()}))
 print("\n".join(log[-3:]))
 print(sim.metrics_text(total_simul_time=int(dt)))
+
+if args.route:
+    print_route(sim.route_m)
