@@ -650,11 +650,31 @@ TD_API int td_simb_pools_n(td_simb *s, int world, int max_pools, int32_t *record
  * the sum of d_drop - d_pick over the dropped-off members, solo_time = the sum of their direct ways, max_over_loss = the
  * largest ride * 100 - solo * (100 + max_loss_pct) seen (INT64_MIN before the first drop-off; <= 0 iff every driven ride
  * keeps the loss rule).  Both are TD_EINVAL on a handle that never had routes.  td_sim_state and td_sim_metrics keep their
- * layouts.  A handle that never calls td_sim_route launches the kernels it launched before; a batch has no routes. */
+ * layouts.  A handle that never calls td_sim_route launches the kernels it launched before.
+ *
+ * A batch routes every world or some of them.  td_simb_route: on[b] != 0 hands out routes in world b from
+ * the next begin on (on [B]: host or device); the first call with a world on allocates the route storage of the whole batch
+ * (8 stop words and a position per cab of all fleets, the drop-off tick per request, one record column per list, four
+ * counters per world, on [B]; td_workspace_bytes counts it, td_simb_destroy returns it) and queues one init launch.
+ * on[b] == 0 stops handing out routes in world b; its cabs that are mid-route finish theirs.  A world whose routes are off
+ * behaves exactly as in a batch without routes, whatever its neighbours do, and a routed batch queues the kernels of the
+ * same batch unrouted, in the same order.  All zeros on a handle that never had routes is TD_OK and allocates nothing.
+ * TD_EINVAL, nothing changed: a null handle or on, a call while a tick waits for its apply, on[b] != 0 for a world without
+ * a td_simb_pooling_n policy (k_hi[b] == 0: pairs have no drop-off order; the message names the world), a world on in a
+ * handle that logs.  While a world's routes are on td_simb_pooling is TD_EINVAL, as is a td_simb_pooling_n call that leaves
+ * that world pooling pairs, and td_simb_log with a non-zero mask is TD_EINVAL ("not built") on a handle that has route storage.
+ * td_simb_route_state: world `world`'s segment only, as td_sim_route_state of a one-world handle reports it: r_drop [the
+ * world's requests], c_pos [its cabs], c_stops [8 * its cabs] with the request index counted from where the world's table
+ * begins (-1 stays -1).  Host or device destinations, NULL to skip.  td_simb_route_metrics: TD_SIM_N_ROUTE_METRICS words per
+ * world, world after world; a world that never dropped anyone off reports 0, 0, 0, INT64_MIN.  Both are TD_EINVAL on a
+ * handle without route storage ("no routes") and for a world outside 0 .. B - 1. */
 #define TD_SIM_N_ROUTE_METRICS 4
 TD_API int td_sim_route(td_sim *s, int on);
 TD_API int td_sim_route_state(td_sim *s, int32_t *r_drop, int32_t *c_pos, int32_t *c_stops /* 8 * n_cabs */);
 TD_API int td_sim_route_metrics(td_sim *s, int64_t out[TD_SIM_N_ROUTE_METRICS]);
+TD_API int td_simb_route(td_simb *s, const int32_t *on /* [B] */);
+TD_API int td_simb_route_state(td_simb *s, int world, int32_t *r_drop, int32_t *c_pos, int32_t *c_stops /* 8 * n_cabs of the world */);
+TD_API int td_simb_route_metrics(td_simb *s, int64_t *out /* B * TD_SIM_N_ROUTE_METRICS */);
 
 /* ---- the dispatch policy of a world ------------------------------------------------------------------------------
  * Until *_dispatch is called a world dispatches as Simulator.java:163-208 does, "the LCM down to max_non_lcm, then the

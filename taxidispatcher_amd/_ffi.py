@@ -111,6 +111,9 @@ SIGNATURES = {
     "td_sim_route": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "td_sim_route_state": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p]),
     "td_sim_route_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "td_simb_route": (ctypes.c_int, [ctypes.c_void_p, c_i32p]),
+    "td_simb_route_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p, c_i32p, c_i32p]),
+    "td_simb_route_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "td_simb_pool_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     "td_sim_pools_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i32p, c_i32p, ctypes.POINTER(ctypes.c_int32)]),
     "td_simb_pooling_n": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int64]),

@@ -57,10 +57,13 @@ struct EvOn {
 // ---- the route model (td_sim_route).  A routed cab drives its pool's plan: 8 stop words per cab, a stop word
 // = request index * 2 + (1: drop-off, 0: pick-up), -1 = no stop, and the position of the next stop to serve.  The rules take
 // the route as a template parameter the way they take the event log's emitter: RouteOff is empty and compiles to nothing (the
-// instantiation of every handle that never asked for routes, and of every batch), RouteOn holds the handle's route storage.
+// instantiation of every handle that never asked for routes), RouteOn holds a td_sim handle's route storage, RouteOnB a batch's.
+// What a batch adds is per world, so a kernel binds the route to its world once, `rt.of(b)`, and the rules below see one
+// world's route: RouteOff and RouteOn return themselves, RouteOnB a RouteOn of world b (td_simb_route).
 struct RouteOff {
     static constexpr bool on = false;
     struct Acc {};
+    __device__ __forceinline__ const RouteOff &of(int) const { return *this; }
 };
 struct RouteAcc {   // what one thread's served drop-offs add to the route counters
     long long drops = 0, ride = 0, solo = 0, over = INT64_MIN;
@@ -74,6 +77,23 @@ struct RouteOn {
     // what a dispatching thread builds a stop list from: the tick's 9-int records, the tick's demand list (a record's members
     // are positions in it), and the record of each customer of the demand after pooling / of the kept demand (-1: none)
     const int32_t *recs, *dem_idx, *d_rec, *kd_rec;
+    __device__ __forceinline__ const RouteOn &of(int) const { return *this; }
+};
+// B worlds behind one handle.  Stops, positions, r_drop and the record columns are indexed by the concatenated cab / request /
+// list row, as c_from and r_pick are; per world: four counters, the loss of the world's policy, its slab of `stride` records,
+// and its demand list (a record's members are positions in it; what lies there indexes the concatenated request table).
+struct RouteOnB {
+    static constexpr bool on = true;
+    using Acc = RouteAcc;
+    int32_t *stops, *pos, *r_drop;
+    long long *cnt;                  // [4 B]
+    const int32_t *loss;             // [B]
+    const int32_t *recs, *dem_idx, *d_rec, *kd_rec, *dem_off;
+    int stride;
+    __device__ __forceinline__ RouteOn of(int b) const
+    {
+        return RouteOn{stops, pos, r_drop, cnt + 4 * (size_t)b, loss[b], recs + (size_t)9 * ((size_t)b * (size_t)stride), dem_idx + dem_off[b], d_rec, kd_rec};
+    }
 };
 
 // Simulator.java:469-474

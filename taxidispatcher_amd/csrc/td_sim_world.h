@@ -155,7 +155,7 @@ struct SegOff {
 };
 
 // ev: the event log's emitter (td_sim_core.h): EvOff, or EvOn on the arrival stage, slot = the cab's row
-// rt: the route model (td_sim_core.h): RouteOff, or RouteOn of a handle that has route storage
+// rt: the route model (td_sim_core.h): RouteOff, or RouteOn / RouteOnB of a handle that has route storage
 template <class S, class EV, class R>
 __global__ __launch_bounds__(CB) void k_arrive(World w, S cabs, int t, Ctl *ctl, EV ev, R rt)
 {
@@ -163,9 +163,10 @@ __global__ __launch_bounds__(CB) void k_arrive(World w, S cabs, int t, Ctl *ctl,
     const int b = blockIdx.y, l = blockIdx.x * CB + threadIdx.x;
     int lo, n;
     cabs(b, &lo, &n);
+    const auto &rv = rt.of(b);   // the route of this workgroup's world
     typename R::Acc acc;
-    const int got = l < n ? arrive_as(w, t, lo + l, l, ev, lo + l, rt, acc) : 0;
-    route_flush(rt, acc);
+    const int got = l < n ? arrive_as(w, t, lo + l, l, ev, lo + l, rv, acc) : 0;
+    route_flush(rv, acc);
     const int tot = block_sum(got, s_red);
     if (threadIdx.x == 0) {
         if (blockIdx.x == 0) ctl[b].opt_count = 0;   // this tick's OPT count starts from zero
@@ -360,17 +361,27 @@ struct PoolEmitN {
 // writes, the way MorePartners carries the partner columns; the dispatching thread builds the stop list from the record.
 // (The record index and not the stops: one word per customer and list instead of eight, and the tick's records stay where
 // k_pool_records left them until the apply.)  Handles without routes keep their emitters, and so their kernels, as they are.
-template <class E>
+// N: how many records world b has: a number (td_sim), or RecCountB of a batch: the world's own count, and none at all in a
+// world that pools pairs (its ainfo holds a plan index, not a record index) or whose routes are off; no customer of such a
+// world has a record, so no cab of it ever gets a stop
+struct RecCountB {
+    const int32_t *k_hi, *on, *n_rec;
+    int stride;
+    __device__ __forceinline__ int operator()(int b) const { return k_hi[b] && on[b] ? min(n_rec[b], stride) : 0; }
+};
+__device__ __forceinline__ int rec_count(int n, int) { return n; }
+__device__ __forceinline__ int rec_count(const RecCountB &n, int b) { return n(b); }
+template <class E, class N = int>
 struct WithRec {   // the demand after pooling
     E e;
     const int32_t *ainfo;
-    int n_rec;
+    N n_rec;
     int32_t *rec;
     __device__ void operator()(int o, int o2, int d, int b) const
     {
         e(o, o2, d, b);
         const int p = ainfo[d];
-        rec[o] = p >= 0 && p < n_rec ? p : -1;
+        rec[o] = p >= 0 && p < rec_count(n_rec, b) ? p : -1;
     }
 };
 template <class E>
@@ -521,7 +532,7 @@ __global__ __launch_bounds__(256) void k_pair_map(D dec, L max_non_lcm, S sup, S
 // ev: EvOff, or EvOn on the pairs stage (cleared by the host before the launch): thread l of world b owns slots
 // 2 (s0 + d0 + l) and + 1, so the cab loop's records precede the request loop's and :654 precedes the same request's :432.
 // px: the partner columns behind the first (NP = 3: a world of td_*_pooling_n with pools of three or four, never logged)
-// rt: RouteOff, or RouteOn: the cab loop hands a pooled customer's cab its stop list
+// rt: RouteOff, or RouteOn / RouteOnB bound to world b: the cab loop hands a pooled customer's cab its stop list
 template <class D, class S, class EV, class L, int NP, class R>
 __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, L max_non_lcm, S cabs, S sup, S d2,
                                                     const int32_t *__restrict__ pair_cab, const int32_t *__restrict__ pair_dem,
@@ -544,14 +555,15 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, L max
     const int l = blockIdx.x * CB + threadIdx.x;
     const int slot = 2 * (s0 + d0 + l);
     int numb = 0, ptime = 0, second = 0;
+    const auto &rv = rt.of(b);
     typename R::Acc acc;
     if (l < n_s) {
         const int p = pair_cab[s0 + l];
         if (p != NONE) {
             const int d = d0 + dec.cols[base + p];
             int rec = -1;
-            if constexpr (R::on) rec = rt.d_rec[d];
-            dispatch(w, t, sup_cab[s0 + l], sup_to[s0 + l], d_idx[d], d_partner[d], d_cost[d], numb, ptime, ev, slot, EV_LCM, sup_cab[s0 + l] - c0, rt,
+            if constexpr (R::on) rec = rv.d_rec[d];
+            dispatch(w, t, sup_cab[s0 + l], sup_to[s0 + l], d_idx[d], d_partner[d], d_cost[d], numb, ptime, ev, slot, EV_LCM, sup_cab[s0 + l] - c0, rv,
                      rec, acc);
         }
     } else if (l < n_s + n_d) {
@@ -582,7 +594,7 @@ __global__ __launch_bounds__(CB) void k_apply_pairs(World w, int t, D dec, L max
             }
         }
     }
-    route_flush(rt, acc);
+    route_flush(rv, acc);
     const int tn = block_sum(numb, s_red), tp = block_sum(ptime, s_red), ts = block_sum(second, s_red);
     if (threadIdx.x == 0) {
         if (tn) atomicAdd((unsigned long long *)&ctl[b].pickup_numb, (unsigned long long)tn);
@@ -631,6 +643,7 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, L 
     const int32_t *l_partner = lcm ? kd_partner : d_partner, *l_plan = lcm ? kd_plan : d_plan, *l_cost = lcm ? kd_cost : d_cost;
     const int l = blockIdx.x * CB + threadIdx.x;
     int count = 0, numb = 0, ptime = 0, second = 0;
+    const auto &rv = rt.of(b);
     typename R::Acc acc;
     if (l < n_s) {
         const int s = s0 + l;
@@ -665,12 +678,12 @@ __global__ __launch_bounds__(CB) void k_apply_solution(World w, int t, D dec, L 
                     }
                 }
                 int rec = -1;
-                if constexpr (R::on) rec = (lcm ? rt.kd_rec : rt.d_rec)[e];
-                dispatch(w, t, cab, l_to[s], idx, partner, l_cost[e], numb, ptime, ev, slot0 + 2 * l + 1, EV_OPT, cab - c0, rt, rec, acc);
+                if constexpr (R::on) rec = (lcm ? rv.kd_rec : rv.d_rec)[e];
+                dispatch(w, t, cab, l_to[s], idx, partner, l_cost[e], numb, ptime, ev, slot0 + 2 * l + 1, EV_OPT, cab - c0, rv, rec, acc);
             }
         }
     }
-    route_flush(rt, acc);
+    route_flush(rv, acc);
     const int tc = block_sum(count, s_red), tn = block_sum(numb, s_red), tp = block_sum(ptime, s_red), ts = block_sum(second, s_red);
     if (threadIdx.x == 0) {
         if (tc) atomicAdd(&ctl[b].opt_count, tc);

@@ -39,6 +39,13 @@
 //
 // The event log (td_simb_log / td_simb_events) is td_sim's with the world dimension of the grid: one flush per
 // tick over all worlds, three launches whatever B is, world 0's records first.  Off by default: the EvOff instantiations.
+//
+// The route model (td_simb_route) is td_sim's with the world bound per workgroup (RouteOnB::of, td_sim_core.h):
+// a world whose routes are on hands a dispatched cab its record's stop list, every other world of the batch behaves as
+// without routes (its record column holds -1 everywhere).  A handle that never asked for routes launches the RouteOff
+// instantiations, as before; with route storage k_arrive runs routed, and a tick in which some world's routes are on runs
+// the last begin compaction, the kept-demand compaction and the two apply kernels in their routed forms: the same launches
+// in the same order.
 #include <limits.h>
 
 #include "td_sim_world.h"
@@ -123,8 +130,26 @@ struct SimbPlansN {
     __device__ __forceinline__ int base(int b) const { return k_hi[b] ? rec_base[b] : pl.base(b); }
 };
 
+// td_simb_route: what the first call with a world on adds to a handle
+struct SimbRoute {
+    bool any = false;            // some world's routes are on: the ticks from the next begin on run the routed forms
+    bool tick = false;           // the begun tick carries the record columns
+    std::vector<int32_t> on;     // [B] on the host
+    Buf mem;                     // mem.p: the handle has route storage, and k_arrive drives what is in it
+    int32_t *stops = nullptr, *pos, *r_drop;   // 8 stop words and a position per cab of the concatenated fleet, the drop-off tick per request
+    int32_t *d2_rec, *kd_rec;                  // the record of each customer of the demand after pooling / the kept demand
+    long long *cnt;                            // [4 B]: drop_numb, ride_time, solo_time, max_over_loss of every world
+    int32_t *d_on;                             // [B]
+    int32_t *local;                            // [8 max_cabs]: one world's stop words, world-local, for td_simb_route_state
+};
+
 struct td_simb : SimbDev, SimbPin {   // td_sim_layout.h: every device array of the handle, and the pinned block
     SimbPoolN pn;
+    SimbRoute rt;
+    RouteOnB route() const
+    {
+        return RouteOnB{rt.stops, rt.pos, rt.r_drop, rt.cnt, pn.d_loss, pn.recs, dem_idx, rt.d2_rec, rt.kd_rec, dem_off, pn.stride};
+    }
     World w;                     // the concatenated tables
     int B = 0, max_non_lcm = 0;
     int words = 0;               // of one stand bitset
@@ -172,6 +197,26 @@ static auto with_rule(const td_simb *s, F f)
 }
 
 namespace {
+
+// the route storage's first state in every world: no stop anywhere, nobody dropped off, the counters empty
+__global__ __launch_bounds__(256) void k_routeb_init(int B, int n_cabs, int n_req, int32_t *__restrict__ stops, int32_t *__restrict__ pos,
+                                                     int32_t *__restrict__ r_drop, long long *__restrict__ cnt)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 8 * n_cabs) stops[i] = -1;
+    if (i < n_cabs) pos[i] = 0;
+    if (i < n_req) r_drop[i] = -1;
+    if (i < 4 * B) cnt[i] = (i & 3) == 3 ? INT64_MIN : 0;
+}
+
+// a world's stop words as a one-world handle reports them: the request index counts from where the world's table begins
+__global__ __launch_bounds__(256) void k_route_local(const int32_t *__restrict__ stops, int n, int r0, int32_t *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int wd = stops[i];
+    out[i] = wd < 0 ? -1 : wd - 2 * r0;
+}
 
 // ONE workgroup: per-workgroup counts -> per-world totals -> offset arrays (exclusive scans over the worlds, B in slices of CB).
 //   off_a = the list counted in cnt_a; off_b (cnt_b non-null) = the list counted in cnt_b.
@@ -517,6 +562,8 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     const bool log = s->ev.kinds != 0;
     if (log)
         k_arrive<<<grid_c, CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOn{s->ev.st_arr}, RouteOff{});
+    else if (s->rt.mem.p)   // a handle with route storage never logs
+        k_arrive<<<grid_c, CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOff{}, s->route());
     else
         k_arrive<<<grid_c, CB, 0, c.stream>>>(w, cabs, t, s->ctl, EvOff{}, RouteOff{});
     k_flags<<<grid_c, CB, shm, c.stream>>>(cabs, w.n_stands, w.c_to, w.c_clnt, s->bits, 0);
@@ -541,6 +588,7 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     if (*h_of(s, s->gerr)) return fail(TD_EINTERNAL, "td_simb: device error word %d", *h_of(s, s->gerr));
     s->last_t = t;
     s->pool_ragged = 0;
+    s->rt.tick = s->rt.any;   // td_simb_route is refused inside a tick: the begin and the apply agree
     s->h_npool.assign((size_t)B, 0);
     const int32_t *hd = h_of(s, s->dem_off), *hs = h_of(s, s->sup_off), *hp = h_of(s, s->pl_off);
     int max_dem = 0, max_act = 0;
@@ -636,7 +684,18 @@ int simb_begin(td_simb *s, int t, int32_t *info)
     const PoolEmit<SimbPlans, SegOff> pe{pl, dem, s->dem_idx, s->dem_from, s->ainfo, s->pb, s->pp, s->pc, s->d2_idx, s->d2_from, s->d2_partner,
                                          s->d2_plan, s->d2_cost, s->tk_from};
     const SimbPoolN &pn = s->pn;
-    if (!pn.set)
+    // with routes the record of a first pick-up travels beside its columns (a world on implies pn.set)
+    const RecCountB rcnt{pn.d_hi, s->rt.d_on, s->n_pools, pn.stride};
+    if (s->rt.tick && pn.any3)
+        k_scatter<PoolPred, WithRec<PoolEmitB<3>, RecCountB>><<<grid_d, CB, 0, c.stream>>>(
+            s->dem_off, pp,
+            WithRec<PoolEmitB<3>, RecCountB>{PoolEmitB<3>{pe, pn.d_hi, pn.recs, pn.size, pn.stride, {pn.d2_more[0], pn.d2_more[1]}}, s->ainfo, rcnt, s->rt.d2_rec},
+            s->cnt_a, s->d2_off, s->tk_off);
+    else if (s->rt.tick)
+        k_scatter<PoolPred, WithRec<PoolEmitB<1>, RecCountB>><<<grid_d, CB, 0, c.stream>>>(
+            s->dem_off, pp, WithRec<PoolEmitB<1>, RecCountB>{PoolEmitB<1>{pe, pn.d_hi, pn.recs, pn.size, pn.stride, {nullptr, nullptr}}, s->ainfo, rcnt, s->rt.d2_rec},
+            s->cnt_a, s->d2_off, s->tk_off);
+    else if (!pn.set)
         k_scatter<PoolPred, PoolEmit<SimbPlans, SegOff>><<<grid_d, CB, 0, c.stream>>>(s->dem_off, pp, pe, s->cnt_a, s->d2_off, s->tk_off);
     else if (pn.any3)
         k_scatter<PoolPred, PoolEmitB<3>><<<grid_d, CB, 0, c.stream>>>(
@@ -705,6 +764,7 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
     const bool log = s->ev.kinds != 0;
     // pools of three or four in some world: the partner columns behind the first travel with the apply kernels (such a handle never logs)
     const bool more = s->pn.set && s->pn.any3;
+    const bool route = s->rt.tick;   // some world hands out routes in this tick (such a handle never logs)
     const MorePartners<3> px3{{s->pn.d2_more[0], s->pn.d2_more[1]}, {s->pn.kd_more[0], s->pn.kd_more[1]}};
     if (log && (rc = ev_clear_apply(s->ev, (size_t)hs[B], (size_t)h2[B]))) return rc;
     rc = with_rule(s, [&](auto mnl) -> int {
@@ -714,16 +774,20 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
         TD_HIP(hipMemsetAsync(s->pair_dem, 0x7f, sizeof(int32_t) * (size_t)h2[B], c.stream));
         if (max_pairs > 0)
             k_pair_map<<<dim3((max_pairs + 255) / 256, B), 256, 0, c.stream>>>(dec, mnl, sup, d2, s->pair_cab, s->pair_dem, s->gerr);
-        auto pairs = [&](auto ev, auto px) {
+        auto pairs = [&](auto ev, auto px, auto rt) {
             k_apply_pairs<<<dim3(nchunks(max_sd), B), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, s->pair_cab, s->pair_dem, s->sup_cab, s->sup_to,
-                                                                       s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, s->gerr, ev, px, RouteOff{});
+                                                                       s->d2_idx, s->d2_partner, s->d2_cost, s->ctl, s->gerr, ev, px, rt);
         };
-        if (more)
-            pairs(EvOff{}, px3);
+        if (route && more)
+            pairs(EvOff{}, px3, s->route());
+        else if (route)
+            pairs(EvOff{}, MorePartners<1>{}, s->route());
+        else if (more)
+            pairs(EvOff{}, px3, RouteOff{});
         else if (log)
-            pairs(EvOn{s->ev.st_pairs}, MorePartners<1>{});
+            pairs(EvOn{s->ev.st_pairs}, MorePartners<1>{}, RouteOff{});
         else
-            pairs(EvOff{}, MorePartners<1>{});
+            pairs(EvOff{}, MorePartners<1>{}, RouteOff{});
         const dim3 grid_s(nchunks(max_s), B), grid_d(nchunks(max_d), B);
         const KeptPred<SegOff, L> ps{s->pair_cab, sup, d2, mnl}, pd{s->pair_dem, sup, d2, mnl};
         k_count<SegOff, KeptPred<SegOff, L>><<<grid_s, CB, 0, c.stream>>>(sup, ps, s->cnt_a);
@@ -732,24 +796,34 @@ int simb_apply(td_simb *s, const SimbDec &dec, int max_pairs, const int32_t *h_s
         k_scatter<KeptPred<SegOff, L>, KeptSupEmit><<<grid_s, CB, 0, c.stream>>>(s->sup_off, ps, KeptSupEmit{s->sup_cab, s->sup_to, s->ks_cab, s->ks_to},
                                                                             s->cnt_a, s->ks_off, nullptr);
         const KeptDemEmit ke{s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost};
-        if (more)
-            k_scatter<KeptPred<SegOff, L>, KeptDemEmitN<3>><<<grid_d, CB, 0, c.stream>>>(
-                s->d2_off, pd, KeptDemEmitN<3>{ke, {s->pn.d2_more[0], s->pn.d2_more[1]}, {s->pn.kd_more[0], s->pn.kd_more[1]}}, s->cnt_b, s->kd_off, nullptr);
+        const KeptDemEmitN<3> ke3{ke, {s->pn.d2_more[0], s->pn.d2_more[1]}, {s->pn.kd_more[0], s->pn.kd_more[1]}};
+        if (route && more)   // with routes the record column travels to the kept demand too
+            k_scatter<KeptPred<SegOff, L>, KeptRec<KeptDemEmitN<3>>><<<grid_d, CB, 0, c.stream>>>(
+                s->d2_off, pd, KeptRec<KeptDemEmitN<3>>{ke3, s->rt.d2_rec, s->rt.kd_rec}, s->cnt_b, s->kd_off, nullptr);
+        else if (route)
+            k_scatter<KeptPred<SegOff, L>, KeptRec<KeptDemEmit>><<<grid_d, CB, 0, c.stream>>>(
+                s->d2_off, pd, KeptRec<KeptDemEmit>{ke, s->rt.d2_rec, s->rt.kd_rec}, s->cnt_b, s->kd_off, nullptr);
+        else if (more)
+            k_scatter<KeptPred<SegOff, L>, KeptDemEmitN<3>><<<grid_d, CB, 0, c.stream>>>(s->d2_off, pd, ke3, s->cnt_b, s->kd_off, nullptr);
         else
             k_scatter<KeptPred<SegOff, L>, KeptDemEmit><<<grid_d, CB, 0, c.stream>>>(s->d2_off, pd, ke, s->cnt_b, s->kd_off, nullptr);
     }
-    auto solution = [&](auto ev, auto px) {
+    auto solution = [&](auto ev, auto px, auto rt) {
         k_apply_solution<<<dim3(nchunks(max_s), B), CB, 0, c.stream>>>(w, t, dec, mnl, cabs, sup, d2, SegOff{s->ks_off}, SegOff{s->kd_off}, s->sup_cab,
                                                                      s->sup_to, s->d2_idx, s->d2_from, s->d2_partner, s->d2_plan, s->d2_cost, s->ks_cab,
                                                                      s->ks_to, s->kd_idx, s->kd_from, s->kd_partner, s->kd_plan, s->kd_cost, s->ctl, s->gerr,
-                                                                     ev, px, RouteOff{});
+                                                                     ev, px, rt);
     };
-    if (any_sup && more)
-        solution(EvOff{}, px3);
+    if (any_sup && route && more)
+        solution(EvOff{}, px3, s->route());
+    else if (any_sup && route)
+        solution(EvOff{}, MorePartners<1>{}, s->route());
+    else if (any_sup && more)
+        solution(EvOff{}, px3, RouteOff{});
     else if (any_sup && log)
-        solution(EvOn{s->ev.st_sol}, MorePartners<1>{});
+        solution(EvOn{s->ev.st_sol}, MorePartners<1>{}, RouteOff{});
     else if (any_sup)
-        solution(EvOff{}, MorePartners<1>{});
+        solution(EvOff{}, MorePartners<1>{}, RouteOff{});
     return TD_OK;
     });
     if (rc) return rc;
@@ -946,6 +1020,7 @@ extern "C" int td_simb_destroy(td_simb *s)
     if (ctx().inited) (void)hipStreamSynchronize(ctx().stream);
     buf_free(s->mem);
     buf_free(s->pn.mem);
+    buf_free(s->rt.mem);
     ev_off(s->ev);
     if (s->pin) (void)hipHostFree(s->pin);
     delete s;
@@ -967,6 +1042,9 @@ extern "C" int td_simb_pooling(td_simb *s, const int32_t *mode, const double *ma
     TD_REQUIRE_INIT();
     if (!s) return fail(TD_EINVAL, "null handle");
     if (s->begun) return fail(TD_EINVAL, "td_simb_pooling: tick %d still waits for td_simb_apply", s->last_t);
+    for (int b = 0; b < s->B && s->rt.any; b++)
+        if (s->rt.on[b])
+            return fail(TD_EINVAL, "td_simb_pooling: world %d's routes are on (td_simb_route) and pairs have no drop-off order to drive; switch them off first", b);
     const size_t B = (size_t)s->B;
     int rc;
     std::vector<int32_t> hm(B, TD_POOL_GREEDY);
@@ -1019,6 +1097,8 @@ extern "C" int td_simb_pooling_n(td_simb *s, const int32_t *k_hi, const int32_t 
             if (hw[b] < 0 || hs[b] < 0)
                 return fail(TD_EINVAL, "td_simb_pooling_n: max_wait[%zu] = %d, max_loss_pct[%zu] = %d: nothing negative", b, hw[b], b, hs[b]);
         }
+        if (hh[b] == 0 && s->rt.any && s->rt.on[b])
+            return fail(TD_EINVAL, "td_simb_pooling_n: world %zu's routes are on (td_simb_route) and k_hi[%zu] = 0 leaves it pooling pairs", b, b);
         any = any || hh[b];
         any3 = any3 || hh[b] > 2;
     }
@@ -1299,6 +1379,7 @@ extern "C" int td_simb_log(td_simb *s, uint32_t kinds, int64_t capacity)
     if (kinds & ~TD_EV_ALL) return fail(TD_EINVAL, "td_simb_log: kinds = 0x%x has bits outside 1 .. 11", kinds);
     if (kinds && (capacity <= 0 || capacity > INT_MAX)) return fail(TD_EINVAL, "td_simb_log: capacity = %lld outside 1 .. 2^31 - 1", (long long)capacity);
     if (s->begun) return fail(TD_EINVAL, "td_simb_log: tick %d still waits for td_simb_apply", s->last_t);
+    if (kinds && s->rt.mem.p) return fail(TD_EINVAL, "td_simb_log: not built: the event log of routed worlds (the handle has routes, td_simb_route)");
     if (kinds && s->pn.set && s->pn.any3)
         return fail(TD_EINVAL, "td_simb_log: not built: the event log of pools of three and four (a world under td_simb_pooling_n has k_hi > 2)");
     const size_t nc = (size_t)s->max_cabs, nr = (size_t)s->max_req;
@@ -1316,4 +1397,85 @@ extern "C" int td_simb_events(td_simb *s, int64_t max_records, int32_t *records,
         s->ev.begin_flushed = true;
     }
     return ev_drain(s->ev, "td_simb_events", max_records, records, n, lost);
+}
+
+extern "C" int td_simb_route(td_simb *s, const int32_t *on)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (!on) return fail(TD_EINVAL, "td_simb_route: null on");
+    if (s->begun) return fail(TD_EINVAL, "td_simb_route: tick %d still waits for td_simb_apply", s->last_t);
+    Ctx &c = ctx();
+    const size_t B = (size_t)s->B;
+    SimbRoute &rt = s->rt;
+    int rc;
+    std::vector<int32_t> ho;
+    if ((rc = host_copy(on, B, ho))) return rc;
+    bool any = false;
+    for (size_t b = 0; b < B; b++) {
+        ho[b] = ho[b] != 0;
+        if (ho[b] && !(s->pn.set && s->pn.hi[b]))
+            return fail(TD_EINVAL, "td_simb_route: world %zu pools pairs, which have no drop-off order to drive; give it a td_simb_pooling_n policy first", b);
+        any = any || ho[b];
+    }
+    if (any && s->ev.kinds) return fail(TD_EINVAL, "td_simb_route: not built: the event log of routed worlds (the handle logs)");
+    if (!any && !rt.mem.p) return TD_OK;   // a handle that never had routes stays one
+    if (!rt.mem.p) {   // the handle's, from the first call on: nothing is allocated per tick
+        const size_t nc = (size_t)s->nc_tot, nr = (size_t)std::max(s->nr_tot, 1);
+        SimbRoute d;
+        rc = carve_buf(rt.mem, [&](Carve &cv) {
+            d.stops = (int32_t *)cv.take<int4>(2 * nc);   // a cab's eight words are two 16-byte vectors
+            d.cnt = cv.take<long long>(4 * B);
+            d.pos = cv.take<int32_t>(nc);
+            d.r_drop = cv.take<int32_t>(nr);
+            d.d2_rec = cv.take<int32_t>(nr);
+            d.kd_rec = cv.take<int32_t>(nr);
+            d.d_on = cv.take<int32_t>(B);
+            d.local = cv.take<int32_t>(8 * (size_t)std::max(s->max_cabs, 1));
+        });
+        if (rc) return rc;
+        rt.stops = d.stops, rt.cnt = d.cnt, rt.pos = d.pos, rt.r_drop = d.r_drop, rt.d2_rec = d.d2_rec, rt.kd_rec = d.kd_rec, rt.d_on = d.d_on, rt.local = d.local;
+        const int n = (int)std::max(std::max(8 * nc, nr), 4 * B);
+        k_routeb_init<<<(n + 255) / 256, 256, 0, c.stream>>>((int)B, s->nc_tot, s->nr_tot, rt.stops, rt.pos, rt.r_drop, rt.cnt);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            buf_free(rt.mem);
+            return hip_fail(e, "td_simb_route launch");
+        }
+    }
+    TD_HIP(hipMemcpyAsync(rt.d_on, ho.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, c.stream));
+    TD_HIP(hipStreamSynchronize(c.stream));   // `ho` leaves scope
+    rt.on = ho;
+    rt.any = any;
+    return TD_OK;
+}
+
+extern "C" int td_simb_route_state(td_simb *s, int world, int32_t *r_drop, int32_t *c_pos, int32_t *c_stops)
+{
+    TD_REQUIRE_INIT();
+    if (!s) return fail(TD_EINVAL, "null handle");
+    if (!s->rt.mem.p) return fail(TD_EINVAL, "td_simb_route_state: the handle has no routes (td_simb_route)");
+    if (world < 0 || world >= s->B) return fail(TD_EINVAL, "td_simb_route_state: world %d outside 0 .. %d", world, s->B - 1);
+    const int c0 = s->cab_off[world], ncab = s->cab_off[world + 1] - c0, r0 = s->req_off[world], nreq = s->req_off[world + 1] - r0;
+    int rc;
+    if (c_stops) {
+        k_route_local<<<(8 * ncab + 255) / 256, 256, 0, ctx().stream>>>(s->rt.stops + (size_t)8 * c0, 8 * ncab, r0, s->rt.local);
+        TD_HIP(hipGetLastError());
+    }
+    if ((rc = get(r_drop, s->rt.r_drop + r0, (size_t)nreq)) || (rc = get(c_pos, s->rt.pos + c0, (size_t)ncab)) ||
+        (rc = get(c_stops, s->rt.local, (size_t)8 * ncab)))
+        return rc;
+    TD_HIP(hipStreamSynchronize(ctx().stream));
+    return TD_OK;
+}
+
+extern "C" int td_simb_route_metrics(td_simb *s, int64_t *out)
+{
+    TD_REQUIRE_INIT();
+    if (!s || !out) return fail(TD_EINVAL, "null argument");
+    if (!s->rt.mem.p) return fail(TD_EINVAL, "td_simb_route_metrics: the handle has no routes (td_simb_route)");
+    static_assert(sizeof(long long) == sizeof(int64_t), "the counters are read back as they lie");
+    TD_HIP(hipMemcpyAsync(out, s->rt.cnt, sizeof(int64_t) * TD_SIM_N_ROUTE_METRICS * (size_t)s->B, hipMemcpyDeviceToHost, ctx().stream));
+    TD_HIP(hipStreamSynchronize(ctx().stream));
+    return TD_OK;
 }

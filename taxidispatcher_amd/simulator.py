@@ -1187,20 +1187,37 @@ class DeviceSimulatorBatch(_DeviceEvents):
     records, `set_pool_n` changes the policies between two ticks.  A batch that logs events takes such policies with k_hi = 2 only.
     pool_buffer: > 0: every pool round of the pool_n worlds is td_pool_n_banded_batched's kernel with this plan buffer per
     workgroup (td_simb_pool_buffer; 24 * 512 .. 2^22), so no tick is refused for a world's number of happy plans;
-    `set_pool_buffer` changes it between two ticks, 0 switches it off.  0: td_simb_pool_buffer is never called."""
+    `set_pool_buffer` changes it between two ticks, 0 switches it off.  0: td_simb_pool_buffer is never called.
+    route (keyword only): True, or a list with one bool per world: a pooled cab of such a world drives its record as `Simulator(route=True)`
+    specifies (td_simb_route); a routed world needs a pool_n policy, and a routed batch takes no events (ValueError, before
+    the library is touched).  A world whose routes are off behaves as in a batch without routes.  `set_route` switches the
+    worlds between two ticks (cabs mid-route finish theirs); `route_state(b)` and `route_metrics()` read what the routes add,
+    per world as `DeviceSimulator` reports them.  False: td_simb_route is never called."""
 
     M_KEYS, CAB_KEYS, REQ_KEYS = DeviceSimulator.M_KEYS, DeviceSimulator.CAB_KEYS, DeviceSimulator.REQ_KEYS
+    ROUTE_M_KEYS = DeviceSimulator.ROUTE_M_KEYS
     format_line = staticmethod(DeviceSimulator.format_line)
 
     # dispatch / max_non_lcm / parts: the dispatch policy per world (td_simb_dispatch), each a list with one entry per world or one
     # value for all; dispatch=None with a scalar max_non_lcm: the batch never calls td_simb_dispatch and dispatches as it always did
     def __init__(self, demand_rows_list, n_cabs_list, n_stands=None, drop_time=None, max_non_lcm=None, big_cost=None, dist=None,
                  events=None, event_capacity=None, pool="greedy", max_loss=None, dispatch=None, parts=4, pool_n=None, pool_wait=0, pool_loss=0,
-                 max_happy=0, pool_buffer=0):
+                 max_happy=0, pool_buffer=0, **routing):
         import ctypes
+        # route= is keyword-only and is taken from **routing: the keywords a batch has had since before it could be routed stay
+        # the whole of its named signature (tests/test_sim_route_cpu.py reads it); any other extra keyword is a TypeError
+        route = routing.pop("route", False)
+        if routing:
+            raise TypeError("DeviceSimulatorBatch() got an unexpected keyword argument %r" % sorted(routing)[0])
         pool_buffer = pool_buffer_size(pool_buffer, 512, POOL_BUFFER_BATCH_MAX)
         n_cabs_list = list(n_cabs_list)
         nb = len(n_cabs_list)
+        routes = self._route_list(route, nb)
+        if any(routes):
+            sizes = list(pool_n) if isinstance(pool_n, list) else [pool_n] * nb
+            self._check_routes(routes, sizes)
+            if event_kinds_mask(events):
+                raise ValueError("not built: the event log of routed worlds")
         mnl_list = None
         if isinstance(max_non_lcm, (list, tuple, np.ndarray)):      # a max_non_lcm per world is part of the dispatch policy
             mnl_list = [int(v) for v in max_non_lcm]
@@ -1267,6 +1284,46 @@ class DeviceSimulatorBatch(_DeviceEvents):
         self.dispatch, self.max_non_lcms, self.parts = ["lcm+opt"] * nb, [self.max_non_lcm] * nb, [4] * nb
         if dispatch is not None:                          # a default batch never calls td_simb_dispatch
             self.set_dispatch(dispatch, mnl_list, parts)
+        self.route = [False] * nb
+        if any(routes):                                   # a batch without routes never calls td_simb_route
+            self.set_route(routes)
+
+    @staticmethod
+    def _route_list(route, nb):
+        routes = [bool(v) for v in route] if isinstance(route, (list, tuple, np.ndarray)) else [bool(route)] * nb
+        if len(routes) != nb:
+            raise ValueError("route: %d entries for %d worlds" % (len(routes), nb))
+        return routes
+
+    @staticmethod
+    def _check_routes(routes, sizes):
+        for b, on in enumerate(routes):
+            if on and (b >= len(sizes) or sizes[b] is None):
+                raise ValueError("route: world %d needs a pool_n policy: pairs have no drop-off order to drive" % b)
+
+    def set_route(self, route):
+        """td_simb_route: hand routes out in the worlds of `route` (a bool for all, or one per world) from the next begin on;
+        a world switched off stops getting routes, its cabs that are mid-route finish theirs"""
+        routes = self._route_list(route, self.batch)
+        self._check_routes(routes, self.pool_n)
+        if any(routes) and self.event_kinds:
+            raise ValueError("not built: the event log of routed worlds")
+        on = np.array(routes, np.int32)
+        self._ffi.check(self._lib.td_simb_route(self._h, self._ffi.addr(on)))
+        self.route = routes
+
+    def route_state(self, b):
+        """td_simb_route_state of world b under Simulator's names: d_drop [n_req], c_pos [n_cabs], c_stops [n_cabs, 8]"""
+        nc, nr = self.n_cabs[b], self.n_req[b]
+        drop, pos, stops = np.empty(max(nr, 1), np.int32), np.empty(max(nc, 1), np.int32), np.empty((max(nc, 1), 8), np.int32)
+        self._ffi.check(self._lib.td_simb_route_state(self._h, int(b), *[self._ffi.addr(a) for a in (drop, pos, stops)]))
+        return dict(d_drop=drop[:nr], c_pos=pos[:nc], c_stops=stops[:nc])
+
+    def route_metrics(self):
+        """td_simb_route_metrics: Simulator.route_m of every world"""
+        out = np.zeros((self.batch, len(self.ROUTE_M_KEYS)), np.int64)
+        self._ffi.check(self._lib.td_simb_route_metrics(self._h, self._ffi.addr(out)))
+        return [{k: int(v) for k, v in zip(self.ROUTE_M_KEYS, row)} for row in out]
 
     def set_dispatch(self, dispatch, max_non_lcm=None, parts=4):
         """td_simb_dispatch: the dispatch method ("lcm+opt", "opt", "lcm", "split"), max_non_lcm (None: as created) and the
